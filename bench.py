@@ -22,13 +22,17 @@ Extra objects on the JSON line:
                 all three kernels (fwd_frac repeats the forward's, north_star's 60 % target).  traffic: HBM bytes per
                 launch from the committed rocprofv3 PMC run (profiles/*_pmc.json) if present, else null;
                 traffic_source names that file (it is NOT measured inside this run).
-  cpu_baseline  the reference's eager fp32 algorithm (oracle/sink_oracle.py restatement, dense N x N, torch on all
-                host cores) timed on a bounded slice of the same workload (1 batch element x 1 KV group = 4 q heads),
-                rank 0 at N=1 only: one warm-up repetition, then the median of three.
+  cpu_baseline  the reference's eager fp32 algorithm (oracle/sink_oracle.py restatement, dense N x N, torch on the
+                cores this process may use) timed on a bounded slice of the same workload (1 batch element x 1 KV group =
+                4 q heads), rank 0 at N=1 only: one warm-up repetition, then the median of three.
   sustained     the same step run back to back for >= --sustain-seconds (default 2 s) AFTER the contract region (no stage
                 events, nothing else between the steps): ms_per_step / value once the chip has settled into the clock it
                 holds under this load (the 20-step contract region lasts ~0.12 s).  The contract fields above are
                 untouched by it.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (O of the forward; dQ, dK, dV of the backward)
+as DIR/<name>.npy, float32: a fixed, seeded sample of whole rows of each tensor (48 MiB in all; see dump_outputs()).
+The inputs come from a fixed seed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -75,7 +79,9 @@ def cpu_baseline(w, reps=3):
     from oracle import sink_oracle as O
     g = w["Hq"] // w["Hkv"]
     N, D = w["N"], w["D"]
-    torch.set_num_threads(os.cpu_count())
+    # the cores this process may use (its affinity mask, or OMP_NUM_THREADS where that is set), not every core the
+    # host has: more threads than cores only slows the sample down
+    torch.set_num_threads(int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0)))
     gen = torch.Generator().manual_seed(1)
     q = torch.randn(1, g, N, D, generator=gen).requires_grad_(True)
     k = torch.randn(1, 1, N, D, generator=gen).requires_grad_(True)
@@ -113,6 +119,32 @@ def pmc_traffic(kernel_key):
         except Exception:
             pass
     return best
+
+
+DUMP_BYTES = 48 << 20   # all of --dump-outputs together (float32)
+
+
+def dump_rows(outputs):
+    """name -> sorted row indices that dump_outputs() writes of that tensor (viewed as rows of its last dim).  Fixed
+    seed, so tensors of one shape share their rows; the rows are shared out in proportion to the tensors' sizes."""
+    import numpy as np
+    total = sum(t.numel() for t in outputs.values())
+    idx = {}
+    for name, t in outputs.items():
+        n_rows = t.numel() // t.shape[-1]
+        n = min(n_rows, DUMP_BYTES // 4 * t.numel() // total // t.shape[-1])
+        idx[name] = np.sort(np.random.default_rng(20240601).choice(n_rows, size=n, replace=False))
+    return idx
+
+
+def dump_outputs(path, outputs):
+    """outputs: name -> tensor [..., D] on the device.  Writes path/<name>.npy, float32 [rows, D]: the rows of dump_rows()."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, idx in dump_rows(outputs).items():
+        rows = outputs[name].detach().reshape(-1, outputs[name].shape[-1])
+        sample = rows.index_select(0, torch.from_numpy(idx).to(rows.device)).float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), sample)
 
 
 def reduce_max_seconds(dt, device, world):
@@ -169,9 +201,14 @@ def main():
                     help="after the timed region run ONE more step and save the tensors of the last (batch, KV head) "
                          "unit (q, k, v, dO, O, dQ, dK, dV) to PATH: tests/test_gpu_bench_contract.py checks them "
                          "against the oracle, so the bench cannot go fast on a wrong answer")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region write what its LAST step returned (O, dQ, dK, dV: a fixed, seeded "
+                         "sample of rows, float32, 48 MiB in all) as DIR/<name>.npy, rank 0 only")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank control path (gloo, no kernels, value is meaningless)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dry_run:
         return dry_run(args)
 
@@ -199,6 +236,7 @@ def main():
     stages = [HipEvents(4) for _ in range(args.steps)]     # one set per timed step: per-kernel AVERAGES over the region
     fwd_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     paths = {}
+    last = {}   # --dump-outputs: what the last timed step returned (kept, not copied: the step does no extra work)
 
     def step(i=None):
         if i is not None:
@@ -208,6 +246,8 @@ def main():
             fwd_ev[i][1].record()
         paths["fwd"] = _native.last_path()
         out.backward(do)
+        if i == args.steps - 1 and rank == 0 and args.dump_outputs:
+            last.update(o=out.detach(), dq=q.grad, dk=k.grad, dv=v.grad)
         q.grad = k.grad = v.grad = None
 
     def barrier():
@@ -233,6 +273,10 @@ def main():
     f_fb = flops_fwd_bwd(B, Hq, N, D, ns, W)
     f_f = flops_fwd(B, Hq, N, D, ns, W)
     value = job_value(f_fb, world, dt / args.steps)
+
+    if last:
+        dump_outputs(args.dump_outputs, last)
+        last.clear()
 
     if rank == 0 and args.dump_slice:
         out = sink_flash_attention(q, k, v, num_sink=ns, window_size=W)

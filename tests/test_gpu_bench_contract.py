@@ -13,9 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract(tmp_path):
     dump = str(tmp_path / "slice.pt")
+    outs = str(tmp_path / "outputs")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2",
-                          "--no-cpu-baseline", "--sustain-seconds", "0.5", "--dump-slice", dump], capture_output=True, text=True, timeout=900,
-                         cwd=ROOT)
+                          "--no-cpu-baseline", "--sustain-seconds", "0.5", "--dump-slice", dump, "--dump-outputs", outs],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -54,3 +55,23 @@ def test_bench_json_contract(tmp_path):
     assert_close(t["dq"], dq_r, 5e-2, 5e-2, "bench dq")
     assert_close(t["dk"], dk_r, 5e-2 * max(1.0, dk_r.abs().max().item()), 5e-2, "bench dk")
     assert_close(t["dv"], dv_r, 5e-2 * max(1.0, dv_r.abs().max().item()), 5e-2, "bench dv")
+
+    # --dump-outputs: the sampled rows of the last timed step, float32, 64 MB at most; the (batch, KV head) unit above is
+    # the last rows of each tensor, so the sampled rows that fall in it must be that unit's rows (same inputs)
+    import numpy as np
+    import bench
+    w = bench.WORKLOAD
+    B, Hq, Hkv, N, D = (w[x] for x in ("B", "Hq", "Hkv", "N", "D"))
+    shapes = {"o": (B, Hq, N, D), "dq": (B, Hq, N, D), "dk": (B, Hkv, N, D), "dv": (B, Hkv, N, D)}
+    rows = bench.dump_rows({n: torch.empty(s, device="meta") for n, s in shapes.items()})
+    assert sorted(os.listdir(outs)) == sorted(n + ".npy" for n in shapes)
+    assert sum(os.path.getsize(os.path.join(outs, f)) for f in os.listdir(outs)) <= 64 * 10**6
+    for name, idx in rows.items():
+        a = np.load(os.path.join(outs, name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (len(idx), D) and np.isfinite(a).all(), name
+        unit = t[name].reshape(-1, D).float()
+        first = B * shapes[name][1] * N - unit.shape[0]
+        sel = idx >= first
+        assert sel.any(), name
+        assert_close(torch.from_numpy(a[sel]), unit[torch.from_numpy(idx[sel] - first)],
+                     1e-2 * max(1.0, unit.abs().max().item()), 1e-2, "dumped " + name)
