@@ -232,6 +232,40 @@ int sfa_decode_ring_step_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, cons
                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
                              void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream);
 
+/*
+ * n >= 1 NEW tokens over the sink + ring cache in one pass (speculative verify, chunked continuation): what n successive
+ * sfa_decode_ring_step calls compute, without committing first.  Replaces SinkCacheLayer.update()'s append-then-
+ * linearise of sink_attention/cache.py:129-216 for N_q > 1, which lets a chunk token see keys that the chunk itself
+ * evicted.
+ *   q, o        [B, Hq, n, D]           k_new, v_new [B, Hkv, n, D]   Hq % Hkv == 0
+ *   sink_k/v    [B, Hkv, num_sink, D]   sink_len <= num_sink valid rows
+ *   window_k/v  [B, Hkv, Wc, D]         Wc >= 1 = ring capacity; window_len <= Wc valid slots; write_pos = the slot
+ *               the next token goes to (write_pos == window_len until the ring is full, any slot once it is)
+ *   sink_len / window_len / write_pos describe the cache BEFORE the chunk.
+ * Mask.  Ring slot s has the chronological index r = (s - write_pos + window_len) mod Wc (0 = oldest).  Query t (0 <= t < n)
+ * attends to every sink row, to ring slot s iff window_len - r + t <= Wc - 1, and to chunk token u iff u <= t and
+ * t - u <= Wc - 1.  Softmax scale `scale`; s_aux (nullable [Hq] float32) enters the denominator only.
+ * commit = 0: the cache is not touched (a verify pass: rejected drafts never enter the ring).
+ * commit != 0: after every read of the cache (a later launch on `stream`), chunk token t >= n - Wc is stored into ring slot
+ *   (write_pos + t) mod Wc: the buffers are then bitwise what n sfa_decode_ring_step calls leave.  The caller advances its
+ *   counters: write_pos += n (mod Wc), window_len = min(window_len + n, Wc).
+ * Kernels: bf16 / f16 at head dims 64 / 80 / 96 / 128 run on MFMA; fp32 and every other head dim whose row is a
+ * multiple of 16 bytes and <= 1 KiB on an exact-f32-accumulate kernel (also with SFA_FLAG_FORCE_GENERIC).  No atomics:
+ * the same inputs give bitwise-identical outputs.
+ *   Every tensor: 16-byte aligned data pointer and B/H/N strides that are multiples of 16 bytes.
+ *   workspace: sfa_decode_multi_workspace_bytes(B, Hq, Hkv, n, sink_len + window_len + n, D, dtype) bytes, 256-byte
+ *   aligned, no initialisation, no state between calls.  Monotonic in Nkv for a fixed n_new: a workspace sized for
+ *   num_sink + Wc + n serves every fill level.  0 = unsupported head dim / dtype.
+ */
+size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
+                                        int dtype);
+
+int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                          const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
+                          unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -410,3 +410,70 @@ int sfa_decode_ring_step_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, cons
 }
 
 }  // extern "C"
+
+extern "C" {
+
+size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
+                                        int dtype) {
+    return decode_multi_workspace(B, Hq, Hkv, n_new, Nkv, D, dtype);
+}
+
+int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                          const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
+                          unsigned flags, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k")) ||
+        (st = check_tensor(sink_v, "sink_v")) || (st = check_tensor(window_k, "window_k")) ||
+        (st = check_tensor(window_v, "window_v")) || (st = check_tensor(k_new, "k_new")) ||
+        (st = check_tensor(v_new, "v_new")))
+        return st;
+    if ((st = same_shape(q, o, "q", "o")) || (st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
+        (st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k_new, v_new, "k_new", "v_new")))
+        return st;
+    const int64_t B = q->shape[0], Hq = q->shape[1], n = q->shape[2], D = q->shape[3], Hkv = k_new->shape[1];
+    const int64_t Wc = window_k->shape[2];
+    SFA_CHECK_ARG(q->dtype == sink_k->dtype && q->dtype == window_k->dtype && q->dtype == k_new->dtype,
+                  "q, the cache buffers and k_new / v_new must share one dtype");
+    SFA_CHECK_ARG(n >= 1, "decode_multi: the chunk needs at least one token");
+    SFA_CHECK_ARG(k_new->shape[0] == B && k_new->shape[2] == n && k_new->shape[3] == D,
+                  "k_new / v_new must be [B, H_kv, n, D] with the n = %lld rows of q", (long long)n);
+    SFA_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "H_q (%lld) must be divisible by H_kv (%lld)", (long long)Hq, (long long)Hkv);
+    SFA_CHECK_ARG(sink_k->shape[0] == B && sink_k->shape[1] == Hkv && sink_k->shape[3] == D &&
+                      window_k->shape[0] == B && window_k->shape[1] == Hkv && window_k->shape[3] == D,
+                  "sink / window buffers must be [B, H_kv, *, D] like k_new");
+    SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
+    SFA_CHECK_ARG(sink_len >= 0 && sink_len <= sink_k->shape[2], "sink_len %lld outside [0, %lld]", (long long)sink_len,
+                  (long long)sink_k->shape[2]);
+    SFA_CHECK_ARG(window_len >= 0 && window_len <= Wc, "window_len %lld outside [0, %lld]", (long long)window_len,
+                  (long long)Wc);
+    SFA_CHECK_ARG(write_pos >= 0 && write_pos < Wc, "write_pos %lld outside [0, %lld)", (long long)write_pos, (long long)Wc);
+    SFA_CHECK_ARG(window_len == Wc || write_pos == window_len,
+                  "write_pos (%lld) must equal window_len (%lld) until the ring is full", (long long)write_pos,
+                  (long long)window_len);
+    SFA_CHECK_ARG(std::isfinite(scale), "scale must be finite");
+    SFA_CHECK_ARG(sink_len + window_len + n < (1ll << 30) && B * Hq * n < (1ll << 30) && Wc < (1ll << 30),
+                  "problem too large");
+    if ((st = decode_multi_check_head_dim(D, q->dtype))) return st;
+    const int es = dtype_size(q->dtype);
+    const sfa_tensor* ts[8] = {q, o, sink_k, sink_v, window_k, window_v, k_new, v_new};
+    for (const sfa_tensor* t : ts) {
+        if (t->shape[0] == 0 || t->shape[1] == 0 || t->shape[2] == 0) continue;
+        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
+                          (t->stride[2] * es) % 16 == 0,
+                      "decode_multi: rows of every tensor must be 16-byte aligned");
+    }
+    if (B == 0 || Hq == 0) return SFA_OK;
+    const size_t need = decode_multi_workspace(B, Hq, Hkv, n, sink_len + window_len + n, D, q->dtype);
+    if (workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
+        set_error("decode_multi workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
+                  workspace);
+        return SFA_ERR_WORKSPACE;
+    }
+    return decode_multi_launch(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o,
+                               s_aux, commit, workspace, scale, flags, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,629 @@
+// Multi-token decode over the sink + ring KV cache (speculative verify, chunked continuation): n new queries attend to
+// the cache as it is BEFORE the chunk plus the chunk itself, with the mask n successive single-token steps would apply.
+//
+// Key positions.  Every key gets a chronological position c relative to the chunk start: sink rows are always visible;
+// ring slot s (0 <= s < window_len) holds the token of position c = ((s - write_pos + window_len) mod Wc) - window_len
+// (-window_len = oldest, -1 = newest); chunk token u has c = u.  Query t sees c in [t - Wc + 1, t].  Softmax is order-free,
+// so the ring is walked in PHYSICAL slot order (contiguous rows); c is only needed for the mask.
+//
+// MFMA path (bf16 / f16, head dims 64 / 80 / 96 / 128): the G = H_q / H_kv query heads and the n chunk queries of one
+// KV head are R = G * n rows, ordered rho = t * G + g, cut into 32-row blocks (a block covers ceil(32 / G) consecutive
+// queries, so its mask band is narrow).  A workgroup = (batch, KV head, key split, row block), 4 waves; the split's
+// 32-key tiles are dealt round-robin to the waves, each wave streams its tiles through its own LDS slot (no barriers in
+// the loop) with the next tile's global loads in flight during the current tile's math:
+//   * X^T = K Q^T with mfma_f32_32x32x16 (keys on the accumulator rows, the block's query rows on the lanes): the
+//     per-row max / sum are per-lane values plus one half-wave swap;
+//   * O^T += V^T X^T takes the (exponentiated) accumulator as the B operand without lane movement, V^T comes from LDS
+//     by ds_read_b64_tr_b16 - the layouts of the forward kernel (sfa_fwd_mfma.hip);
+//   * every tile is classified scalar-wise against the block's [t_min, t_max]: full (no mask work), edge (per-element
+//     mask) or dead (skipped, never loaded).
+// At the end of the split the 4 waves merge (m, l, O) through LDS in a fixed order and write one partial per row.
+// The f32-accumulate path (fp32, other head dims up to 1 KiB per row) writes the same partials, one wave per row.
+// The reduce kernel folds the partials and the s_aux virtual split (m = s_aux, l = 1, o = 0) in split order and writes
+// o in q's dtype; with `commit` its trailing workgroups then store the chunk into the ring (stream order puts that
+// after every read of the slots it overwrites; the split kernels never write the cache).  No atomics anywhere: the same
+// inputs give bitwise-identical outputs.
+#include "sfa_common.hpp"
+#include "sfa_internal.hpp"
+
+#include <climits>
+
+namespace sfa {
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+
+template <typename T> struct Mma;
+template <> struct Mma<bf16_t> {
+    using frag = bf16x8_t;
+    using elem = __bf16;
+    static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mma<f16_t> {
+    using frag = f16x8_t;
+    using elem = _Float16;
+    static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
+
+constexpr int kTile = 32;        // keys per tile
+constexpr int kWaves = 4;        // waves per workgroup of the MFMA split kernel
+constexpr int kMinTiles = 4;     // a split gives every wave at least one tile
+
+struct MultiArgs {
+    View q, sk, sv, wk, wv, kn, vn, o;
+    const float* s_aux;
+    float *Mp, *Lp, *Op;         // partials [rows][S], [rows][S], [rows][S][D]; rows = B * Hkv * R
+    int B, Hkv, G, n, D, R, nrb;
+    int sink_len, wl, wp, wc;    // cache state before the chunk; wc = ring capacity
+    int T0, T1, T;               // tiles: sink [0, T0), ring [T0, T1), chunk [T1, T)
+    int tps, S;                  // tiles per split, splits
+    float scale_log2;            // softmax scale * log2(e): scores live in the log2 domain up to the output
+    int commit;
+};
+
+// one 32-key tile: rows [start, start + count) of one segment of the (b, KV head) slice
+struct TileInfo {
+    const char* k;
+    const char* v;
+    int64_t ksn, vsn;            // row strides in BYTES
+    int seg;                     // 0 sink, 1 ring, 2 chunk
+    int start, count;
+    int cmin, cmax;              // chronological range of its keys (sink: unused)
+};
+
+__device__ __forceinline__ int ring_chron(const MultiArgs& a, int s) {
+    int x = s - a.wp + a.wl;
+    if (x >= a.wc) x -= a.wc;
+    if (x < 0) x += a.wc;
+    return x - a.wl;
+}
+
+__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, int i, int b, int hk, int es) {
+    TileInfo ti;
+    const View *kv, *vv;
+    int len;
+    if (i < a.T0) {
+        ti.seg = 0, ti.start = kTile * i, len = a.sink_len, kv = &a.sk, vv = &a.sv;
+    } else if (i < a.T1) {
+        ti.seg = 1, ti.start = kTile * (i - a.T0), len = a.wl, kv = &a.wk, vv = &a.wv;
+    } else {
+        ti.seg = 2, ti.start = kTile * (i - a.T1), len = a.n, kv = &a.kn, vv = &a.vn;
+    }
+    ti.count = len - ti.start < kTile ? len - ti.start : kTile;
+    ti.ksn = kv->sn * es;
+    ti.vsn = vv->sn * es;
+    ti.k = kv->ptr + ((int64_t)b * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
+    ti.v = vv->ptr + ((int64_t)b * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)ti.start * ti.vsn;
+    if (ti.seg == 2) {
+        ti.cmin = ti.start, ti.cmax = ti.start + ti.count - 1;
+    } else if (ti.seg == 1) {
+        const int s1 = ti.start + ti.count - 1;
+        if (a.wl == a.wc && ti.start < a.wp && a.wp <= s1) ti.cmin = -a.wc, ti.cmax = -1;   // the wrap is inside
+        else ti.cmin = ring_chron(a, ti.start), ti.cmax = ring_chron(a, s1);
+    } else {
+        ti.cmin = ti.cmax = 0;
+    }
+    return ti;
+}
+
+// 0 dead (no row of [tmin, tmax] sees a key), 1 full (every row sees every key), 2 edge
+__device__ __forceinline__ int tile_class(const MultiArgs& a, const TileInfo& ti, int tmin, int tmax) {
+    if (ti.seg == 0) return ti.count == kTile ? 1 : 2;
+    if (ti.cmax < tmin - a.wc + 1 || ti.cmin > tmax) return 0;
+    return (ti.count == kTile && ti.cmin >= tmax - a.wc + 1 && ti.cmax <= tmin) ? 1 : 2;
+}
+
+__device__ __forceinline__ bool key_visible(const MultiArgs& a, const TileInfo& ti, int kk, int t) {
+    if (kk >= ti.count) return false;
+    if (ti.seg == 0) return true;
+    const int c = ti.seg == 2 ? ti.start + kk : ring_chron(a, ti.start + kk);
+    return c <= t && c >= t - a.wc + 1;
+}
+
+__device__ __forceinline__ float half_swap_max(float x) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float half_swap_sum(float x) {
+    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// XCD-aware work id (speed only): consecutive block ids land on different XCDs; give each XCD a contiguous range of
+// work ids, so that the row blocks of one (batch, KV head, split) - which read the same K/V tiles - share an L2
+__device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a) {
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
+    constexpr int DVB = (D + 31) / 32;   // 32-wide output column blocks
+    constexpr int CPR = D / 8;           // 16-byte chunks per row
+    constexpr int ROWB = D <= 64 ? 128 : 256;
+    constexpr int TILE_BYTES = kTile * ROWB;
+    constexpr int NLD = kTile * CPR / 64;   // chunks per lane and tile (CPR is even for every served head dim)
+    constexpr int DP = D + 1;               // merge rows: padded against bank conflicts
+    static_assert(kTile * CPR % 64 == 0, "tile chunks must split evenly over a wave");
+    static_assert(2 * kWaves * 32 * 4 + 32 * DP * 4 <= kWaves * 2 * TILE_BYTES, "merge area must fit the tile area");
+    __shared__ __attribute__((aligned(16))) char smem[kWaves * 2 * TILE_BYTES];
+
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int rb = wid % a.nrb;
+    int rest = wid / a.nrb;
+    const int split = rest % a.S;
+    rest /= a.S;
+    const int hk = rest % a.Hkv;
+    const int b = rest / a.Hkv;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int rho = 32 * rb + r;
+    const bool row_live = rho < a.R;
+    const int tq = row_live ? rho / a.G : 0;            // the lane's query index (dead rows: any, never stored)
+    const int tmin = (32 * rb) / a.G;
+    const int tmax = ((32 * rb + 31 < a.R - 1) ? 32 * rb + 31 : a.R - 1) / a.G;
+
+    // ---- Q fragments: B operand of X^T = K Q^T; lane (r, h) holds Q[row r][16 ks + 8 h .. +8)
+    frag qf[DK];
+    {
+        const int head = hk * a.G + (row_live ? rho % a.G : 0);
+        const char* qp = a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)tq * a.q.sn) * 2;
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            u32x4 raw = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
+            if (!row_live) raw = u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(frag, raw);
+        }
+    }
+
+    char* kl = smem + wave * 2 * TILE_BYTES;
+    char* vl = kl + TILE_BYTES;
+    u32x4 kst[NLD], vst[NLD];
+    auto issue_loads = [&](const TileInfo& ti) {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int c = lane + 64 * j;
+            const int key = c / CPR, ch = c % CPR;
+            const int row = key < ti.count ? key : ti.count - 1;   // rows past the segment: a valid row, masked later
+            kst[j] = *reinterpret_cast<const u32x4*>(ti.k + row * ti.ksn + ch * 16);
+            vst[j] = *reinterpret_cast<const u32x4*>(ti.v + row * ti.vsn + ch * 16);
+        }
+    };
+    auto write_lds = [&]() {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int c = lane + 64 * j;
+            const int key = c / CPR, ch = c % CPR;
+            const int ksw = ROWB == 256 ? (key & 15) : ((key >> 1) & 7);
+            const int vsw = ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2);
+            *reinterpret_cast<u32x4*>(kl + key * ROWB + ((ch ^ ksw) << 4)) = kst[j];
+            *reinterpret_cast<u32x4*>(vl + key * ROWB + ((ch ^ vsw) << 4)) = vst[j];
+        }
+    };
+
+    // per-lane LDS read addressing (kh = 0 of the forward kernel's 64-key tile)
+    const int ksw_l = ROWB == 256 ? (r & 15) : ((r >> 1) & 7);
+    const int k_rowoff = r * ROWB;
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    const int vsw_l = ROWB == 256 ? (q4 << 2) : (((q4 >> 1) & 1) << 2);
+    const int v_rowoff = (4 * h + q4) * ROWB + (p4 & 1) * 8;
+    const int v_chunk_lo = 2 * g1 + (p4 >> 1);
+
+    float m = -INFINITY, l = 0.f;   // log2 domain; l: this half-wave's partial sum
+    f32x16 o[DVB];
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+    const int es = 2;
+
+    const int tbeg = split * a.tps;
+    const int tend = tbeg + a.tps < a.T ? tbeg + a.tps : a.T;
+    auto next_live = [&](int i, TileInfo& ti, int& cls) {
+        for (; i < tend; i += kWaves) {
+            ti = tile_info(a, i, b, hk, es);
+            cls = tile_class(a, ti, tmin, tmax);
+            if (cls != 0) break;
+        }
+        return i;
+    };
+    TileInfo cur, nxt;
+    int ccls = 0, ncls = 0;
+    int ic = next_live(tbeg + wave, cur, ccls);
+    if (ic < tend) {
+        issue_loads(cur);
+        write_lds();
+    }
+    while (ic < tend) {
+        const int in = next_live(ic + kWaves, nxt, ncls);
+        if (in < tend) issue_loads(nxt);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this tile's LDS writes landed (the wave reads other lanes' rows)
+
+        f32x16 s;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = 0.f;
+        {
+            frag kf[DK];
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) kf[ks] = *reinterpret_cast<const frag*>(kl + k_rowoff + (((2 * ks + h) ^ ksw_l) << 4));
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) s = M::run(kf[ks], qf[ks], s);
+        }
+        if (ccls == 2) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                s[i] = key_visible(a, cur, kk, tq) ? s[i] : -INFINITY;
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[i]);
+        mx = half_swap_max(mx);
+        const float m_new = fmaxf(m, mx * c2);
+        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+        float rs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], c2, -m_safe));
+            rs += s[i];
+        }
+        l = fmaf(l, alpha, rs);
+        m = m_new;
+#pragma unroll
+        for (int db = 0; db < DVB; ++db)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
+        // O^T += V^T X^T: the exponentiated accumulator is the B operand (k index = key, permuted as in the forward)
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            frag pf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pf[j] = (typename M::elem)s[8 * st + j];
+            const char* vrow = vl + 16 * st * ROWB + v_rowoff;
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                const int ch = (4 * db + v_chunk_lo) ^ vsw_l;
+                const char* p1 = vrow + (ch << 4);
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1 + 8 * ROWB));
+                s16x8 vv;
+                vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
+                vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
+                o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+            }
+        }
+        if (in < tend) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of this tile returned before the overwrite
+            write_lds();
+        }
+        ic = in;
+        cur = nxt;
+        ccls = ncls;
+    }
+
+    // ---- merge the 4 waves' (m, l, O) in wave order through LDS (the tile area is free after the barrier)
+    const float lw = half_swap_sum(l);
+    __syncthreads();
+    float* sm = reinterpret_cast<float*>(smem);      // [wave][32]
+    float* sl = sm + kWaves * 32;                    // [wave][32]
+    float* so = sl + kWaves * 32;                    // [32][DP]
+    if (h == 0) {
+        sm[wave * 32 + r] = m;
+        sl[wave * 32 + r] = lw;
+    }
+    __syncthreads();
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) mstar = fmaxf(mstar, sm[w * 32 + r]);
+    const float wgt = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mstar);
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int db = 0; db < DVB; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int col = 32 * db + 8 * (i >> 2) + 4 * h + (i & 3);
+                    if (col < D) {
+                        float* p = so + r * DP + col;
+                        *p = (w == 0 ? 0.f : *p) + o[db][i] * wgt;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    const int64_t row0 = ((int64_t)b * a.Hkv + hk) * a.R + 32 * rb;   // partial row of the block's first row
+    const int nrows = a.R - 32 * rb < 32 ? a.R - 32 * rb : 32;
+    if (tid < nrows) {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) ms = fmaxf(ms, sm[w * 32 + tid]);
+        float lt = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const float mw = sm[w * 32 + tid];
+            lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
+        }
+        a.Mp[(row0 + tid) * a.S + split] = ms;
+        a.Lp[(row0 + tid) * a.S + split] = lt;
+    }
+    for (int e = tid; e < nrows * D; e += kWaves * 64) {
+        const int rr = e / D, d = e - rr * D;
+        a.Op[((row0 + rr) * a.S + split) * D + d] = so[rr * DP + d];
+    }
+}
+
+// f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
+template <typename T>
+__global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
+    constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
+    const int lane = threadIdx.x & 63;
+    const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int split = blockIdx.y;
+    const int64_t nrow = (int64_t)a.B * a.Hkv * a.R;
+    if (rowid >= nrow) return;
+    const int rho = (int)(rowid % a.R);
+    const int hk = (int)((rowid / a.R) % a.Hkv);
+    const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
+    const int t = rho / a.G, head = hk * a.G + rho % a.G;
+    const int D = a.D;
+    const int es = (int)sizeof(T);
+    const T* qp = reinterpret_cast<const T*>(a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)t * a.q.sn) * es);
+    float qf[MAXJ], acc[MAXJ];
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+        const int d = lane + 64 * j;
+        qf[j] = d < D ? to_f32(qp[d]) * a.scale_log2 : 0.f;
+        acc[j] = 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    const int tbeg = split * a.tps;
+    const int tend = tbeg + a.tps < a.T ? tbeg + a.tps : a.T;
+    for (int i = tbeg; i < tend; ++i) {
+        const TileInfo ti = tile_info(a, i, b, hk, es);
+        if (tile_class(a, ti, t, t) == 0) continue;
+        for (int kk = 0; kk < ti.count; ++kk) {
+            if (!key_visible(a, ti, kk, t)) continue;
+            const T* kp = reinterpret_cast<const T*>(ti.k + kk * ti.ksn);
+            const T* vp = reinterpret_cast<const T*>(ti.v + kk * ti.vsn);
+            float x = 0.f;
+#pragma unroll
+            for (int j = 0; j < MAXJ; ++j) {
+                const int d = lane + 64 * j;
+                if (d < D) x = fmaf(qf[j], to_f32(kp[d]), x);
+            }
+            x = wave_sum(x);   // a butterfly: every lane ends with the same bits
+            const float m_new = fmaxf(m, x);
+            const float alpha = exp2f(m - m_new);   // m = -inf at the first key: 0
+            const float p = exp2f(x - m_new);
+            l = l * alpha + p;
+#pragma unroll
+            for (int j = 0; j < MAXJ; ++j) {
+                const int d = lane + 64 * j;
+                if (d < D) acc[j] = fmaf(p, to_f32(vp[d]), acc[j] * alpha);
+            }
+            m = m_new;
+        }
+    }
+    if (lane == 0) {
+        a.Mp[rowid * a.S + split] = m;
+        a.Lp[rowid * a.S + split] = l;
+    }
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+        const int d = lane + 64 * j;
+        if (d < D) a.Op[(rowid * a.S + split) * D + d] = acc[j];
+    }
+}
+
+// blocks [0, nred): one wave per partial row folds the S partials and s_aux, writes o.  Blocks [nred, ...) with commit:
+// store chunk tokens t >= n - Wc into ring slot (write_pos + t) mod Wc, one 16-byte piece of K and of V per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred) {
+    const int es = (int)sizeof(T);
+    if ((int)blockIdx.x >= nred) {
+        const int cpr = a.D * es / 16;
+        const int ncm = a.n < a.wc ? a.n : a.wc;
+        const int64_t item = (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x;
+        if (item >= (int64_t)a.B * a.Hkv * ncm * cpr) return;
+        const int ch = (int)(item % cpr);
+        int64_t rest = item / cpr;
+        const int j = (int)(rest % ncm);
+        rest /= ncm;
+        const int hk = (int)(rest % a.Hkv);
+        const int b = (int)(rest / a.Hkv);
+        const int t = a.n - ncm + j;
+        const int slot = (int)(((int64_t)a.wp + t) % a.wc);
+        const int64_t so = (int64_t)ch * 16;
+        const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)t * a.kn.sn) * es + so;
+        const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)t * a.vn.sn) * es + so;
+        char* kd = a.wk.ptr + ((int64_t)b * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
+        char* vd = a.wv.ptr + ((int64_t)b * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+        *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+        *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (rowid >= (int64_t)a.B * a.Hkv * a.R) return;
+    const int rho = (int)(rowid % a.R);
+    const int hk = (int)((rowid / a.R) % a.Hkv);
+    const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
+    const int t = rho / a.G, head = hk * a.G + rho % a.G;
+    const int S = a.S, D = a.D;
+    const float* Mr = a.Mp + rowid * S;
+    const float* Lr = a.Lp + rowid * S;
+    const float* Or = a.Op + rowid * S * D;
+    const float sa = a.s_aux ? a.s_aux[head] * kLog2e : -INFINITY;
+    // split statistics spread over the lanes (latency-bound: one round of loads, not S dependent ones), folded by the
+    // fixed butterflies of wave_max / wave_sum
+    float mloc = -INFINITY;
+    for (int s = lane; s < S; s += 64) mloc = fmaxf(mloc, Mr[s]);
+    const float mstar = fmaxf(wave_max(mloc), sa);   // finite: every row sees at least its own token
+    float lloc = 0.f;
+    for (int s = lane; s < S; s += 64) {
+        const float ms = Mr[s];
+        if (ms != -INFINITY) lloc += Lr[s] * __builtin_amdgcn_exp2f(ms - mstar);
+    }
+    const float L = wave_sum(lloc) + (sa == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sa - mstar));
+    const float inv = 1.f / L;
+    T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)t * a.o.sn) * es);
+    for (int d = lane; d < D; d += 64) {
+        float acc = 0.f;
+#pragma unroll 8
+        for (int s = 0; s < S; ++s) {
+            const float ms = Mr[s];
+            if (ms != -INFINITY) acc = fmaf(Or[(int64_t)s * D + d], __builtin_amdgcn_exp2f(ms - mstar), acc);
+        }
+        orow[d] = from_f32<T>(acc * inv);
+    }
+}
+
+constexpr int64_t kTargetWgs = 2048;
+
+int64_t want_splits(int64_t B, int64_t Hkv, int64_t nrb) {
+    const int64_t base = B * Hkv * nrb > 0 ? B * Hkv * nrb : 1;
+    const int64_t w = cdiv64(kTargetWgs, base);
+    return w < 1 ? 1 : w;
+}
+
+// largest split count any cache state with at most Nkv keys (sink + ring + chunk) plans: the tiles of three segments
+// number at most ceil(Nkv / 32) + 2
+int64_t max_splits(int64_t B, int64_t Hkv, int64_t nrb, int64_t Nkv) {
+    int64_t s = cdiv64(cdiv64(Nkv, kTile) + 2, kMinTiles);
+    const int64_t w = want_splits(B, Hkv, nrb);
+    if (s > w) s = w;
+    return s < 1 ? 1 : s;
+}
+
+bool mfma_head_dim(int D) { return D == 64 || D == 80 || D == 96 || D == 128; }
+
+template <typename T, int D>
+int launch_mfma(const MultiArgs& a, hipStream_t stream) {
+    const int64_t nblk = (int64_t)a.B * a.Hkv * a.S * a.nrb;
+    multi_split_mfma_kernel<T, D><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
+    return launch_status("decode_multi_mfma");
+}
+
+template <typename T>
+int launch_mfma_d(const MultiArgs& a, hipStream_t stream) {
+    switch (a.D) {
+        case 64: return launch_mfma<T, 64>(a, stream);
+        case 80: return launch_mfma<T, 80>(a, stream);
+        case 96: return launch_mfma<T, 96>(a, stream);
+        case 128: return launch_mfma<T, 128>(a, stream);
+    }
+    set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
+    return SFA_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
+    int st = SFA_OK;
+    const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, stream) : SFA_OK;
+    if (!mfma) {
+        multi_split_f32_kernel<T><<<dim3((unsigned)cdiv64(rows, 4), (unsigned)a.S), 256, 0, stream>>>(a);
+        st = launch_status("decode_multi_f32");
+    }
+    if (st) return st;
+    const int nred = (int)cdiv64(rows, 4);
+    int64_t ncommit = 0;
+    if (a.commit) {
+        const int64_t ncm = a.n < a.wc ? a.n : a.wc;
+        ncommit = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)sizeof(T) / 16), 256);
+    }
+    multi_reduce_kernel<T><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
+    return launch_status("decode_multi_reduce");
+}
+
+}  // namespace
+
+int decode_multi_check_head_dim(int64_t D, int dtype) {
+    const int64_t row_bytes = D * dtype_size(dtype);
+    if (D <= 0 || row_bytes % 16 != 0 || row_bytes > 1024) {
+        set_error("decode_multi: head dim %lld (%lld bytes/row) must be a multiple of 16 bytes and <= 1024 bytes",
+                  (long long)D, (long long)row_bytes);
+        return SFA_ERR_UNSUPPORTED;
+    }
+    return SFA_OK;
+}
+
+size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D, int dtype) {
+    if (decode_multi_check_head_dim(D, dtype) != SFA_OK) return 0;
+    if (B <= 0 || Hkv <= 0 || Hq % Hkv != 0 || n_new <= 0 || Nkv < n_new) return 0;
+    const int64_t R = Hq / Hkv * n_new;
+    const int64_t S = max_splits(B, Hkv, cdiv64(R, 32), Nkv);
+    const size_t rows = (size_t)(B * Hkv * R);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    return 2 * al(rows * S * sizeof(float)) + al(rows * S * (size_t)D * sizeof(float));
+}
+
+int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                        const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
+                        const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
+                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream) {
+    MultiArgs a;
+    a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
+    a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
+    a.s_aux = s_aux;
+    a.B = (int)q->shape[0];
+    a.Hkv = (int)k_new->shape[1];
+    a.G = (int)(q->shape[1] / k_new->shape[1]);
+    a.n = (int)q->shape[2];
+    a.D = (int)q->shape[3];
+    a.R = a.G * a.n;
+    a.nrb = (int)cdiv64(a.R, 32);
+    a.sink_len = (int)sink_len, a.wl = (int)window_len, a.wp = (int)write_pos, a.wc = (int)window_k->shape[2];
+    a.T0 = (int)cdiv64(sink_len, kTile);
+    a.T1 = a.T0 + (int)cdiv64(window_len, kTile);
+    a.T = a.T1 + (int)cdiv64(a.n, kTile);
+    const int64_t Nkv = sink_len + window_len + a.n;
+    int64_t S = max_splits(a.B, a.Hkv, a.nrb, Nkv);
+    const int64_t s_tiles = cdiv64(a.T, kMinTiles);
+    if (S > s_tiles) S = s_tiles;
+    a.tps = (int)cdiv64(a.T, S);
+    a.S = (int)cdiv64(a.T, a.tps);
+    a.scale_log2 = scale * kLog2e;
+    a.commit = commit ? 1 : 0;
+    const size_t rows = (size_t)a.B * a.Hkv * a.R;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    a.Mp = reinterpret_cast<float*>(workspace);
+    a.Lp = reinterpret_cast<float*>((char*)workspace + al(rows * a.S * sizeof(float)));
+    a.Op = reinterpret_cast<float*>((char*)workspace + 2 * al(rows * a.S * sizeof(float)));
+    if ((int64_t)a.B * a.Hkv * a.S * a.nrb >= (1ll << 31) || cdiv64((int64_t)rows, 4) >= (1ll << 31) - 65536) {
+        set_error("decode_multi: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    const int dt = q->dtype;
+    const bool mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(flags & SFA_FLAG_FORCE_GENERIC);
+    const char* dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
+    int st;
+    if (dt == SFA_DTYPE_F32) st = launch_rest<float>(a, false, stream);
+    else if (dt == SFA_DTYPE_F16) st = launch_rest<f16_t>(a, mfma, stream);
+    else st = launch_rest<bf16_t>(a, mfma, stream);
+    if (st) return st;
+    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_s%d%s", dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
+    else set_path("decode_multi_f32_%s_d%d_s%d%s", dname, a.D, a.S, commit ? "_commit" : "");
+    return SFA_OK;
+}
+
+}  // namespace sfa

@@ -52,4 +52,12 @@ int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                   const sfa_tensor* v_new = nullptr, int new_slot = -1, int* dyn_state = nullptr,
                   bool one_pass = false);
 
+// sfa_decode_multi.hip: several new tokens over the sink + ring cache (sfa_decode_ring_multi); arguments already checked
+int decode_multi_check_head_dim(int64_t D, int dtype);
+size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D, int dtype);
+int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                        const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
+                        const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
+                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream);
+
 }  // namespace sfa

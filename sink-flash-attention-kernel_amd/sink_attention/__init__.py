@@ -5,7 +5,7 @@ and ``unpatch_verl`` (plus the sink + ring KV cache with a copy-free decode, the
 sequence-parallel helpers and packed-sequence attention); kernels are hand-written HIP
 behind libsfa.so (no Triton)."""
 from .sink_flash_attention import sink_flash_attention, SinkFlashAttentionFunc
-from .decode_kernel import sink_decode_attention, sink_decode_attention_ring
+from .decode_kernel import sink_decode_attention, sink_decode_attention_ring, sink_decode_attention_ring_multi
 from .cache import SinkCacheLayer, SinkAttentionCache
 from .verl_patch import patch_verl_with_sink_attention, unpatch_verl
 from .generate_patch import patch_for_generation, unpatch_generation
@@ -22,6 +22,7 @@ __all__ = [
     "unpatch_verl",
     "SinkFlashAttentionFunc",
     "sink_decode_attention_ring",
+    "sink_decode_attention_ring_multi",
     "SinkCacheLayer",
     "SinkAttentionCache",
     "patch_for_generation",

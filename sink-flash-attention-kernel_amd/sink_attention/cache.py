@@ -172,6 +172,79 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.check(rc, "sfa_decode_ring_step")
         return out
 
+    # ------------------------------------------- several new tokens (speculative verify, chunked continuation)
+    def extend_attention(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                         s_aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Attention of n new queries ``q [B, H_q, n, D]`` over the cache plus the chunk's own ``k_new`` / ``v_new``
+        ``[B, H_kv, n, D]``, exactly as n successive ``decode_step`` calls would see it, WITHOUT modifying the cache
+        (``sfa_decode_ring_multi``, commit off).  Speculative verify: ``out = extend_attention(q, k, v)``, then
+        ``append(k[:, :, :a], v[:, :, :a])`` for the ``a`` accepted drafts - rejected ones never enter the ring."""
+        return self._ring_multi(q, k_new, v_new, s_aux, commit=False)
+
+    def extend_step(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                    s_aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``extend_attention`` followed by the commit of all n tokens: afterwards the cache is bitwise the state that
+        ``append(k_new, v_new)`` leaves (the kernels store the chunk after every read of the slots it overwrites)."""
+        n = q.shape[2]
+        out = self._ring_multi(q, k_new, v_new, s_aux, commit=True)
+        self.seen_tokens += n
+        self.write_pos = (self.write_pos + n) % self.window_size
+        self.window_len = min(self.window_len + n, self.window_size)
+        return out
+
+    def _ring_multi(self, q, k_new, v_new, s_aux, commit):
+        """sfa_decode_ring_multi with the per-layer constants (buffer descriptors, workspace for the full cache) built once
+        per chunk shape, as _ring_step does."""
+        import math
+        from . import _native as N
+        if not (self.is_initialized and self.prefilled):
+            raise ValueError("extend_attention / extend_step need a prefilled cache: the first chunk is a prefill "
+                             "(sink_flash_attention)")
+        N.require_gpu(q, k_new, v_new, s_aux)
+        if self.window_size < 1:
+            raise ValueError("extend_attention / extend_step need a ring of at least one slot (window_size >= 1)")
+        if not self.window_k.is_cuda:
+            raise RuntimeError("sink_attention runs only on MI355X (HIP) tensors; got a CPU cache and there is no CPU "
+                               "fallback")
+        B, H_q, n, D = q.shape
+        H_kv = self.sink_k.shape[1]
+        if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = {(B, H_kv, n, D)}, got {tuple(k_new.shape)}")
+        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
+            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+        st = getattr(self, "_multi_state", None)
+        key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
+        if st is None or st["key"] != key:
+            lib = N.lib()
+            ws_bytes = lib.sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
+                                                            N.SFA_DTYPE[q.dtype])
+            if ws_bytes == 0:
+                raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB")
+            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
+                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
+                      ws=torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
+            self._multi_state = st
+
+        def rows16(t):
+            t = N.unit_inner(t.detach())
+            es = t.element_size()
+            if t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3)):
+                t = t.contiguous()
+            return t
+
+        q, k_new, v_new = rows16(q), rows16(k_new), rows16(v_new)
+        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
+        sk, sv, wk, wv = st["descs"]
+        with torch.cuda.device(q.device):
+            rc = st["lib"].sfa_decode_ring_multi(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
+                                                 self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                                 s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                 1 if commit else 0, st["ws"].data_ptr(), st["ws"].numel(),
+                                                 st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_multi")
+        return out
+
     one_pass = False     # opt-in: SFA_FLAG_DECODE_ONE_PASS (last-arriver fold inside the split kernel, one launch)
 
     def _decode_flags(self, N) -> int:
@@ -303,6 +376,17 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     def decode_step(self, q, key_states, value_states, layer_idx: int, s_aux=None):
         """Fused cache update + attention of one layer for one new token (``SinkCacheLayer.decode_step``)."""
         out = self._layer(layer_idx).decode_step(q, key_states, value_states, s_aux=s_aux)
+        if layer_idx == 0:
+            self._seen_tokens = self.layers[0].seen_tokens
+        return out
+
+    def extend_attention(self, q, key_states, value_states, layer_idx: int, s_aux=None):
+        """n new tokens of one layer attended over its cache WITHOUT committing them (``SinkCacheLayer.extend_attention``)."""
+        return self._layer(layer_idx).extend_attention(q, key_states, value_states, s_aux=s_aux)
+
+    def extend_step(self, q, key_states, value_states, layer_idx: int, s_aux=None):
+        """n new tokens of one layer: attention + commit (``SinkCacheLayer.extend_step``)."""
+        out = self._layer(layer_idx).extend_step(q, key_states, value_states, s_aux=s_aux)
         if layer_idx == 0:
             self._seen_tokens = self.layers[0].seen_tokens
         return out

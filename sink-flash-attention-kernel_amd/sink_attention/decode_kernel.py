@@ -130,3 +130,84 @@ def sink_decode_attention_ring(q: torch.Tensor, sink_k: torch.Tensor, sink_v: to
                                      1.0 / math.sqrt(D), 0, N.stream_ptr(q.device))
     N.check(st, "sfa_decode_ring_step" if fused else "sfa_decode_ring")
     return out
+
+
+def sink_decode_attention_ring_multi(q: torch.Tensor, sink_k: torch.Tensor, sink_v: torch.Tensor, sink_len: int,
+                                     window_k: torch.Tensor, window_v: torch.Tensor, window_len: int, write_pos: int,
+                                     k_new: torch.Tensor, v_new: torch.Tensor, s_aux: torch.Tensor = None,
+                                     commit: bool = False) -> torch.Tensor:
+    """n >= 1 new tokens over a sink buffer + window ring in one pass (``sfa_decode_ring_multi``): speculative verify,
+    chunked continuation.  Computes what n successive single-token cache steps compute.
+        q [B,H_q,n,D]; k_new / v_new [B,H_kv,n,D]: the chunk's own keys / values;
+        sink_k/v [B,H_kv,num_sink,D] (first ``sink_len`` rows valid); window_k/v [B,H_kv,Wc,D] with ``window_len`` valid
+        slots and ``write_pos`` the slot the next token goes to - the cache state BEFORE the chunk.
+    Query t sees every sink row, ring slot s iff ``window_len - r + t <= Wc - 1`` with r = (s - write_pos + window_len)
+    mod Wc its chronological index, and chunk token u iff ``u <= t`` and ``t - u <= Wc - 1``.
+    ``commit=False`` leaves the cache untouched; ``commit=True`` then stores chunk token t >= n - Wc into ring slot
+    (write_pos + t) mod Wc (``window_k`` / ``window_v`` modified IN PLACE); the caller advances its counters.
+    q / k_new / v_new may be strided views (e.g. [B,n,H,D] transposed): no copy when the rows are 16-byte aligned.
+    """
+    N.require_gpu(q, sink_k, sink_v, window_k, window_v, k_new, v_new, s_aux)
+    B, H_q, n, D = q.shape
+    H_kv = sink_k.shape[1]
+    Wc = window_k.shape[2]
+    if n < 1:
+        raise ValueError("the chunk needs at least one token")
+    if H_q % H_kv:
+        raise ValueError(f"H_q ({H_q}) must be divisible by H_kv ({H_kv})")
+    if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
+        raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = {(B, H_kv, n, D)}, got {tuple(k_new.shape)}, "
+                         f"{tuple(v_new.shape)}")
+    if sink_v.shape != sink_k.shape or window_v.shape != window_k.shape or window_k.shape[:2] != sink_k.shape[:2] \
+            or window_k.shape[3] != D or sink_k.shape[3] != D or sink_k.shape[0] != B:
+        raise ValueError("sink / window buffers must be [B, H_kv, *, D]")
+    if Wc < 1:
+        raise ValueError("the ring needs a capacity of at least one slot")
+    if not (0 <= sink_len <= sink_k.shape[2] and 0 <= window_len <= Wc and 0 <= write_pos < Wc):
+        raise ValueError(f"cache state out of range: sink_len {sink_len}, window_len {window_len}, write_pos {write_pos}")
+    if window_len < Wc and write_pos != window_len:
+        raise ValueError(f"write_pos ({write_pos}) must equal window_len ({window_len}) until the ring is full")
+    for t in (sink_k, sink_v, window_k, window_v, k_new, v_new):
+        if t.dtype != q.dtype:
+            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+    if q.dtype not in N.SFA_DTYPE:
+        raise TypeError(f"unsupported dtype {q.dtype}")
+    row_bytes = D * q.element_size()
+    if row_bytes % 16 or row_bytes > 1024:
+        raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB")
+
+    def aligned(t):
+        es = t.element_size()
+        return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(3))
+
+    def rows16(t):
+        t = N.unit_inner(t.detach())
+        if t.numel() and not aligned(t):
+            t = t.contiguous()
+        return t
+
+    if commit:
+        for t in (window_k, window_v):   # the reduce kernel writes the ring in place: no silent copies allowed here
+            if not aligned(t):
+                raise ValueError("commit: the ring buffers must have 16-byte aligned rows")
+    else:
+        window_k, window_v = rows16(window_k), rows16(window_v)
+    q, k_new, v_new, sink_k, sink_v = (rows16(t) for t in (q, k_new, v_new, sink_k, sink_v))
+    s_aux_f = None
+    if s_aux is not None:
+        if s_aux.shape != (H_q,):
+            raise ValueError(f"s_aux shape must be [H_q={H_q}], got {tuple(s_aux.shape)}")
+        s_aux_f = s_aux.detach().contiguous().float()
+    out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
+    lib = N.lib()
+    ws_bytes = lib.sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, int(sink_len) + int(window_len) + n, D,
+                                                    N.SFA_DTYPE[q.dtype])
+    ws = torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8)
+    with torch.cuda.device(q.device):
+        st = lib.sfa_decode_ring_multi(N.desc(q), N.desc(sink_k), N.desc(sink_v), int(sink_len), N.desc(window_k),
+                                       N.desc(window_v), int(window_len), int(write_pos), N.desc(k_new), N.desc(v_new),
+                                       N.desc(out), s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                       1 if commit else 0, ws.data_ptr(), ws.numel(), 1.0 / math.sqrt(D), 0,
+                                       N.stream_ptr(q.device))
+    N.check(st, "sfa_decode_ring_multi")
+    return out
