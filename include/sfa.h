@@ -266,6 +266,39 @@ int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const s
                           const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
                           unsigned flags, void* stream);
 
+/*
+ * sfa_decode_ring_multi with the cache state on the DEVICE, so that a speculative step (verify every layer, accept in
+ * device code, commit the accepted prefix) can be captured into a hipGraph and replayed without host integers or a sync.
+ *   state: int32 {sink_len, window_len, write_pos} in device memory, the cache BEFORE the chunk.  It must describe a
+ *   prefilled cache: sink_len <= num_sink, window_len <= Wc, write_pos == window_len until the ring is full (the kernels
+ *   clamp each field into the buffers, so a corrupt state cannot address outside them, but its output is undefined).
+ * Same mask, kernels and output as sfa_decode_ring_multi at that state, bitwise: every workgroup reads the state and
+ * recomputes the tile / split plan with the host formulas; the grid is sized for the full cache (sink_len = num_sink,
+ * window_len = Wc) and the workgroups of splits the state does not plan exit at once.
+ * commit = 0: neither the cache nor the state changes.  commit != 0: chunk token t >= n - Wc is stored into ring slot
+ *   (write_pos + t) mod Wc after every read of the cache, then (a trailing one-thread launch, after every reader of the
+ *   state) write_pos = (write_pos + n) mod Wc, window_len = min(window_len + n, Wc); sink_len is unchanged.
+ *   workspace: sfa_decode_multi_workspace_bytes(B, Hq, Hkv, n, num_sink + Wc + n, D, dtype), 256-byte aligned.
+ * Every host-checkable argument is checked as in sfa_decode_ring_multi (at the full cache) before anything launches.
+ */
+int sfa_decode_ring_multi_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                              int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                              void* stream);
+
+/*
+ * Commit the accepted prefix of a chunk into the ring, driven by a DEVICE count (the acceptance rule runs on the
+ * device; no host sync).  a = clamp(*count, 0, n): chunk tokens t in [max(0, a - Wc), a) are stored into ring slot
+ * (write_pos + t) mod Wc, then write_pos = (write_pos + a) mod Wc, window_len = min(window_len + a, Wc); sink_len is
+ * unchanged (the cache is prefilled).  Afterwards the buffers and the state are what append() of the first a tokens
+ * leaves.  16 bytes per thread; two launches (the copy, then a one-thread advance after every reader of the state).
+ *   window_k/v [B, Hkv, Wc, D]   k_new/v_new [B, Hkv, n, D] (n >= 1) in the ring's dtype, rows multiples of 16 bytes,
+ *   16-byte aligned.   count: device int32 (one value).   state: as for sfa_decode_ring_multi_dyn.
+ */
+int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                        const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

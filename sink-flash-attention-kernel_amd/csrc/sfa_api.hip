@@ -411,19 +411,12 @@ int sfa_decode_ring_step_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, cons
 
 }  // extern "C"
 
-extern "C" {
+namespace {
 
-size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
-                                        int dtype) {
-    return decode_multi_workspace(B, Hq, Hkv, n_new, Nkv, D, dtype);
-}
-
-int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
-                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
-                          const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
-                          unsigned flags, void* stream) {
-    g_err[0] = 0;
+// every host-checkable argument of sfa_decode_ring_multi(_dyn); nothing launches
+int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
+                const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, float scale) {
     int st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k")) ||
         (st = check_tensor(sink_v, "sink_v")) || (st = check_tensor(window_k, "window_k")) ||
@@ -465,15 +458,96 @@ int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const s
                           (t->stride[2] * es) % 16 == 0,
                       "decode_multi: rows of every tensor must be 16-byte aligned");
     }
-    if (B == 0 || Hq == 0) return SFA_OK;
-    const size_t need = decode_multi_workspace(B, Hq, Hkv, n, sink_len + window_len + n, D, q->dtype);
+    return SFA_OK;
+}
+
+int check_multi_workspace(const sfa_tensor* q, const sfa_tensor* k_new, int64_t Nkv, void* workspace,
+                          size_t workspace_bytes) {
+    const size_t need = decode_multi_workspace(q->shape[0], q->shape[1], k_new->shape[1], q->shape[2], Nkv, q->shape[3],
+                                               q->dtype);
     if (workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
         set_error("decode_multi workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
                   workspace);
         return SFA_ERR_WORKSPACE;
     }
+    return SFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
+                                        int dtype) {
+    return decode_multi_workspace(B, Hq, Hkv, n_new, Nkv, D, dtype);
+}
+
+int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                          const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
+                          unsigned flags, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o, scale)))
+        return st;
+    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;
+    if ((st = check_multi_workspace(q, k_new, sink_len + window_len + q->shape[2], workspace, workspace_bytes))) return st;
     return decode_multi_launch(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o,
                                s_aux, commit, workspace, scale, flags, (hipStream_t)stream);
+}
+
+int sfa_decode_ring_multi_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                              int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                              void* stream) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    // every check of the host-state call, at the full cache (the launch geometry and workspace cover every fill level)
+    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
+    if (q->shape[0] == 0 || q->shape[1] == 0) {
+        if (!commit) return SFA_OK;
+        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream);
+    }
+    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
+    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
+                               scale, flags, (hipStream_t)stream, state);
+}
+
+int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                        const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
+        (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
+        return st;
+    if ((st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k_new, v_new, "k_new", "v_new")))
+        return st;
+    SFA_CHECK_ARG(count != nullptr, "count: null device pointer");
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(k_new->dtype == window_k->dtype, "k_new / v_new and the ring must share one dtype");
+    const int64_t n = k_new->shape[2], Wc = window_k->shape[2];
+    SFA_CHECK_ARG(n >= 1, "ring_commit: the chunk needs at least one token");
+    SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
+    SFA_CHECK_ARG(k_new->shape[0] == window_k->shape[0] && k_new->shape[1] == window_k->shape[1] &&
+                      k_new->shape[3] == window_k->shape[3],
+                  "k_new / v_new must be [B, H_kv, n, D] like the ring [B, H_kv, Wc, D]");
+    SFA_CHECK_ARG(n < (1ll << 30) && Wc < (1ll << 30), "problem too large");
+    const int es = dtype_size(k_new->dtype);
+    SFA_CHECK_ARG(k_new->shape[3] > 0 && (k_new->shape[3] * es) % 16 == 0,
+                  "ring_commit: K/V rows must be a multiple of 16 bytes (head dim %lld)", (long long)k_new->shape[3]);
+    const sfa_tensor* ts[4] = {window_k, window_v, k_new, v_new};
+    for (const sfa_tensor* t : ts) {
+        if (t->shape[0] == 0 || t->shape[1] == 0) continue;
+        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
+                          (t->stride[2] * es) % 16 == 0,
+                      "ring_commit: rows of every tensor must be 16-byte aligned");
+    }
+    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream);
 }
 
 }  // extern "C"

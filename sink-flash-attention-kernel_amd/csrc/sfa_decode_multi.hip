@@ -62,14 +62,69 @@ constexpr int kMinTiles = 4;     // a split gives every wave at least one tile
 struct MultiArgs {
     View q, sk, sv, wk, wv, kn, vn, o;
     const float* s_aux;
-    float *Mp, *Lp, *Op;         // partials [rows][S], [rows][S], [rows][S][D]; rows = B * Hkv * R
+    float *Mp, *Lp, *Op;         // partials [rows][Sw], [rows][Sw], [rows][Sw][D]; rows = B * Hkv * R
     int B, Hkv, G, n, D, R, nrb;
     int sink_len, wl, wp, wc;    // cache state before the chunk; wc = ring capacity
     int T0, T1, T;               // tiles: sink [0, T0), ring [T0, T1), chunk [T1, T)
     int tps, S;                  // tiles per split, splits
+    int Sw;                      // launched splits = stride of the partials (S, or the full-cache bound in dyn mode)
     float scale_log2;            // softmax scale * log2(e): scores live in the log2 domain up to the output
     int commit;
+    // dyn mode (sfa_decode_ring_multi_dyn): state = device {sink_len, window_len, write_pos}; every workgroup reads it and
+    // replans (T0, T1, T, tps, S) with multi_plan.  Null: the host plan above holds.
+    const int* state;
+    int ns;                      // sink buffer rows (dyn: clamp of sink_len)
+    int want;                    // want_splits(B, Hkv, nrb): the workgroup-target cap of the split count
 };
+
+inline __host__ __device__ int cdiv_i(int x, int y) { return (x + y - 1) / y; }
+
+struct MultiPlan {
+    int T0, T1, T, tps, S;
+};
+
+// the tile / split plan of one cache state; the host (sfa_decode_ring_multi) and the dyn kernels (from the device state)
+// both call it, so that the same state gives the same tile-to-split assignment bitwise.  Every count < 2^30.
+inline __host__ __device__ MultiPlan multi_plan(int sink_len, int wl, int n, int want) {
+    MultiPlan p;
+    p.T0 = cdiv_i(sink_len, kTile);
+    p.T1 = p.T0 + cdiv_i(wl, kTile);
+    p.T = p.T1 + cdiv_i(n, kTile);
+    // max_splits(Nkv = sink_len + wl + n), then at most one split per kMinTiles tiles
+    int s = cdiv_i(cdiv_i(sink_len + wl + n, kTile) + 2, kMinTiles);
+    if (s > want) s = want;
+    if (s < 1) s = 1;
+    const int s_tiles = cdiv_i(p.T, kMinTiles);
+    if (s > s_tiles) s = s_tiles;
+    p.tps = cdiv_i(p.T, s);
+    p.S = cdiv_i(p.T, p.tps);
+    return p;
+}
+
+// the state-dependent part of the arguments, kept apart from the (read-only, kernarg) MultiArgs
+struct Fill {
+    int sink_len, wl, wp;
+    int T0, T1, T, tps, S;
+};
+
+template <bool Dyn>
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a) {
+    if constexpr (!Dyn) {
+        return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S};
+    } else {
+        // dyn mode: the cache state from the device (clamped into the buffers, so that a corrupt state cannot address
+        // outside them), replanned.  Wave-uniform: scalar loads of 12 bytes.
+        int sl = __builtin_amdgcn_readfirstlane(a.state[0]);
+        int wl = __builtin_amdgcn_readfirstlane(a.state[1]);
+        int wp = __builtin_amdgcn_readfirstlane(a.state[2]);
+        sl = sl < 0 ? 0 : (sl > a.ns ? a.ns : sl);
+        wl = wl < 0 ? 0 : (wl > a.wc ? a.wc : wl);
+        wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
+        const MultiPlan p = multi_plan(sl, wl, a.n, a.want);
+        auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };   // keep the plan in SGPRs
+        return Fill{sl, wl, wp, u(p.T0), u(p.T1), u(p.T), u(p.tps), u(p.S)};
+    }
+}
 
 // one 32-key tile: rows [start, start + count) of one segment of the (b, KV head) slice
 struct TileInfo {
@@ -81,23 +136,23 @@ struct TileInfo {
     int cmin, cmax;              // chronological range of its keys (sink: unused)
 };
 
-__device__ __forceinline__ int ring_chron(const MultiArgs& a, int s) {
-    int x = s - a.wp + a.wl;
+__device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int s) {
+    int x = s - f.wp + f.wl;
     if (x >= a.wc) x -= a.wc;
     if (x < 0) x += a.wc;
-    return x - a.wl;
+    return x - f.wl;
 }
 
-__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, int i, int b, int hk, int es) {
+__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int hk, int es) {
     TileInfo ti;
     const View *kv, *vv;
     int len;
-    if (i < a.T0) {
-        ti.seg = 0, ti.start = kTile * i, len = a.sink_len, kv = &a.sk, vv = &a.sv;
-    } else if (i < a.T1) {
-        ti.seg = 1, ti.start = kTile * (i - a.T0), len = a.wl, kv = &a.wk, vv = &a.wv;
+    if (i < f.T0) {
+        ti.seg = 0, ti.start = kTile * i, len = f.sink_len, kv = &a.sk, vv = &a.sv;
+    } else if (i < f.T1) {
+        ti.seg = 1, ti.start = kTile * (i - f.T0), len = f.wl, kv = &a.wk, vv = &a.wv;
     } else {
-        ti.seg = 2, ti.start = kTile * (i - a.T1), len = a.n, kv = &a.kn, vv = &a.vn;
+        ti.seg = 2, ti.start = kTile * (i - f.T1), len = a.n, kv = &a.kn, vv = &a.vn;
     }
     ti.count = len - ti.start < kTile ? len - ti.start : kTile;
     ti.ksn = kv->sn * es;
@@ -108,8 +163,8 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, int i, int b, 
         ti.cmin = ti.start, ti.cmax = ti.start + ti.count - 1;
     } else if (ti.seg == 1) {
         const int s1 = ti.start + ti.count - 1;
-        if (a.wl == a.wc && ti.start < a.wp && a.wp <= s1) ti.cmin = -a.wc, ti.cmax = -1;   // the wrap is inside
-        else ti.cmin = ring_chron(a, ti.start), ti.cmax = ring_chron(a, s1);
+        if (f.wl == a.wc && ti.start < f.wp && f.wp <= s1) ti.cmin = -a.wc, ti.cmax = -1;   // the wrap is inside
+        else ti.cmin = ring_chron(a, f, ti.start), ti.cmax = ring_chron(a, f, s1);
     } else {
         ti.cmin = ti.cmax = 0;
     }
@@ -123,10 +178,10 @@ __device__ __forceinline__ int tile_class(const MultiArgs& a, const TileInfo& ti
     return (ti.count == kTile && ti.cmin >= tmax - a.wc + 1 && ti.cmax <= tmin) ? 1 : 2;
 }
 
-__device__ __forceinline__ bool key_visible(const MultiArgs& a, const TileInfo& ti, int kk, int t) {
+__device__ __forceinline__ bool key_visible(const MultiArgs& a, const Fill& f, const TileInfo& ti, int kk, int t) {
     if (kk >= ti.count) return false;
     if (ti.seg == 0) return true;
-    const int c = ti.seg == 2 ? ti.start + kk : ring_chron(a, ti.start + kk);
+    const int c = ti.seg == 2 ? ti.start + kk : ring_chron(a, f, ti.start + kk);
     return c <= t && c >= t - a.wc + 1;
 }
 
@@ -146,7 +201,7 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-template <typename T, int D>
+template <typename T, int D, bool Dyn>
 __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -164,10 +219,12 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     const int wid = xcd_work_id(blockIdx.x, gridDim.x);
     const int rb = wid % a.nrb;
     int rest = wid / a.nrb;
-    const int split = rest % a.S;
-    rest /= a.S;
+    const int split = rest % a.Sw;   // decomposition over the LAUNCHED splits
+    rest /= a.Sw;
     const int hk = rest % a.Hkv;
     const int b = rest / a.Hkv;
+    const Fill f = get_fill<Dyn>(a);
+    if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -233,11 +290,11 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     const float c2 = a.scale_log2;
     const int es = 2;
 
-    const int tbeg = split * a.tps;
-    const int tend = tbeg + a.tps < a.T ? tbeg + a.tps : a.T;
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info(a, i, b, hk, es);
+            ti = tile_info(a, f, i, b, hk, es);
             cls = tile_class(a, ti, tmin, tmax);
             if (cls != 0) break;
         }
@@ -269,7 +326,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
-                s[i] = key_visible(a, cur, kk, tq) ? s[i] : -INFINITY;
+                s[i] = key_visible(a, f, cur, kk, tq) ? s[i] : -INFINITY;
             }
         }
         float mx = -INFINITY;
@@ -362,22 +419,24 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
             const float mw = sm[w * 32 + tid];
             lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
         }
-        a.Mp[(row0 + tid) * a.S + split] = ms;
-        a.Lp[(row0 + tid) * a.S + split] = lt;
+        a.Mp[(row0 + tid) * a.Sw + split] = ms;
+        a.Lp[(row0 + tid) * a.Sw + split] = lt;
     }
     for (int e = tid; e < nrows * D; e += kWaves * 64) {
         const int rr = e / D, d = e - rr * D;
-        a.Op[((row0 + rr) * a.S + split) * D + d] = so[rr * DP + d];
+        a.Op[((row0 + rr) * a.Sw + split) * D + d] = so[rr * DP + d];
     }
 }
 
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
-template <typename T>
+template <typename T, bool Dyn>
 __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
     const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int split = blockIdx.y;
+    const Fill f = get_fill<Dyn>(a);
+    if (Dyn && split >= f.S) return;
     const int64_t nrow = (int64_t)a.B * a.Hkv * a.R;
     if (rowid >= nrow) return;
     const int rho = (int)(rowid % a.R);
@@ -395,13 +454,13 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
         acc[j] = 0.f;
     }
     float m = -INFINITY, l = 0.f;
-    const int tbeg = split * a.tps;
-    const int tend = tbeg + a.tps < a.T ? tbeg + a.tps : a.T;
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
-        const TileInfo ti = tile_info(a, i, b, hk, es);
+        const TileInfo ti = tile_info(a, f, i, b, hk, es);
         if (tile_class(a, ti, t, t) == 0) continue;
         for (int kk = 0; kk < ti.count; ++kk) {
-            if (!key_visible(a, ti, kk, t)) continue;
+            if (!key_visible(a, f, ti, kk, t)) continue;
             const T* kp = reinterpret_cast<const T*>(ti.k + kk * ti.ksn);
             const T* vp = reinterpret_cast<const T*>(ti.v + kk * ti.vsn);
             float x = 0.f;
@@ -424,41 +483,55 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
         }
     }
     if (lane == 0) {
-        a.Mp[rowid * a.S + split] = m;
-        a.Lp[rowid * a.S + split] = l;
+        a.Mp[rowid * a.Sw + split] = m;
+        a.Lp[rowid * a.Sw + split] = l;
     }
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
         const int d = lane + 64 * j;
-        if (d < D) a.Op[(rowid * a.S + split) * D + d] = acc[j];
+        if (d < D) a.Op[(rowid * a.Sw + split) * D + d] = acc[j];
     }
+}
+
+// one 16-byte piece of the commit: item = ((b * Hkv + hk) * nslot + j) * cpr + ch over the nslot = min(n, Wc) chunk
+// tokens a commit can store; piece j is chunk token first + j (stored only if < last) -> ring slot (write_pos + t) mod Wc
+__device__ __forceinline__ void commit_piece(const MultiArgs& a, int wp, int64_t item, int es, int first, int last) {
+    const int cpr = a.D * es / 16;
+    const int nslot = a.n < a.wc ? a.n : a.wc;
+    if (item >= (int64_t)a.B * a.Hkv * nslot * cpr) return;
+    const int ch = (int)(item % cpr);
+    int64_t rest = item / cpr;
+    const int j = (int)(rest % nslot);
+    rest /= nslot;
+    const int hk = (int)(rest % a.Hkv);
+    const int b = (int)(rest / a.Hkv);
+    const int t = first + j;
+    if (t >= last) return;
+    const int slot = (int)(((int64_t)wp + t) % a.wc);
+    const int64_t so = (int64_t)ch * 16;
+    const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)t * a.kn.sn) * es + so;
+    const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)t * a.vn.sn) * es + so;
+    char* kd = a.wk.ptr + ((int64_t)b * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
+    char* vd = a.wv.ptr + ((int64_t)b * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+}
+
+__device__ __forceinline__ int clamp_count(const int* count, int n) {
+    const int c = *count;
+    return c < 0 ? 0 : (c > n ? n : c);
 }
 
 // blocks [0, nred): one wave per partial row folds the S partials and s_aux, writes o.  Blocks [nred, ...) with commit:
 // store chunk tokens t >= n - Wc into ring slot (write_pos + t) mod Wc, one 16-byte piece of K and of V per thread.
-template <typename T>
+// Dyn: S and write_pos come from the device state (which this launch only reads; ring_advance_kernel moves it on).
+template <typename T, bool Dyn>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred) {
     const int es = (int)sizeof(T);
+    const Fill f = get_fill<Dyn>(a);
     if ((int)blockIdx.x >= nred) {
-        const int cpr = a.D * es / 16;
         const int ncm = a.n < a.wc ? a.n : a.wc;
-        const int64_t item = (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x;
-        if (item >= (int64_t)a.B * a.Hkv * ncm * cpr) return;
-        const int ch = (int)(item % cpr);
-        int64_t rest = item / cpr;
-        const int j = (int)(rest % ncm);
-        rest /= ncm;
-        const int hk = (int)(rest % a.Hkv);
-        const int b = (int)(rest / a.Hkv);
-        const int t = a.n - ncm + j;
-        const int slot = (int)(((int64_t)a.wp + t) % a.wc);
-        const int64_t so = (int64_t)ch * 16;
-        const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)t * a.kn.sn) * es + so;
-        const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)t * a.vn.sn) * es + so;
-        char* kd = a.wk.ptr + ((int64_t)b * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
-        char* vd = a.wv.ptr + ((int64_t)b * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
-        *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
-        *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+        commit_piece(a, f.wp, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, a.n - ncm, a.n);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -468,10 +541,10 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     const int hk = (int)((rowid / a.R) % a.Hkv);
     const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
-    const int S = a.S, D = a.D;
-    const float* Mr = a.Mp + rowid * S;
-    const float* Lr = a.Lp + rowid * S;
-    const float* Or = a.Op + rowid * S * D;
+    const int S = f.S, D = a.D;
+    const float* Mr = a.Mp + rowid * a.Sw;
+    const float* Lr = a.Lp + rowid * a.Sw;
+    const float* Or = a.Op + rowid * a.Sw * D;
     const float sa = a.s_aux ? a.s_aux[head] * kLog2e : -INFINITY;
     // split statistics spread over the lanes (latency-bound: one round of loads, not S dependent ones), folded by the
     // fixed butterflies of wave_max / wave_sum
@@ -497,6 +570,25 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     }
 }
 
+// sfa_ring_commit_dyn: a = clamp(*count, 0, n) accepted chunk tokens; tokens [max(0, a - Wc), a) go to ring slot
+// (write_pos + t) mod Wc of the device state.  Reads the state only: ring_advance_kernel moves it on afterwards.
+__global__ __launch_bounds__(256) void ring_commit_kernel(MultiArgs a, const int* count, int es) {
+    int wp = a.state[2];
+    wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
+    const int acc = count ? clamp_count(count, a.n) : a.n;
+    commit_piece(a, wp, (int64_t)blockIdx.x * 256 + threadIdx.x, es, acc > a.wc ? acc - a.wc : 0, acc);
+}
+
+// one thread, the launch after every reader of the state: write_pos += a (mod Wc), window_len = min(window_len + a, Wc)
+__global__ void ring_advance_kernel(int* state, const int* count, int n, int wc) {
+    const int acc = count ? clamp_count(count, n) : n;
+    int wl = state[1], wp = state[2];
+    wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
+    wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
+    state[1] = wl + acc < wc ? wl + acc : wc;
+    state[2] = (int)(((int64_t)wp + acc) % wc);
+}
+
 constexpr int64_t kTargetWgs = 2048;
 
 int64_t want_splits(int64_t B, int64_t Hkv, int64_t nrb) {
@@ -518,8 +610,9 @@ bool mfma_head_dim(int D) { return D == 64 || D == 80 || D == 96 || D == 128; }
 
 template <typename T, int D>
 int launch_mfma(const MultiArgs& a, hipStream_t stream) {
-    const int64_t nblk = (int64_t)a.B * a.Hkv * a.S * a.nrb;
-    multi_split_mfma_kernel<T, D><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
+    const int64_t nblk = (int64_t)a.B * a.Hkv * a.Sw * a.nrb;
+    if (a.state) multi_split_mfma_kernel<T, D, true><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
+    else multi_split_mfma_kernel<T, D, false><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
     return launch_status("decode_multi_mfma");
 }
 
@@ -541,7 +634,9 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
     if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, stream) : SFA_OK;
     if (!mfma) {
-        multi_split_f32_kernel<T><<<dim3((unsigned)cdiv64(rows, 4), (unsigned)a.S), 256, 0, stream>>>(a);
+        const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
+        if (a.state) multi_split_f32_kernel<T, true><<<grid, 256, 0, stream>>>(a);
+        else multi_split_f32_kernel<T, false><<<grid, 256, 0, stream>>>(a);
         st = launch_status("decode_multi_f32");
     }
     if (st) return st;
@@ -551,8 +646,14 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
         const int64_t ncm = a.n < a.wc ? a.n : a.wc;
         ncommit = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)sizeof(T) / 16), 256);
     }
-    multi_reduce_kernel<T><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
-    return launch_status("decode_multi_reduce");
+    if (a.state) multi_reduce_kernel<T, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
+    else multi_reduce_kernel<T, false><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
+    if ((st = launch_status("decode_multi_reduce"))) return st;
+    if (a.state && a.commit) {   // every reader of the state has finished: advance it by n
+        ring_advance_kernel<<<1, 1, 0, stream>>>(const_cast<int*>(a.state), nullptr, a.n, a.wc);
+        st = launch_status("ring_advance");
+    }
+    return st;
 }
 
 }  // namespace
@@ -580,7 +681,7 @@ size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new,
 int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
-                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream) {
+                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state) {
     MultiArgs a;
     a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
     a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
@@ -593,23 +694,22 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     a.R = a.G * a.n;
     a.nrb = (int)cdiv64(a.R, 32);
     a.sink_len = (int)sink_len, a.wl = (int)window_len, a.wp = (int)write_pos, a.wc = (int)window_k->shape[2];
-    a.T0 = (int)cdiv64(sink_len, kTile);
-    a.T1 = a.T0 + (int)cdiv64(window_len, kTile);
-    a.T = a.T1 + (int)cdiv64(a.n, kTile);
-    const int64_t Nkv = sink_len + window_len + a.n;
-    int64_t S = max_splits(a.B, a.Hkv, a.nrb, Nkv);
-    const int64_t s_tiles = cdiv64(a.T, kMinTiles);
-    if (S > s_tiles) S = s_tiles;
-    a.tps = (int)cdiv64(a.T, S);
-    a.S = (int)cdiv64(a.T, a.tps);
+    a.want = (int)want_splits(a.B, a.Hkv, a.nrb);
+    const MultiPlan p = multi_plan(a.sink_len, a.wl, a.n, a.want);
+    a.T0 = p.T0, a.T1 = p.T1, a.T = p.T, a.tps = p.tps, a.S = p.S;
+    // dyn: (sink_len, window_len) = the full cache here; the grid covers the largest plan of any fill level and every
+    // workgroup replans from the device state (workgroups of splits >= its S exit)
+    a.state = state;
+    a.ns = (int)sink_k->shape[2];
+    a.Sw = state ? (int)max_splits(a.B, a.Hkv, a.nrb, sink_len + window_len + a.n) : a.S;
     a.scale_log2 = scale * kLog2e;
     a.commit = commit ? 1 : 0;
     const size_t rows = (size_t)a.B * a.Hkv * a.R;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     a.Mp = reinterpret_cast<float*>(workspace);
-    a.Lp = reinterpret_cast<float*>((char*)workspace + al(rows * a.S * sizeof(float)));
-    a.Op = reinterpret_cast<float*>((char*)workspace + 2 * al(rows * a.S * sizeof(float)));
-    if ((int64_t)a.B * a.Hkv * a.S * a.nrb >= (1ll << 31) || cdiv64((int64_t)rows, 4) >= (1ll << 31) - 65536) {
+    a.Lp = reinterpret_cast<float*>((char*)workspace + al(rows * a.Sw * sizeof(float)));
+    a.Op = reinterpret_cast<float*>((char*)workspace + 2 * al(rows * a.Sw * sizeof(float)));
+    if ((int64_t)a.B * a.Hkv * a.Sw * a.nrb >= (1ll << 31) || cdiv64((int64_t)rows, 4) >= (1ll << 31) - 65536) {
         set_error("decode_multi: grid too large");
         return SFA_ERR_UNSUPPORTED;
     }
@@ -621,8 +721,41 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     else if (dt == SFA_DTYPE_F16) st = launch_rest<f16_t>(a, mfma, stream);
     else st = launch_rest<bf16_t>(a, mfma, stream);
     if (st) return st;
-    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_s%d%s", dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
-    else set_path("decode_multi_f32_%s_d%d_s%d%s", dname, a.D, a.S, commit ? "_commit" : "");
+    if (state) {
+        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_dyn%s", dname, a.D, a.nrb, commit ? "_commit" : "");
+        else set_path("decode_multi_f32_%s_d%d_dyn%s", dname, a.D, commit ? "_commit" : "");
+    } else {
+        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_s%d%s", dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
+        else set_path("decode_multi_f32_%s_d%d_s%d%s", dname, a.D, a.S, commit ? "_commit" : "");
+    }
+    return SFA_OK;
+}
+
+int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream) {
+    MultiArgs a{};
+    a.wk = make_view(window_k), a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new);
+    a.B = (int)k_new->shape[0];
+    a.Hkv = (int)k_new->shape[1];
+    a.n = (int)k_new->shape[2];
+    a.D = (int)k_new->shape[3];
+    a.wc = (int)window_k->shape[2];
+    a.state = state;
+    const int es = dtype_size(k_new->dtype);
+    const int64_t ncm = a.n < a.wc ? a.n : a.wc;
+    const int64_t nblk = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)es / 16), 256);
+    if (nblk >= (1ll << 31)) {
+        set_error("ring_commit: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    int st;
+    if (nblk > 0) {
+        ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        if ((st = launch_status("ring_commit"))) return st;
+    }
+    ring_advance_kernel<<<1, 1, 0, stream>>>(state, count, a.n, a.wc);   // after every reader of the state
+    if ((st = launch_status("ring_advance"))) return st;
+    set_path("ring_commit_dyn");
     return SFA_OK;
 }
 

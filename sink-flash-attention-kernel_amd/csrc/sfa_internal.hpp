@@ -58,6 +58,10 @@ size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new,
 int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
-                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream);
+                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream,
+                        int32_t* state = nullptr);   // dyn: sink_len / window_len = the full cache, write_pos = 0
+// sfa_ring_commit_dyn: store clamp(*count, 0, n) chunk tokens into the ring at the device state, then advance it
+int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream);
 
 }  // namespace sfa

@@ -112,6 +112,10 @@ def _bind(lib):
     lib.sfa_decode_multi_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i32]
     lib.sfa_decode_ring_multi.restype = i32
     lib.sfa_decode_ring_multi.argtypes = [P, P, P, i64, P, P, i64, i64, P, P, P, vp, i32, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_multi_dyn.restype = i32
+    lib.sfa_decode_ring_multi_dyn.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, sz, f32, u32, vp]
+    lib.sfa_ring_commit_dyn.restype = i32
+    lib.sfa_ring_commit_dyn.argtypes = [P, P, P, P, vp, vp, vp]
 
 
 def lib():

@@ -256,15 +256,20 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     # ------------------------------------------------ device-resident state (hipGraph capture)
     def enable_device_state(self) -> torch.Tensor:
         """Move the ring bookkeeping {sink_len, window_len, write_pos} to a device int32 tensor so that
-        ``decode_step_dyn`` needs no host-side integers: a whole generation step can then be captured with
-        ``torch.cuda.graph`` and replayed (the kernels read and advance the state themselves).  Call after prefill."""
+        ``decode_step_dyn``, ``extend_attention_dyn``, ``extend_step_dyn`` and ``commit_dyn`` need no host-side integers:
+        a whole generation or speculative step can then be captured with ``torch.cuda.graph`` and replayed (the kernels
+        read and advance the state themselves; the calls may be mixed on one state).  Call after prefill.  The host-state
+        calls (``append``, ``decode_step``, ``extend_step``) do not update the device state, nor the dyn calls the host
+        counters: switch with ``enable_device_state()`` / ``pull_state()``."""
         assert self.is_initialized and self.prefilled and self.window_size > 0, "prefill the cache first"
         self._dev_state = torch.tensor([self.sink_len, self.window_len, self.write_pos], dtype=torch.int32,
                                        device=self.window_k.device)
         return self._dev_state
 
     def pull_state(self) -> None:
-        """Refresh the host-side counters from the device state (one small device-to-host copy)."""
+        """Refresh the host-side counters from the device state (one small device-to-host copy).  ``seen_tokens`` is
+        exact only while fewer than ``window_size`` tokens were committed since the last pull (the state holds no token
+        count: a full ring's ``write_pos`` is taken modulo ``window_size``)."""
         st = getattr(self, "_dev_state", None)
         if st is not None:
             sl, wl, wp = st.tolist()
@@ -312,6 +317,115 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                                     ss["ws"].data_ptr(), ss["ws"].numel(), ss["scale"],
                                                     self._decode_flags(N), N.stream_ptr(q.device))
         N.check(rc, "sfa_decode_ring_step_dyn")
+        return out
+
+    # ---------------------------- several new tokens with the state on the device (capturable speculative step)
+    def extend_attention_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                             s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``extend_attention`` with the state on the device (``sfa_decode_ring_multi_dyn``, commit off): capturable into a
+        hipGraph, no host sync.  Neither the cache nor the device state changes.  The output is bitwise what
+        ``extend_attention`` gives at the same state.  ``out`` (optional, [B, H_q, n, D]) is a static output buffer."""
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False)
+
+    def extend_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``extend_step`` with the state on the device: attend, commit all n tokens, advance the device state.  The host
+        counters are refreshed by ``pull_state()``."""
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=True)
+
+    def commit_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, count: torch.Tensor) -> None:
+        """Store the first ``a = clamp(count, 0, n)`` tokens of a chunk ``[B, H_kv, n, D]`` into the ring and advance the
+        device state (``sfa_ring_commit_dyn``): afterwards buffers and state are what ``append(k_new[:, :, :a], ...)``
+        leaves.  ``count`` is a 0-d or 1-element integer tensor on the GPU (the acceptance count of a speculative step,
+        computed by torch ops); it is never read on the host."""
+        from . import _native as N
+        st = self._require_dyn("commit_dyn")
+        if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
+                or count.dtype == torch.bool:
+            raise TypeError("count must be an integer tensor")
+        if count.numel() != 1:
+            raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
+        N.require_gpu(k_new, v_new, count, self.window_k)
+        B, H_kv, _w, D = self.window_k.shape
+        if k_new.dim() != 4 or k_new.shape[:2] != (B, H_kv) or k_new.shape[3] != D or v_new.shape != k_new.shape \
+                or k_new.shape[2] < 1:
+            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = [{B}, {H_kv}, n, {D}], got {tuple(k_new.shape)}")
+        if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
+            raise TypeError("k_new / v_new must have the cache buffers' dtype")
+        k_new, v_new = self._rows16(k_new), self._rows16(v_new)
+        cnt = count.reshape(1)
+        if cnt.dtype != torch.int32:
+            cnt = cnt.to(torch.int32)      # a cast kernel: capturable
+        wk, wv = self._ring_descs()
+        with torch.cuda.device(k_new.device):
+            rc = N.lib().sfa_ring_commit_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
+                                             N.stream_ptr(k_new.device))
+        N.check(rc, "sfa_ring_commit_dyn")
+
+    def _require_dyn(self, what):
+        if not (self.is_initialized and self.prefilled):
+            raise ValueError(f"{what} needs a prefilled cache: the first chunk is a prefill (sink_flash_attention)")
+        st = getattr(self, "_dev_state", None)
+        if st is None:
+            raise RuntimeError(f"{what} needs the state on the device: call enable_device_state() first")
+        return st
+
+    @staticmethod
+    def _rows16(t):
+        from . import _native as N
+        t = N.unit_inner(t.detach())
+        es = t.element_size()
+        if t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3)):
+            t = t.contiguous()
+        return t
+
+    def _ring_descs(self):
+        key = (self.window_k.data_ptr(), self.window_v.data_ptr())
+        rd = getattr(self, "_ring_desc", None)
+        if rd is None or rd[0] != key:
+            from . import _native as N
+            rd = (key, (N.desc(self.window_k), N.desc(self.window_v)))
+            self._ring_desc = rd
+        return rd[1]
+
+    def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit):
+        """sfa_decode_ring_multi_dyn with the per-layer constants (buffer descriptors, a workspace for the full cache plus
+        the chunk) built once per chunk shape, as _ring_multi does."""
+        import math
+        from . import _native as N
+        dev_state = self._require_dyn("extend_step_dyn" if commit else "extend_attention_dyn")
+        N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
+        B, H_q, n, D = q.shape
+        H_kv = self.sink_k.shape[1]
+        if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = {(B, H_kv, n, D)}, got {tuple(k_new.shape)}")
+        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
+            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+        if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
+            raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
+        st = getattr(self, "_multi_dyn_state", None)
+        key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
+        if st is None or st["key"] != key:
+            lib = N.lib()
+            ws_bytes = lib.sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
+                                                            N.SFA_DTYPE[q.dtype])
+            if ws_bytes == 0:
+                raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB")
+            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
+                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
+                      ws=torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
+            self._multi_dyn_state = st
+        q, k_new, v_new = self._rows16(q), self._rows16(k_new), self._rows16(v_new)
+        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        if out is None:
+            out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
+        sk, sv, wk, wv = st["descs"]
+        with torch.cuda.device(q.device):
+            rc = st["lib"].sfa_decode_ring_multi_dyn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                                     s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                     1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
+                                                     st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_multi_dyn")
         return out
 
     # ------------------------------------------------------- HF layer surface
@@ -390,6 +504,19 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         if layer_idx == 0:
             self._seen_tokens = self.layers[0].seen_tokens
         return out
+
+    def extend_attention_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None):
+        """``SinkCacheLayer.extend_attention_dyn`` of one layer: verify with the state on the device (capturable)."""
+        return self._layer(layer_idx).extend_attention_dyn(q, key_states, value_states, s_aux=s_aux, out=out)
+
+    def extend_step_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None):
+        """``SinkCacheLayer.extend_step_dyn`` of one layer: attention + commit of all n tokens, state on the device.
+        ``seen_tokens`` follows after ``pull_state()`` of layer 0."""
+        return self._layer(layer_idx).extend_step_dyn(q, key_states, value_states, s_aux=s_aux, out=out)
+
+    def commit_dyn(self, key_states, value_states, count, layer_idx: int) -> None:
+        """``SinkCacheLayer.commit_dyn`` of one layer: store the first ``count`` (device tensor) tokens of the chunk."""
+        self._layer(layer_idx).commit_dyn(key_states, value_states, count)
 
     def get_seq_length(self, layer_idx: int = 0, *_, **__) -> int:
         return self.layers[layer_idx].get_seq_length() if layer_idx < len(self.layers) else 0
