@@ -299,6 +299,62 @@ int sfa_decode_ring_multi_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, con
 int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                         const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream);
 
+/*
+ * Per-sequence device state (ragged batches).  The calls below take `state` = int32 [B][4] in device memory, one row
+ * {sink_len, window_len, write_pos, seen} per batch row b (row-major, contiguous): the first three fields mean what the
+ * shared state of the *_dyn calls means, for row b's slice of the buffers alone; `seen` is the row's token count (the
+ * position its next token takes).  The kernels advance `seen` with the row and never read it for attention.  The launch
+ * geometry and workspace are those of the shared *_dyn call (the full cache); each row plans from its own state.
+ */
+
+/*
+ * sfa_decode_ring_step_dyn with per-sequence state: row b stores its token into its own write_pos, attends over its own
+ * sink rows [0, sink_len) and ring slots [0, min(window_len + 1, Wc)), then its state advances (seen += 1).  Arguments,
+ * checks and workspace as for sfa_decode_ring_step_dyn.  SFA_FLAG_DECODE_ONE_PASS: the grid-level last arriver advances
+ * all B rows.
+ */
+int sfa_decode_ring_step_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
+                              void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
+/*
+ * sfa_decode_ring_multi_dyn with per-sequence state: batch row b attends with the mask and plan of its own state row
+ * (row b of the output is bitwise that of a shared-state call at row b's state).  commit != 0: every row stores all n
+ * chunk tokens at its own slots and advances by n (seen += n).  Arguments, checks and workspace as for
+ * sfa_decode_ring_multi_dyn.
+ */
+int sfa_decode_ring_multi_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                               int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                               void* stream);
+
+/*
+ * sfa_ring_commit_dyn with per-sequence state and counts: count = device int32 [B].  Row b stores chunk tokens
+ * [max(0, a_b - Wc), a_b) with a_b = clamp(count[b], 0, n) into its ring slots (write_pos_b + t) mod Wc, then advances
+ * by a_b (seen += a_b): afterwards row b is what append() of its first a_b tokens leaves.  Tensor arguments and checks
+ * as for sfa_ring_commit_dyn.
+ */
+int sfa_ring_commit_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                         const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream);
+
+/*
+ * Prefill a ragged batch: store the K/V of n_seq packed sequences (the layout sfa_fwd_varlen takes) into per-sequence
+ * cache buffers and write their state rows, in one launch (16 bytes per thread, no host sync: capturable).
+ *   k, v        [1, Hkv, T, D]   sequence b = rows [cu_seqlens[b], cu_seqlens[b + 1]), length L_b
+ *   sink_k/v    [n_seq, Hkv, num_sink, D]   window_k/v [n_seq, Hkv, Wc, D], Wc >= 1, k's dtype, rows multiples of 16
+ *               bytes and 16-byte aligned
+ *   cu_seqlens  device int32 [n_seq + 1]; read on the device and not validated (as sfa_fwd_varlen); offsets are
+ *               clamped into [0, T], so that bad ones cannot address outside the pack.
+ * Row b gets the placement of a prefill of its sequence alone: with sl = min(L, num_sink) and r = L - sl, sink row
+ * j < sl holds token j; if r <= Wc ring slot s < r holds token sl + s, else slot s holds token L - Wc + s.  Rows and
+ * slots beyond those keep their content.  state[b] = {sl, min(r, Wc), r < Wc ? r : 0, L}.
+ */
+int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                         const int32_t* cu_seqlens, int n_seq, int32_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,7 +305,7 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                   const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
                   size_t workspace_bytes, float scale, void* stream, const sfa_tensor* k_new = nullptr,
                   const sfa_tensor* v_new = nullptr, int64_t new_slot = -1, int* dyn_state = nullptr,
-                  unsigned flags = 0) {
+                  unsigned flags = 0, bool state_rows = false) {
     g_err[0] = 0;
     int st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")) ||
@@ -363,7 +363,7 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
     }
     return decode_launch(q, k, v, n1, n2 ? k2 : nullptr, n2 ? v2 : nullptr, n2, o, s_aux, workspace, scale, pl,
                          (hipStream_t)stream, k_new, v_new, (int)new_slot, dyn_state,
-                         (flags & SFA_FLAG_DECODE_ONE_PASS) != 0);
+                         (flags & SFA_FLAG_DECODE_ONE_PASS) != 0, state_rows);
 }
 
 }  // namespace
@@ -407,6 +407,19 @@ int sfa_decode_ring_step_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, cons
     // launch geometry and workspace are sized for the FULL cache (every sink row, every ring slot)
     return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
                          workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags);
+}
+
+int sfa_decode_ring_step_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
+                              void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    // the state rows [B][4] are per batch row of the cache buffers (decode_common checks q / k_new against them)
+    return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
+                         workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags, true);
 }
 
 }  // extern "C"
@@ -518,9 +531,34 @@ int sfa_decode_ring_multi_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, con
                                scale, flags, (hipStream_t)stream, state);
 }
 
-int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                        const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
+int sfa_decode_ring_multi_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                               int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                               void* stream) {
     g_err[0] = 0;
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
+    if (q->shape[0] == 0) return SFA_OK;               // no rows: no state to read or advance
+    if (q->shape[1] == 0) {
+        if (!commit) return SFA_OK;
+        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream, true);
+    }
+    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
+    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
+                               scale, flags, (hipStream_t)stream, state, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+// every host-checkable argument of sfa_ring_commit_dyn / _rows; nothing launches
+int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                 const sfa_tensor* v_new, const int32_t* count, int32_t* state) {
     int st;
     if ((st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
@@ -547,7 +585,68 @@ int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, 
                           (t->stride[2] * es) % 16 == 0,
                       "ring_commit: rows of every tensor must be 16-byte aligned");
     }
+    return SFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                        const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
     return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream);
+}
+
+int sfa_ring_commit_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                         const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
+    if (k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, true);
+}
+
+int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                         const int32_t* cu_seqlens, int n_seq, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_tensor(sink_k, "sink_k")) || (st = check_tensor(sink_v, "sink_v")) ||
+        (st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
+        (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")))
+        return st;
+    if ((st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
+        (st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k, v, "k", "v")))
+        return st;
+    SFA_CHECK_ARG(cu_seqlens != nullptr, "cu_seqlens: null device pointer");
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
+    SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
+    SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
+                  "k / v and the cache buffers must share one dtype");
+    const int64_t Hkv = k->shape[1], D = k->shape[3], Wc = window_k->shape[2];
+    SFA_CHECK_ARG(sink_k->shape[0] == n_seq && window_k->shape[0] == n_seq,
+                  "n_seq (%d) must match the cache buffers' batch (sink %lld, window %lld)", n_seq,
+                  (long long)sink_k->shape[0], (long long)window_k->shape[0]);
+    SFA_CHECK_ARG(sink_k->shape[1] == Hkv && sink_k->shape[3] == D && window_k->shape[1] == Hkv && window_k->shape[3] == D,
+                  "sink / window buffers must be [n_seq, H_kv, *, D] like k");
+    SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
+    SFA_CHECK_ARG(k->shape[2] < (1ll << 30) && sink_k->shape[2] + Wc < (1ll << 30), "problem too large");
+    const int es = dtype_size(k->dtype);
+    SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_fill_varlen: K/V rows must be a multiple of 16 bytes (head dim %lld)",
+                  (long long)D);
+    const sfa_tensor* ts[6] = {sink_k, sink_v, window_k, window_v, k, v};
+    for (const sfa_tensor* t : ts) {
+        if (t->shape[0] == 0 || t->shape[1] == 0 || t->shape[2] == 0) continue;
+        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
+                          (t->stride[2] * es) % 16 == 0,
+                      "ring_fill_varlen: rows of every tensor must be 16-byte aligned");
+    }
+    return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
+                                   (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -163,12 +163,23 @@ struct OnePass {
 // a whole generation step can sit in a captured hipGraph: the split kernel takes its key counts and the write slot
 // from there (the grid is sized for the full cache; splits past the end produce empty partials) and the reduce kernel,
 // which the stream orders after every reader, advances the state.
+// `stride` (sfa_decode_ring_step_rows): 4 = one state row {sink_len, window_len, write_pos, seen} per batch row b at
+// dyn + 4 b, each row planned, appended to and advanced on its own (seen += 1); 0 = one state for the whole batch.
 struct Fresh {
     View kn, vn;
     int slot;
     int* dyn;       // device {sink_len, window_len before the append, write_pos} or null
     int wsize;      // ring capacity (dyn only)
+    int stride;     // state row stride (dyn only)
 };
+
+// advance one device state row by one token; per-sequence rows (seen) also count it.  Plain stores from a vector lane.
+__device__ __forceinline__ void advance_row(int* st, int wsize, bool seen) {
+    const int wl = st[1], wp = st[2];
+    st[1] = wl + 1 < wsize ? wl + 1 : wsize;
+    st[2] = wp + 1 == wsize ? 0 : wp + 1;
+    if (seen) st[3] += 1;
+}
 
 template <typename T, int LPK, int GT>
 __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View v, View k2, View v2, int N1, Fresh fr,
@@ -193,10 +204,11 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
     const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
     const int g = Hq / Hkv;
     if (fr.dyn) {
-        N1 = fr.dyn[0];
-        const int wl = fr.dyn[1] + 1 < fr.wsize ? fr.dyn[1] + 1 : fr.wsize;
+        const int* st = fr.dyn + (int64_t)b * fr.stride;   // the grid (kps, S) is the full cache's: splits past this
+        N1 = st[0];                                        // row's keys give empty partials
+        const int wl = st[1] + 1 < fr.wsize ? st[1] + 1 : fr.wsize;
         Nkv = N1 + wl;
-        fr.slot = fr.dyn[2];
+        fr.slot = st[2];
     }
     const int k_beg = split * kps;
     const int k_end = (k_beg + kps < Nkv) ? (k_beg + kps) : Nkv;
@@ -374,10 +386,9 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
                 for (int hh = wave; hh < g; hh += 4) reduce_head<T, true, 64>(Mp, Lp, Op, op1.s_aux, op1.o, Hq, S, D, b, hk * g + hh, lane, 64);
             }
         }
-        if (last_flag[1] && fr.dyn && threadIdx.x == 0) {  // every workgroup has read the state: advance it
-            const int wl = fr.dyn[1], wp = fr.dyn[2];
-            fr.dyn[1] = wl + 1 < fr.wsize ? wl + 1 : fr.wsize;
-            fr.dyn[2] = wp + 1 == fr.wsize ? 0 : wp + 1;
+        if (last_flag[1] && fr.dyn) {      // every workgroup has read the state: advance it (every row of it)
+            const int nrow = fr.stride ? (int)gridDim.z : 1;
+            for (int r = threadIdx.x; r < nrow; r += blockDim.x) advance_row(fr.dyn + (int64_t)r * fr.stride, fr.wsize, fr.stride != 0);
         }
     }
 }
@@ -387,13 +398,10 @@ template <typename T>
 __global__ __launch_bounds__(128) void decode_reduce_kernel(const float* __restrict__ Mp, const float* __restrict__ Lp,
                                                            const float* __restrict__ Op,
                                                            const float* __restrict__ s_aux, View o, int Hq, int S,
-                                                           int D, int* dyn, int wsize) {
+                                                           int D, int* dyn, int wsize, int stride) {
     const int h = blockIdx.x, b = blockIdx.y;
-    if (dyn && h == 0 && b == 0 && threadIdx.x == 0) {      // every reader of the state (split kernel) has finished
-        const int wl = dyn[1], wp = dyn[2];
-        dyn[1] = wl + 1 < wsize ? wl + 1 : wsize;
-        dyn[2] = wp + 1 == wsize ? 0 : wp + 1;
-    }
+    // every reader of the state (split kernel) has finished: block (0, 0) advances a shared state, block (0, b) row b
+    if (dyn && h == 0 && (stride || b == 0) && threadIdx.x == 0) advance_row(dyn + (int64_t)b * stride, wsize, stride != 0);
     reduce_head<T>(Mp, Lp, Op, s_aux, o, Hq, S, D, b, h, threadIdx.x, 128);
 }
 
@@ -477,15 +485,16 @@ int decode_plan(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nkv, int64_t D, int 
 int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, int64_t n1, const sfa_tensor* k2,
                   const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
                   float scale, const DecodePlan& pl, hipStream_t stream, const sfa_tensor* k_new,
-                  const sfa_tensor* v_new, int new_slot, int* dyn_state, bool one_pass) {
+                  const sfa_tensor* v_new, int new_slot, int* dyn_state, bool one_pass, bool state_rows) {
     const int B = (int)q->shape[0], Hq = (int)q->shape[1], D = (int)q->shape[3];
     const int Hkv = (int)k->shape[1], Nkv = (int)(n1 + n2), N1 = (int)n1;
     const View kv2 = k2 ? make_view(k2) : make_view(k);
     const View vv2 = v2 ? make_view(v2) : make_view(v);
     const int wsize = k2 ? (int)k2->shape[2] : 0;
-    Fresh fr{kv2, vv2, -1, nullptr, wsize};
+    const int stride = dyn_state && state_rows ? 4 : 0;
+    Fresh fr{kv2, vv2, -1, nullptr, wsize, 0};
     if (k_new && v_new && (new_slot >= 0 || dyn_state))
-        fr = Fresh{make_view(k_new), make_view(v_new), dyn_state ? 0 : new_slot, dyn_state, wsize};
+        fr = Fresh{make_view(k_new), make_view(v_new), dyn_state ? 0 : new_slot, dyn_state, wsize, stride};
     const int S = pl.splits;
     // counters of the one-pass mode sit at the START of the workspace (their place must not move when the split count
     // changes from one step to the next while a ring fills), the partials behind them
@@ -507,17 +516,17 @@ int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                                       Op, Hq, Hkv, Nkv, D, scale);
     if (st != SFA_OK) return st;
     if (one_pass) {
-        set_path("decode_splitkv%s_1pass_lpk%d_gt%d_s%d", dyn_state ? "_ringstep_dyn" : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
+        set_path("decode_splitkv%s_1pass_lpk%d_gt%d_s%d", dyn_state ? (stride ? "_ringstep_rows" : "_ringstep_dyn") : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
         return SFA_OK;
     }
     dim3 rgrid(Hq, B);
     if (q->dtype == SFA_DTYPE_F32)
-        decode_reduce_kernel<float><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize);
+        decode_reduce_kernel<float><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
     else if (q->dtype == SFA_DTYPE_F16)
-        decode_reduce_kernel<f16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize);
+        decode_reduce_kernel<f16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
     else
-        decode_reduce_kernel<bf16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize);
-    set_path("decode_splitkv%s_lpk%d_gt%d_s%d", dyn_state ? "_ringstep_dyn" : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
+        decode_reduce_kernel<bf16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
+    set_path("decode_splitkv%s_lpk%d_gt%d_s%d", dyn_state ? (stride ? "_ringstep_rows" : "_ringstep_dyn") : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
     return launch_status("decode_reduce");
 }
 

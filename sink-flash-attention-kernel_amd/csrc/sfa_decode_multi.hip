@@ -73,6 +73,7 @@ struct MultiArgs {
     // dyn mode (sfa_decode_ring_multi_dyn): state = device {sink_len, window_len, write_pos}; every workgroup reads it and
     // replans (T0, T1, T, tps, S) with multi_plan.  Null: the host plan above holds.
     const int* state;
+    int sstride;                 // state row stride: 0 = one state shared by the batch, 4 = per-sequence rows [B][4]
     int ns;                      // sink buffer rows (dyn: clamp of sink_len)
     int want;                    // want_splits(B, Hkv, nrb): the workgroup-target cap of the split count
 };
@@ -107,16 +108,25 @@ struct Fill {
     int T0, T1, T, tps, S;
 };
 
+// the write slot of batch row b's state, clamped into the ring (dyn); the host state otherwise
+__device__ __forceinline__ int state_wp(const MultiArgs& a, int b) {
+    if (!a.state) return a.wp;
+    const int wp = a.state[(int64_t)b * a.sstride + 2];
+    return wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
+}
+
+// b: the batch row, wave-uniform (per-sequence state reads row b; a shared state has stride 0)
 template <bool Dyn>
-__device__ __forceinline__ Fill get_fill(const MultiArgs& a) {
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int b) {
     if constexpr (!Dyn) {
         return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S};
     } else {
         // dyn mode: the cache state from the device (clamped into the buffers, so that a corrupt state cannot address
-        // outside them), replanned.  Wave-uniform: scalar loads of 12 bytes.
-        int sl = __builtin_amdgcn_readfirstlane(a.state[0]);
-        int wl = __builtin_amdgcn_readfirstlane(a.state[1]);
-        int wp = __builtin_amdgcn_readfirstlane(a.state[2]);
+        // outside them), replanned.  Wave-uniform: loads of 12 bytes, broadcast from the first lane.
+        const int* st = a.state + (int64_t)b * a.sstride;
+        int sl = __builtin_amdgcn_readfirstlane(st[0]);
+        int wl = __builtin_amdgcn_readfirstlane(st[1]);
+        int wp = __builtin_amdgcn_readfirstlane(st[2]);
         sl = sl < 0 ? 0 : (sl > a.ns ? a.ns : sl);
         wl = wl < 0 ? 0 : (wl > a.wc ? a.wc : wl);
         wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     rest /= a.Sw;
     const int hk = rest % a.Hkv;
     const int b = rest / a.Hkv;
-    const Fill f = get_fill<Dyn>(a);
+    const Fill f = get_fill<Dyn>(a, b);
     if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -435,13 +445,14 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int split = blockIdx.y;
-    const Fill f = get_fill<Dyn>(a);
-    if (Dyn && split >= f.S) return;
     const int64_t nrow = (int64_t)a.B * a.Hkv * a.R;
     if (rowid >= nrow) return;
     const int rho = (int)(rowid % a.R);
     const int hk = (int)((rowid / a.R) % a.Hkv);
     const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
+    // per wave: with R < 4 one workgroup holds rows of different sequences, and each has its own fill
+    const Fill f = get_fill<Dyn>(a, b);
+    if (Dyn && split >= f.S) return;
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
     const int D = a.D;
     const int es = (int)sizeof(T);
@@ -493,9 +504,16 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     }
 }
 
+__device__ __forceinline__ int clamp_count(const int* count, int n) {
+    const int c = *count;
+    return c < 0 ? 0 : (c > n ? n : c);
+}
+
 // one 16-byte piece of the commit: item = ((b * Hkv + hk) * nslot + j) * cpr + ch over the nslot = min(n, Wc) chunk
-// tokens a commit can store; piece j is chunk token first + j (stored only if < last) -> ring slot (write_pos + t) mod Wc
-__device__ __forceinline__ void commit_piece(const MultiArgs& a, int wp, int64_t item, int es, int first, int last) {
+// tokens a commit can store.  Row b stores acc = clamp(count, 0, n) tokens (all n without a count): piece j is chunk
+// token first + j with first = max(0, acc - Wc), stored only if < acc -> ring slot (write_pos + t) mod Wc, write_pos
+// of row b's state.  count: one value shared by the batch, or [B] with per-sequence state.
+__device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, int es, const int* count) {
     const int cpr = a.D * es / 16;
     const int nslot = a.n < a.wc ? a.n : a.wc;
     if (item >= (int64_t)a.B * a.Hkv * nslot * cpr) return;
@@ -505,9 +523,10 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int wp, int64_t
     rest /= nslot;
     const int hk = (int)(rest % a.Hkv);
     const int b = (int)(rest / a.Hkv);
-    const int t = first + j;
+    const int last = count ? clamp_count(count + (a.sstride ? b : 0), a.n) : a.n;
+    const int t = (last > a.wc ? last - a.wc : 0) + j;
     if (t >= last) return;
-    const int slot = (int)(((int64_t)wp + t) % a.wc);
+    const int slot = (int)(((int64_t)state_wp(a, b) + t) % a.wc);
     const int64_t so = (int64_t)ch * 16;
     const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)t * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)t * a.vn.sn) * es + so;
@@ -517,21 +536,16 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int wp, int64_t
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
 
-__device__ __forceinline__ int clamp_count(const int* count, int n) {
-    const int c = *count;
-    return c < 0 ? 0 : (c > n ? n : c);
-}
-
 // blocks [0, nred): one wave per partial row folds the S partials and s_aux, writes o.  Blocks [nred, ...) with commit:
 // store chunk tokens t >= n - Wc into ring slot (write_pos + t) mod Wc, one 16-byte piece of K and of V per thread.
 // Dyn: S and write_pos come from the device state (which this launch only reads; ring_advance_kernel moves it on).
+// With per-sequence state both are row b's: S per wave (a workgroup can hold rows of different sequences), write_pos
+// per commit piece.
 template <typename T, bool Dyn>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred) {
     const int es = (int)sizeof(T);
-    const Fill f = get_fill<Dyn>(a);
     if ((int)blockIdx.x >= nred) {
-        const int ncm = a.n < a.wc ? a.n : a.wc;
-        commit_piece(a, f.wp, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, a.n - ncm, a.n);
+        commit_piece(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -540,6 +554,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     const int rho = (int)(rowid % a.R);
     const int hk = (int)((rowid / a.R) % a.Hkv);
     const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
+    const Fill f = get_fill<Dyn>(a, b);
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
     const int S = f.S, D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
@@ -570,23 +585,88 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     }
 }
 
-// sfa_ring_commit_dyn: a = clamp(*count, 0, n) accepted chunk tokens; tokens [max(0, a - Wc), a) go to ring slot
-// (write_pos + t) mod Wc of the device state.  Reads the state only: ring_advance_kernel moves it on afterwards.
+// sfa_ring_commit_dyn / _rows: a = clamp(count, 0, n) accepted chunk tokens (per row with per-sequence state); tokens
+// [max(0, a - Wc), a) go to ring slot (write_pos + t) mod Wc of the row's device state.  Reads the state only:
+// ring_advance_kernel moves it on afterwards.
 __global__ __launch_bounds__(256) void ring_commit_kernel(MultiArgs a, const int* count, int es) {
-    int wp = a.state[2];
-    wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
-    const int acc = count ? clamp_count(count, a.n) : a.n;
-    commit_piece(a, wp, (int64_t)blockIdx.x * 256 + threadIdx.x, es, acc > a.wc ? acc - a.wc : 0, acc);
+    commit_piece(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
 }
 
-// one thread, the launch after every reader of the state: write_pos += a (mod Wc), window_len = min(window_len + a, Wc)
-__global__ void ring_advance_kernel(int* state, const int* count, int n, int wc) {
-    const int acc = count ? clamp_count(count, n) : n;
-    int wl = state[1], wp = state[2];
+// sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
+// K/V, one 16-byte piece per thread.  item = ((b * Hkv + hk) * (ns + Wc) + j) * cpr + ch: j < ns is sink row j, j >= ns
+// ring slot s = j - ns.  Sequence b = rows [cu[b], cu[b + 1]) of length L (offsets clamped into [0, T], so that bad
+// offsets cannot address outside the pack): sink row j <- token j for j < sl = min(L, ns); with rest = L - sl, slot s <-
+// token sl + s for s < rest when rest <= Wc, else token L - Wc + s (the newest Wc, wrapped at slot 0).  Rows and slots
+// the sequence does not reach keep their content.  The first piece of each sequence writes its state row
+// {sl, min(rest, Wc), rest < Wc ? rest : 0, L} (rest <= 0: window_len = write_pos = 0).
+__global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv, View wk, View wv, View k, View v,
+                                                               const int* cu, int* state, int n_seq, int Hkv, int ns,
+                                                               int wc, int T, int cpr, int es) {
+    const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int nj = ns + wc;
+    if (item >= (int64_t)n_seq * Hkv * nj * cpr) return;
+    const int ch = (int)(item % cpr);
+    int64_t rest = item / cpr;
+    const int j = (int)(rest % nj);
+    rest /= nj;
+    const int hk = (int)(rest % Hkv);
+    const int b = (int)(rest / Hkv);
+    int c0 = cu[b], c1 = cu[b + 1];
+    c0 = c0 < 0 ? 0 : (c0 > T ? T : c0);
+    c1 = c1 < c0 ? c0 : (c1 > T ? T : c1);
+    const int L = c1 - c0;
+    const int sl = L < ns ? L : ns;
+    const int rem = L - sl;
+    if (hk == 0 && j == 0 && ch == 0) {
+        int* st = state + (int64_t)b * 4;
+        st[0] = sl;
+        st[1] = rem < wc ? rem : wc;
+        st[2] = rem < wc ? rem : 0;
+        st[3] = L;
+    }
+    int src;   // token index within the sequence, -1: nothing to store
+    const View *dk, *dv;
+    int row;
+    if (j < ns) {
+        src = j < sl ? j : -1, row = j, dk = &sk, dv = &sv;
+    } else {
+        const int s = j - ns;
+        src = rem <= wc ? (s < rem ? sl + s : -1) : L - wc + s;
+        row = s, dk = &wk, dv = &wv;
+    }
+    if (src < 0) return;
+    const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src;
+    const char* ks = k.ptr + ((int64_t)hk * k.sh + tok * k.sn) * es + so;
+    const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
+    char* kd = dk->ptr + ((int64_t)b * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * es + so;
+    char* vd = dv->ptr + ((int64_t)b * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * es + so;
+    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+}
+
+// the launch after every reader of the state, one thread per state row (`rows` of them, stride `stride`): write_pos += a
+// (mod Wc), window_len = min(window_len + a, Wc); per-sequence rows (stride 4, count [rows]) also seen += a.
+// Plain stores from vector lanes.
+__global__ void ring_advance_kernel(int* state, const int* count, int n, int wc, int rows, int stride) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= rows) return;
+    int* st = state + (int64_t)r * stride;
+    const int acc = count ? clamp_count(count + (stride ? r : 0), n) : n;
+    int wl = st[1], wp = st[2];
     wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
     wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
-    state[1] = wl + acc < wc ? wl + acc : wc;
-    state[2] = (int)(((int64_t)wp + acc) % wc);
+    st[1] = wl + acc < wc ? wl + acc : wc;
+    st[2] = (int)(((int64_t)wp + acc) % wc);
+    if (stride) st[3] += acc;
+}
+
+// advance every state row after the launches that read it (shared state: one row)
+int launch_advance(int* state, const int* count, int n, int wc, int B, bool rows, hipStream_t stream) {
+    const int nrow = rows ? B : 1;
+    if (nrow <= 0) return SFA_OK;
+    ring_advance_kernel<<<dim3((unsigned)cdiv64(nrow, 256)), nrow < 256 ? nrow : 256, 0, stream>>>(
+        state, count, n, wc, nrow, rows ? 4 : 0);
+    return launch_status("ring_advance");
 }
 
 constexpr int64_t kTargetWgs = 2048;
@@ -649,10 +729,8 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
     if (a.state) multi_reduce_kernel<T, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
     else multi_reduce_kernel<T, false><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
     if ((st = launch_status("decode_multi_reduce"))) return st;
-    if (a.state && a.commit) {   // every reader of the state has finished: advance it by n
-        ring_advance_kernel<<<1, 1, 0, stream>>>(const_cast<int*>(a.state), nullptr, a.n, a.wc);
-        st = launch_status("ring_advance");
-    }
+    if (a.state && a.commit)     // every reader of the state has finished: advance it (each row) by n
+        st = launch_advance(const_cast<int*>(a.state), nullptr, a.n, a.wc, a.B, a.sstride != 0, stream);
     return st;
 }
 
@@ -681,7 +759,8 @@ size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new,
 int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
-                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state) {
+                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state,
+                        bool state_rows) {
     MultiArgs a;
     a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
     a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
@@ -700,6 +779,7 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     // dyn: (sink_len, window_len) = the full cache here; the grid covers the largest plan of any fill level and every
     // workgroup replans from the device state (workgroups of splits >= its S exit)
     a.state = state;
+    a.sstride = state && state_rows ? 4 : 0;
     a.ns = (int)sink_k->shape[2];
     a.Sw = state ? (int)max_splits(a.B, a.Hkv, a.nrb, sink_len + window_len + a.n) : a.S;
     a.scale_log2 = scale * kLog2e;
@@ -722,8 +802,9 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     else st = launch_rest<bf16_t>(a, mfma, stream);
     if (st) return st;
     if (state) {
-        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_dyn%s", dname, a.D, a.nrb, commit ? "_commit" : "");
-        else set_path("decode_multi_f32_%s_d%d_dyn%s", dname, a.D, commit ? "_commit" : "");
+        const char* dyn = state_rows ? "_rows" : "_dyn";
+        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d%s%s", dname, a.D, a.nrb, dyn, commit ? "_commit" : "");
+        else set_path("decode_multi_f32_%s_d%d%s%s", dname, a.D, dyn, commit ? "_commit" : "");
     } else {
         if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_s%d%s", dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
         else set_path("decode_multi_f32_%s_d%d_s%d%s", dname, a.D, a.S, commit ? "_commit" : "");
@@ -732,7 +813,7 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
 }
 
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream) {
+                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream, bool rows) {
     MultiArgs a{};
     a.wk = make_view(window_k), a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new);
     a.B = (int)k_new->shape[0];
@@ -741,6 +822,7 @@ int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_
     a.D = (int)k_new->shape[3];
     a.wc = (int)window_k->shape[2];
     a.state = state;
+    a.sstride = rows ? 4 : 0;
     const int es = dtype_size(k_new->dtype);
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
     const int64_t nblk = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)es / 16), 256);
@@ -753,9 +835,30 @@ int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_
         ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
         if ((st = launch_status("ring_commit"))) return st;
     }
-    ring_advance_kernel<<<1, 1, 0, stream>>>(state, count, a.n, a.wc);   // after every reader of the state
-    if ((st = launch_status("ring_advance"))) return st;
-    set_path("ring_commit_dyn");
+    if ((st = launch_advance(state, count, a.n, a.wc, a.B, rows, stream))) return st;   // after every reader of the state
+    set_path(rows ? "ring_commit_rows" : "ring_commit_dyn");
+    return SFA_OK;
+}
+
+int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                            const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
+                            int n_seq, int32_t* state, hipStream_t stream) {
+    const int es = dtype_size(k->dtype);
+    const int Hkv = (int)k->shape[1], ns = (int)sink_k->shape[2], wc = (int)window_k->shape[2];
+    const int cpr = (int)(k->shape[3] * es / 16);
+    const int64_t nblk = cdiv64((int64_t)n_seq * Hkv * (ns + wc) * cpr, 256);
+    if (nblk >= (1ll << 31)) {
+        set_error("ring_fill_varlen: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (nblk > 0) {
+        ring_fill_varlen_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(
+            make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+            cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es);
+        int st;
+        if ((st = launch_status("ring_fill_varlen"))) return st;
+    }
+    set_path("ring_fill_varlen");
     return SFA_OK;
 }
 

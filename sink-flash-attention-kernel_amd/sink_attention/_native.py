@@ -116,6 +116,14 @@ def _bind(lib):
     lib.sfa_decode_ring_multi_dyn.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, sz, f32, u32, vp]
     lib.sfa_ring_commit_dyn.restype = i32
     lib.sfa_ring_commit_dyn.argtypes = [P, P, P, P, vp, vp, vp]
+    lib.sfa_decode_ring_step_rows.restype = i32
+    lib.sfa_decode_ring_step_rows.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_multi_rows.restype = i32
+    lib.sfa_decode_ring_multi_rows.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, sz, f32, u32, vp]
+    lib.sfa_ring_commit_rows.restype = i32
+    lib.sfa_ring_commit_rows.argtypes = [P, P, P, P, vp, vp, vp]
+    lib.sfa_ring_fill_varlen.restype = i32
+    lib.sfa_ring_fill_varlen.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp]
 
 
 def lib():

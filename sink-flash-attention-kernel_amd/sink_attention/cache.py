@@ -75,6 +75,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def append(self, k: torch.Tensor, v: torch.Tensor) -> None:
         """Write decoded token(s) ``[B, H_kv, n, D]`` into the ring (oldest evicted).  No linearisation."""
+        self._refuse_per_seq("append")
         if not self.is_initialized:
             self.lazy_initialization(k)
         if not self.prefilled:      # first tokens ever: same placement as a prefill (sinks first)
@@ -91,6 +92,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def update(self, key_states, value_states, cache_kwargs: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference-compatible update: prefill returns the full input K/V, decode returns linearised [sink, window]."""
+        self._refuse_per_seq("update")
         if not self.is_initialized:
             self.lazy_initialization(key_states)
         if not self.prefilled:
@@ -100,6 +102,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def get_kv(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """Chronological ``[B, H_kv, sink_len + window_len, D]`` copy (oldest first) - only for callers that need it."""
+        self._refuse_per_seq("get_kv")
         ks, vs = [self.sink_k[:, :, :self.sink_len]], [self.sink_v[:, :, :self.sink_len]]
         if self.window_len > 0:
             if self.window_len < self.window_size or self.write_pos == 0:
@@ -113,6 +116,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     # -------------------------------------------------------------- attention
     def decode_attention(self, q: torch.Tensor, s_aux: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Single-query attention of ``q [B, H_q, 1, D]`` over the cached keys, reading both buffers in place."""
+        self._refuse_per_seq("decode_attention")
         from .decode_kernel import sink_decode_attention_ring
         return sink_decode_attention_ring(q, self.sink_k, self.sink_v, self.sink_len, self.window_k, self.window_v,
                                           self.window_len, s_aux=s_aux)
@@ -122,6 +126,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         """One generation step = ``append(k_new, v_new)`` + ``decode_attention(q)``, as ONE kernel pass once the cache
         is in steady state (``sfa_decode_ring_step``: the kernel stores the token into its ring slot and attends over
         the updated cache; no ``torch.cat``, no separate slot-write launches)."""
+        self._refuse_per_seq("decode_step")
         steady = (self.prefilled and self.window_size > 0 and k_new.shape[2] == 1 and self.window_k is not None
                   and self.window_k.is_cuda)
         if not steady:
@@ -179,12 +184,14 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``[B, H_kv, n, D]``, exactly as n successive ``decode_step`` calls would see it, WITHOUT modifying the cache
         (``sfa_decode_ring_multi``, commit off).  Speculative verify: ``out = extend_attention(q, k, v)``, then
         ``append(k[:, :, :a], v[:, :, :a])`` for the ``a`` accepted drafts - rejected ones never enter the ring."""
+        self._refuse_per_seq("extend_attention")
         return self._ring_multi(q, k_new, v_new, s_aux, commit=False)
 
     def extend_step(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
                     s_aux: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``extend_attention`` followed by the commit of all n tokens: afterwards the cache is bitwise the state that
         ``append(k_new, v_new)`` leaves (the kernels store the chunk after every read of the slots it overwrites)."""
+        self._refuse_per_seq("extend_step")
         n = q.shape[2]
         out = self._ring_multi(q, k_new, v_new, s_aux, commit=True)
         self.seen_tokens += n
@@ -254,14 +261,29 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         return N.FLAG_DECODE_ONE_PASS if self.one_pass else 0
 
     # ------------------------------------------------ device-resident state (hipGraph capture)
-    def enable_device_state(self) -> torch.Tensor:
+    def enable_device_state(self, per_sequence: bool = False) -> torch.Tensor:
         """Move the ring bookkeeping {sink_len, window_len, write_pos} to a device int32 tensor so that
         ``decode_step_dyn``, ``extend_attention_dyn``, ``extend_step_dyn`` and ``commit_dyn`` need no host-side integers:
         a whole generation or speculative step can then be captured with ``torch.cuda.graph`` and replayed (the kernels
         read and advance the state themselves; the calls may be mixed on one state).  Call after prefill.  The host-state
         calls (``append``, ``decode_step``, ``extend_step``) do not update the device state, nor the dyn calls the host
-        counters: switch with ``enable_device_state()`` / ``pull_state()``."""
+        counters: switch with ``enable_device_state()`` / ``pull_state()``.
+
+        ``per_sequence=True``: one state row ``{sink_len, window_len, write_pos, seen}`` per batch row, an int32 ``[B, 4]``
+        tensor, every row starting from the host counters (``seen = seen_tokens``).  The cache then enters per-sequence
+        mode, as after ``prefill_varlen``: the dyn calls advance each row on its own (``commit_dyn`` takes B counts) and
+        the host-state methods raise."""
+        if self._per_seq:
+            if per_sequence:
+                return self._dev_state
+            raise RuntimeError("this cache is in per-sequence mode: its state is the [B, 4] tensor of "
+                               "enable_device_state(per_sequence=True) / prefill_varlen")
         assert self.is_initialized and self.prefilled and self.window_size > 0, "prefill the cache first"
+        if per_sequence:
+            row = [self.sink_len, self.window_len, self.write_pos, self.seen_tokens]
+            self._dev_state = torch.tensor([row] * self.window_k.shape[0], dtype=torch.int32, device=self.window_k.device)
+            self._per_seq = True
+            return self._dev_state
         self._dev_state = torch.tensor([self.sink_len, self.window_len, self.write_pos], dtype=torch.int32,
                                        device=self.window_k.device)
         return self._dev_state
@@ -269,9 +291,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def pull_state(self) -> None:
         """Refresh the host-side counters from the device state (one small device-to-host copy).  ``seen_tokens`` is
         exact only while fewer than ``window_size`` tokens were committed since the last pull (the state holds no token
-        count: a full ring's ``write_pos`` is taken modulo ``window_size``)."""
+        count: a full ring's ``write_pos`` is taken modulo ``window_size``).  Per-sequence mode: ``sink_len``,
+        ``window_len``, ``write_pos`` and ``seen_tokens`` become host lists with one exact value per sequence."""
         st = getattr(self, "_dev_state", None)
-        if st is not None:
+        if st is not None and self._per_seq:
+            rows = st.tolist()
+            self.sink_len, self.window_len, self.write_pos, self.seen_tokens = ([r[i] for r in rows] for i in range(4))
+        elif st is not None:
             sl, wl, wp = st.tolist()
             W = self.window_size
             if wl < W:                       # still filling: one slot per step
@@ -286,7 +312,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def decode_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``decode_step`` with the state on the device (``sfa_decode_ring_step_dyn``): capturable into a hipGraph.
-        ``out`` (optional, [B,H_q,1,D]) lets the caller keep a static output buffer across replays."""
+        ``out`` (optional, [B,H_q,1,D]) lets the caller keep a static output buffer across replays.  Per-sequence mode
+        (``sfa_decode_ring_step_rows``): every row stores its token at its own slot and attends over its own keys."""
         import math
         from . import _native as N
         st = getattr(self, "_dev_state", None)
@@ -312,11 +339,12 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = ss["descs"]
         with torch.cuda.device(q.device):
-            rc = ss["lib"].sfa_decode_ring_step_dyn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                                    s_aux_f.data_ptr() if s_aux_f is not None else None, st.data_ptr(),
-                                                    ss["ws"].data_ptr(), ss["ws"].numel(), ss["scale"],
-                                                    self._decode_flags(N), N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_step_dyn")
+            fn = ss["lib"].sfa_decode_ring_step_rows if self._per_seq else ss["lib"].sfa_decode_ring_step_dyn
+            rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
+                    s_aux_f.data_ptr() if s_aux_f is not None else None, st.data_ptr(),
+                    ss["ws"].data_ptr(), ss["ws"].numel(), ss["scale"],
+                    self._decode_flags(N), N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_step_rows" if self._per_seq else "sfa_decode_ring_step_dyn")
         return out
 
     # ---------------------------- several new tokens with the state on the device (capturable speculative step)
@@ -324,7 +352,9 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                              s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``extend_attention`` with the state on the device (``sfa_decode_ring_multi_dyn``, commit off): capturable into a
         hipGraph, no host sync.  Neither the cache nor the device state changes.  The output is bitwise what
-        ``extend_attention`` gives at the same state.  ``out`` (optional, [B, H_q, n, D]) is a static output buffer."""
+        ``extend_attention`` gives at the same state.  ``out`` (optional, [B, H_q, n, D]) is a static output buffer.
+        Per-sequence mode (``sfa_decode_ring_multi_rows``): each row attends with its own state; ``extend_step_dyn``
+        then advances every row by n."""
         return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False)
 
     def extend_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
@@ -337,12 +367,15 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         """Store the first ``a = clamp(count, 0, n)`` tokens of a chunk ``[B, H_kv, n, D]`` into the ring and advance the
         device state (``sfa_ring_commit_dyn``): afterwards buffers and state are what ``append(k_new[:, :, :a], ...)``
         leaves.  ``count`` is a 0-d or 1-element integer tensor on the GPU (the acceptance count of a speculative step,
-        computed by torch ops); it is never read on the host."""
+        computed by torch ops); it is never read on the host.  Per-sequence mode (``sfa_ring_commit_rows``): ``count``
+        holds B values, row b commits its first ``clamp(count[b], 0, n)`` tokens."""
         from . import _native as N
         st = self._require_dyn("commit_dyn")
         if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
                 or count.dtype == torch.bool:
             raise TypeError("count must be an integer tensor")
+        if self._per_seq:
+            return self._commit_rows(k_new, v_new, count, st)
         if count.numel() != 1:
             raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
         N.require_gpu(k_new, v_new, count, self.window_k)
@@ -361,6 +394,93 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             rc = N.lib().sfa_ring_commit_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
                                              N.stream_ptr(k_new.device))
         N.check(rc, "sfa_ring_commit_dyn")
+
+    def _commit_rows(self, k_new, v_new, count, st):
+        from . import _native as N
+        B, H_kv, _w, D = self.window_k.shape
+        if count.numel() != B:
+            raise ValueError(f"count must hold B = {B} values in per-sequence mode (one per sequence), "
+                             f"got shape {tuple(count.shape)}")
+        N.require_gpu(k_new, v_new, count, self.window_k)
+        if k_new.dim() != 4 or k_new.shape[:2] != (B, H_kv) or k_new.shape[3] != D or v_new.shape != k_new.shape \
+                or k_new.shape[2] < 1:
+            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = [{B}, {H_kv}, n, {D}], got {tuple(k_new.shape)}")
+        if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
+            raise TypeError("k_new / v_new must have the cache buffers' dtype")
+        k_new, v_new = self._rows16(k_new), self._rows16(v_new)
+        cnt = count.reshape(B)
+        if cnt.dtype != torch.int32:
+            cnt = cnt.to(torch.int32)      # a cast kernel: capturable
+        cnt = cnt.contiguous()
+        wk, wv = self._ring_descs()
+        with torch.cuda.device(k_new.device):
+            rc = N.lib().sfa_ring_commit_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
+                                              N.stream_ptr(k_new.device))
+        N.check(rc, "sfa_ring_commit_rows")
+
+    # ------------------------------------------------ per-sequence state (ragged batches)
+    _per_seq = False     # set by prefill_varlen / enable_device_state(per_sequence=True)
+
+    def _refuse_per_seq(self, what):
+        if self._per_seq:
+            raise RuntimeError(f"{what}() works on the host-side state, which a cache in per-sequence mode "
+                               "(prefill_varlen / enable_device_state(per_sequence=True)) does not keep: use "
+                               "decode_step_dyn / extend_attention_dyn / extend_step_dyn / commit_dyn")
+
+    def prefill_varlen(self, k: torch.Tensor, v: torch.Tensor, cu_seqlens) -> torch.Tensor:
+        """Prefill a ragged batch: ``k`` / ``v`` ``[1, H_kv, T, D]`` hold n_seq packed sequences (sequence b = rows
+        ``cu_seqlens[b] : cu_seqlens[b + 1]``, the layout ``sink_flash_attention_varlen`` takes).  Allocates
+        ``[n_seq, H_kv, num_sink / window_size, D]`` buffers, stores every sequence with the placement a prefill of it
+        alone gives (``sfa_ring_fill_varlen``, one launch) and enters per-sequence mode; returns the ``[n_seq, 4]``
+        device state ``{sink_len, window_len, write_pos, seen}``.  ``cu_seqlens``: a device int32 tensor (not validated,
+        no sync) or a host list / CPU tensor (checked here).  The prompt attention itself is the caller's
+        ``sink_flash_attention_varlen`` call on the same pack."""
+        from . import _native as N
+        N.require_gpu(k, v)
+        if self.window_size < 1:
+            raise ValueError("prefill_varlen needs a ring of at least one slot (window_size >= 1)")
+        if k.dim() != 4 or k.shape[0] != 1 or v.shape != k.shape:
+            raise ValueError(f"k / v must be packed [1, H_kv, T, D] tensors of one shape, got {tuple(k.shape)} / "
+                             f"{tuple(v.shape)}")
+        if k.dtype not in N.SFA_DTYPE or v.dtype != k.dtype:
+            raise TypeError("k / v must share one of the dtypes float32 / float16 / bfloat16")
+        _one, H_kv, T, D = k.shape
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if cu_seqlens.dtype.is_floating_point or cu_seqlens.dtype == torch.bool or cu_seqlens.dim() != 1:
+                raise TypeError("cu_seqlens must be a 1-D integer tensor")
+            cu = cu_seqlens.to(device=k.device, dtype=torch.int32).contiguous()
+        else:
+            lst = cu_seqlens.tolist() if isinstance(cu_seqlens, torch.Tensor) else [int(x) for x in cu_seqlens]
+            if len(lst) < 2 or lst[0] != 0 or lst[-1] > T or any(b < a for a, b in zip(lst[:-1], lst[1:])):
+                raise ValueError(f"bad cu_seqlens {lst} for T={T}: need 0 = c_0 <= c_1 <= ... <= T")
+            cu = torch.tensor(lst, dtype=torch.int32, device=k.device)
+        n_seq = cu.numel() - 1
+        if n_seq < 1:
+            raise ValueError("cu_seqlens needs at least two offsets")
+        mk = lambda n: torch.zeros(n_seq, H_kv, n, D, dtype=k.dtype, device=k.device)
+        self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
+        self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
+        state = torch.empty(n_seq, 4, dtype=torch.int32, device=k.device)
+        k, v = self._rows16(k), self._rows16(v)
+        with torch.cuda.device(k.device):
+            rc = N.lib().sfa_ring_fill_varlen(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k,
+                                                                     self.window_v, k, v)),
+                                              cu.data_ptr(), n_seq, state.data_ptr(), N.stream_ptr(k.device))
+        N.check(rc, "sfa_ring_fill_varlen")
+        self.sink_len = self.window_len = self.write_pos = self.seen_tokens = 0   # not kept in this mode
+        self.is_initialized = self.prefilled = True
+        self._per_seq = True
+        self._dev_state = state
+        return state
+
+    def positions(self) -> torch.Tensor:
+        """Per-sequence mode: the ``seen`` column of the device state, ``[B]`` int32 (a view that follows the state, no
+        sync): the position the next token of each sequence takes, for per-row RoPE positions built in torch ops."""
+        st = self._require_dyn("positions")
+        if not self._per_seq:
+            raise RuntimeError("positions() needs per-sequence mode (prefill_varlen / enable_device_state(per_sequence="
+                               "True)): the shared state holds no token count")
+        return st[:, 3]
 
     def _require_dyn(self, what):
         if not (self.is_initialized and self.prefilled):
@@ -421,15 +541,17 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
-            rc = st["lib"].sfa_decode_ring_multi_dyn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                                     s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                                     1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
-                                                     st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_multi_dyn")
+            fn = st["lib"].sfa_decode_ring_multi_rows if self._per_seq else st["lib"].sfa_decode_ring_multi_dyn
+            rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
+                    s_aux_f.data_ptr() if s_aux_f is not None else None,
+                    1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
+                    st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_multi_rows" if self._per_seq else "sfa_decode_ring_multi_dyn")
         return out
 
     # ------------------------------------------------------- HF layer surface
     def get_seq_length(self, *_, **__) -> int:
+        self._refuse_per_seq("get_seq_length")
         return self.sink_len + self.window_len
 
     def get_mask_sizes(self, cache_position, *_, **__) -> Tuple[int, int]:
@@ -447,6 +569,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         idx = beam_idx.to(self.sink_k.device)
         self.sink_k, self.sink_v = self.sink_k.index_select(0, idx), self.sink_v.index_select(0, idx)
         self.window_k, self.window_v = self.window_k.index_select(0, idx), self.window_v.index_select(0, idx)
+        if self._per_seq:       # the state rows follow their sequences
+            self._dev_state = self._dev_state.index_select(0, idx.to(self._dev_state.device))
 
 
 class SinkAttentionCache(_HFCache if _HAS_HF else object):
@@ -517,6 +641,10 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     def commit_dyn(self, key_states, value_states, count, layer_idx: int) -> None:
         """``SinkCacheLayer.commit_dyn`` of one layer: store the first ``count`` (device tensor) tokens of the chunk."""
         self._layer(layer_idx).commit_dyn(key_states, value_states, count)
+
+    def prefill_varlen(self, key_states, value_states, cu_seqlens, layer_idx: int) -> torch.Tensor:
+        """``SinkCacheLayer.prefill_varlen`` of one layer: a packed ragged batch into per-sequence buffers and state."""
+        return self._layer(layer_idx).prefill_varlen(key_states, value_states, cu_seqlens)
 
     def get_seq_length(self, layer_idx: int = 0, *_, **__) -> int:
         return self.layers[layer_idx].get_seq_length() if layer_idx < len(self.layers) else 0
