@@ -355,6 +355,61 @@ int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, con
                          const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
                          const int32_t* cu_seqlens, int n_seq, int32_t* state, void* stream);
 
+/*
+ * Tree-structured speculative verification (Medusa / EAGLE / SpecInfer style): the n new tokens of a chunk form a
+ * forest, verified in one pass that reads the cache once.
+ *   parent: device int32, row b's tree at parent + b * parent_bstride, entries u in [0, n) (1 <= n <= 64);
+ *           parent_bstride = 0: one tree shared by the batch, else >= n (one row per sequence).
+ *   parent[u] in [-1, u): -1 = u hangs directly off the cache (several roots are allowed).  On the device any value
+ *           outside [-1, u) reads as -1, so the order is topological and a corrupt tree cannot loop or leave the chunk.
+ *   depth[u] = 0 for a root, depth[parent[u]] + 1 otherwise; anc[u] = u and all of its ancestors.
+ * Mask.  Query u attends to every sink row; to ring slot s with chronological position c = r - window_len
+ * (r = (s - write_pos + window_len) mod Wc, so c in [-window_len, -1]) iff c >= depth[u] - Wc + 1; to chunk token v iff
+ * v in anc[u] and depth[u] - depth[v] <= Wc - 1.  Node u thus sees exactly what the last of depth[u] + 1 successive
+ * sfa_decode_ring_step calls sees when they append its root-to-u path; parent[u] = u - 1 is the mask of
+ * sfa_decode_ring_multi, bit for bit.  s_aux enters the denominator only.
+ * Same kernels, plan, partials and reduce as sfa_decode_ring_multi (tree instances of the split kernels derive depth
+ * and ancestors in-kernel); no commit: a tree chunk is never stored whole (sfa_ring_commit_path_* stores a path).
+ * Arguments, checks and workspace (sfa_decode_multi_workspace_bytes) as for the sfa_decode_ring_multi sibling, plus
+ * n <= 64, a non-null parent and a valid parent_bstride, all checked before anything launches.
+ */
+int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                         const float* s_aux, const int32_t* parent, int64_t parent_bstride, void* workspace,
+                         size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
+/* sfa_decode_ring_tree with the shared device state of sfa_decode_ring_multi_dyn (bitwise the host-state call at that
+ * state); neither the cache nor the state changes. */
+int sfa_decode_ring_tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                             const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                             const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                             int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
+                             float scale, unsigned flags, void* stream);
+
+/* sfa_decode_ring_tree_dyn with per-sequence state rows [B][4]: row b attends with its own state and its own tree
+ * (parent + b * parent_bstride). */
+int sfa_decode_ring_tree_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                              int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
+                              float scale, unsigned flags, void* stream);
+
+/*
+ * Commit an accepted tree PATH: sfa_ring_commit_dyn / sfa_ring_commit_rows with the j-th stored token taken from chunk
+ * row path[b * path_bstride + j] (clamped into [0, n)) instead of row j.  a = clamp(count, 0, n): path tokens
+ * j in [max(0, a - Wc), a) go to ring slot (write_pos + j) mod Wc, then the state advances by a (the trailing launch
+ * of sfa_ring_commit_dyn).  Afterwards buffers and state are what append() of k_new[:, :, path[:a]] leaves.
+ *   path: device int32, path_bstride 0 (one path for the batch) or >= n.  Other arguments as for the siblings.
+ */
+int sfa_ring_commit_path_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                             const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                             int32_t* state, void* stream);
+
+int sfa_ring_commit_path_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                              int32_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

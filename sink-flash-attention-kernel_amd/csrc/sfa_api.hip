@@ -556,6 +556,77 @@ int sfa_decode_ring_multi_rows(const sfa_tensor* q, const sfa_tensor* sink_k, co
 
 namespace {
 
+// the tree-specific checks of sfa_decode_ring_tree*, after check_multi
+int check_tree(const sfa_tensor* q, const int32_t* parent, int64_t parent_bstride) {
+    const int64_t n = q->shape[2];
+    SFA_CHECK_ARG(n <= 64, "decode_tree: a tree chunk holds at most 64 nodes (got n = %lld)", (long long)n);
+    SFA_CHECK_ARG(parent != nullptr, "parent: null device pointer");
+    SFA_CHECK_ARG(parent_bstride == 0 || (parent_bstride >= n && parent_bstride < (1ll << 30)),
+                  "parent_bstride %lld: 0 (one tree shared by the batch) or >= n = %lld (one row per sequence)",
+                  (long long)parent_bstride, (long long)n);
+    return SFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                         const float* s_aux, const int32_t* parent, int64_t parent_bstride, void* workspace,
+                         size_t workspace_bytes, float scale, unsigned flags, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o, scale)))
+        return st;
+    if ((st = check_tree(q, parent, parent_bstride))) return st;
+    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;
+    if ((st = check_multi_workspace(q, k_new, sink_len + window_len + q->shape[2], workspace, workspace_bytes))) return st;
+    return decode_multi_launch(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o,
+                               s_aux, 0, workspace, scale, flags, (hipStream_t)stream, nullptr, false, parent,
+                               parent_bstride);
+}
+
+static int tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                    const sfa_tensor* window_v, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                    const float* s_aux, const int32_t* parent, int64_t parent_bstride, int32_t* state, void* workspace,
+                    size_t workspace_bytes, float scale, unsigned flags, void* stream, bool rows) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
+    if ((st = check_tree(q, parent, parent_bstride))) return st;
+    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;   // nothing to attend; a tree call never commits
+    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
+    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, 0, workspace,
+                               scale, flags, (hipStream_t)stream, state, rows, parent, parent_bstride);
+}
+
+int sfa_decode_ring_tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                             const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                             const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                             int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
+                             float scale, unsigned flags, void* stream) {
+    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
+                    workspace, workspace_bytes, scale, flags, stream, false);
+}
+
+int sfa_decode_ring_tree_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                              int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
+                              float scale, unsigned flags, void* stream) {
+    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
+                    workspace, workspace_bytes, scale, flags, stream, true);
+}
+
+}  // extern "C"
+
+namespace {
+
 // every host-checkable argument of sfa_ring_commit_dyn / _rows; nothing launches
 int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                  const sfa_tensor* v_new, const int32_t* count, int32_t* state) {
@@ -607,6 +678,34 @@ int sfa_ring_commit_rows(const sfa_tensor* window_k, const sfa_tensor* window_v,
     if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
     if (k_new->shape[0] == 0) return SFA_OK;
     return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, true);
+}
+
+static int commit_path(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                       const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                       int32_t* state, void* stream, bool rows) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
+    const int64_t n = k_new->shape[2];
+    SFA_CHECK_ARG(path != nullptr, "path: null device pointer");
+    SFA_CHECK_ARG(path_bstride == 0 || (path_bstride >= n && path_bstride < (1ll << 30)),
+                  "path_bstride %lld: 0 (one path shared by the batch) or >= n = %lld (one row per sequence)",
+                  (long long)path_bstride, (long long)n);
+    if (rows && k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, rows, path,
+                                  path_bstride);
+}
+
+int sfa_ring_commit_path_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                             const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                             int32_t* state, void* stream) {
+    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, false);
+}
+
+int sfa_ring_commit_path_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                              const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                              int32_t* state, void* stream) {
+    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, true);
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

@@ -76,6 +76,12 @@ struct MultiArgs {
     int sstride;                 // state row stride: 0 = one state shared by the batch, 4 = per-sequence rows [B][4]
     int ns;                      // sink buffer rows (dyn: clamp of sink_len)
     int want;                    // want_splits(B, Hkv, nrb): the workgroup-target cap of the split count
+    // tree calls (sfa_decode_ring_tree*): parent[b * pstride + u], u < n <= 64 (pstride 0: one tree shared by the batch)
+    const int* parent;
+    int pstride;
+    // path commit (sfa_ring_commit_path_*): chunk token path[b * pathstride + j] is the j-th one stored
+    const int* path;
+    int pathstride;
 };
 
 inline __host__ __device__ int cdiv_i(int x, int y) { return (x + y - 1) / y; }
@@ -195,6 +201,67 @@ __device__ __forceinline__ bool key_visible(const MultiArgs& a, const Fill& f, c
     return c <= t && c >= t - a.wc + 1;
 }
 
+// ---- tree chunks.  Node u sees ring position c iff c >= depth[u] - Wc + 1 and chunk token v iff
+// v in anc[u] and depth[u] - depth[v] <= Wc - 1: the chain's mask with the query index replaced by the depth and the
+// prefix by the ancestor set.  `vis` is the second set as a bitmask over the chunk (n <= 64).
+struct TreeNode {
+    int depth;
+    uint64_t vis;
+};
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
+    const unsigned lo = __shfl((unsigned)x, src), hi = __shfl((unsigned)(x >> 32), src);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// every lane of the wave must call it (cross-lane reads); lane u < n returns node u of batch row b's tree.  One
+// coalesced load of parent, then pointer jumping: after round r, j = the 2^r-th ancestor (-1: above the root), d = the
+// edges from u up to j (to the root when j = -1), anc = u and its ancestors below j; 6 rounds cover depth 63.  When
+// the window clips the chunk (Wc < n), the Wc-th ancestor k is composed from the same jumps (bits of Wc) and
+// vis = anc[u] minus anc[k].  An entry outside [-1, u) reads as -1, so a corrupt tree cannot loop or leave the chunk.
+__device__ __forceinline__ TreeNode tree_node(const MultiArgs& a, int b, int lane) {
+    int p = lane < a.n ? a.parent[(int64_t)b * a.pstride + lane] : -1;
+    if (p < -1 || p >= lane) p = -1;
+    int j = p, d = p >= 0 ? 1 : 0;
+    uint64_t anc = 1ull << lane;
+    const bool clip = a.wc < a.n;        // otherwise depth <= n - 1 <= Wc - 1: every ancestor is in the window
+    int kth = lane;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        if (clip && ((a.wc >> r) & 1)) {
+            const int x = __shfl(j, kth < 0 ? lane : kth);
+            kth = kth < 0 ? -1 : x;
+        }
+        const int src = j < 0 ? lane : j;
+        const int jj = __shfl(j, src), dd = __shfl(d, src);
+        const uint64_t aa = shfl64(anc, src);
+        if (j >= 0) d += dd, anc |= aa, j = jj;
+    }
+    if (clip) {
+        const uint64_t ak = shfl64(anc, kth < 0 ? lane : kth);
+        if (kth >= 0) anc &= ~ak;
+    }
+    return TreeNode{d, anc};
+}
+
+// chunk tiles of a tree call: dead when no row of the block sees a key of the tile (vor = OR of the rows' vis), edge
+// otherwise; sink and ring tiles as the chain's, against the block's depth range [dlo, dhi]
+template <bool Tree>
+__device__ __forceinline__ int tile_class_t(const MultiArgs& a, const TileInfo& ti, int dlo, int dhi, uint64_t vor) {
+    if (Tree && ti.seg == 2) {
+        const uint64_t m = ti.count >= 64 ? ~0ull : ((1ull << ti.count) - 1);
+        return ((vor >> ti.start) & m) ? 2 : 0;
+    }
+    return tile_class(a, ti, dlo, dhi);
+}
+
+template <bool Tree>
+__device__ __forceinline__ bool key_visible_t(const MultiArgs& a, const Fill& f, const TileInfo& ti, int kk, int t,
+                                              uint64_t vis) {
+    if (Tree && ti.seg == 2) return kk < ti.count && ((vis >> (ti.start + kk)) & 1);
+    return key_visible(a, f, ti, kk, t);
+}
+
 __device__ __forceinline__ float half_swap_max(float x) {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
@@ -211,7 +278,7 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-template <typename T, int D, bool Dyn>
+template <typename T, int D, bool Dyn, bool Tree>
 __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -242,8 +309,30 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     const int rho = 32 * rb + r;
     const bool row_live = rho < a.R;
     const int tq = row_live ? rho / a.G : 0;            // the lane's query index (dead rows: any, never stored)
-    const int tmin = (32 * rb) / a.G;
-    const int tmax = ((32 * rb + 31 < a.R - 1) ? 32 * rb + 31 : a.R - 1) / a.G;
+    int tmin = (32 * rb) / a.G;
+    int tmax = ((32 * rb + 31 < a.R - 1) ? 32 * rb + 31 : a.R - 1) / a.G;
+    // tree: the lane's row is node tq at depth td; [tmin, tmax] becomes the block's depth range over its live rows
+    int td = tq;
+    uint64_t tvis = 0, vor = 0;
+    if constexpr (Tree) {
+        const TreeNode me = tree_node(a, b, lane);
+        // every lane runs the cross-lane reads (a source lane masked off by a branch would read as 0), then selects
+        td = __shfl(me.depth, tq);
+        const uint64_t v = shfl64(me.vis, tq);
+        tvis = row_live ? v : 0;
+        int lo = row_live ? td : INT_MAX, hi = row_live ? td : -1;
+        vor = tvis;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            lo = min(lo, __shfl_xor(lo, s));
+            hi = max(hi, __shfl_xor(hi, s));
+            vor |= shfl64(vor, lane ^ s);
+        }
+        tmin = __builtin_amdgcn_readfirstlane(lo);   // wave-uniform: keep the tile classification scalar
+        tmax = __builtin_amdgcn_readfirstlane(hi);
+        vor = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(vor >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)vor);
+    }
 
     // ---- Q fragments: B operand of X^T = K Q^T; lane (r, h) holds Q[row r][16 ks + 8 h .. +8)
     frag qf[DK];
@@ -305,7 +394,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
             ti = tile_info(a, f, i, b, hk, es);
-            cls = tile_class(a, ti, tmin, tmax);
+            cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor);
             if (cls != 0) break;
         }
         return i;
@@ -336,7 +425,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
-                s[i] = key_visible(a, f, cur, kk, tq) ? s[i] : -INFINITY;
+                s[i] = key_visible_t<Tree>(a, f, cur, kk, td, tvis) ? s[i] : -INFINITY;
             }
         }
         float mx = -INFINITY;
@@ -439,7 +528,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
 }
 
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
-template <typename T, bool Dyn>
+template <typename T, bool Dyn, bool Tree>
 __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
@@ -465,13 +554,22 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
         acc[j] = 0.f;
     }
     float m = -INFINITY, l = 0.f;
+    int td = t;   // tree: the row's node t at depth td, chunk keys vis (wave-uniform)
+    uint64_t vis = 0;
+    if constexpr (Tree) {
+        const TreeNode me = tree_node(a, b, lane);
+        td = __builtin_amdgcn_readfirstlane(__shfl(me.depth, t));
+        const uint64_t v = shfl64(me.vis, t);
+        vis = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
+    }
     const int tbeg = split * f.tps;
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
         const TileInfo ti = tile_info(a, f, i, b, hk, es);
-        if (tile_class(a, ti, t, t) == 0) continue;
+        if (tile_class_t<Tree>(a, ti, td, td, vis) == 0) continue;
         for (int kk = 0; kk < ti.count; ++kk) {
-            if (!key_visible(a, f, ti, kk, t)) continue;
+            if (!key_visible_t<Tree>(a, f, ti, kk, td, vis)) continue;
             const T* kp = reinterpret_cast<const T*>(ti.k + kk * ti.ksn);
             const T* vp = reinterpret_cast<const T*>(ti.v + kk * ti.vsn);
             float x = 0.f;
@@ -513,6 +611,8 @@ __device__ __forceinline__ int clamp_count(const int* count, int n) {
 // tokens a commit can store.  Row b stores acc = clamp(count, 0, n) tokens (all n without a count): piece j is chunk
 // token first + j with first = max(0, acc - Wc), stored only if < acc -> ring slot (write_pos + t) mod Wc, write_pos
 // of row b's state.  count: one value shared by the batch, or [B] with per-sequence state.
+// Path: the j-th stored token is chunk row path[b * pathstride + j] (clamped into [0, n)) instead of row j.
+template <bool Path = false>
 __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, int es, const int* count) {
     const int cpr = a.D * es / 16;
     const int nslot = a.n < a.wc ? a.n : a.wc;
@@ -527,9 +627,14 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
     const int t = (last > a.wc ? last - a.wc : 0) + j;
     if (t >= last) return;
     const int slot = (int)(((int64_t)state_wp(a, b) + t) % a.wc);
+    int src = t;
+    if constexpr (Path) {
+        src = a.path[(int64_t)b * a.pathstride + t];
+        src = src < 0 ? 0 : (src >= a.n ? a.n - 1 : src);
+    }
     const int64_t so = (int64_t)ch * 16;
-    const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)t * a.kn.sn) * es + so;
-    const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)t * a.vn.sn) * es + so;
+    const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)src * a.kn.sn) * es + so;
+    const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)src * a.vn.sn) * es + so;
     char* kd = a.wk.ptr + ((int64_t)b * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
     char* vd = a.wv.ptr + ((int64_t)b * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
     *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
@@ -590,6 +695,12 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
 // ring_advance_kernel moves it on afterwards.
 __global__ __launch_bounds__(256) void ring_commit_kernel(MultiArgs a, const int* count, int es) {
     commit_piece(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
+}
+
+// sfa_ring_commit_path_dyn / _rows: the same with the j-th stored token taken from chunk row path[b][j] (a tree's
+// accepted root-to-leaf path), so that tokens [max(0, a - Wc), a) of the path go to slot (write_pos + j) mod Wc
+__global__ __launch_bounds__(256) void ring_commit_path_kernel(MultiArgs a, const int* count, int es) {
+    commit_piece<true>(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
 }
 
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
@@ -691,8 +802,14 @@ bool mfma_head_dim(int D) { return D == 64 || D == 80 || D == 96 || D == 128; }
 template <typename T, int D>
 int launch_mfma(const MultiArgs& a, hipStream_t stream) {
     const int64_t nblk = (int64_t)a.B * a.Hkv * a.Sw * a.nrb;
-    if (a.state) multi_split_mfma_kernel<T, D, true><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
-    else multi_split_mfma_kernel<T, D, false><<<dim3((unsigned)nblk), kWaves * 64, 0, stream>>>(a);
+    const dim3 grid((unsigned)nblk);
+    if (a.parent) {
+        if (a.state) multi_split_mfma_kernel<T, D, true, true><<<grid, kWaves * 64, 0, stream>>>(a);
+        else multi_split_mfma_kernel<T, D, false, true><<<grid, kWaves * 64, 0, stream>>>(a);
+        return launch_status("decode_tree_mfma");
+    }
+    if (a.state) multi_split_mfma_kernel<T, D, true, false><<<grid, kWaves * 64, 0, stream>>>(a);
+    else multi_split_mfma_kernel<T, D, false, false><<<grid, kWaves * 64, 0, stream>>>(a);
     return launch_status("decode_multi_mfma");
 }
 
@@ -715,9 +832,15 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
     if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
-        if (a.state) multi_split_f32_kernel<T, true><<<grid, 256, 0, stream>>>(a);
-        else multi_split_f32_kernel<T, false><<<grid, 256, 0, stream>>>(a);
-        st = launch_status("decode_multi_f32");
+        if (a.parent) {
+            if (a.state) multi_split_f32_kernel<T, true, true><<<grid, 256, 0, stream>>>(a);
+            else multi_split_f32_kernel<T, false, true><<<grid, 256, 0, stream>>>(a);
+            st = launch_status("decode_tree_f32");
+        } else {
+            if (a.state) multi_split_f32_kernel<T, true, false><<<grid, 256, 0, stream>>>(a);
+            else multi_split_f32_kernel<T, false, false><<<grid, 256, 0, stream>>>(a);
+            st = launch_status("decode_multi_f32");
+        }
     }
     if (st) return st;
     const int nred = (int)cdiv64(rows, 4);
@@ -760,8 +883,10 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
                         int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state,
-                        bool state_rows) {
+                        bool state_rows, const int32_t* parent, int64_t parent_bstride) {
     MultiArgs a;
+    a.parent = parent, a.pstride = (int)parent_bstride;   // tree call (never with commit)
+    a.path = nullptr, a.pathstride = 0;
     a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
     a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
     a.s_aux = s_aux;
@@ -801,20 +926,23 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     else if (dt == SFA_DTYPE_F16) st = launch_rest<f16_t>(a, mfma, stream);
     else st = launch_rest<bf16_t>(a, mfma, stream);
     if (st) return st;
+    const char* fam = parent ? "tree" : "multi";
     if (state) {
         const char* dyn = state_rows ? "_rows" : "_dyn";
-        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d%s%s", dname, a.D, a.nrb, dyn, commit ? "_commit" : "");
-        else set_path("decode_multi_f32_%s_d%d%s%s", dname, a.D, dyn, commit ? "_commit" : "");
+        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d%s%s", fam, dname, a.D, a.nrb, dyn, commit ? "_commit" : "");
+        else set_path("decode_%s_f32_%s_d%d%s%s", fam, dname, a.D, dyn, commit ? "_commit" : "");
     } else {
-        if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_s%d%s", dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
-        else set_path("decode_multi_f32_%s_d%d_s%d%s", dname, a.D, a.S, commit ? "_commit" : "");
+        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_s%d%s", fam, dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
+        else set_path("decode_%s_f32_%s_d%d_s%d%s", fam, dname, a.D, a.S, commit ? "_commit" : "");
     }
     return SFA_OK;
 }
 
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream, bool rows) {
+                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream, bool rows,
+                           const int32_t* path, int64_t path_bstride) {
     MultiArgs a{};
+    a.path = path, a.pathstride = (int)path_bstride;
     a.wk = make_view(window_k), a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new);
     a.B = (int)k_new->shape[0];
     a.Hkv = (int)k_new->shape[1];
@@ -832,11 +960,13 @@ int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_
     }
     int st;
     if (nblk > 0) {
-        ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
-        if ((st = launch_status("ring_commit"))) return st;
+        if (path) ring_commit_path_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        else ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        if ((st = launch_status(path ? "ring_commit_path" : "ring_commit"))) return st;
     }
     if ((st = launch_advance(state, count, a.n, a.wc, a.B, rows, stream))) return st;   // after every reader of the state
-    set_path(rows ? "ring_commit_rows" : "ring_commit_dyn");
+    if (path) set_path(rows ? "ring_commit_path_rows" : "ring_commit_path_dyn");
+    else set_path(rows ? "ring_commit_rows" : "ring_commit_dyn");
     return SFA_OK;
 }
 

@@ -60,11 +60,15 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
                         int commit, void* workspace, float scale, unsigned flags, hipStream_t stream,
                         int32_t* state = nullptr,    // dyn: sink_len / window_len = the full cache, write_pos = 0
-                        bool rows = false);          // state = per-sequence rows [B][4] (sfa_decode_ring_multi_rows)
+                        bool rows = false,           // state = per-sequence rows [B][4] (sfa_decode_ring_multi_rows)
+                        const int32_t* parent = nullptr,   // tree chunk (sfa_decode_ring_tree*, n <= 64, no commit)
+                        int64_t parent_bstride = 0);
+
 // sfa_ring_commit_dyn / _rows: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                            const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream,
-                           bool rows = false);
+                           bool rows = false, const int32_t* path = nullptr,   // path: sfa_ring_commit_path_*
+                           int64_t path_bstride = 0);
 // sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,

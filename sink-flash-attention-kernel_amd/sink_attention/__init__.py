@@ -5,8 +5,10 @@ and ``unpatch_verl`` (plus the sink + ring KV cache with a copy-free decode, the
 sequence-parallel helpers and packed-sequence attention); kernels are hand-written HIP
 behind libsfa.so (no Triton)."""
 from .sink_flash_attention import sink_flash_attention, SinkFlashAttentionFunc
-from .decode_kernel import sink_decode_attention, sink_decode_attention_ring, sink_decode_attention_ring_multi
+from .decode_kernel import (sink_decode_attention, sink_decode_attention_ring, sink_decode_attention_ring_multi,
+                            sink_decode_attention_ring_tree)
 from .cache import SinkCacheLayer, SinkAttentionCache
+from .spec_tree import tree_depth, tree_ancestor_mask, greedy_accept
 from .verl_patch import patch_verl_with_sink_attention, unpatch_verl
 from .generate_patch import patch_for_generation, unpatch_generation
 from .sp_utils import prepare_sink_kv_for_sp, reduce_sink_kv_grads, SinkAttentionSPWrapper
@@ -23,6 +25,10 @@ __all__ = [
     "SinkFlashAttentionFunc",
     "sink_decode_attention_ring",
     "sink_decode_attention_ring_multi",
+    "sink_decode_attention_ring_tree",
+    "tree_depth",
+    "tree_ancestor_mask",
+    "greedy_accept",
     "SinkCacheLayer",
     "SinkAttentionCache",
     "patch_for_generation",

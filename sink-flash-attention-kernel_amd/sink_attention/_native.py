@@ -122,6 +122,16 @@ def _bind(lib):
     lib.sfa_decode_ring_multi_rows.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, sz, f32, u32, vp]
     lib.sfa_ring_commit_rows.restype = i32
     lib.sfa_ring_commit_rows.argtypes = [P, P, P, P, vp, vp, vp]
+    lib.sfa_decode_ring_tree.restype = i32
+    lib.sfa_decode_ring_tree.argtypes = [P, P, P, i64, P, P, i64, i64, P, P, P, vp, vp, i64, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_tree_dyn.restype = i32
+    lib.sfa_decode_ring_tree_dyn.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i64, vp, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_tree_rows.restype = i32
+    lib.sfa_decode_ring_tree_rows.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i64, vp, vp, sz, f32, u32, vp]
+    lib.sfa_ring_commit_path_dyn.restype = i32
+    lib.sfa_ring_commit_path_dyn.argtypes = [P, P, P, P, vp, vp, i64, vp, vp]
+    lib.sfa_ring_commit_path_rows.restype = i32
+    lib.sfa_ring_commit_path_rows.argtypes = [P, P, P, P, vp, vp, i64, vp, vp]
     lib.sfa_ring_fill_varlen.restype = i32
     lib.sfa_ring_fill_varlen.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp]
 

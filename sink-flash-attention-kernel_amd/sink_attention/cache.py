@@ -199,7 +199,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         self.window_len = min(self.window_len + n, self.window_size)
         return out
 
-    def _ring_multi(self, q, k_new, v_new, s_aux, commit):
+    def _ring_multi(self, q, k_new, v_new, s_aux, commit, tree=None):
         """sfa_decode_ring_multi with the per-layer constants (buffer descriptors, workspace for the full cache) built once
         per chunk shape, as _ring_step does."""
         import math
@@ -244,12 +244,19 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
-            rc = st["lib"].sfa_decode_ring_multi(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
-                                                 self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                                 s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                                 1 if commit else 0, st["ws"].data_ptr(), st["ws"].numel(),
-                                                 st["scale"], 0, N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_multi")
+            if tree is not None:
+                rc = st["lib"].sfa_decode_ring_tree(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
+                                                    self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                                    s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                    tree[0].data_ptr(), tree[1], st["ws"].data_ptr(), st["ws"].numel(),
+                                                    st["scale"], 0, N.stream_ptr(q.device))
+            else:
+                rc = st["lib"].sfa_decode_ring_multi(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
+                                                     self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                                     s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                     1 if commit else 0, st["ws"].data_ptr(), st["ws"].numel(),
+                                                     st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_tree" if tree is not None else "sfa_decode_ring_multi")
         return out
 
     one_pass = False     # opt-in: SFA_FLAG_DECODE_ONE_PASS (last-arriver fold inside the split kernel, one launch)
@@ -369,13 +376,16 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         leaves.  ``count`` is a 0-d or 1-element integer tensor on the GPU (the acceptance count of a speculative step,
         computed by torch ops); it is never read on the host.  Per-sequence mode (``sfa_ring_commit_rows``): ``count``
         holds B values, row b commits its first ``clamp(count[b], 0, n)`` tokens."""
+        return self._commit_dyn(k_new, v_new, count, None)
+
+    def _commit_dyn(self, k_new, v_new, count, path):
         from . import _native as N
-        st = self._require_dyn("commit_dyn")
+        st = self._require_dyn("commit_path_dyn" if path is not None else "commit_dyn")
         if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
                 or count.dtype == torch.bool:
             raise TypeError("count must be an integer tensor")
         if self._per_seq:
-            return self._commit_rows(k_new, v_new, count, st)
+            return self._commit_rows(k_new, v_new, count, st, path)
         if count.numel() != 1:
             raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
         N.require_gpu(k_new, v_new, count, self.window_k)
@@ -390,12 +400,20 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if cnt.dtype != torch.int32:
             cnt = cnt.to(torch.int32)      # a cast kernel: capturable
         wk, wv = self._ring_descs()
+        if path is not None:
+            from .decode_kernel import tree_path_dev
+            pt, pstride = tree_path_dev(path, B, k_new.shape[2], k_new.device)
+            with torch.cuda.device(k_new.device):
+                rc = N.lib().sfa_ring_commit_path_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), pt.data_ptr(),
+                                                      pstride, st.data_ptr(), N.stream_ptr(k_new.device))
+            N.check(rc, "sfa_ring_commit_path_dyn")
+            return
         with torch.cuda.device(k_new.device):
             rc = N.lib().sfa_ring_commit_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
                                              N.stream_ptr(k_new.device))
         N.check(rc, "sfa_ring_commit_dyn")
 
-    def _commit_rows(self, k_new, v_new, count, st):
+    def _commit_rows(self, k_new, v_new, count, st, path=None):
         from . import _native as N
         B, H_kv, _w, D = self.window_k.shape
         if count.numel() != B:
@@ -413,10 +431,78 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             cnt = cnt.to(torch.int32)      # a cast kernel: capturable
         cnt = cnt.contiguous()
         wk, wv = self._ring_descs()
+        if path is not None:
+            from .decode_kernel import tree_path_dev
+            pt, pstride = tree_path_dev(path, B, k_new.shape[2], k_new.device)
+            with torch.cuda.device(k_new.device):
+                rc = N.lib().sfa_ring_commit_path_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
+                                                       pt.data_ptr(), pstride, st.data_ptr(), N.stream_ptr(k_new.device))
+            N.check(rc, "sfa_ring_commit_path_rows")
+            return
         with torch.cuda.device(k_new.device):
             rc = N.lib().sfa_ring_commit_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
                                               N.stream_ptr(k_new.device))
         N.check(rc, "sfa_ring_commit_rows")
+
+    # ------------------------------- tree-structured speculative verify (Medusa / EAGLE / SpecInfer draft trees)
+    def extend_attention_tree(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, parent,
+                              s_aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Verify a draft TREE of n <= 64 nodes in one pass (``sfa_decode_ring_tree``), host state, cache untouched.
+        ``parent`` ([n] shared or [B, n]; list or integer tensor): ``parent[u]`` in [-1, u), -1 = a root hanging off the
+        cache; checked on the host (a device tensor is synced).  Row u of ``q`` / ``k_new`` / ``v_new`` is node u; it
+        attends to what the last of ``depth[u] + 1`` ``decode_step`` calls appending its root-to-u path would see
+        (RoPE position of node u: ``seen_tokens + depth[u]``, see ``spec_tree.tree_depth``).  A chain
+        (``parent = [-1, 0, ..., n - 2]``) gives ``extend_attention`` bitwise.  Commit the accepted path with
+        ``commit_path``."""
+        self._refuse_per_seq("extend_attention_tree")
+        from .decode_kernel import tree_parent_host
+        tree = tree_parent_host(parent, q.shape[0], q.shape[2], q.device)
+        return self._ring_multi(q, k_new, v_new, s_aux, commit=False, tree=tree)
+
+    def extend_attention_tree_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                                  parent: torch.Tensor, s_aux: Optional[torch.Tensor] = None,
+                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``extend_attention_tree`` with the state on the device (``sfa_decode_ring_tree_dyn``; per-sequence mode
+        ``sfa_decode_ring_tree_rows``, row b with its own state and tree): capturable, no host sync, neither the cache
+        nor the state changes.  ``parent`` is an integer tensor ([n] or [B, n]) that is never read on the host: an entry
+        outside [-1, u) reads as -1 (a root)."""
+        from .decode_kernel import tree_parent_dev
+        if q.shape[2] > 64:
+            raise ValueError(f"a tree chunk holds at most 64 nodes, got n = {q.shape[2]}")
+        tree = tree_parent_dev(parent, q.shape[0], q.shape[2], q.device)
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False, tree=tree)
+
+    def commit_path_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, path: torch.Tensor,
+                        count: torch.Tensor) -> None:
+        """Store an accepted tree path (``sfa_ring_commit_path_dyn`` / ``_rows``): with ``a = clamp(count, 0, n)`` the
+        chunk rows ``path[:a]`` (``path`` [n] or [B, n], entries clamped into [0, n)) enter the ring in that order and
+        the device state advances by a - buffers and state are then what ``append(k_new[:, :, path[:a]], ...)`` leaves.
+        ``count`` follows the rules of ``commit_dyn`` (one value, or B values in per-sequence mode).  No host sync."""
+        if not isinstance(path, torch.Tensor):
+            raise TypeError("path must be an integer tensor")
+        return self._commit_dyn(k_new, v_new, count, path)
+
+    def commit_path(self, k_new: torch.Tensor, v_new: torch.Tensor, path) -> None:
+        """Host-state commit of a tree path: ``append`` of the chunk rows ``path`` ([a] shared or [B, a]; list or
+        integer tensor, entries in [0, n), checked on the host) in that order."""
+        self._refuse_per_seq("commit_path")
+        n = k_new.shape[2]
+        p = path if isinstance(path, torch.Tensor) else torch.tensor(path, dtype=torch.long)
+        if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool or p.dim() not in (1, 2) or \
+                (p.dim() == 2 and p.shape[0] != k_new.shape[0]):
+            raise ValueError(f"path must be an integer [a] or [B, a] index, got {tuple(p.shape)} {p.dtype}")
+        h = p.detach().cpu().long()
+        if h.numel() and bool(((h < 0) | (h >= n)).any()):
+            raise ValueError(f"path entries must lie in [0, {n}): got {h.tolist()}")
+        if h.shape[-1] == 0:
+            return
+        idx = h.to(k_new.device)
+        if idx.dim() == 1:
+            kk, vv = k_new.index_select(2, idx), v_new.index_select(2, idx)
+        else:
+            g = idx[:, None, :, None].expand(k_new.shape[0], k_new.shape[1], idx.shape[1], k_new.shape[3])
+            kk, vv = k_new.gather(2, g), v_new.gather(2, g)
+        self.append(kk, vv)
 
     # ------------------------------------------------ per-sequence state (ragged batches)
     _per_seq = False     # set by prefill_varlen / enable_device_state(per_sequence=True)
@@ -508,12 +594,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             self._ring_desc = rd
         return rd[1]
 
-    def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit):
+    def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit, tree=None):
         """sfa_decode_ring_multi_dyn with the per-layer constants (buffer descriptors, a workspace for the full cache plus
         the chunk) built once per chunk shape, as _ring_multi does."""
         import math
         from . import _native as N
-        dev_state = self._require_dyn("extend_step_dyn" if commit else "extend_attention_dyn")
+        dev_state = self._require_dyn("extend_attention_tree_dyn" if tree is not None else
+                                      "extend_step_dyn" if commit else "extend_attention_dyn")
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
         B, H_q, n, D = q.shape
         H_kv = self.sink_k.shape[1]
@@ -541,12 +628,19 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
-            fn = st["lib"].sfa_decode_ring_multi_rows if self._per_seq else st["lib"].sfa_decode_ring_multi_dyn
-            rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                    s_aux_f.data_ptr() if s_aux_f is not None else None,
-                    1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
-                    st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_multi_rows" if self._per_seq else "sfa_decode_ring_multi_dyn")
+            if tree is not None:
+                name = "sfa_decode_ring_tree_rows" if self._per_seq else "sfa_decode_ring_tree_dyn"
+                rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                              s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                              tree[0].data_ptr(), tree[1], dev_state.data_ptr(), st["ws"].data_ptr(),
+                                              st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
+            else:
+                name = "sfa_decode_ring_multi_rows" if self._per_seq else "sfa_decode_ring_multi_dyn"
+                rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
+                                              s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                              1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
+                                              st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, name)
         return out
 
     # ------------------------------------------------------- HF layer surface
@@ -641,6 +735,25 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     def commit_dyn(self, key_states, value_states, count, layer_idx: int) -> None:
         """``SinkCacheLayer.commit_dyn`` of one layer: store the first ``count`` (device tensor) tokens of the chunk."""
         self._layer(layer_idx).commit_dyn(key_states, value_states, count)
+
+    def extend_attention_tree(self, q, key_states, value_states, parent, layer_idx: int, s_aux=None):
+        """``SinkCacheLayer.extend_attention_tree`` of one layer: verify a draft tree, host state, nothing committed."""
+        return self._layer(layer_idx).extend_attention_tree(q, key_states, value_states, parent, s_aux=s_aux)
+
+    def extend_attention_tree_dyn(self, q, key_states, value_states, parent, layer_idx: int, s_aux=None, out=None):
+        """``SinkCacheLayer.extend_attention_tree_dyn`` of one layer: verify a draft tree, state on the device."""
+        return self._layer(layer_idx).extend_attention_tree_dyn(q, key_states, value_states, parent, s_aux=s_aux,
+                                                                out=out)
+
+    def commit_path(self, key_states, value_states, path, layer_idx: int) -> None:
+        """``SinkCacheLayer.commit_path`` of one layer: append the chunk rows of an accepted path (host state)."""
+        self._layer(layer_idx).commit_path(key_states, value_states, path)
+        if layer_idx == 0:
+            self._seen_tokens = self.layers[0].seen_tokens
+
+    def commit_path_dyn(self, key_states, value_states, path, count, layer_idx: int) -> None:
+        """``SinkCacheLayer.commit_path_dyn`` of one layer: store the first ``count`` (device) rows of ``path``."""
+        self._layer(layer_idx).commit_path_dyn(key_states, value_states, path, count)
 
     def prefill_varlen(self, key_states, value_states, cu_seqlens, layer_idx: int) -> torch.Tensor:
         """``SinkCacheLayer.prefill_varlen`` of one layer: a packed ragged batch into per-sequence buffers and state."""

@@ -147,6 +147,62 @@ def sink_decode_attention_ring_multi(q: torch.Tensor, sink_k: torch.Tensor, sink
     (write_pos + t) mod Wc (``window_k`` / ``window_v`` modified IN PLACE); the caller advances its counters.
     q / k_new / v_new may be strided views (e.g. [B,n,H,D] transposed): no copy when the rows are 16-byte aligned.
     """
+    return _ring_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, s_aux,
+                       commit, None)
+
+
+def tree_parent_host(parent, B: int, n: int, device) -> tuple:
+    """Validate a tree's ``parent`` ([n] shared, or [B, n] one tree per sequence; list or tensor) on the host - every
+    entry of node u in [-1, u), n <= 64 - and return (device int32 tensor, batch stride).  Syncs when it is a device
+    tensor: the host-state tree calls only."""
+    t = parent if isinstance(parent, torch.Tensor) else torch.tensor(parent)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError("parent must hold integers")
+    if not (1 <= n <= 64):
+        raise ValueError(f"a tree chunk holds 1 to 64 nodes, got n = {n}")
+    if t.dim() not in (1, 2) or t.shape[-1] != n or (t.dim() == 2 and t.shape[0] != B):
+        raise ValueError(f"parent must be [n] or [B, n] = [{B}, {n}], got {tuple(t.shape)}")
+    h = t.detach().cpu().long()
+    u = torch.arange(n)
+    if bool(((h < -1) | (h >= u)).any()):
+        raise ValueError(f"parent[u] must lie in [-1, u) for every node u: got {h.tolist()}")
+    return tree_parent_dev(t, B, n, device)
+
+
+def tree_parent_dev(t: torch.Tensor, B: int, n: int, device) -> tuple:
+    """(device int32 contiguous tensor, batch stride) of a [n] / [B, n] index tensor; no sync, no value check (the
+    kernels clamp).  A cast / copy kernel at most: capturable."""
+    if not isinstance(t, torch.Tensor) or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError("tree index tensors (parent / path) must be integer tensors")
+    if t.dim() not in (1, 2) or t.shape[-1] != n or (t.dim() == 2 and t.shape[0] != B):
+        raise ValueError(f"tree index tensors must be [n] or [B, n] = [{B}, {n}], got {tuple(t.shape)}")
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    return t, (0 if t.dim() == 1 else n)
+
+
+def tree_path_dev(t: torch.Tensor, B: int, n: int, device) -> tuple:
+    """The accepted path of a tree commit as (device int32 tensor, batch stride); entries clamped on the device."""
+    return tree_parent_dev(t, B, n, device)
+
+
+def sink_decode_attention_ring_tree(q: torch.Tensor, sink_k: torch.Tensor, sink_v: torch.Tensor, sink_len: int,
+                                    window_k: torch.Tensor, window_v: torch.Tensor, window_len: int, write_pos: int,
+                                    k_new: torch.Tensor, v_new: torch.Tensor, parent, s_aux: torch.Tensor = None
+                                    ) -> torch.Tensor:
+    """Tree-structured speculative verify over a sink buffer + window ring in one pass (``sfa_decode_ring_tree``): the n
+    chunk tokens (n <= 64) form a forest given by ``parent`` ([n] shared or [B, n]; ``parent[u]`` in [-1, u), -1 = a
+    root that hangs off the cache; validated here).  Node u sees what the last of ``depth[u] + 1`` single-token steps
+    appending its root-to-u path would see: every sink row, ring keys within ``Wc - 1 - depth[u]`` of the newest, and
+    its ancestors within the window.  The cache is never modified.  Other arguments as for
+    ``sink_decode_attention_ring_multi``; ``parent = [-1, 0, 1, ..., n - 2]`` gives its output bitwise."""
+    B, n = q.shape[0], q.shape[2]
+    par = tree_parent_host(parent, B, n, q.device)
+    return _ring_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, s_aux,
+                       False, par)
+
+
+def _ring_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, s_aux, commit,
+                tree):
     N.require_gpu(q, sink_k, sink_v, window_k, window_v, k_new, v_new, s_aux)
     B, H_q, n, D = q.shape
     H_kv = sink_k.shape[1]
@@ -204,10 +260,17 @@ def sink_decode_attention_ring_multi(q: torch.Tensor, sink_k: torch.Tensor, sink
                                                     N.SFA_DTYPE[q.dtype])
     ws = torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8)
     with torch.cuda.device(q.device):
-        st = lib.sfa_decode_ring_multi(N.desc(q), N.desc(sink_k), N.desc(sink_v), int(sink_len), N.desc(window_k),
-                                       N.desc(window_v), int(window_len), int(write_pos), N.desc(k_new), N.desc(v_new),
-                                       N.desc(out), s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                       1 if commit else 0, ws.data_ptr(), ws.numel(), 1.0 / math.sqrt(D), 0,
-                                       N.stream_ptr(q.device))
-    N.check(st, "sfa_decode_ring_multi")
+        if tree is not None:
+            st = lib.sfa_decode_ring_tree(N.desc(q), N.desc(sink_k), N.desc(sink_v), int(sink_len), N.desc(window_k),
+                                          N.desc(window_v), int(window_len), int(write_pos), N.desc(k_new),
+                                          N.desc(v_new), N.desc(out), s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                          tree[0].data_ptr(), tree[1], ws.data_ptr(), ws.numel(), 1.0 / math.sqrt(D), 0,
+                                          N.stream_ptr(q.device))
+        else:
+            st = lib.sfa_decode_ring_multi(N.desc(q), N.desc(sink_k), N.desc(sink_v), int(sink_len), N.desc(window_k),
+                                           N.desc(window_v), int(window_len), int(write_pos), N.desc(k_new),
+                                           N.desc(v_new), N.desc(out), s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                           1 if commit else 0, ws.data_ptr(), ws.numel(), 1.0 / math.sqrt(D), 0,
+                                           N.stream_ptr(q.device))
+    N.check(st, "sfa_decode_ring_tree" if tree is not None else "sfa_decode_ring_multi")
     return out
