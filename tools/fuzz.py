@@ -1,24 +1,39 @@
 #!/usr/bin/env python3
 """Randomised cross-check on the GPU: MFMA kernels against the exact-f32 kernels of the same library (and the
 N_q < N_kv / packed paths against their padded / per-sequence formulations) on random shapes.
-usage: python tools/fuzz.py [n_cases] [seed] [skew]      (skew: only shapes of the short-window dK/dV kernel - no sink keys,
-head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or packed)"""
+usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe]
+(skew: only shapes of the short-window dK/dV kernel - no sink keys, head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or
+packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn)"""
 import os
 import random
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT]
+sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT, os.path.join(ROOT, "tests")]
 import torch
+
+import probe_inputs
 
 from sink_attention.sink_flash_attention import _sink_flash_attention_ex
 from sink_attention.varlen import sink_flash_attention_varlen
 
+inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
+assert inputs in ("randn", "probe"), inputs
+sys.argv = [a for a in sys.argv if not a.startswith("--inputs=")]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
 focus_skew = len(sys.argv) > 3 and sys.argv[3] == "skew"
 bad = 0
+
+
+def draw(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, cu=None):
+    """q, k, v, dO on the GPU: randn, or the mask-edge probes of the same shapes"""
+    if inputs == "probe":
+        pr = probe_inputs.dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, rng.randrange(1 << 30), cu=cu)
+        return tuple(pr[x].cuda() for x in ("q", "k", "v", "do"))
+    return (torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt), torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt),
+            torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt), torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt))
 
 
 def run(q, k, v, do, ns, W, sa, generic):
@@ -46,20 +61,14 @@ for case in range(n_cases):
         mode = rng.choice(["plain", "plain", "varlen"])
     sa = (torch.randn(Hq, device="cuda") * 0.5) if aux else None
     tol_o, tol_g = (2e-2, 2e-1) if dt == torch.bfloat16 else (5e-3, 6e-2)
-    desc = f"{mode} B{B} Hq{Hq} Hkv{Hkv} N{N} D{D} ns{ns} W{W} {str(dt)[6:]} aux{int(aux)}"
+    desc = f"{inputs} {mode} B{B} Hq{Hq} Hkv{Hkv} N{N} D{D} ns{ns} W{W} {str(dt)[6:]} aux{int(aux)}"
     try:
         if mode == "plain":
-            q = torch.randn(B, Hq, N, D, device="cuda", dtype=dt)
-            k = torch.randn(B, Hkv, N, D, device="cuda", dtype=dt)
-            v = torch.randn(B, Hkv, N, D, device="cuda", dtype=dt)
-            do = torch.randn(B, Hq, N, D, device="cuda", dtype=dt)
+            q, k, v, do = draw(B, Hq, Hkv, N, N, D, ns, W, dt)
             a, b = run(q, k, v, do, ns, W, sa, False), run(q, k, v, do, ns, W, sa, True)
         elif mode == "offset":
             Nk = N + rng.choice([1, 17, 64, 100, 300])
-            q = torch.randn(B, Hq, N, D, device="cuda", dtype=dt)
-            k = torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt)
-            v = torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt)
-            do = torch.randn(B, Hq, N, D, device="cuda", dtype=dt)
+            q, k, v, do = draw(B, Hq, Hkv, N, Nk, D, ns, W, dt)
             a = run(q, k, v, do, ns, W, sa, False)
             qp = torch.cat([torch.zeros(B, Hq, Nk - N, D, device="cuda", dtype=dt), q], 2)
             dop = torch.cat([torch.zeros(B, Hq, Nk - N, D, device="cuda", dtype=dt), do], 2)
@@ -75,10 +84,7 @@ for case in range(n_cases):
             for L in lens:
                 cu.append(cu[-1] + L)
             T = cu[-1]
-            q = torch.randn(1, Hq, T, D, device="cuda", dtype=dt)
-            k = torch.randn(1, Hkv, T, D, device="cuda", dtype=dt)
-            v = torch.randn(1, Hkv, T, D, device="cuda", dtype=dt)
-            do = torch.randn(1, Hq, T, D, device="cuda", dtype=dt)
+            q, k, v, do = draw(1, Hq, Hkv, T, T, D, ns, W, dt, cu=cu)
             qq, kk, vv = (t.clone().requires_grad_(True) for t in (q, k, v))
             ss = sa.clone().requires_grad_(True) if aux else None
             o = sink_flash_attention_varlen(qq, kk, vv, cu, ns, W, ss)

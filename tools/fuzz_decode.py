@@ -1,21 +1,44 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
-fused-step / device-state / one-pass variants against the linearised cache.  usage: python tools/fuzz_decode.py [n] [seed]"""
+fused-step / device-state / one-pass variants against the linearised cache.
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe]   (probe: keys are the +-1 codes of tests/probe_inputs.py and
+every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
+one just evicted or the last sink)"""
 import os
 import random
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT]
+sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT, os.path.join(ROOT, "tests")]
 import torch
+
+import probe_inputs
 
 from sink_attention import sink_decode_attention
 from sink_attention.cache import SinkCacheLayer
 
+inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
+assert inputs in ("randn", "probe"), inputs
+sys.argv = [a for a in sys.argv if not a.startswith("--inputs=")]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
 bad = 0
+
+
+def keys(B, H, n, D, dt):
+    if inputs == "probe":
+        return probe_inputs.codes((B, H, n, D), None, dt, device="cuda")
+    return torch.randn(B, H, n, D, device="cuda", dtype=dt)
+
+
+def query(B, Hq, D, dt, hist, ns, W):
+    """randn, or amplitude * the code of one edge key of the history hist [B, Hkv, L, D] (the new token is its last row)"""
+    if inputs != "probe":
+        return torch.randn(B, Hq, 1, D, device="cuda", dtype=dt)
+    L = hist.shape[2]
+    t = rng.choice([x for x in (L - 1, L - W, L - W - 1, ns - 1) if 0 <= x < L])
+    return (probe_inputs.amplitude(D) * hist[:, :, t:t + 1]).repeat_interleave(Hq // hist.shape[1], 1).to(dt)
 
 
 def ref_decode(q, k, v, sa):
@@ -41,18 +64,20 @@ for case in range(n_cases):
     Hq = Hkv * g
     sa = torch.randn(Hq, device="cuda") * 0.5 if aux else None
     tol = 1e-4 if dt == torch.float32 else (2e-2 if dt == torch.bfloat16 else 4e-3)
-    desc = f"B{B} Hq{Hq} Hkv{Hkv} D{D} ns{ns} W{W} pre{pre} {str(dt)[6:]} aux{int(aux)}"
+    desc = f"{inputs} B{B} Hq{Hq} Hkv{Hkv} D{D} ns{ns} W{W} pre{pre} {str(dt)[6:]} aux{int(aux)}"
     try:
         a, b, c = SinkCacheLayer(ns, W), SinkCacheLayer(ns, W), SinkCacheLayer(ns, W)
         c.one_pass = True
-        kp, vp = torch.randn(B, Hkv, pre, D, device="cuda", dtype=dt), torch.randn(B, Hkv, pre, D, device="cuda", dtype=dt)
+        kp, vp = keys(B, Hkv, pre, D, dt), torch.randn(B, Hkv, pre, D, device="cuda", dtype=dt)
+        hist = kp
         for l in (a, b, c):
             l.update(kp, vp)
         b.enable_device_state()
         ok = True
         for step in range(rng.choice([1, 3, W + 3])):
-            q = torch.randn(B, Hq, 1, D, device="cuda", dtype=dt)
-            kn, vn = torch.randn(B, Hkv, 1, D, device="cuda", dtype=dt), torch.randn(B, Hkv, 1, D, device="cuda", dtype=dt)
+            kn, vn = keys(B, Hkv, 1, D, dt), torch.randn(B, Hkv, 1, D, device="cuda", dtype=dt)
+            hist = torch.cat([hist, kn], dim=2)
+            q = query(B, Hq, D, dt, hist, ns, W)
             o1 = a.decode_step(q, kn, vn, s_aux=sa)
             o2 = b.decode_step_dyn(q, kn, vn, s_aux=sa)
             o3 = c.decode_step(q, kn, vn, s_aux=sa)
