@@ -410,6 +410,74 @@ int sfa_ring_commit_path_rows(const sfa_tensor* window_k, const sfa_tensor* wind
                               const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
                               int32_t* state, void* stream);
 
+/*
+ * Slot-indexed calls (continuous batching).  The cache is a POOL of S slots that outlives any one batch:
+ *   sink_k/v [S, Hkv, num_sink, D]   window_k/v [S, Hkv, Wc, D]   state int32 [S][4] (the per-sequence rows above)
+ * and a step names the slots it works on: `slots` = device int32 [B].  Everything indexed by the batch row today (q,
+ * k_new, v_new, o, count, parent, path) keeps B rows and stays indexed by b; batch row b works on cache row and state row
+ * slots[b].  One rule for every call:
+ *   - slots[b] outside [0, S) (use -1) marks an INACTIVE row: its o rows are written as zeros, nothing is stored for it
+ *     and no state row moves.  Decided on the device (no host sync), so a step captured at a fixed B replays at any
+ *     occupancy.
+ *   - Equivalence.  Let P[s] be the pool gathered by index_select(0, s) (four buffers and the state).  X_slots(pool,
+ *     slots, args) writes for every active b bitwise the o[b] that X_rows(P[slots], args) writes at the same B, and
+ *     leaves pool[slots[b]] (buffers and state row) bitwise what X_rows leaves in row b.  Pool rows that no active
+ *     batch row names are not touched.  Plan, grid and workspace are those of the rows call for B (not for S): a step
+ *     costs what its active rows cost.
+ *   - The same slot twice in one call: allowed for calls that write nothing (commit = 0, the tree call); undefined for a
+ *     call that stores or advances.  The device array is not validated.
+ * Host checks before anything launches, as in the siblings: the cache buffers share shape[0] = S >= 1 ("pool: ..."),
+ * q / k_new / v_new / o share shape[0] = B, `slots` is non-null ("slots: null device pointer"), and everything the
+ * rows call checks, at the full cache.  State writes stay in the positions of the rows calls (trailing launch; reduce
+ * block / last arriver of the single-token step), addressed through slots.  sfa_last_path() names carry "_slots"
+ * where the rows calls carry "_rows".
+ */
+
+/* sfa_decode_ring_step_rows on a pool (two launches, or one with SFA_FLAG_DECODE_ONE_PASS: the grid's last arriver
+ * advances state[slots[b]] of every active b).  Workspace: sfa_decode_workspace_bytes(B, Hq, Hkv, num_sink + Wc, D, dtype). */
+int sfa_decode_ring_step_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
+                               const int32_t* slots, void* workspace, size_t workspace_bytes, float scale,
+                               unsigned flags, void* stream);
+
+/* sfa_decode_ring_multi_rows on a pool (commit 0 / 1).  Workspace: sfa_decode_multi_workspace_bytes(B, Hq, Hkv, n,
+ * num_sink + Wc + n, D, dtype). */
+int sfa_decode_ring_multi_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                                int32_t* state, const int32_t* slots, void* workspace, size_t workspace_bytes,
+                                float scale, unsigned flags, void* stream);
+
+/* sfa_decode_ring_tree_rows on a pool: row b verifies its tree (parent + b * parent_bstride) against slot slots[b]. */
+int sfa_decode_ring_tree_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                               int64_t parent_bstride, int32_t* state, const int32_t* slots, void* workspace,
+                               size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
+/* sfa_ring_commit_rows on a pool: row b (count[b], k_new[b]) stores into the ring of slot slots[b] and advances that
+ * state row.  window_k/v [S, Hkv, Wc, D], k_new/v_new [B, Hkv, n, D], count device int32 [B]. */
+int sfa_ring_commit_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                          const sfa_tensor* v_new, const int32_t* count, int32_t* state, const int32_t* slots,
+                          void* stream);
+
+/* sfa_ring_commit_path_rows on a pool. */
+int sfa_ring_commit_path_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                               int32_t* state, const int32_t* slots, void* stream);
+
+/*
+ * sfa_ring_fill_varlen into a pool: sequence i of the pack (n_seq of them, slots = device int32 [n_seq]) is placed in
+ * slot slots[i] and writes that state row; every other slot keeps buffers and state (a sequence whose slot is outside
+ * [0, S) is skipped).  This admits a request while the others keep decoding, and reuses a released slot.  S comes from
+ * the buffers; the same slot twice is undefined.
+ */
+int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                               const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                               const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,7 +305,7 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                   const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
                   size_t workspace_bytes, float scale, void* stream, const sfa_tensor* k_new = nullptr,
                   const sfa_tensor* v_new = nullptr, int64_t new_slot = -1, int* dyn_state = nullptr,
-                  unsigned flags = 0, bool state_rows = false) {
+                  unsigned flags = 0, bool state_rows = false, const int32_t* slots = nullptr, bool pool = false) {
     g_err[0] = 0;
     int st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")) ||
@@ -315,7 +315,11 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
     SFA_CHECK_ARG(q->dtype == k->dtype, "q and k differ in dtype");
     // decode_kernel.py:146-147
     SFA_CHECK_ARG(q->shape[2] == 1, "sink_decode_attention requires N_q=1, got %lld", (long long)q->shape[2]);
-    SFA_CHECK_ARG(q->shape[0] == k->shape[0] && q->shape[3] == k->shape[3], "q/k batch or head-dim mismatch");
+    // pool (sfa_decode_ring_step_slots): the cache buffers hold S >= 1 slots, q / k_new / v_new / o the B batch rows
+    if (pool)
+        SFA_CHECK_ARG(k->shape[0] >= 1 && k->shape[0] < (1ll << 30),
+                      "pool: the cache buffers need shape[0] = S slots, 1 <= S < 2^30 (got %lld)", (long long)k->shape[0]);
+    SFA_CHECK_ARG((pool || q->shape[0] == k->shape[0]) && q->shape[3] == k->shape[3], "q/k batch or head-dim mismatch");
     SFA_CHECK_ARG(k->shape[1] > 0 && q->shape[1] % k->shape[1] == 0, "H_q (%lld) must be divisible by H_kv (%lld)",
                   (long long)q->shape[1], (long long)k->shape[1]);
     SFA_CHECK_ARG(std::isfinite(scale), "scale must be finite");
@@ -325,6 +329,9 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
         SFA_CHECK_ARG(k2 && v2, "second key segment needs both k and v");
         if ((st = check_tensor(k2, "k2")) || (st = check_tensor(v2, "v2")) || (st = same_shape(k2, v2, "k2", "v2")))
             return st;
+        if (pool)
+            SFA_CHECK_ARG(k2->shape[0] == k->shape[0], "pool: sink and window buffers must share shape[0] = S (sink %lld, window %lld)",
+                          (long long)k->shape[0], (long long)k2->shape[0]);
         SFA_CHECK_ARG(k2->dtype == k->dtype && k2->shape[0] == k->shape[0] && k2->shape[1] == k->shape[1] &&
                           k2->shape[3] == k->shape[3],
                       "the two key segments must agree in dtype, batch, heads and head dim");
@@ -337,7 +344,10 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
         if ((st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")) ||
             (st = same_shape(k_new, v_new, "k_new", "v_new")))
             return st;
-        SFA_CHECK_ARG(k_new->dtype == k2->dtype && k_new->shape[0] == k2->shape[0] && k_new->shape[1] == k2->shape[1] &&
+        if (pool)
+            SFA_CHECK_ARG(k_new->shape[0] == q->shape[0], "q, k_new, v_new and o must share shape[0] = B (q %lld, k_new %lld)",
+                          (long long)q->shape[0], (long long)k_new->shape[0]);
+        SFA_CHECK_ARG(k_new->dtype == k2->dtype && (pool || k_new->shape[0] == k2->shape[0]) && k_new->shape[1] == k2->shape[1] &&
                           k_new->shape[2] == 1 && k_new->shape[3] == k2->shape[3],
                       "k_new / v_new must be [B, H_kv, 1, D] in the ring's dtype");
         SFA_CHECK_ARG(dyn_state || (new_slot >= 0 && new_slot < n2), "write slot %lld outside the %lld valid ring slots",
@@ -363,7 +373,7 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
     }
     return decode_launch(q, k, v, n1, n2 ? k2 : nullptr, n2 ? v2 : nullptr, n2, o, s_aux, workspace, scale, pl,
                          (hipStream_t)stream, k_new, v_new, (int)new_slot, dyn_state,
-                         (flags & SFA_FLAG_DECODE_ONE_PASS) != 0, state_rows);
+                         (flags & SFA_FLAG_DECODE_ONE_PASS) != 0, state_rows, slots);
 }
 
 }  // namespace
@@ -422,6 +432,21 @@ int sfa_decode_ring_step_rows(const sfa_tensor* q, const sfa_tensor* sink_k, con
                          workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags, true);
 }
 
+int sfa_decode_ring_step_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
+                               const int32_t* slots, void* workspace, size_t workspace_bytes, float scale,
+                               unsigned flags, void* stream) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    // plan, grid and workspace are those of the rows call for q's B rows at the full cache; the buffers are the pool
+    return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
+                         workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags, true, slots, true);
+}
+
 }  // extern "C"
 
 namespace {
@@ -429,7 +454,7 @@ namespace {
 // every host-checkable argument of sfa_decode_ring_multi(_dyn); nothing launches
 int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                 const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
-                const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, float scale) {
+                const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, float scale, bool pool = false) {
     int st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k")) ||
         (st = check_tensor(sink_v, "sink_v")) || (st = check_tensor(window_k, "window_k")) ||
@@ -447,8 +472,14 @@ int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor*
     SFA_CHECK_ARG(k_new->shape[0] == B && k_new->shape[2] == n && k_new->shape[3] == D,
                   "k_new / v_new must be [B, H_kv, n, D] with the n = %lld rows of q", (long long)n);
     SFA_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "H_q (%lld) must be divisible by H_kv (%lld)", (long long)Hq, (long long)Hkv);
-    SFA_CHECK_ARG(sink_k->shape[0] == B && sink_k->shape[1] == Hkv && sink_k->shape[3] == D &&
-                      window_k->shape[0] == B && window_k->shape[1] == Hkv && window_k->shape[3] == D,
+    if (pool) {     // *_slots: the buffers hold S >= 1 slots, the activations B batch rows
+        SFA_CHECK_ARG(sink_k->shape[0] >= 1 && sink_k->shape[0] == window_k->shape[0],
+                      "pool: sink and window buffers must share shape[0] = S >= 1 (sink %lld, window %lld)",
+                      (long long)sink_k->shape[0], (long long)window_k->shape[0]);
+        SFA_CHECK_ARG(sink_k->shape[0] < (1ll << 30), "problem too large");
+    }
+    SFA_CHECK_ARG((pool || sink_k->shape[0] == B) && sink_k->shape[1] == Hkv && sink_k->shape[3] == D &&
+                      (pool || window_k->shape[0] == B) && window_k->shape[1] == Hkv && window_k->shape[3] == D,
                   "sink / window buffers must be [B, H_kv, *, D] like k_new");
     SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
     SFA_CHECK_ARG(sink_len >= 0 && sink_len <= sink_k->shape[2], "sink_len %lld outside [0, %lld]", (long long)sink_len,
@@ -552,6 +583,29 @@ int sfa_decode_ring_multi_rows(const sfa_tensor* q, const sfa_tensor* sink_k, co
                                scale, flags, (hipStream_t)stream, state, true);
 }
 
+int sfa_decode_ring_multi_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                                int32_t* state, const int32_t* slots, void* workspace, size_t workspace_bytes,
+                                float scale, unsigned flags, void* stream) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+    int st;
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, true))) return st;
+    if (q->shape[0] == 0) return SFA_OK;               // no rows: no state to read or advance
+    if (q->shape[1] == 0) {
+        if (!commit) return SFA_OK;
+        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream, true, nullptr,
+                                      0, slots);
+    }
+    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
+    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
+                               scale, flags, (hipStream_t)stream, state, true, nullptr, 0, slots);
+}
+
 }  // extern "C"
 
 namespace {
@@ -591,18 +645,20 @@ int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sf
 static int tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                     const sfa_tensor* window_v, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
                     const float* s_aux, const int32_t* parent, int64_t parent_bstride, int32_t* state, void* workspace,
-                    size_t workspace_bytes, float scale, unsigned flags, void* stream, bool rows) {
+                    size_t workspace_bytes, float scale, unsigned flags, void* stream, bool rows,
+                    const int32_t* slots = nullptr, bool pool = false) {
     g_err[0] = 0;
     SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
     const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
     int st;
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, pool))) return st;
     if ((st = check_tree(q, parent, parent_bstride))) return st;
     if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;   // nothing to attend; a tree call never commits
     if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
     return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, 0, workspace,
-                               scale, flags, (hipStream_t)stream, state, rows, parent, parent_bstride);
+                               scale, flags, (hipStream_t)stream, state, rows, parent, parent_bstride, slots);
 }
 
 int sfa_decode_ring_tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
@@ -623,13 +679,22 @@ int sfa_decode_ring_tree_rows(const sfa_tensor* q, const sfa_tensor* sink_k, con
                     workspace, workspace_bytes, scale, flags, stream, true);
 }
 
+int sfa_decode_ring_tree_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
+                               int64_t parent_bstride, int32_t* state, const int32_t* slots, void* workspace,
+                               size_t workspace_bytes, float scale, unsigned flags, void* stream) {
+    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
+                    workspace, workspace_bytes, scale, flags, stream, true, slots, true);
+}
+
 }  // extern "C"
 
 namespace {
 
 // every host-checkable argument of sfa_ring_commit_dyn / _rows; nothing launches
 int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                 const sfa_tensor* v_new, const int32_t* count, int32_t* state) {
+                 const sfa_tensor* v_new, const int32_t* count, int32_t* state, bool pool = false) {
     int st;
     if ((st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
@@ -642,7 +707,10 @@ int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const s
     const int64_t n = k_new->shape[2], Wc = window_k->shape[2];
     SFA_CHECK_ARG(n >= 1, "ring_commit: the chunk needs at least one token");
     SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
-    SFA_CHECK_ARG(k_new->shape[0] == window_k->shape[0] && k_new->shape[1] == window_k->shape[1] &&
+    if (pool)
+        SFA_CHECK_ARG(window_k->shape[0] >= 1 && window_k->shape[0] < (1ll << 30),
+                      "pool: the ring needs shape[0] = S >= 1 slots (got %lld)", (long long)window_k->shape[0]);
+    SFA_CHECK_ARG((pool || k_new->shape[0] == window_k->shape[0]) && k_new->shape[1] == window_k->shape[1] &&
                       k_new->shape[3] == window_k->shape[3],
                   "k_new / v_new must be [B, H_kv, n, D] like the ring [B, H_kv, Wc, D]");
     SFA_CHECK_ARG(n < (1ll << 30) && Wc < (1ll << 30), "problem too large");
@@ -682,10 +750,11 @@ int sfa_ring_commit_rows(const sfa_tensor* window_k, const sfa_tensor* window_v,
 
 static int commit_path(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                        const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
-                       int32_t* state, void* stream, bool rows) {
+                       int32_t* state, void* stream, bool rows, const int32_t* slots = nullptr, bool pool = false) {
     g_err[0] = 0;
     int st;
-    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
+    SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
+    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state, pool))) return st;
     const int64_t n = k_new->shape[2];
     SFA_CHECK_ARG(path != nullptr, "path: null device pointer");
     SFA_CHECK_ARG(path_bstride == 0 || (path_bstride >= n && path_bstride < (1ll << 30)),
@@ -693,7 +762,7 @@ static int commit_path(const sfa_tensor* window_k, const sfa_tensor* window_v, c
                   (long long)path_bstride, (long long)n);
     if (rows && k_new->shape[0] == 0) return SFA_OK;
     return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, rows, path,
-                                  path_bstride);
+                                  path_bstride, slots);
 }
 
 int sfa_ring_commit_path_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
@@ -708,9 +777,32 @@ int sfa_ring_commit_path_rows(const sfa_tensor* window_k, const sfa_tensor* wind
     return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, true);
 }
 
-int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
-                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
-                         const int32_t* cu_seqlens, int n_seq, int32_t* state, void* stream) {
+int sfa_ring_commit_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                          const sfa_tensor* v_new, const int32_t* count, int32_t* state, const int32_t* slots,
+                          void* stream) {
+    g_err[0] = 0;
+    int st;
+    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
+    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state, true))) return st;
+    if (k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, true, nullptr, 0,
+                                  slots);
+}
+
+int sfa_ring_commit_path_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                               const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
+                               int32_t* state, const int32_t* slots, void* stream) {
+    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, true, slots, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+// sfa_ring_fill_varlen (slots null: sequence i -> cache row i of n_seq) and sfa_ring_fill_varlen_slots (pool)
+int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu_seqlens,
+                int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool) {
     g_err[0] = 0;
     int st;
     if ((st = check_tensor(sink_k, "sink_k")) || (st = check_tensor(sink_v, "sink_v")) ||
@@ -722,14 +814,20 @@ int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, con
         return st;
     SFA_CHECK_ARG(cu_seqlens != nullptr, "cu_seqlens: null device pointer");
     SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
     SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
     SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
                   "k / v and the cache buffers must share one dtype");
     const int64_t Hkv = k->shape[1], D = k->shape[3], Wc = window_k->shape[2];
-    SFA_CHECK_ARG(sink_k->shape[0] == n_seq && window_k->shape[0] == n_seq,
-                  "n_seq (%d) must match the cache buffers' batch (sink %lld, window %lld)", n_seq,
-                  (long long)sink_k->shape[0], (long long)window_k->shape[0]);
+    if (pool)
+        SFA_CHECK_ARG(sink_k->shape[0] >= 1 && sink_k->shape[0] == window_k->shape[0] && sink_k->shape[0] < (1ll << 30),
+                      "pool: sink and window buffers must share shape[0] = S >= 1 (sink %lld, window %lld)",
+                      (long long)sink_k->shape[0], (long long)window_k->shape[0]);
+    else
+        SFA_CHECK_ARG(sink_k->shape[0] == n_seq && window_k->shape[0] == n_seq,
+                      "n_seq (%d) must match the cache buffers' batch (sink %lld, window %lld)", n_seq,
+                      (long long)sink_k->shape[0], (long long)window_k->shape[0]);
     SFA_CHECK_ARG(sink_k->shape[1] == Hkv && sink_k->shape[3] == D && window_k->shape[1] == Hkv && window_k->shape[3] == D,
                   "sink / window buffers must be [n_seq, H_kv, *, D] like k");
     SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
@@ -745,7 +843,24 @@ int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, con
                       "ring_fill_varlen: rows of every tensor must be 16-byte aligned");
     }
     return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
-                                   (hipStream_t)stream);
+                                   (hipStream_t)stream, slots);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                         const int32_t* cu_seqlens, int n_seq, int32_t* state, void* stream) {
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, nullptr, false);
+}
+
+int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                               const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                               const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                               void* stream) {
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true);
 }
 
 }  // extern "C"

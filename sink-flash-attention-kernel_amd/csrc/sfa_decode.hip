@@ -181,12 +181,16 @@ __device__ __forceinline__ void advance_row(int* st, int wsize, bool seen) {
     if (seen) st[3] += 1;
 }
 
-template <typename T, int LPK, int GT>
+// SL (sfa_decode_ring_step_slots, instances of their own): batch row b works on cache row and state row c = slots[b] of
+// a pool of npool rows: k / v / k2 / v2 and fr.dyn are indexed by c, everything else (q, fr.kn / fr.vn, the partials,
+// the arrival counters, o) by b.  c outside [0, npool): an inactive row - its workgroups compute nothing, its o rows
+// are zeros (written by the reduce kernel, or by the last arriver in one-pass mode) and no state row moves for it.
+template <typename T, int LPK, int GT, bool SL = false>
 __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View v, View k2, View v2, int N1, Fresh fr,
                                                           OnePass op1,
                                                           float* __restrict__ Mp, float* __restrict__ Lp,
                                                           float* __restrict__ Op, int Hq, int Hkv, int Nkv, int D,
-                                                          int kps, int S, float scale) {
+                                                          int kps, int S, float scale, const int* slots, int npool) {
     constexpr int EPL = 16 / sizeof(T);
     constexpr int KPW = 64 / LPK;
     constexpr int NSTREAM = 4 * KPW;
@@ -203,8 +207,16 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
     const int d0 = dact ? chunk * EPL : 0;
     const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
     const int g = Hq / Hkv;
-    if (fr.dyn) {
-        const int* st = fr.dyn + (int64_t)b * fr.stride;   // the grid (kps, S) is the full cache's: splits past this
+    int c = b;                    // the cache row: per workgroup, in an SGPR
+    bool active = true;
+    if constexpr (SL) {
+        c = __builtin_amdgcn_readfirstlane(slots[b]);
+        active = (unsigned)c < (unsigned)npool;
+        if (!active && !op1.cnt) return;      // two launches: the reduce kernel writes the zeros
+        if (!active) c = 0;                   // one pass: the workgroup only arrives at the counters below; no state row
+    }                                         // is read for it (the pointers built from row 0 are never dereferenced)
+    if (fr.dyn && (!SL || active)) {
+        const int* st = fr.dyn + (int64_t)c * fr.stride;   // the grid (kps, S) is the full cache's: splits past this
         N1 = st[0];                                        // row's keys give empty partials
         const int wl = st[1] + 1 < fr.wsize ? st[1] + 1 : fr.wsize;
         Nkv = N1 + wl;
@@ -214,22 +226,22 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
     const int k_end = (k_beg + kps < Nkv) ? (k_beg + kps) : Nkv;
     const int sid = wave * KPW + kg;
 
-    const T* kb = reinterpret_cast<const T*>(k.ptr) + (int64_t)b * k.sb + (int64_t)hk * k.sh + d0;
-    const T* vb = reinterpret_cast<const T*>(v.ptr) + (int64_t)b * v.sb + (int64_t)hk * v.sh + d0;
-    const T* kb2 = reinterpret_cast<const T*>(k2.ptr) + (int64_t)b * k2.sb + (int64_t)hk * k2.sh + d0;
-    const T* vb2 = reinterpret_cast<const T*>(v2.ptr) + (int64_t)b * v2.sb + (int64_t)hk * v2.sh + d0;
+    const T* kb = reinterpret_cast<const T*>(k.ptr) + (int64_t)c * k.sb + (int64_t)hk * k.sh + d0;
+    const T* vb = reinterpret_cast<const T*>(v.ptr) + (int64_t)c * v.sb + (int64_t)hk * v.sh + d0;
+    const T* kb2 = reinterpret_cast<const T*>(k2.ptr) + (int64_t)c * k2.sb + (int64_t)hk * k2.sh + d0;
+    const T* vb2 = reinterpret_cast<const T*>(v2.ptr) + (int64_t)c * v2.sb + (int64_t)hk * v2.sh + d0;
     const T* knb = kb2;
     const T* vnb = vb2;
     if (fr.slot >= 0) {
         knb = reinterpret_cast<const T*>(fr.kn.ptr) + (int64_t)b * fr.kn.sb + (int64_t)hk * fr.kn.sh + d0;
         vnb = reinterpret_cast<const T*>(fr.vn.ptr) + (int64_t)b * fr.vn.sb + (int64_t)hk * fr.vn.sh + d0;
-        if (split == 0 && wave == 0 && kg == 0 && dact) {      // the append: one 16-byte piece per lane
+        if ((!SL || active) && split == 0 && wave == 0 && kg == 0 && dact) {      // the append: one 16-byte piece per lane
             *reinterpret_cast<u32x4*>(const_cast<T*>(kb2) + (int64_t)fr.slot * k2.sn) = *reinterpret_cast<const u32x4*>(knb);
             *reinterpret_cast<u32x4*>(const_cast<T*>(vb2) + (int64_t)fr.slot * v2.sn) = *reinterpret_cast<const u32x4*>(vnb);
         }
     }
 
-    for (int h0 = 0; h0 < g; h0 += GT) {
+    for (int h0 = 0; h0 < (SL && !active ? 0 : g); h0 += GT) {
         float qf[GT][EPL];
         float m[GT], l[GT], acc[GT][EPL];
 #pragma unroll
@@ -377,7 +389,13 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
             if (oldg == total - 1) __hip_atomic_store(&op1.cnt[gridDim.z * Hkv], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
-        if (last_flag[0]) {
+        if (SL && !active) {
+            if (last_flag[0]) {                // an inactive row's head group: zeros, no partials exist
+                for (int e = threadIdx.x; e < g * D; e += blockDim.x)
+                    (reinterpret_cast<T*>(op1.o.ptr) + (int64_t)b * op1.o.sb + (int64_t)(hk * g + e / D) * op1.o.sh)[e % D] =
+                        from_f32<T>(0.f);
+            }
+        } else if (last_flag[0]) {
             // (the partials are fetched with sc1 loads: they cannot hit stale lines of this XCD's L2)
             if (D <= 128 && g > 4) {       // two heads per wave (a half-wave covers 32 x 4 columns): the group in one round up to 8 heads
                 for (int hh = wave * 2 + (lane >> 5); hh < g; hh += 8)
@@ -388,7 +406,14 @@ __global__ __launch_bounds__(256) void decode_split_kernel(View q, View k, View 
         }
         if (last_flag[1] && fr.dyn) {      // every workgroup has read the state: advance it (every row of it)
             const int nrow = fr.stride ? (int)gridDim.z : 1;
-            for (int r = threadIdx.x; r < nrow; r += blockDim.x) advance_row(fr.dyn + (int64_t)r * fr.stride, fr.wsize, fr.stride != 0);
+            for (int r = threadIdx.x; r < nrow; r += blockDim.x) {
+                int cr = r;
+                if constexpr (SL) {
+                    cr = slots[r];
+                    if ((unsigned)cr >= (unsigned)npool) continue;
+                }
+                advance_row(fr.dyn + (int64_t)cr * fr.stride, fr.wsize, fr.stride != 0);
+            }
         }
     }
 }
@@ -405,19 +430,51 @@ __global__ __launch_bounds__(128) void decode_reduce_kernel(const float* __restr
     reduce_head<T>(Mp, Lp, Op, s_aux, o, Hq, S, D, b, h, threadIdx.x, 128);
 }
 
+// sfa_decode_ring_step_slots: the same with the state row of slots[b]; an inactive row gets zeros (no partial exists)
+template <typename T>
+__global__ __launch_bounds__(128) void decode_reduce_slots_kernel(const float* __restrict__ Mp, const float* __restrict__ Lp,
+                                                                 const float* __restrict__ Op,
+                                                                 const float* __restrict__ s_aux, View o, int Hq, int S,
+                                                                 int D, int* dyn, int wsize, const int* slots, int npool) {
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int c = __builtin_amdgcn_readfirstlane(slots[b]);
+    if ((unsigned)c >= (unsigned)npool) {
+        T* orow = reinterpret_cast<T*>(o.ptr) + (int64_t)b * o.sb + (int64_t)h * o.sh;
+        for (int d = threadIdx.x; d < D; d += 128) orow[d] = from_f32<T>(0.f);
+        return;
+    }
+    if (h == 0 && threadIdx.x == 0) advance_row(dyn + (int64_t)c * 4, wsize, true);
+    reduce_head<T>(Mp, Lp, Op, s_aux, o, Hq, S, D, b, h, threadIdx.x, 128);
+}
+
 template <typename T, int LPK>
 int launch_split(int gt, dim3 grid, hipStream_t stream, View q, View k, View v, View k2, View v2, int N1, Fresh fr,
                  OnePass op1, float* Mp,
-                 float* Lp, float* Op, int Hq, int Hkv, int Nkv, int D, int kps, int S, float scale) {
+                 float* Lp, float* Op, int Hq, int Hkv, int Nkv, int D, int kps, int S, float scale, const int* slots,
+                 int npool) {
+    if (slots) {
+        switch (gt) {
+            case 8:
+                decode_split_kernel<T, LPK, 8, true><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, slots, npool);
+                break;
+            case 4:
+                decode_split_kernel<T, LPK, 4, true><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, slots, npool);
+                break;
+            default:
+                decode_split_kernel<T, LPK, 1, true><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, slots, npool);
+                break;
+        }
+        return launch_status("decode_split_slots");
+    }
     switch (gt) {
         case 8:
-            decode_split_kernel<T, LPK, 8><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale);
+            decode_split_kernel<T, LPK, 8><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, nullptr, 0);
             break;
         case 4:
-            decode_split_kernel<T, LPK, 4><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale);
+            decode_split_kernel<T, LPK, 4><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, nullptr, 0);
             break;
         default:
-            decode_split_kernel<T, LPK, 1><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale);
+            decode_split_kernel<T, LPK, 1><<<grid, 256, 0, stream>>>(q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, kps, S, scale, nullptr, 0);
             break;
     }
     return launch_status("decode_split");
@@ -425,11 +482,12 @@ int launch_split(int gt, dim3 grid, hipStream_t stream, View q, View k, View v, 
 
 template <typename T>
 int launch_split_lpk(const DecodePlan& pl, dim3 grid, hipStream_t stream, View q, View k, View v, View k2, View v2,
-                     int N1, Fresh fr, OnePass op1, float* Mp, float* Lp, float* Op, int Hq, int Hkv, int Nkv, int D, float scale) {
+                     int N1, Fresh fr, OnePass op1, float* Mp, float* Lp, float* Op, int Hq, int Hkv, int Nkv, int D, float scale,
+                     const int* slots, int npool) {
 #define SFA_LPK_CASE(L)                                                                                        \
     case L:                                                                                                    \
         return launch_split<T, L>(pl.gt, grid, stream, q, k, v, k2, v2, N1, fr, op1, Mp, Lp, Op, Hq, Hkv, Nkv, D, \
-                                  pl.keys_per_split, pl.splits, scale);
+                                  pl.keys_per_split, pl.splits, scale, slots, npool);
     switch (pl.lpk) {
         SFA_LPK_CASE(2)
         SFA_LPK_CASE(4)
@@ -485,13 +543,15 @@ int decode_plan(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nkv, int64_t D, int 
 int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, int64_t n1, const sfa_tensor* k2,
                   const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
                   float scale, const DecodePlan& pl, hipStream_t stream, const sfa_tensor* k_new,
-                  const sfa_tensor* v_new, int new_slot, int* dyn_state, bool one_pass, bool state_rows) {
+                  const sfa_tensor* v_new, int new_slot, int* dyn_state, bool one_pass, bool state_rows,
+                  const int32_t* slots) {
     const int B = (int)q->shape[0], Hq = (int)q->shape[1], D = (int)q->shape[3];
     const int Hkv = (int)k->shape[1], Nkv = (int)(n1 + n2), N1 = (int)n1;
     const View kv2 = k2 ? make_view(k2) : make_view(k);
     const View vv2 = v2 ? make_view(v2) : make_view(v);
     const int wsize = k2 ? (int)k2->shape[2] : 0;
     const int stride = dyn_state && state_rows ? 4 : 0;
+    const int npool = (int)k->shape[0];      // slot call: the cache is a pool, B = q's rows
     Fresh fr{kv2, vv2, -1, nullptr, wsize, 0};
     if (k_new && v_new && (new_slot >= 0 || dyn_state))
         fr = Fresh{make_view(k_new), make_view(v_new), dyn_state ? 0 : new_slot, dyn_state, wsize, stride};
@@ -507,26 +567,38 @@ int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
     int st;
     if (q->dtype == SFA_DTYPE_F32)
         st = launch_split_lpk<float>(pl, grid, stream, make_view(q), make_view(k), make_view(v), kv2, vv2, N1, fr, op1, Mp, Lp,
-                                     Op, Hq, Hkv, Nkv, D, scale);
+                                     Op, Hq, Hkv, Nkv, D, scale, slots, npool);
     else if (q->dtype == SFA_DTYPE_F16)
         st = launch_split_lpk<f16_t>(pl, grid, stream, make_view(q), make_view(k), make_view(v), kv2, vv2, N1, fr, op1, Mp, Lp,
-                                     Op, Hq, Hkv, Nkv, D, scale);
+                                     Op, Hq, Hkv, Nkv, D, scale, slots, npool);
     else
         st = launch_split_lpk<bf16_t>(pl, grid, stream, make_view(q), make_view(k), make_view(v), kv2, vv2, N1, fr, op1, Mp, Lp,
-                                      Op, Hq, Hkv, Nkv, D, scale);
+                                      Op, Hq, Hkv, Nkv, D, scale, slots, npool);
     if (st != SFA_OK) return st;
+    const char* kind = slots ? "_ringstep_slots"
+                             : dyn_state ? (stride ? "_ringstep_rows" : "_ringstep_dyn") : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : ""));
     if (one_pass) {
-        set_path("decode_splitkv%s_1pass_lpk%d_gt%d_s%d", dyn_state ? (stride ? "_ringstep_rows" : "_ringstep_dyn") : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
+        set_path("decode_splitkv%s_1pass_lpk%d_gt%d_s%d", kind, pl.lpk, pl.gt, S);
         return SFA_OK;
     }
     dim3 rgrid(Hq, B);
+    if (slots) {
+        if (q->dtype == SFA_DTYPE_F32)
+            decode_reduce_slots_kernel<float><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, slots, npool);
+        else if (q->dtype == SFA_DTYPE_F16)
+            decode_reduce_slots_kernel<f16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, slots, npool);
+        else
+            decode_reduce_slots_kernel<bf16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, slots, npool);
+        set_path("decode_splitkv%s_lpk%d_gt%d_s%d", kind, pl.lpk, pl.gt, S);
+        return launch_status("decode_reduce_slots");
+    }
     if (q->dtype == SFA_DTYPE_F32)
         decode_reduce_kernel<float><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
     else if (q->dtype == SFA_DTYPE_F16)
         decode_reduce_kernel<f16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
     else
         decode_reduce_kernel<bf16_t><<<rgrid, 128, 0, stream>>>(Mp, Lp, Op, s_aux, make_view(o), Hq, S, D, dyn_state, wsize, stride);
-    set_path("decode_splitkv%s_lpk%d_gt%d_s%d", dyn_state ? (stride ? "_ringstep_rows" : "_ringstep_dyn") : (fr.slot >= 0 ? "_ringstep" : (k2 ? "_ring" : "")), pl.lpk, pl.gt, S);
+    set_path("decode_splitkv%s_lpk%d_gt%d_s%d", kind, pl.lpk, pl.gt, S);
     return launch_status("decode_reduce");
 }
 

@@ -82,6 +82,10 @@ struct MultiArgs {
     // path commit (sfa_ring_commit_path_*): chunk token path[b * pathstride + j] is the j-th one stored
     const int* path;
     int pathstride;
+    // slot calls (sfa_*_slots): batch row b works on cache row and state row slots[b] of a pool of npool rows; a value
+    // outside [0, npool) marks an inactive row.  Null: cache row b (every other call).
+    const int* slots;
+    int npool;
 };
 
 inline __host__ __device__ int cdiv_i(int x, int y) { return (x + y - 1) / y; }
@@ -114,22 +118,33 @@ struct Fill {
     int T0, T1, T, tps, S;
 };
 
-// the write slot of batch row b's state, clamped into the ring (dyn); the host state otherwise
-__device__ __forceinline__ int state_wp(const MultiArgs& a, int b) {
+// the cache row (and state row) of batch row b: b itself, or slots[b] of a slot call (-1: an inactive row)
+template <bool Slots>
+__device__ __forceinline__ int cache_row(const MultiArgs& a, int b) {
+    if constexpr (!Slots) {
+        return b;
+    } else {
+        const int c = a.slots[b];
+        return (unsigned)c < (unsigned)a.npool ? c : -1;
+    }
+}
+
+// the write slot of cache row c's state, clamped into the ring (dyn); the host state otherwise
+__device__ __forceinline__ int state_wp(const MultiArgs& a, int c) {
     if (!a.state) return a.wp;
-    const int wp = a.state[(int64_t)b * a.sstride + 2];
+    const int wp = a.state[(int64_t)c * a.sstride + 2];
     return wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
 }
 
-// b: the batch row, wave-uniform (per-sequence state reads row b; a shared state has stride 0)
+// c: the cache row, wave-uniform (per-sequence state reads row c; a shared state has stride 0)
 template <bool Dyn>
-__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int b) {
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c) {
     if constexpr (!Dyn) {
         return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S};
     } else {
         // dyn mode: the cache state from the device (clamped into the buffers, so that a corrupt state cannot address
         // outside them), replanned.  Wave-uniform: loads of 12 bytes, broadcast from the first lane.
-        const int* st = a.state + (int64_t)b * a.sstride;
+        const int* st = a.state + (int64_t)c * a.sstride;
         int sl = __builtin_amdgcn_readfirstlane(st[0]);
         int wl = __builtin_amdgcn_readfirstlane(st[1]);
         int wp = __builtin_amdgcn_readfirstlane(st[2]);
@@ -142,7 +157,7 @@ __device__ __forceinline__ Fill get_fill(const MultiArgs& a, int b) {
     }
 }
 
-// one 32-key tile: rows [start, start + count) of one segment of the (b, KV head) slice
+// one 32-key tile: rows [start, start + count) of one segment of the (cache row c / chunk row b, KV head) slice
 struct TileInfo {
     const char* k;
     const char* v;
@@ -159,22 +174,22 @@ __device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int
     return x - f.wl;
 }
 
-__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int hk, int es) {
+__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es) {
     TileInfo ti;
     const View *kv, *vv;
-    int len;
+    int len, row = c;            // sink and ring: the cache row; the chunk: the batch row
     if (i < f.T0) {
         ti.seg = 0, ti.start = kTile * i, len = f.sink_len, kv = &a.sk, vv = &a.sv;
     } else if (i < f.T1) {
         ti.seg = 1, ti.start = kTile * (i - f.T0), len = f.wl, kv = &a.wk, vv = &a.wv;
     } else {
-        ti.seg = 2, ti.start = kTile * (i - f.T1), len = a.n, kv = &a.kn, vv = &a.vn;
+        ti.seg = 2, ti.start = kTile * (i - f.T1), len = a.n, kv = &a.kn, vv = &a.vn, row = b;
     }
     ti.count = len - ti.start < kTile ? len - ti.start : kTile;
     ti.ksn = kv->sn * es;
     ti.vsn = vv->sn * es;
-    ti.k = kv->ptr + ((int64_t)b * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
-    ti.v = vv->ptr + ((int64_t)b * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)ti.start * ti.vsn;
+    ti.k = kv->ptr + ((int64_t)row * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
+    ti.v = vv->ptr + ((int64_t)row * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)ti.start * ti.vsn;
     if (ti.seg == 2) {
         ti.cmin = ti.start, ti.cmax = ti.start + ti.count - 1;
     } else if (ti.seg == 1) {
@@ -278,7 +293,7 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-template <typename T, int D, bool Dyn, bool Tree>
+template <typename T, int D, bool Dyn, bool Tree, bool Slots = false>
 __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -300,7 +315,12 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     rest /= a.Sw;
     const int hk = rest % a.Hkv;
     const int b = rest / a.Hkv;
-    const Fill f = get_fill<Dyn>(a, b);
+    int c = b;                         // the cache row: per workgroup, in an SGPR
+    if constexpr (Slots) {
+        c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
+        if (c < 0) return;             // inactive row (whole workgroup): the reduce writes its zeros
+    }
+    const Fill f = get_fill<Dyn>(a, c);
     if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -393,7 +413,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info(a, f, i, b, hk, es);
+            ti = tile_info(a, f, i, b, c, hk, es);
             cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor);
             if (cls != 0) break;
         }
@@ -528,7 +548,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
 }
 
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
-template <typename T, bool Dyn, bool Tree>
+template <typename T, bool Dyn, bool Tree, bool Slots = false>
 __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
@@ -539,8 +559,13 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     const int rho = (int)(rowid % a.R);
     const int hk = (int)((rowid / a.R) % a.Hkv);
     const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
-    // per wave: with R < 4 one workgroup holds rows of different sequences, and each has its own fill
-    const Fill f = get_fill<Dyn>(a, b);
+    // per wave: with R < 4 one workgroup holds rows of different sequences, and each has its own fill (and slot)
+    int c = b;
+    if constexpr (Slots) {
+        c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
+        if (c < 0) return;
+    }
+    const Fill f = get_fill<Dyn>(a, c);
     if (Dyn && split >= f.S) return;
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
     const int D = a.D;
@@ -566,7 +591,7 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     const int tbeg = split * f.tps;
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
-        const TileInfo ti = tile_info(a, f, i, b, hk, es);
+        const TileInfo ti = tile_info(a, f, i, b, c, hk, es);
         if (tile_class_t<Tree>(a, ti, td, td, vis) == 0) continue;
         for (int kk = 0; kk < ti.count; ++kk) {
             if (!key_visible_t<Tree>(a, f, ti, kk, td, vis)) continue;
@@ -612,7 +637,8 @@ __device__ __forceinline__ int clamp_count(const int* count, int n) {
 // token first + j with first = max(0, acc - Wc), stored only if < acc -> ring slot (write_pos + t) mod Wc, write_pos
 // of row b's state.  count: one value shared by the batch, or [B] with per-sequence state.
 // Path: the j-th stored token is chunk row path[b * pathstride + j] (clamped into [0, n)) instead of row j.
-template <bool Path = false>
+// Slots: ring and state are those of cache row slots[b] (an inactive row stores nothing); chunk, count and path stay on b.
+template <bool Path = false, bool Slots = false>
 __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, int es, const int* count) {
     const int cpr = a.D * es / 16;
     const int nslot = a.n < a.wc ? a.n : a.wc;
@@ -623,10 +649,12 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
     rest /= nslot;
     const int hk = (int)(rest % a.Hkv);
     const int b = (int)(rest / a.Hkv);
+    const int c = cache_row<Slots>(a, b);
+    if (Slots && c < 0) return;
     const int last = count ? clamp_count(count + (a.sstride ? b : 0), a.n) : a.n;
     const int t = (last > a.wc ? last - a.wc : 0) + j;
     if (t >= last) return;
-    const int slot = (int)(((int64_t)state_wp(a, b) + t) % a.wc);
+    const int slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
     int src = t;
     if constexpr (Path) {
         src = a.path[(int64_t)b * a.pathstride + t];
@@ -635,8 +663,8 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
     const int64_t so = (int64_t)ch * 16;
     const char* ks = a.kn.ptr + ((int64_t)b * a.kn.sb + (int64_t)hk * a.kn.sh + (int64_t)src * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)b * a.vn.sb + (int64_t)hk * a.vn.sh + (int64_t)src * a.vn.sn) * es + so;
-    char* kd = a.wk.ptr + ((int64_t)b * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
-    char* vd = a.wv.ptr + ((int64_t)b * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
+    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
     *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
@@ -646,11 +674,13 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // Dyn: S and write_pos come from the device state (which this launch only reads; ring_advance_kernel moves it on).
 // With per-sequence state both are row b's: S per wave (a workgroup can hold rows of different sequences), write_pos
 // per commit piece.
-template <typename T, bool Dyn>
+// Slots: S, write_pos and the ring are those of cache row slots[b]; an inactive row gets zeros in o (no partial of it
+// was written) and stores nothing.
+template <typename T, bool Dyn, bool Slots = false>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred) {
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        commit_piece(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
+        commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -659,8 +689,17 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     const int rho = (int)(rowid % a.R);
     const int hk = (int)((rowid / a.R) % a.Hkv);
     const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
-    const Fill f = get_fill<Dyn>(a, b);
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
+    int c = b;
+    if constexpr (Slots) {
+        c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
+        if (c < 0) {
+            T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)t * a.o.sn) * es);
+            for (int d = lane; d < a.D; d += 64) orow[d] = from_f32<T>(0.f);
+            return;
+        }
+    }
+    const Fill f = get_fill<Dyn>(a, c);
     const int S = f.S, D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
     const float* Lr = a.Lp + rowid * a.Sw;
@@ -703,6 +742,12 @@ __global__ __launch_bounds__(256) void ring_commit_path_kernel(MultiArgs a, cons
     commit_piece<true>(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
 }
 
+// sfa_ring_commit_slots / sfa_ring_commit_path_slots: the two kernels above on the rings and states of slots[b]
+template <bool Path>
+__global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, const int* count, int es) {
+    commit_piece<Path, true>(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
+}
+
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
 // K/V, one 16-byte piece per thread.  item = ((b * Hkv + hk) * (ns + Wc) + j) * cpr + ch: j < ns is sink row j, j >= ns
 // ring slot s = j - ns.  Sequence b = rows [cu[b], cu[b + 1]) of length L (offsets clamped into [0, T], so that bad
@@ -710,9 +755,13 @@ __global__ __launch_bounds__(256) void ring_commit_path_kernel(MultiArgs a, cons
 // token sl + s for s < rest when rest <= Wc, else token L - Wc + s (the newest Wc, wrapped at slot 0).  Rows and slots
 // the sequence does not reach keep their content.  The first piece of each sequence writes its state row
 // {sl, min(rest, Wc), rest < Wc ? rest : 0, L} (rest <= 0: window_len = write_pos = 0).
+// Slots (sfa_ring_fill_varlen_slots): sequence b goes to cache row and state row slots[b] of a pool of npool rows (a
+// value outside [0, npool): the sequence is skipped); every other row of the pool keeps buffers and state.
+template <bool Slots>
 __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv, View wk, View wv, View k, View v,
                                                                const int* cu, int* state, int n_seq, int Hkv, int ns,
-                                                               int wc, int T, int cpr, int es) {
+                                                               int wc, int T, int cpr, int es, const int* slots,
+                                                               int npool) {
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nj = ns + wc;
     if (item >= (int64_t)n_seq * Hkv * nj * cpr) return;
@@ -722,6 +771,11 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     rest /= nj;
     const int hk = (int)(rest % Hkv);
     const int b = (int)(rest / Hkv);
+    int c = b;                   // the cache row
+    if constexpr (Slots) {
+        c = slots[b];
+        if ((unsigned)c >= (unsigned)npool) return;
+    }
     int c0 = cu[b], c1 = cu[b + 1];
     c0 = c0 < 0 ? 0 : (c0 > T ? T : c0);
     c1 = c1 < c0 ? c0 : (c1 > T ? T : c1);
@@ -729,7 +783,7 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     const int sl = L < ns ? L : ns;
     const int rem = L - sl;
     if (hk == 0 && j == 0 && ch == 0) {
-        int* st = state + (int64_t)b * 4;
+        int* st = state + (int64_t)c * 4;
         st[0] = sl;
         st[1] = rem < wc ? rem : wc;
         st[2] = rem < wc ? rem : 0;
@@ -749,8 +803,8 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src;
     const char* ks = k.ptr + ((int64_t)hk * k.sh + tok * k.sn) * es + so;
     const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
-    char* kd = dk->ptr + ((int64_t)b * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * es + so;
-    char* vd = dv->ptr + ((int64_t)b * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * es + so;
+    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * es + so;
+    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * es + so;
     *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
@@ -771,10 +825,34 @@ __global__ void ring_advance_kernel(int* state, const int* count, int n, int wc,
     if (stride) st[3] += acc;
 }
 
+// the same for a slot call: thread r advances state row slots[r] by count[r] (all n without a count); an inactive row
+// moves nothing
+__global__ void ring_advance_slots_kernel(int* state, const int* count, int n, int wc, int rows, const int* slots,
+                                          int npool) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= rows) return;
+    const int c = slots[r];
+    if ((unsigned)c >= (unsigned)npool) return;
+    int* st = state + (int64_t)c * 4;
+    const int acc = count ? clamp_count(count + r, n) : n;
+    int wl = st[1], wp = st[2];
+    wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
+    wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
+    st[1] = wl + acc < wc ? wl + acc : wc;
+    st[2] = (int)(((int64_t)wp + acc) % wc);
+    st[3] += acc;
+}
+
 // advance every state row after the launches that read it (shared state: one row)
-int launch_advance(int* state, const int* count, int n, int wc, int B, bool rows, hipStream_t stream) {
+int launch_advance(int* state, const int* count, int n, int wc, int B, bool rows, hipStream_t stream,
+                   const int* slots = nullptr, int npool = 0) {
     const int nrow = rows ? B : 1;
     if (nrow <= 0) return SFA_OK;
+    if (slots) {
+        ring_advance_slots_kernel<<<dim3((unsigned)cdiv64(nrow, 256)), nrow < 256 ? nrow : 256, 0, stream>>>(
+            state, count, n, wc, nrow, slots, npool);
+        return launch_status("ring_advance_slots");
+    }
     ring_advance_kernel<<<dim3((unsigned)cdiv64(nrow, 256)), nrow < 256 ? nrow : 256, 0, stream>>>(
         state, count, n, wc, nrow, rows ? 4 : 0);
     return launch_status("ring_advance");
@@ -803,6 +881,11 @@ template <typename T, int D>
 int launch_mfma(const MultiArgs& a, hipStream_t stream) {
     const int64_t nblk = (int64_t)a.B * a.Hkv * a.Sw * a.nrb;
     const dim3 grid((unsigned)nblk);
+    if (a.slots) {       // slot calls: dyn instances of their own
+        if (a.parent) multi_split_mfma_kernel<T, D, true, true, true><<<grid, kWaves * 64, 0, stream>>>(a);
+        else multi_split_mfma_kernel<T, D, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a);
+        return launch_status(a.parent ? "decode_tree_mfma_slots" : "decode_multi_mfma_slots");
+    }
     if (a.parent) {
         if (a.state) multi_split_mfma_kernel<T, D, true, true><<<grid, kWaves * 64, 0, stream>>>(a);
         else multi_split_mfma_kernel<T, D, false, true><<<grid, kWaves * 64, 0, stream>>>(a);
@@ -832,7 +915,11 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
     if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
-        if (a.parent) {
+        if (a.slots) {
+            if (a.parent) multi_split_f32_kernel<T, true, true, true><<<grid, 256, 0, stream>>>(a);
+            else multi_split_f32_kernel<T, true, false, true><<<grid, 256, 0, stream>>>(a);
+            st = launch_status(a.parent ? "decode_tree_f32_slots" : "decode_multi_f32_slots");
+        } else if (a.parent) {
             if (a.state) multi_split_f32_kernel<T, true, true><<<grid, 256, 0, stream>>>(a);
             else multi_split_f32_kernel<T, false, true><<<grid, 256, 0, stream>>>(a);
             st = launch_status("decode_tree_f32");
@@ -849,11 +936,12 @@ int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
         const int64_t ncm = a.n < a.wc ? a.n : a.wc;
         ncommit = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)sizeof(T) / 16), 256);
     }
-    if (a.state) multi_reduce_kernel<T, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
+    if (a.slots) multi_reduce_kernel<T, true, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
+    else if (a.state) multi_reduce_kernel<T, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
     else multi_reduce_kernel<T, false><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
     if ((st = launch_status("decode_multi_reduce"))) return st;
     if (a.state && a.commit)     // every reader of the state has finished: advance it (each row) by n
-        st = launch_advance(const_cast<int*>(a.state), nullptr, a.n, a.wc, a.B, a.sstride != 0, stream);
+        st = launch_advance(const_cast<int*>(a.state), nullptr, a.n, a.wc, a.B, a.sstride != 0, stream, a.slots, a.npool);
     return st;
 }
 
@@ -883,10 +971,11 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
                         const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
                         int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state,
-                        bool state_rows, const int32_t* parent, int64_t parent_bstride) {
+                        bool state_rows, const int32_t* parent, int64_t parent_bstride, const int32_t* slots) {
     MultiArgs a;
     a.parent = parent, a.pstride = (int)parent_bstride;   // tree call (never with commit)
     a.path = nullptr, a.pathstride = 0;
+    a.slots = slots, a.npool = (int)sink_k->shape[0];     // slot call (state_rows; B = q's rows, not the pool's)
     a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
     a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
     a.s_aux = s_aux;
@@ -928,7 +1017,7 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
     if (st) return st;
     const char* fam = parent ? "tree" : "multi";
     if (state) {
-        const char* dyn = state_rows ? "_rows" : "_dyn";
+        const char* dyn = slots ? "_slots" : state_rows ? "_rows" : "_dyn";
         if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d%s%s", fam, dname, a.D, a.nrb, dyn, commit ? "_commit" : "");
         else set_path("decode_%s_f32_%s_d%d%s%s", fam, dname, a.D, dyn, commit ? "_commit" : "");
     } else {
@@ -940,9 +1029,10 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
 
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                            const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream, bool rows,
-                           const int32_t* path, int64_t path_bstride) {
+                           const int32_t* path, int64_t path_bstride, const int32_t* slots) {
     MultiArgs a{};
     a.path = path, a.pathstride = (int)path_bstride;
+    a.slots = slots, a.npool = (int)window_k->shape[0];
     a.wk = make_view(window_k), a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new);
     a.B = (int)k_new->shape[0];
     a.Hkv = (int)k_new->shape[1];
@@ -960,19 +1050,22 @@ int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_
     }
     int st;
     if (nblk > 0) {
-        if (path) ring_commit_path_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        if (slots && path) ring_commit_slots_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        else if (slots) ring_commit_slots_kernel<false><<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
+        else if (path) ring_commit_path_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
         else ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
         if ((st = launch_status(path ? "ring_commit_path" : "ring_commit"))) return st;
     }
-    if ((st = launch_advance(state, count, a.n, a.wc, a.B, rows, stream))) return st;   // after every reader of the state
-    if (path) set_path(rows ? "ring_commit_path_rows" : "ring_commit_path_dyn");
-    else set_path(rows ? "ring_commit_rows" : "ring_commit_dyn");
+    // after every reader of the state
+    if ((st = launch_advance(state, count, a.n, a.wc, a.B, rows, stream, slots, a.npool))) return st;
+    if (path) set_path(slots ? "ring_commit_path_slots" : rows ? "ring_commit_path_rows" : "ring_commit_path_dyn");
+    else set_path(slots ? "ring_commit_slots" : rows ? "ring_commit_rows" : "ring_commit_dyn");
     return SFA_OK;
 }
 
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream) {
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots) {
     const int es = dtype_size(k->dtype);
     const int Hkv = (int)k->shape[1], ns = (int)sink_k->shape[2], wc = (int)window_k->shape[2];
     const int cpr = (int)(k->shape[3] * es / 16);
@@ -982,13 +1075,18 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         return SFA_ERR_UNSUPPORTED;
     }
     if (nblk > 0) {
-        ring_fill_varlen_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(
-            make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-            cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es);
+        if (slots)
+            ring_fill_varlen_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0]);
+        else
+            ring_fill_varlen_kernel<false><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, nullptr, 0);
         int st;
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
-    set_path("ring_fill_varlen");
+    set_path(slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
     return SFA_OK;
 }
 

@@ -50,7 +50,8 @@ int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                   const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
                   float scale, const DecodePlan& plan, hipStream_t stream, const sfa_tensor* k_new = nullptr,
                   const sfa_tensor* v_new = nullptr, int new_slot = -1, int* dyn_state = nullptr,
-                  bool one_pass = false, bool state_rows = false);   // state_rows: dyn_state = per-sequence rows [B][4]
+                  bool one_pass = false, bool state_rows = false,    // state_rows: dyn_state = per-sequence rows [B][4]
+                  const int32_t* slots = nullptr);   // slot call: row b of q works on row slots[b] of the cache and the state
 
 // sfa_decode_multi.hip: several new tokens over the sink + ring cache (sfa_decode_ring_multi); arguments already checked
 int decode_multi_check_head_dim(int64_t D, int dtype);
@@ -62,16 +63,18 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
                         int32_t* state = nullptr,    // dyn: sink_len / window_len = the full cache, write_pos = 0
                         bool rows = false,           // state = per-sequence rows [B][4] (sfa_decode_ring_multi_rows)
                         const int32_t* parent = nullptr,   // tree chunk (sfa_decode_ring_tree*, n <= 64, no commit)
-                        int64_t parent_bstride = 0);
+                        int64_t parent_bstride = 0,
+                        const int32_t* slots = nullptr);   // slot call (rows): the buffers are a pool, B = q's rows
 
 // sfa_ring_commit_dyn / _rows: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                            const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream,
                            bool rows = false, const int32_t* path = nullptr,   // path: sfa_ring_commit_path_*
-                           int64_t path_bstride = 0);
+                           int64_t path_bstride = 0, const int32_t* slots = nullptr);   // slots: sfa_ring_commit*_slots
 // sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream);
+                            int n_seq, int32_t* state, hipStream_t stream,
+                            const int32_t* slots = nullptr);   // slots: sequence i -> row slots[i] of a pool
 
 }  // namespace sfa

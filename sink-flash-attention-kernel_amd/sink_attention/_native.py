@@ -134,6 +134,19 @@ def _bind(lib):
     lib.sfa_ring_commit_path_rows.argtypes = [P, P, P, P, vp, vp, i64, vp, vp]
     lib.sfa_ring_fill_varlen.restype = i32
     lib.sfa_ring_fill_varlen.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp]
+    # slot-indexed siblings (continuous batching): the rows call plus `slots` after `state`
+    lib.sfa_decode_ring_step_slots.restype = i32
+    lib.sfa_decode_ring_step_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_multi_slots.restype = i32
+    lib.sfa_decode_ring_multi_slots.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_tree_slots.restype = i32
+    lib.sfa_decode_ring_tree_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i64, vp, vp, vp, sz, f32, u32, vp]
+    lib.sfa_ring_commit_slots.restype = i32
+    lib.sfa_ring_commit_slots.argtypes = [P, P, P, P, vp, vp, vp, vp]
+    lib.sfa_ring_commit_path_slots.restype = i32
+    lib.sfa_ring_commit_path_slots.argtypes = [P, P, P, P, vp, vp, i64, vp, vp, vp]
+    lib.sfa_ring_fill_varlen_slots.restype = i32
+    lib.sfa_ring_fill_varlen_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp]
 
 
 def lib():

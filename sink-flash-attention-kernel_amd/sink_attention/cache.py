@@ -317,12 +317,16 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             self.sink_len, self.window_len, self.write_pos = sl, wl, wp
 
     def decode_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
-                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        slots=None) -> torch.Tensor:
         """``decode_step`` with the state on the device (``sfa_decode_ring_step_dyn``): capturable into a hipGraph.
         ``out`` (optional, [B,H_q,1,D]) lets the caller keep a static output buffer across replays.  Per-sequence mode
-        (``sfa_decode_ring_step_rows``): every row stores its token at its own slot and attends over its own keys."""
+        (``sfa_decode_ring_step_rows``): every row stores its token at its own slot and attends over its own keys.
+        ``slots`` (``sfa_decode_ring_step_slots``, see ``init_pool``): batch row b works on cache row ``slots[b]``; a row
+        with ``slots[b] = -1`` is inactive (zeros in ``out``, nothing stored, no state moves)."""
         import math
         from . import _native as N
+        slots = self._slots_arg(slots, q.shape[0], writes=True)
         st = getattr(self, "_dev_state", None)
         assert st is not None, "call enable_device_state() first"
         ss = getattr(self, "_step_state", None)
@@ -345,6 +349,17 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if out is None:
             out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = ss["descs"]
+        if slots is not None:
+            N.require_gpu(slots)
+            with torch.cuda.device(q.device):
+                rc = ss["lib"].sfa_decode_ring_step_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
+                                                          N.desc(out),
+                                                          s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                          st.data_ptr(), slots.data_ptr(), ss["ws"].data_ptr(),
+                                                          ss["ws"].numel(), ss["scale"], self._decode_flags(N),
+                                                          N.stream_ptr(q.device))
+            N.check(rc, "sfa_decode_ring_step_slots")
+            return out
         with torch.cuda.device(q.device):
             fn = ss["lib"].sfa_decode_ring_step_rows if self._per_seq else ss["lib"].sfa_decode_ring_step_dyn
             rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
@@ -356,36 +371,42 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     # ---------------------------- several new tokens with the state on the device (capturable speculative step)
     def extend_attention_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
-                             s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                             slots=None) -> torch.Tensor:
         """``extend_attention`` with the state on the device (``sfa_decode_ring_multi_dyn``, commit off): capturable into a
         hipGraph, no host sync.  Neither the cache nor the device state changes.  The output is bitwise what
         ``extend_attention`` gives at the same state.  ``out`` (optional, [B, H_q, n, D]) is a static output buffer.
         Per-sequence mode (``sfa_decode_ring_multi_rows``): each row attends with its own state; ``extend_step_dyn``
-        then advances every row by n."""
-        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False)
+        then advances every row by n.  ``slots`` (``sfa_decode_ring_multi_slots``): row b attends over cache row
+        ``slots[b]`` of the pool; the same slot may be named twice here (nothing is written)."""
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False, slots=slots)
 
     def extend_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
-                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        slots=None) -> torch.Tensor:
         """``extend_step`` with the state on the device: attend, commit all n tokens, advance the device state.  The host
-        counters are refreshed by ``pull_state()``."""
-        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=True)
+        counters are refreshed by ``pull_state()``.  ``slots``: as for ``decode_step_dyn`` (each slot at most once)."""
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=True, slots=slots)
 
-    def commit_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, count: torch.Tensor) -> None:
+    def commit_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, count: torch.Tensor, slots=None) -> None:
         """Store the first ``a = clamp(count, 0, n)`` tokens of a chunk ``[B, H_kv, n, D]`` into the ring and advance the
         device state (``sfa_ring_commit_dyn``): afterwards buffers and state are what ``append(k_new[:, :, :a], ...)``
         leaves.  ``count`` is a 0-d or 1-element integer tensor on the GPU (the acceptance count of a speculative step,
         computed by torch ops); it is never read on the host.  Per-sequence mode (``sfa_ring_commit_rows``): ``count``
-        holds B values, row b commits its first ``clamp(count[b], 0, n)`` tokens."""
-        return self._commit_dyn(k_new, v_new, count, None)
+        holds B values, row b commits its first ``clamp(count[b], 0, n)`` tokens.  ``slots``
+        (``sfa_ring_commit_slots``): row b commits into cache row ``slots[b]`` (each slot at most once; an inactive row
+        commits nothing)."""
+        return self._commit_dyn(k_new, v_new, count, None, slots)
 
-    def _commit_dyn(self, k_new, v_new, count, path):
+    def _commit_dyn(self, k_new, v_new, count, path, slots=None):
         from . import _native as N
+        slots = self._slots_arg(slots, k_new.shape[0], writes=True)
         st = self._require_dyn("commit_path_dyn" if path is not None else "commit_dyn")
         if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
                 or count.dtype == torch.bool:
             raise TypeError("count must be an integer tensor")
         if self._per_seq:
-            return self._commit_rows(k_new, v_new, count, st, path)
+            return self._commit_rows(k_new, v_new, count, st, path, slots)
         if count.numel() != 1:
             raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
         N.require_gpu(k_new, v_new, count, self.window_k)
@@ -413,13 +434,15 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                              N.stream_ptr(k_new.device))
         N.check(rc, "sfa_ring_commit_dyn")
 
-    def _commit_rows(self, k_new, v_new, count, st, path=None):
+    def _commit_rows(self, k_new, v_new, count, st, path=None, slots=None):
         from . import _native as N
         B, H_kv, _w, D = self.window_k.shape
+        if slots is not None:           # the buffers are the pool: B is the chunk's
+            B = slots.numel()
         if count.numel() != B:
             raise ValueError(f"count must hold B = {B} values in per-sequence mode (one per sequence), "
                              f"got shape {tuple(count.shape)}")
-        N.require_gpu(k_new, v_new, count, self.window_k)
+        N.require_gpu(k_new, v_new, count, self.window_k, slots)
         if k_new.dim() != 4 or k_new.shape[:2] != (B, H_kv) or k_new.shape[3] != D or v_new.shape != k_new.shape \
                 or k_new.shape[2] < 1:
             raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = [{B}, {H_kv}, n, {D}], got {tuple(k_new.shape)}")
@@ -435,14 +458,24 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             from .decode_kernel import tree_path_dev
             pt, pstride = tree_path_dev(path, B, k_new.shape[2], k_new.device)
             with torch.cuda.device(k_new.device):
-                rc = N.lib().sfa_ring_commit_path_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
-                                                       pt.data_ptr(), pstride, st.data_ptr(), N.stream_ptr(k_new.device))
-            N.check(rc, "sfa_ring_commit_path_rows")
+                if slots is not None:
+                    rc = N.lib().sfa_ring_commit_path_slots(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
+                                                            pt.data_ptr(), pstride, st.data_ptr(), slots.data_ptr(),
+                                                            N.stream_ptr(k_new.device))
+                else:
+                    rc = N.lib().sfa_ring_commit_path_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
+                                                           pt.data_ptr(), pstride, st.data_ptr(),
+                                                           N.stream_ptr(k_new.device))
+            N.check(rc, "sfa_ring_commit_path_slots" if slots is not None else "sfa_ring_commit_path_rows")
             return
         with torch.cuda.device(k_new.device):
-            rc = N.lib().sfa_ring_commit_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
-                                              N.stream_ptr(k_new.device))
-        N.check(rc, "sfa_ring_commit_rows")
+            if slots is not None:
+                rc = N.lib().sfa_ring_commit_slots(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
+                                                   slots.data_ptr(), N.stream_ptr(k_new.device))
+            else:
+                rc = N.lib().sfa_ring_commit_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
+                                                  N.stream_ptr(k_new.device))
+        N.check(rc, "sfa_ring_commit_slots" if slots is not None else "sfa_ring_commit_rows")
 
     # ------------------------------- tree-structured speculative verify (Medusa / EAGLE / SpecInfer draft trees)
     def extend_attention_tree(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, parent,
@@ -461,26 +494,28 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def extend_attention_tree_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
                                   parent: torch.Tensor, s_aux: Optional[torch.Tensor] = None,
-                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                  out: Optional[torch.Tensor] = None, slots=None) -> torch.Tensor:
         """``extend_attention_tree`` with the state on the device (``sfa_decode_ring_tree_dyn``; per-sequence mode
         ``sfa_decode_ring_tree_rows``, row b with its own state and tree): capturable, no host sync, neither the cache
         nor the state changes.  ``parent`` is an integer tensor ([n] or [B, n]) that is never read on the host: an entry
-        outside [-1, u) reads as -1 (a root)."""
+        outside [-1, u) reads as -1 (a root).  ``slots`` (``sfa_decode_ring_tree_slots``): row b verifies its tree
+        against cache row ``slots[b]`` (the same slot may be named twice: nothing is written)."""
         from .decode_kernel import tree_parent_dev
         if q.shape[2] > 64:
             raise ValueError(f"a tree chunk holds at most 64 nodes, got n = {q.shape[2]}")
         tree = tree_parent_dev(parent, q.shape[0], q.shape[2], q.device)
-        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False, tree=tree)
+        return self._ring_multi_dyn(q, k_new, v_new, s_aux, out, commit=False, tree=tree, slots=slots)
 
     def commit_path_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, path: torch.Tensor,
-                        count: torch.Tensor) -> None:
+                        count: torch.Tensor, slots=None) -> None:
         """Store an accepted tree path (``sfa_ring_commit_path_dyn`` / ``_rows``): with ``a = clamp(count, 0, n)`` the
         chunk rows ``path[:a]`` (``path`` [n] or [B, n], entries clamped into [0, n)) enter the ring in that order and
         the device state advances by a - buffers and state are then what ``append(k_new[:, :, path[:a]], ...)`` leaves.
-        ``count`` follows the rules of ``commit_dyn`` (one value, or B values in per-sequence mode).  No host sync."""
+        ``count`` follows the rules of ``commit_dyn`` (one value, or B values in per-sequence mode).  No host sync.
+        ``slots`` (``sfa_ring_commit_path_slots``): as for ``commit_dyn``."""
         if not isinstance(path, torch.Tensor):
             raise TypeError("path must be an integer tensor")
-        return self._commit_dyn(k_new, v_new, count, path)
+        return self._commit_dyn(k_new, v_new, count, path, slots)
 
     def commit_path(self, k_new: torch.Tensor, v_new: torch.Tensor, path) -> None:
         """Host-state commit of a tree path: ``append`` of the chunk rows ``path`` ([a] shared or [B, a]; list or
@@ -531,18 +566,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if k.dtype not in N.SFA_DTYPE or v.dtype != k.dtype:
             raise TypeError("k / v must share one of the dtypes float32 / float16 / bfloat16")
         _one, H_kv, T, D = k.shape
-        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
-            if cu_seqlens.dtype.is_floating_point or cu_seqlens.dtype == torch.bool or cu_seqlens.dim() != 1:
-                raise TypeError("cu_seqlens must be a 1-D integer tensor")
-            cu = cu_seqlens.to(device=k.device, dtype=torch.int32).contiguous()
-        else:
-            lst = cu_seqlens.tolist() if isinstance(cu_seqlens, torch.Tensor) else [int(x) for x in cu_seqlens]
-            if len(lst) < 2 or lst[0] != 0 or lst[-1] > T or any(b < a for a, b in zip(lst[:-1], lst[1:])):
-                raise ValueError(f"bad cu_seqlens {lst} for T={T}: need 0 = c_0 <= c_1 <= ... <= T")
-            cu = torch.tensor(lst, dtype=torch.int32, device=k.device)
+        cu = self._cu_arg(cu_seqlens, T, k.device)
         n_seq = cu.numel() - 1
-        if n_seq < 1:
-            raise ValueError("cu_seqlens needs at least two offsets")
         mk = lambda n: torch.zeros(n_seq, H_kv, n, D, dtype=k.dtype, device=k.device)
         self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
         self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
@@ -559,14 +584,137 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         self._dev_state = state
         return state
 
-    def positions(self) -> torch.Tensor:
+    @staticmethod
+    def _cu_arg(cu_seqlens, T, device):
+        """cu_seqlens as a device int32 tensor: a device tensor is taken as it is (no sync), a host list / CPU tensor is
+        checked against the pack length T."""
+        if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.is_cuda:
+            if cu_seqlens.dtype.is_floating_point or cu_seqlens.dtype == torch.bool or cu_seqlens.dim() != 1:
+                raise TypeError("cu_seqlens must be a 1-D integer tensor")
+            cu = cu_seqlens.to(device=device, dtype=torch.int32).contiguous()
+        else:
+            lst = cu_seqlens.tolist() if isinstance(cu_seqlens, torch.Tensor) else [int(x) for x in cu_seqlens]
+            if len(lst) < 2 or lst[0] != 0 or lst[-1] > T or any(b < a for a, b in zip(lst[:-1], lst[1:])):
+                raise ValueError(f"bad cu_seqlens {lst} for T={T}: need 0 = c_0 <= c_1 <= ... <= T")
+            cu = torch.tensor(lst, dtype=torch.int32, device=device)
+        if cu.numel() < 2:
+            raise ValueError("cu_seqlens needs at least two offsets")
+        return cu
+
+    def positions(self, slots=None) -> torch.Tensor:
         """Per-sequence mode: the ``seen`` column of the device state, ``[B]`` int32 (a view that follows the state, no
-        sync): the position the next token of each sequence takes, for per-row RoPE positions built in torch ops."""
+        sync): the position the next token of each sequence takes, for per-row RoPE positions built in torch ops.
+        ``slots`` (list or integer tensor ``[B]``): ``seen`` of the named slots of a pool, gathered by torch indexing (no
+        sync); inactive rows (-1) read 0."""
         st = self._require_dyn("positions")
         if not self._per_seq:
             raise RuntimeError("positions() needs per-sequence mode (prefill_varlen / enable_device_state(per_sequence="
                                "True)): the shared state holds no token count")
-        return st[:, 3]
+        if slots is None:
+            return st[:, 3]
+        idx = self._slots_arg(slots, None, writes=False).to(st.device).long()
+        S = st.shape[0]
+        ok = (idx >= 0) & (idx < S)
+        return torch.where(ok, st[idx.clamp(0, S - 1), 3], torch.zeros_like(st[:1, 3]))
+
+    # ------------------------------------------------ slot pool (continuous batching)
+    _pool = False        # set by init_pool
+
+    def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda") -> torch.Tensor:
+        """Allocate a pool of ``num_slots`` cache rows that lives as long as the server: ``[S, H_kv, num_sink /
+        window_size, D]`` buffers and a zeroed int32 ``[S, 4]`` device state ``{sink_len, window_len, write_pos, seen}``
+        (returned).  The layer enters per-sequence mode (the host-state methods refuse, as after ``prefill_varlen``).  A
+        step then names the slots it works on with the ``slots=`` keyword of the dyn methods: a device int32 ``[B]``
+        tensor (never read on the host, so a captured step replays at any occupancy by rewriting it in place), or a host
+        list, which is checked for range and duplicates and uploaded.  Batch row b works on slot ``slots[b]``; -1 marks
+        an inactive row.  A slot must be prefilled (``prefill_slots``) before it is used: an all-zero state row is not a
+        prefilled cache."""
+        if self.window_size < 1:
+            raise ValueError("init_pool needs a ring of at least one slot (window_size >= 1)")
+        if int(num_slots) < 1:
+            raise ValueError(f"init_pool needs at least one slot, got num_slots = {num_slots}")
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("the pool's dtype must be float32 / float16 / bfloat16")
+        mk = lambda n: torch.zeros(int(num_slots), H_kv, n, D, dtype=dtype, device=device)
+        self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
+        self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
+        self._dev_state = torch.zeros(int(num_slots), 4, dtype=torch.int32, device=device)
+        self.sink_len = self.window_len = self.write_pos = self.seen_tokens = 0   # not kept in this mode
+        self.is_initialized = self.prefilled = True
+        self._per_seq = self._pool = True
+        return self._dev_state
+
+    @property
+    def num_slots(self) -> int:
+        """Rows of the cache buffers (the S of a pool)."""
+        return 0 if self.sink_k is None else self.sink_k.shape[0]
+
+    def _slots_arg(self, slots, B, writes):
+        """``slots=`` of a dyn call as a contiguous int32 tensor on the cache's device (None stays None).  A device tensor
+        is passed through unread.  A host list / CPU tensor is checked: B entries, each -1 or in [0, S), and - for a call
+        that stores or advances (``writes``) - no slot twice."""
+        if slots is None:
+            return None
+        if not self._per_seq:
+            raise RuntimeError("slots= needs per-sequence state rows: init_pool (or prefill_varlen / "
+                               "enable_device_state(per_sequence=True))")
+        S = self.num_slots
+        if isinstance(slots, torch.Tensor) and slots.is_cuda:
+            if slots.dtype.is_floating_point or slots.dtype == torch.bool or slots.dim() != 1:
+                raise TypeError("slots must be a 1-D integer tensor")
+            if B is not None and slots.numel() != B:
+                raise ValueError(f"slots must hold B = {B} entries (one per batch row), got {slots.numel()}")
+            return slots.to(dtype=torch.int32).contiguous()     # an int32 contiguous tensor is passed as it is
+        lst = slots.tolist() if isinstance(slots, torch.Tensor) else [int(x) for x in slots]
+        if B is not None and len(lst) != B:
+            raise ValueError(f"slots must hold B = {B} entries (one per batch row), got {len(lst)}")
+        bad = [x for x in lst if x != -1 and not 0 <= x < S]
+        if bad:
+            raise ValueError(f"slots {bad} outside the pool of {S} slots (use -1 for an inactive row)")
+        live = [x for x in lst if x >= 0]
+        if writes and len(set(live)) != len(live):
+            raise ValueError(f"slots {lst}: a slot is named twice in a call that stores or advances")
+        return torch.tensor(lst, dtype=torch.int32, device=self.window_k.device)
+
+    def prefill_slots(self, k: torch.Tensor, v: torch.Tensor, cu_seqlens, slots) -> torch.Tensor:
+        """Admit requests into a pool: ``k`` / ``v`` ``[1, H_kv, T, D]`` hold packed sequences as for ``prefill_varlen``;
+        sequence i is stored into slot ``slots[i]`` with the placement a prefill of it alone gives and writes that state
+        row (``sfa_ring_fill_varlen_slots``, one launch, no allocation).  Every other slot keeps buffers and state, so
+        this runs while the other sequences keep decoding, and it is how a released slot is reused.  Returns the pool's
+        state."""
+        from . import _native as N
+        if not (self._per_seq and self.is_initialized):
+            raise RuntimeError("prefill_slots needs a pool: call init_pool first")
+        if k.dim() != 4 or k.shape[0] != 1 or v.shape != k.shape:
+            raise ValueError(f"k / v must be packed [1, H_kv, T, D] tensors of one shape, got {tuple(k.shape)} / "
+                             f"{tuple(v.shape)}")
+        n_seq = (cu_seqlens.numel() if isinstance(cu_seqlens, torch.Tensor) else len(cu_seqlens)) - 1
+        slots = self._slots_arg(slots, n_seq, writes=True)
+        N.require_gpu(k, v, self.window_k, slots)
+        if k.dtype != self.window_k.dtype or v.dtype != k.dtype:
+            raise TypeError("k / v must have the pool's dtype")
+        if k.shape[1] != self.window_k.shape[1] or k.shape[3] != self.window_k.shape[3]:
+            raise ValueError(f"k / v must be [1, H_kv, T, D] = [1, {self.window_k.shape[1]}, T, {self.window_k.shape[3]}], "
+                             f"got {tuple(k.shape)}")
+        cu = self._cu_arg(cu_seqlens, k.shape[2], k.device)
+        k, v = self._rows16(k), self._rows16(v)
+        with torch.cuda.device(k.device):
+            rc = N.lib().sfa_ring_fill_varlen_slots(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k,
+                                                                           self.window_v, k, v)),
+                                                    cu.data_ptr(), n_seq, self._dev_state.data_ptr(), slots.data_ptr(),
+                                                    N.stream_ptr(k.device))
+        N.check(rc, "sfa_ring_fill_varlen_slots")
+        return self._dev_state
+
+    def release_slots(self, slots) -> None:
+        """Retire sequences: zero the state rows of ``slots`` (list or integer tensor; -1 entries name nothing) with torch
+        ops on the current stream (no sync, capturable).  The buffers keep their stale content, which no kernel reads
+        beyond a row's ``sink_len`` / ``window_len``.  A released slot must be prefilled again (``prefill_slots``) before
+        it is used: an all-zero state is not a prefilled cache."""
+        st = self._require_dyn("release_slots")
+        idx = self._slots_arg(slots, None, writes=False).to(st.device)
+        hit = (torch.arange(st.shape[0], device=st.device, dtype=torch.int32)[:, None] == idx[None, :]).any(dim=1)
+        st.mul_((~hit).to(torch.int32)[:, None])
 
     def _require_dyn(self, what):
         if not (self.is_initialized and self.prefilled):
@@ -594,14 +742,15 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             self._ring_desc = rd
         return rd[1]
 
-    def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit, tree=None):
+    def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit, tree=None, slots=None):
         """sfa_decode_ring_multi_dyn with the per-layer constants (buffer descriptors, a workspace for the full cache plus
         the chunk) built once per chunk shape, as _ring_multi does."""
         import math
         from . import _native as N
+        slots = self._slots_arg(slots, q.shape[0], writes=bool(commit))
         dev_state = self._require_dyn("extend_attention_tree_dyn" if tree is not None else
                                       "extend_step_dyn" if commit else "extend_attention_dyn")
-        N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
+        N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k, slots)
         B, H_q, n, D = q.shape
         H_kv = self.sink_k.shape[1]
         if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
@@ -628,7 +777,23 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
-            if tree is not None:
+            if slots is not None and tree is not None:
+                name = "sfa_decode_ring_tree_slots"
+                rc = st["lib"].sfa_decode_ring_tree_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
+                                                          N.desc(out),
+                                                          s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                          tree[0].data_ptr(), tree[1], dev_state.data_ptr(),
+                                                          slots.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
+                                                          st["scale"], 0, N.stream_ptr(q.device))
+            elif slots is not None:
+                name = "sfa_decode_ring_multi_slots"
+                rc = st["lib"].sfa_decode_ring_multi_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
+                                                           N.desc(out),
+                                                           s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
+                                                           st["ws"].data_ptr(), st["ws"].numel(), st["scale"], 0,
+                                                           N.stream_ptr(q.device))
+            elif tree is not None:
                 name = "sfa_decode_ring_tree_rows" if self._per_seq else "sfa_decode_ring_tree_dyn"
                 rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
                                               s_aux_f.data_ptr() if s_aux_f is not None else None,
@@ -723,27 +888,33 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
             self._seen_tokens = self.layers[0].seen_tokens
         return out
 
-    def extend_attention_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None):
-        """``SinkCacheLayer.extend_attention_dyn`` of one layer: verify with the state on the device (capturable)."""
-        return self._layer(layer_idx).extend_attention_dyn(q, key_states, value_states, s_aux=s_aux, out=out)
+    def decode_step_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None, slots=None):
+        """``SinkCacheLayer.decode_step_dyn`` of one layer: the fused single-token step with the state on the device."""
+        return self._layer(layer_idx).decode_step_dyn(q, key_states, value_states, s_aux=s_aux, out=out, slots=slots)
 
-    def extend_step_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None):
+    def extend_attention_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None, slots=None):
+        """``SinkCacheLayer.extend_attention_dyn`` of one layer: verify with the state on the device (capturable)."""
+        return self._layer(layer_idx).extend_attention_dyn(q, key_states, value_states, s_aux=s_aux, out=out,
+                                                           slots=slots)
+
+    def extend_step_dyn(self, q, key_states, value_states, layer_idx: int, s_aux=None, out=None, slots=None):
         """``SinkCacheLayer.extend_step_dyn`` of one layer: attention + commit of all n tokens, state on the device.
         ``seen_tokens`` follows after ``pull_state()`` of layer 0."""
-        return self._layer(layer_idx).extend_step_dyn(q, key_states, value_states, s_aux=s_aux, out=out)
+        return self._layer(layer_idx).extend_step_dyn(q, key_states, value_states, s_aux=s_aux, out=out, slots=slots)
 
-    def commit_dyn(self, key_states, value_states, count, layer_idx: int) -> None:
+    def commit_dyn(self, key_states, value_states, count, layer_idx: int, slots=None) -> None:
         """``SinkCacheLayer.commit_dyn`` of one layer: store the first ``count`` (device tensor) tokens of the chunk."""
-        self._layer(layer_idx).commit_dyn(key_states, value_states, count)
+        self._layer(layer_idx).commit_dyn(key_states, value_states, count, slots=slots)
 
     def extend_attention_tree(self, q, key_states, value_states, parent, layer_idx: int, s_aux=None):
         """``SinkCacheLayer.extend_attention_tree`` of one layer: verify a draft tree, host state, nothing committed."""
         return self._layer(layer_idx).extend_attention_tree(q, key_states, value_states, parent, s_aux=s_aux)
 
-    def extend_attention_tree_dyn(self, q, key_states, value_states, parent, layer_idx: int, s_aux=None, out=None):
+    def extend_attention_tree_dyn(self, q, key_states, value_states, parent, layer_idx: int, s_aux=None, out=None,
+                                  slots=None):
         """``SinkCacheLayer.extend_attention_tree_dyn`` of one layer: verify a draft tree, state on the device."""
         return self._layer(layer_idx).extend_attention_tree_dyn(q, key_states, value_states, parent, s_aux=s_aux,
-                                                                out=out)
+                                                                out=out, slots=slots)
 
     def commit_path(self, key_states, value_states, path, layer_idx: int) -> None:
         """``SinkCacheLayer.commit_path`` of one layer: append the chunk rows of an accepted path (host state)."""
@@ -751,13 +922,28 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         if layer_idx == 0:
             self._seen_tokens = self.layers[0].seen_tokens
 
-    def commit_path_dyn(self, key_states, value_states, path, count, layer_idx: int) -> None:
+    def commit_path_dyn(self, key_states, value_states, path, count, layer_idx: int, slots=None) -> None:
         """``SinkCacheLayer.commit_path_dyn`` of one layer: store the first ``count`` (device) rows of ``path``."""
-        self._layer(layer_idx).commit_path_dyn(key_states, value_states, path, count)
+        self._layer(layer_idx).commit_path_dyn(key_states, value_states, path, count, slots=slots)
 
     def prefill_varlen(self, key_states, value_states, cu_seqlens, layer_idx: int) -> torch.Tensor:
         """``SinkCacheLayer.prefill_varlen`` of one layer: a packed ragged batch into per-sequence buffers and state."""
         return self._layer(layer_idx).prefill_varlen(key_states, value_states, cu_seqlens)
+
+    def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda",
+                  layer_idx: int = 0) -> torch.Tensor:
+        """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state."""
+        return self._layer(layer_idx).init_pool(num_slots, H_kv, D, dtype, device)
+
+    def prefill_slots(self, key_states, value_states, cu_seqlens, slots, layer_idx: int) -> torch.Tensor:
+        """``SinkCacheLayer.prefill_slots`` of one layer: packed sequences into the named slots of its pool."""
+        return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
+
+    def release_slots(self, slots) -> None:
+        """``SinkCacheLayer.release_slots`` of every layer that holds a pool (layers without one are skipped)."""
+        for layer in self.layers:
+            if layer._pool:
+                layer.release_slots(slots)
 
     def get_seq_length(self, layer_idx: int = 0, *_, **__) -> int:
         return self.layers[layer_idx].get_seq_length() if layer_idx < len(self.layers) else 0

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
 fused-step / device-state / one-pass variants against the linearised cache.
-usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe]   (probe: keys are the +-1 codes of tests/probe_inputs.py and
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe] [--slots]   (probe: keys are the +-1 codes of tests/probe_inputs.py and
 every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
-one just evicted or the last sink)"""
+one just evicted or the last sink; --slots: the single-token steps (decode_step_dyn only; the multi-token and commit
+calls are not fuzzed here) also run through a slot pool - the B sequences sit in a random permutation of a larger pool and the
+batch carries random inactive rows - and are held to the same reference)"""
 import os
 import random
 import sys
@@ -19,7 +21,8 @@ from sink_attention.cache import SinkCacheLayer
 
 inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
 assert inputs in ("randn", "probe"), inputs
-sys.argv = [a for a in sys.argv if not a.startswith("--inputs=")]
+use_slots = "--slots" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith("--inputs=") and a != "--slots"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
@@ -74,6 +77,25 @@ for case in range(n_cases):
             l.update(kp, vp)
         b.enable_device_state()
         ok = True
+        if use_slots and W >= 1:
+            S = B + rng.randrange(4)
+            where = rng.sample(range(S), B)                       # sequence i lives in slot where[i]
+            rows = sorted(rng.sample(range(B + rng.randrange(3)), B)) if B > 1 else [rng.randrange(2)]
+            Bx = max(rows) + 1 + rng.randrange(2)                 # batch rows, the others inactive
+            slot_list = [-1] * Bx
+            for i, r in enumerate(rows):
+                slot_list[r] = where[i]
+            d = SinkCacheLayer(ns, W)
+            d.one_pass = rng.random() < 0.5
+            d.init_pool(S, Hkv, D, dt, "cuda")
+            d.prefill_slots(kp.transpose(0, 1).reshape(1, Hkv, B * pre, D), vp.transpose(0, 1).reshape(1, Hkv, B * pre, D),
+                            [pre * i for i in range(B + 1)], where)
+            slots_dev = torch.tensor(slot_list, dtype=torch.int32, device="cuda")
+
+            def spread(t):                                        # [B, ...] -> [Bx, ...], garbage on inactive rows
+                x = torch.randn(Bx, *t.shape[1:], device="cuda").to(t.dtype)
+                x[rows] = t
+                return x
         for step in range(rng.choice([1, 3, W + 3])):
             kn, vn = keys(B, Hkv, 1, D, dt), torch.randn(B, Hkv, 1, D, device="cuda", dtype=dt)
             hist = torch.cat([hist, kn], dim=2)
@@ -85,6 +107,12 @@ for case in range(n_cases):
             o4 = sink_decode_attention(q, kc, vc, s_aux=sa)
             r = ref_decode(q, kc, vc, sa)
             e = [(o.double() - r).abs().max().item() for o in (o1, o2, o3, o4)]
+            if use_slots and W >= 1:
+                o5 = d.decode_step_dyn(spread(q), spread(kn), spread(vn), s_aux=sa, slots=slots_dev)
+                e.append((o5[rows].double() - r).abs().max().item())
+                dead = [x for x in range(Bx) if x not in rows]
+                if dead and bool(o5[dead].any()):
+                    e.append(float("inf"))                       # an inactive row must be zeros
             # (the device-state step sizes its launch for the FULL cache, so while the ring is still filling its split
             # plan, hence its summation order, may differ from the host-state step: tolerance, not bitwise)
             if max(e) > tol or any(torch.isnan(o).any() for o in (o1, o2, o3, o4)):
@@ -94,6 +122,8 @@ for case in range(n_cases):
         b.pull_state()
         if ok and (a.write_pos, a.window_len) != (b.write_pos, b.window_len):
             ok, desc = False, desc + " state mismatch"
+        if ok and use_slots and W >= 1 and d.positions(where).tolist() != [hist.shape[2]] * B:
+            ok, desc = False, desc + " slot positions mismatch"
     except Exception as ex:      # noqa: BLE001
         ok, desc = False, desc + " " + repr(ex)[:200]
     if not ok:
