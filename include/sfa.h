@@ -478,6 +478,46 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
                                const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
                                void* stream);
 
+/*
+ * Packed ragged step over a pool (chunked prefill and decode in one call).  The new tokens of n_seq sequences lie back
+ * to back, the layout sfa_fwd_varlen and sfa_ring_fill_varlen take:
+ *   q, o [1, Hq, T, D]   k_new, v_new [1, Hkv, T, D]   cu_q device int32 [n_seq + 1]   slots device int32 [n_seq]
+ *   sink_k/v [S, Hkv, num_sink, D]   window_k/v [S, Hkv, Wc, D]   state int32 [S][4]
+ * Sequence i is packed rows [cu_q[i], cu_q[i + 1]) (n_i >= 0 of them) and works on cache row and state row slots[i].
+ * cu_q is read on the device and not validated: offsets are clamped into [0, T] and made non-decreasing as
+ * sfa_ring_fill_varlen does, so bad offsets cannot address outside the pack.
+ *   - Mask: sequence i is attended exactly as sfa_decode_ring_multi with n = n_i at the state of its slot (sinks always;
+ *     ring position c iff c in [t - Wc + 1, t]; chunk token u iff u <= t and t - u <= Wc - 1).  n_i > Wc is legal.
+ *     s_aux enters the denominator only.
+ *   - Inactive rows and padding: the o rows of a sequence whose slot is outside [0, S), of an empty sequence (none) and
+ *     of packed rows that no sequence covers (the tail behind cu_q[n_seq] of a step captured at a fixed T) are written
+ *     as zeros; nothing is stored or advanced for them.  Decided on the device: a step captured at fixed (T, n_seq)
+ *     replays at any mix of lengths and any occupancy.
+ *   - commit != 0: after every read of the cache (stream order), token t >= n_i - Wc of sequence i goes to ring slot
+ *     (write_pos + t) mod Wc of its slot, and a trailing launch advances each named state row by n_i (seen += n_i).
+ *     Buffers and state rows are then bitwise what sfa_ring_commit_slots leaves for the same tokens.  sink_len never
+ *     changes: the FIRST chunk of a prompt is still a prefill (sfa_ring_fill_varlen_slots writes the sinks); this call
+ *     continues a sequence that has been admitted.
+ *   - The same slot twice in one call: undefined with commit, allowed without.
+ *   - The output rows of a sequence do not depend on where it lies in the pack or on its neighbours: its split plan is
+ *     a function of the call's shape (T, n_seq, heads) and its own (state row, n_i).  No atomics.
+ * Work is sized by T, not by n_seq * max n_i: a workgroup is (sequence, 32-row block of its G * n_i rows, KV head,
+ * split), at most ceil(G T / 32) + n_seq row blocks, mapped by a one-workgroup preparation launch that reads cu_q only.
+ * Host checks before anything launches: q / k_new / v_new / o have shape[0] = 1 and share T; the pool buffers share S;
+ * state, slots and cu_q are non-null; n_seq >= 1; strides, alignment, head dim and dtype as for
+ * sfa_decode_ring_multi_slots; workspace >= sfa_decode_ragged_workspace_bytes(n_seq, Hq, Hkv, T, num_sink + Wc, D,
+ * dtype) bytes, 256-byte aligned (0: unsupported head dim or shape; no GPU needed).  sfa_last_path() names carry
+ * "_ragged".
+ */
+size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                         int64_t D, int dtype);
+
+int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                 const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                 const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                                 int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                 void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

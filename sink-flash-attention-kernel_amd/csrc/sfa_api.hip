@@ -606,6 +606,40 @@ int sfa_decode_ring_multi_slots(const sfa_tensor* q, const sfa_tensor* sink_k, c
                                scale, flags, (hipStream_t)stream, state, true, nullptr, 0, slots);
 }
 
+size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                         int64_t D, int dtype) {
+    return decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+}
+
+int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                 const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                 const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
+                                 int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                 void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
+    SFA_CHECK_ARG(cu_q != nullptr, "cu_q: null device pointer");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
+    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+    int st;
+    // every check of the slots call at the full cache; q / k_new / v_new / o share shape[0] and T there
+    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, true))) return st;
+    SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
+                  (long long)q->shape[0]);
+    SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
+    const size_t need = decode_ragged_workspace(n_seq, q->shape[1], k_new->shape[1], q->shape[2], ns + Wc, q->shape[3],
+                                                q->dtype);
+    if (need == 0 || workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
+        set_error("decode_ragged workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
+                  workspace);
+        return SFA_ERR_WORKSPACE;
+    }
+    return decode_ragged_launch(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, commit, state, slots, cu_q,
+                                n_seq, workspace, scale, flags, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 namespace {

@@ -88,6 +88,65 @@ struct MultiArgs {
     int npool;
 };
 
+// packed calls (sfa_decode_ring_ragged_slots): a second kernel argument that only the ragged instances take.  q / k_new
+// / v_new / o are [1, H, T, D] packs; sequence i = packed rows [cu_q[i], cu_q[i + 1]) (offsets clamped into [0, T] and
+// made non-decreasing, as ring_fill_varlen_kernel does) works on cache row slots[i].  In MultiArgs B = 1, n / R are
+// set per workgroup (wave) from cu_q, nrb = the row-block bound ceil(G * T / 32) + n_seq, partial rows are indexed by
+// packed row: (hk * T + packed row) * G + g.
+struct RaggedArgs {
+    const int* cu_q;             // [n_seq + 1], device, not validated
+    const int2* blk;             // [nrb] row-block id -> (sequence, local 32-row block); sequence -1: surplus
+    const int* rowseq;           // [T] packed row -> sequence, -1: covered by none (padding)
+    int n_seq, T;
+};
+
+// the second argument of a ragged kernel instance (`RA...` is empty for every other instance: its signature, argument
+// block and code stay those of a kernel without the flag)
+__device__ __forceinline__ RaggedArgs ragged_of() { return RaggedArgs{}; }
+__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg) { return rg; }
+
+// sequence i of the pack: first packed row and length
+struct RaggedSeq {
+    int c0, n;
+};
+
+__device__ __forceinline__ RaggedSeq ragged_seq(const RaggedArgs& rg, int i) {
+    int c0 = rg.cu_q[i], c1 = rg.cu_q[i + 1];
+    c0 = c0 < 0 ? 0 : (c0 > rg.T ? rg.T : c0);
+    c1 = c1 < c0 ? c0 : (c1 > rg.T ? rg.T : c1);
+    return RaggedSeq{c0, c1 - c0};
+}
+
+// the preparation launch of a packed call: one workgroup writes the two tables from cu_q alone (it reads no cache state,
+// so the state-ordering rule is unaffected).  Sequence i owns the block ids [start_i, start_i + ceil(G n_i / 32)) with
+// start_i = floor(G c0_i / 32) + i: no scan is needed, the ranges are disjoint (floor(x + y) + 1 >= floor(x) + ceil(y))
+// and end below ceil(G T / 32) + n_seq; start_i and c0_i increase with i, so both maps are a binary search for the
+// last sequence that starts at or before the id, followed by a range check (offsets that are not monotonic find some
+// sequence or none, never an index outside the pack).
+__global__ __launch_bounds__(1024) void ragged_prep_kernel(RaggedArgs rg, int2* blk, int* rowseq, int G, int nrb) {
+    for (int x = threadIdx.x; x < nrb + rg.T; x += 1024) {
+        const bool row = x >= nrb;
+        const int id = row ? x - nrb : x;
+        int lo = 0, hi = rg.n_seq - 1;       // the last i with start(i) <= id; sequence 0 starts at 0
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            int c = rg.cu_q[mid];
+            c = c < 0 ? 0 : (c > rg.T ? rg.T : c);
+            const int64_t start = row ? c : (int64_t)G * c / 32 + mid;
+            if (start <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        const RaggedSeq s = ragged_seq(rg, lo);
+        if (row) {
+            rowseq[id] = (id >= s.c0 && id < s.c0 + s.n) ? lo : -1;
+        } else {
+            const int64_t local = id - ((int64_t)G * s.c0 / 32 + lo);
+            const bool hit = local >= 0 && local * 32 < (int64_t)G * s.n;
+            blk[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
+        }
+    }
+}
+
 inline __host__ __device__ int cdiv_i(int x, int y) { return (x + y - 1) / y; }
 
 struct MultiPlan {
@@ -137,8 +196,9 @@ __device__ __forceinline__ int state_wp(const MultiArgs& a, int c) {
 }
 
 // c: the cache row, wave-uniform (per-sequence state reads row c; a shared state has stride 0)
-template <bool Dyn>
-__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c) {
+// Ragged: the chunk length is n (the sequence's own n_i) in place of a.n
+template <bool Dyn, bool Ragged = false>
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0) {
     if constexpr (!Dyn) {
         return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S};
     } else {
@@ -151,7 +211,7 @@ __device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c) {
         sl = sl < 0 ? 0 : (sl > a.ns ? a.ns : sl);
         wl = wl < 0 ? 0 : (wl > a.wc ? a.wc : wl);
         wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
-        const MultiPlan p = multi_plan(sl, wl, a.n, a.want);
+        const MultiPlan p = multi_plan(sl, wl, Ragged ? n : a.n, a.want);
         auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };   // keep the plan in SGPRs
         return Fill{sl, wl, wp, u(p.T0), u(p.T1), u(p.T), u(p.tps), u(p.S)};
     }
@@ -174,7 +234,10 @@ __device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int
     return x - f.wl;
 }
 
-__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es) {
+// Ragged: the chunk is the n rows of k_new / v_new from packed row crow on, in place of the a.n rows of batch row b
+template <bool Ragged = false>
+__device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es,
+                                              int n = 0, int crow = 0) {
     TileInfo ti;
     const View *kv, *vv;
     int len, row = c;            // sink and ring: the cache row; the chunk: the batch row
@@ -183,7 +246,7 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
     } else if (i < f.T1) {
         ti.seg = 1, ti.start = kTile * (i - f.T0), len = f.wl, kv = &a.wk, vv = &a.wv;
     } else {
-        ti.seg = 2, ti.start = kTile * (i - f.T1), len = a.n, kv = &a.kn, vv = &a.vn, row = b;
+        ti.seg = 2, ti.start = kTile * (i - f.T1), len = Ragged ? n : a.n, kv = &a.kn, vv = &a.vn, row = b;
     }
     ti.count = len - ti.start < kTile ? len - ti.start : kTile;
     ti.ksn = kv->sn * es;
@@ -191,6 +254,7 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
     ti.k = kv->ptr + ((int64_t)row * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
     ti.v = vv->ptr + ((int64_t)row * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)ti.start * ti.vsn;
     if (ti.seg == 2) {
+        if constexpr (Ragged) ti.k += (int64_t)crow * ti.ksn, ti.v += (int64_t)crow * ti.vsn;
         ti.cmin = ti.start, ti.cmax = ti.start + ti.count - 1;
     } else if (ti.seg == 1) {
         const int s1 = ti.start + ti.count - 1;
@@ -293,8 +357,13 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-template <typename T, int D, bool Dyn, bool Tree, bool Slots = false>
-__global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a) {
+// Ragged (packed calls, with Dyn and Slots, never with Tree): the workgroup's row block comes from the table of
+// ragged_prep_kernel; it belongs to ONE sequence, whose length, first packed row and slot become the workgroup's
+// scalars (n, R, prow below), and everything else runs as for B = 1.
+template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
+__global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (Tree || !Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
@@ -309,28 +378,42 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     __shared__ __attribute__((aligned(16))) char smem[kWaves * 2 * TILE_BYTES];
 
     const int wid = xcd_work_id(blockIdx.x, gridDim.x);
-    const int rb = wid % a.nrb;
+    int rb = wid % a.nrb;
     int rest = wid / a.nrb;
     const int split = rest % a.Sw;   // decomposition over the LAUNCHED splits
     rest /= a.Sw;
     const int hk = rest % a.Hkv;
     const int b = rest / a.Hkv;
     int c = b;                         // the cache row: per workgroup, in an SGPR
-    if constexpr (Slots) {
+    // ragged: the sequence's length, rows and first packed row (in place of a.n, a.R and batch row b)
+    [[maybe_unused]] int rn = 0, rR = 0, prow = 0;
+    const auto nrow = [&]() { if constexpr (Ragged) return rR; else return a.R; };
+    if constexpr (Ragged) {
+        const int2 e = rg.blk[rb];
+        const int seq = __builtin_amdgcn_readfirstlane(e.x);
+        if (seq < 0) return;           // surplus of the row-block bound (whole workgroup)
+        rb = __builtin_amdgcn_readfirstlane(e.y);
+        c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+        if (c < 0) return;             // inactive sequence: the reduce writes its zeros
+        const RaggedSeq s = ragged_seq(rg, seq);
+        prow = __builtin_amdgcn_readfirstlane(s.c0);
+        rn = __builtin_amdgcn_readfirstlane(s.n);
+        rR = a.G * rn;
+    } else if constexpr (Slots) {
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) return;             // inactive row (whole workgroup): the reduce writes its zeros
     }
-    const Fill f = get_fill<Dyn>(a, c);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
     if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const int rho = 32 * rb + r;
-    const bool row_live = rho < a.R;
+    const bool row_live = rho < nrow();
     const int tq = row_live ? rho / a.G : 0;            // the lane's query index (dead rows: any, never stored)
     int tmin = (32 * rb) / a.G;
-    int tmax = ((32 * rb + 31 < a.R - 1) ? 32 * rb + 31 : a.R - 1) / a.G;
+    int tmax = ((32 * rb + 31 < nrow() - 1) ? 32 * rb + 31 : nrow() - 1) / a.G;
     // tree: the lane's row is node tq at depth td; [tmin, tmax] becomes the block's depth range over its live rows
     int td = tq;
     uint64_t tvis = 0, vor = 0;
@@ -358,7 +441,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     frag qf[DK];
     {
         const int head = hk * a.G + (row_live ? rho % a.G : 0);
-        const char* qp = a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)tq * a.q.sn) * 2;
+        const char* qp = a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)(Ragged ? prow + tq : tq) * a.q.sn) * 2;
 #pragma unroll
         for (int ks = 0; ks < DK; ++ks) {
             u32x4 raw = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
@@ -413,7 +496,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info(a, f, i, b, c, hk, es);
+            ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
             cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor);
             if (cls != 0) break;
         }
@@ -526,8 +609,9 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
         }
         __syncthreads();
     }
-    const int64_t row0 = ((int64_t)b * a.Hkv + hk) * a.R + 32 * rb;   // partial row of the block's first row
-    const int nrows = a.R - 32 * rb < 32 ? a.R - 32 * rb : 32;
+    // partial row of the block's first row
+    const int64_t row0 = Ragged ? ((int64_t)hk * rg.T + prow) * a.G + 32 * rb : ((int64_t)b * a.Hkv + hk) * a.R + 32 * rb;
+    const int nrows = nrow() - 32 * rb < 32 ? nrow() - 32 * rb : 32;
     if (tid < nrows) {
         float ms = -INFINITY;
 #pragma unroll
@@ -547,30 +631,63 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     }
 }
 
+// a packed (ragged) partial row: rowid = (hk * T + packed row) * G + g.  Finds the row's sequence in the table: the
+// callers go on as for B = 1 with rho = the row within the sequence, n = its length and c0 = its first packed row.
+// False: the row has no work (padding, an empty or inactive sequence); rho = the query head within the group and tp =
+// the packed row then say where its zeros go.
+struct RaggedRow {
+    int rho, hk, c, tp, n, c0;
+};
+
+__device__ __forceinline__ bool ragged_row(const MultiArgs& a, const RaggedArgs& rg, int64_t rowid, RaggedRow& r) {
+    const int64_t per = (int64_t)rg.T * a.G;
+    r.hk = (int)(rowid / per);
+    const int pr = (int)(rowid % per);
+    r.tp = pr / a.G;
+    r.rho = pr % a.G;
+    r.c = -1, r.n = 0, r.c0 = 0;
+    const int seq = __builtin_amdgcn_readfirstlane(rg.rowseq[r.tp]);
+    if (seq < 0) return false;
+    r.c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (r.c < 0) return false;
+    const RaggedSeq s = ragged_seq(rg, seq);
+    r.c0 = __builtin_amdgcn_readfirstlane(s.c0);
+    r.n = __builtin_amdgcn_readfirstlane(s.n);
+    r.rho += (r.tp - r.c0) * a.G;
+    return true;
+}
+
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
-template <typename T, bool Dyn, bool Tree, bool Slots = false>
-__global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
+template <typename T, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
+__global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA... ra) {
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (Tree || !Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
     const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int split = blockIdx.y;
-    const int64_t nrow = (int64_t)a.B * a.Hkv * a.R;
+    const int64_t nrow = Ragged ? (int64_t)a.Hkv * rg.T * a.G : (int64_t)a.B * a.Hkv * a.R;
     if (rowid >= nrow) return;
-    const int rho = (int)(rowid % a.R);
-    const int hk = (int)((rowid / a.R) % a.Hkv);
-    const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
+    int rho = (int)(rowid % a.R);
+    int hk = (int)((rowid / a.R) % a.Hkv);
+    const int b = Ragged ? 0 : (int)(rowid / ((int64_t)a.R * a.Hkv));
     // per wave: with R < 4 one workgroup holds rows of different sequences, and each has its own fill (and slot)
     int c = b;
-    if constexpr (Slots) {
+    [[maybe_unused]] int rn = 0, prow = 0;    // ragged: the sequence's length and first packed row
+    if constexpr (Ragged) {
+        RaggedRow r;
+        if (!ragged_row(a, rg, rowid, r)) return;
+        rho = r.rho, hk = r.hk, c = r.c, rn = r.n, prow = r.c0;
+    } else if constexpr (Slots) {
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) return;
     }
-    const Fill f = get_fill<Dyn>(a, c);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
     if (Dyn && split >= f.S) return;
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
     const int D = a.D;
     const int es = (int)sizeof(T);
-    const T* qp = reinterpret_cast<const T*>(a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)t * a.q.sn) * es);
+    const T* qp = reinterpret_cast<const T*>(a.q.ptr + ((int64_t)b * a.q.sb + (int64_t)head * a.q.sh + (int64_t)(Ragged ? prow + t : t) * a.q.sn) * es);
     float qf[MAXJ], acc[MAXJ];
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
@@ -591,7 +708,7 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a) {
     const int tbeg = split * f.tps;
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
-        const TileInfo ti = tile_info(a, f, i, b, c, hk, es);
+        const TileInfo ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
         if (tile_class_t<Tree>(a, ti, td, td, vis) == 0) continue;
         for (int kk = 0; kk < ti.count; ++kk) {
             if (!key_visible_t<Tree>(a, f, ti, kk, td, vis)) continue;
@@ -669,6 +786,33 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
 
+// the commit piece of a packed call: item = (hk * T + packed row) * cpr + ch.  The row is token t of its sequence i
+// (n_i tokens, slot c): stored iff t >= n_i - Wc, into ring slot (write_pos_c + t) mod Wc - what commit_piece<false, true>
+// stores for a batch row of n_i tokens.  Rows of no sequence and of inactive sequences store nothing.
+__device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es) {
+    const int cpr = a.D * es / 16;
+    if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
+    const int ch = (int)(item % cpr);
+    const int64_t rest = item / cpr;
+    const int tp = (int)(rest % rg.T);
+    const int hk = (int)(rest / rg.T);
+    const int seq = rg.rowseq[tp];
+    if (seq < 0) return;
+    const int c = cache_row<true>(a, seq);
+    if (c < 0) return;
+    const RaggedSeq s = ragged_seq(rg, seq);
+    const int t = tp - s.c0;
+    if (t < s.n - a.wc) return;
+    const int slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
+    const int64_t so = (int64_t)ch * 16;
+    const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + (int64_t)tp * a.kn.sn) * es + so;
+    const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + (int64_t)tp * a.vn.sn) * es + so;
+    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
+    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+}
+
 // blocks [0, nred): one wave per partial row folds the S partials and s_aux, writes o.  Blocks [nred, ...) with commit:
 // store chunk tokens t >= n - Wc into ring slot (write_pos + t) mod Wc, one 16-byte piece of K and of V per thread.
 // Dyn: S and write_pos come from the device state (which this launch only reads; ring_advance_kernel moves it on).
@@ -676,22 +820,36 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // per commit piece.
 // Slots: S, write_pos and the ring are those of cache row slots[b]; an inactive row gets zeros in o (no partial of it
 // was written) and stores nothing.
-template <typename T, bool Dyn, bool Slots = false>
-__global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred) {
+// Ragged: rows are the packed rows (ragged_row); a row without work gets zeros, the commit is commit_piece_ragged.
+template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, typename... RA>
+__global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred, RA... ra) {
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, nred, RaggedArgs)");
+    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
+        if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
+        else commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
         return;
     }
     const int lane = threadIdx.x & 63;
     const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (rowid >= (int64_t)a.B * a.Hkv * a.R) return;
-    const int rho = (int)(rowid % a.R);
-    const int hk = (int)((rowid / a.R) % a.Hkv);
-    const int b = (int)(rowid / ((int64_t)a.R * a.Hkv));
-    const int t = rho / a.G, head = hk * a.G + rho % a.G;
+    if (rowid >= (Ragged ? (int64_t)a.Hkv * rg.T * a.G : (int64_t)a.B * a.Hkv * a.R)) return;
+    int rho = (int)(rowid % a.R);
+    int hk = (int)((rowid / a.R) % a.Hkv);
+    const int b = Ragged ? 0 : (int)(rowid / ((int64_t)a.R * a.Hkv));
     int c = b;
-    if constexpr (Slots) {
+    [[maybe_unused]] int rn = 0, prow = 0;    // ragged: the sequence's length and first packed row
+    if constexpr (Ragged) {
+        RaggedRow r;
+        if (!ragged_row(a, rg, rowid, r)) {
+            T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)(r.hk * a.G + r.rho) * a.o.sh + (int64_t)r.tp * a.o.sn) * es);
+            for (int d = lane; d < a.D; d += 64) orow[d] = from_f32<T>(0.f);
+            return;
+        }
+        rho = r.rho, hk = r.hk, c = r.c, rn = r.n, prow = r.c0;
+    }
+    const int t = rho / a.G, head = hk * a.G + rho % a.G;
+    if constexpr (Slots && !Ragged) {
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) {
             T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)t * a.o.sn) * es);
@@ -699,7 +857,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
             return;
         }
     }
-    const Fill f = get_fill<Dyn>(a, c);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
     const int S = f.S, D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
     const float* Lr = a.Lp + rowid * a.Sw;
@@ -717,7 +875,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
     }
     const float L = wave_sum(lloc) + (sa == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sa - mstar));
     const float inv = 1.f / L;
-    T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)t * a.o.sn) * es);
+    T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)(Ragged ? prow + t : t) * a.o.sn) * es);
     for (int d = lane; d < D; d += 64) {
         float acc = 0.f;
 #pragma unroll 8
@@ -835,6 +993,24 @@ __global__ void ring_advance_slots_kernel(int* state, const int* count, int n, i
     if ((unsigned)c >= (unsigned)npool) return;
     int* st = state + (int64_t)c * 4;
     const int acc = count ? clamp_count(count + r, n) : n;
+    int wl = st[1], wp = st[2];
+    wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
+    wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
+    st[1] = wl + acc < wc ? wl + acc : wc;
+    st[2] = (int)(((int64_t)wp + acc) % wc);
+    st[3] += acc;
+}
+
+// the same for a packed call: thread r advances state row slots[r] by n_r = the length of sequence r; an inactive or
+// empty sequence moves nothing
+__global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int wc, const int* slots, int npool) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= rg.n_seq) return;
+    const int c = slots[r];
+    if ((unsigned)c >= (unsigned)npool) return;
+    const int acc = ragged_seq(rg, r).n;
+    if (acc == 0) return;
+    int* st = state + (int64_t)c * 4;
     int wl = st[1], wp = st[2];
     wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
     wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
@@ -1024,6 +1200,129 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
         if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_s%d%s", fam, dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
         else set_path("decode_%s_f32_%s_d%d_s%d%s", fam, dname, a.D, a.S, commit ? "_commit" : "");
     }
+    return SFA_OK;
+}
+
+namespace {
+
+// host-known geometry of a packed call: nothing here depends on cu_q, the slots or the state
+struct RaggedGeom {
+    int64_t G, nrb, rows, Sw, P;     // P: bound of rows * Sw that sizes the partials
+};
+
+RaggedGeom ragged_geom(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache) {
+    RaggedGeom g;
+    g.G = Hq / Hkv;
+    g.nrb = cdiv64(g.G * T, 32) + n_seq;             // sum of ceil(G n_i / 32) over n_seq sequences of T rows in all
+    g.rows = Hkv * T * g.G;
+    g.Sw = max_splits(1, Hkv, g.nrb, Nkv_cache + T);   // bound of multi_plan's S over every fill and every n_i <= T
+    // rows * Sw <= rows * (splits of the key count alone) and <= rows * ceil(2048 / (Hkv nrb)) <= rows + 2048 * 32
+    // (G T / nrb <= 32): the smaller of two bounds that grow with T and Nkv_cache, so that the workspace size does too
+    // (rows * Sw itself does not: Sw shrinks when the row blocks alone fill the device)
+    const int64_t by_keys = cdiv64(cdiv64(Nkv_cache + T, kTile) + 2, kMinTiles);
+    const int64_t p1 = g.rows * (by_keys < 1 ? 1 : by_keys), p2 = g.rows + kTargetWgs * 32;
+    g.P = p1 < p2 ? p1 : p2;
+    return g;
+}
+
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+template <typename T>
+int launch_ragged(const MultiArgs& a, const RaggedArgs& rg, bool mfma, hipStream_t stream) {
+    int st = SFA_OK;
+    const int64_t rows = (int64_t)a.Hkv * rg.T * a.G;
+    if (mfma) {
+        if constexpr (sizeof(T) == 2) {
+            const dim3 grid((unsigned)((int64_t)a.Hkv * a.Sw * a.nrb));
+            switch (a.D) {
+                case 64: multi_split_mfma_kernel<T, 64, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
+                case 80: multi_split_mfma_kernel<T, 80, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
+                case 96: multi_split_mfma_kernel<T, 96, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
+                default: multi_split_mfma_kernel<T, 128, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
+            }
+            st = launch_status("decode_multi_mfma_ragged");
+        }
+    } else {
+        const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
+        multi_split_f32_kernel<T, true, false, true, true><<<grid, 256, 0, stream>>>(a, rg);
+        st = launch_status("decode_multi_f32_ragged");
+    }
+    if (st) return st;
+    const int nred = (int)cdiv64(rows, 4);
+    const int64_t ncommit = a.commit ? cdiv64((int64_t)a.Hkv * rg.T * (a.D * (int64_t)sizeof(T) / 16), 256) : 0;
+    multi_reduce_kernel<T, true, true, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred, rg);
+    if ((st = launch_status("decode_multi_reduce_ragged"))) return st;
+    if (a.commit) {      // every reader of the state rows has finished: advance each named one by its n_i
+        ring_advance_ragged_kernel<<<dim3((unsigned)cdiv64(rg.n_seq, 256)), rg.n_seq < 256 ? rg.n_seq : 256, 0, stream>>>(
+            const_cast<int*>(a.state), rg, a.wc, a.slots, a.npool);
+        st = launch_status("ring_advance_ragged");
+    }
+    return st;
+}
+
+}  // namespace
+
+size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype) {
+    if (decode_multi_check_head_dim(D, dtype) != SFA_OK) return 0;
+    if (n_seq <= 0 || Hkv <= 0 || Hq <= 0 || Hq % Hkv != 0 || T <= 0 || Nkv_cache <= 0) return 0;
+    if (n_seq >= (1ll << 30) || Hq * T >= (1ll << 30) || Nkv_cache >= (1ll << 30)) return 0;
+    const RaggedGeom g = ragged_geom(n_seq, Hq, Hkv, T, Nkv_cache);
+    return 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)D * sizeof(float)) +
+           al256((size_t)g.nrb * sizeof(int2)) + al256((size_t)T * sizeof(int));
+}
+
+int decode_ragged_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                         const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit, int32_t* state,
+                         const int32_t* slots, const int32_t* cu_q, int n_seq, void* workspace, float scale,
+                         unsigned flags, hipStream_t stream) {
+    const int64_t T = q->shape[2], ns = sink_k->shape[2], Wc = window_k->shape[2];
+    const RaggedGeom g = ragged_geom(n_seq, q->shape[1], k_new->shape[1], T, ns + Wc);
+    MultiArgs a;
+    a.parent = nullptr, a.pstride = 0, a.path = nullptr, a.pathstride = 0;   // no tree form
+    a.slots = slots, a.npool = (int)sink_k->shape[0];
+    a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
+    a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
+    a.s_aux = s_aux;
+    a.B = 1;
+    a.Hkv = (int)k_new->shape[1];
+    a.G = (int)g.G;
+    a.D = (int)q->shape[3];
+    // n / R: the pack's bounds here; every workgroup (wave) replaces them with its sequence's n_i and G * n_i
+    a.n = (int)T, a.R = (int)(g.G * T);
+    a.nrb = (int)g.nrb;
+    a.sink_len = (int)ns, a.wl = (int)Wc, a.wp = 0, a.wc = (int)Wc;
+    a.want = (int)want_splits(1, a.Hkv, g.nrb);     // one value for the call: a sequence's plan depends on the call's
+    a.T0 = a.T1 = a.T = a.tps = a.S = 0;            // shape and on its own (state row, n_i), not on its neighbours
+    a.state = state, a.sstride = 4, a.ns = (int)ns;
+    a.Sw = (int)g.Sw;
+    a.scale_log2 = scale * kLog2e;
+    a.commit = commit ? 1 : 0;
+    char* ws = (char*)workspace;
+    a.Mp = reinterpret_cast<float*>(ws);
+    a.Lp = reinterpret_cast<float*>(ws + al256((size_t)g.P * sizeof(float)));
+    a.Op = reinterpret_cast<float*>(ws + 2 * al256((size_t)g.P * sizeof(float)));
+    char* tab = ws + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)a.D * sizeof(float));
+    int2* blk = reinterpret_cast<int2*>(tab);
+    int* rowseq = reinterpret_cast<int*>(tab + al256((size_t)g.nrb * sizeof(int2)));
+    const RaggedArgs rg{cu_q, blk, rowseq, n_seq, (int)T};
+    if ((int64_t)a.Hkv * a.Sw * g.nrb >= (1ll << 31) || cdiv64(g.rows, 4) >= (1ll << 31) - 65536 ||
+        cdiv64(g.rows, 4) + cdiv64((int64_t)a.Hkv * T * (a.D * 4 / 16), 256) >= (1ll << 31)) {
+        set_error("decode_ragged: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    ragged_prep_kernel<<<1, 1024, 0, stream>>>(rg, blk, rowseq, a.G, a.nrb);
+    int st;
+    if ((st = launch_status("ragged_prep"))) return st;
+    const int dt = q->dtype;
+    const bool mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(flags & SFA_FLAG_FORCE_GENERIC);
+    const char* dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
+    if (dt == SFA_DTYPE_F32) st = launch_ragged<float>(a, rg, false, stream);
+    else if (dt == SFA_DTYPE_F16) st = launch_ragged<f16_t>(a, rg, mfma, stream);
+    else st = launch_ragged<bf16_t>(a, rg, mfma, stream);
+    if (st) return st;
+    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s", dname, a.D, a.nrb, commit ? "_commit" : "");
+    else set_path("decode_multi_f32_%s_d%d_ragged%s", dname, a.D, commit ? "_commit" : "");
     return SFA_OK;
 }
 

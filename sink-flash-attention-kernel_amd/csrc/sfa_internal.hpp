@@ -66,6 +66,15 @@ int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa
                         int64_t parent_bstride = 0,
                         const int32_t* slots = nullptr);   // slot call (rows): the buffers are a pool, B = q's rows
 
+// sfa_decode_ring_ragged_slots: a packed [1, H, T, D] step over a pool (sequence i = rows [cu_q[i], cu_q[i + 1]) on slot
+// slots[i]); arguments already checked.  Workspace: partials for T packed rows plus the tables of the preparation launch
+size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
+int decode_ragged_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                         const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit, int32_t* state,
+                         const int32_t* slots, const int32_t* cu_q, int n_seq, void* workspace, float scale,
+                         unsigned flags, hipStream_t stream);
+
 // sfa_ring_commit_dyn / _rows: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
 int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                            const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream,

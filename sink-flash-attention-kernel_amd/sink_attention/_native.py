@@ -147,6 +147,11 @@ def _bind(lib):
     lib.sfa_ring_commit_path_slots.argtypes = [P, P, P, P, vp, vp, i64, vp, vp, vp]
     lib.sfa_ring_fill_varlen_slots.restype = i32
     lib.sfa_ring_fill_varlen_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp]
+    # packed ragged step over a pool: the slots call plus `cu_q`, `n_seq` after `slots`
+    lib.sfa_decode_ragged_workspace_bytes.restype = sz
+    lib.sfa_decode_ragged_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i32]
+    lib.sfa_decode_ring_ragged_slots.restype = i32
+    lib.sfa_decode_ring_ragged_slots.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp, sz, f32, u32, vp]
 
 
 def lib():

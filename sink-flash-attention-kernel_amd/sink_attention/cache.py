@@ -808,6 +808,92 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.check(rc, name)
         return out
 
+    # ------------------------------------------------ packed ragged step (chunked prefill + decode in one call)
+    def _require_pool(self, what):
+        if not (self._pool and self.is_initialized):
+            raise RuntimeError(f"{what} needs a pool: call init_pool first")
+        return self._dev_state
+
+    def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
+                        s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        commit: bool = True) -> torch.Tensor:
+        """One step over the pool in which every sequence brings its own number of new tokens
+        (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
+        the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
+        ``cu_q[i] : cu_q[i + 1]`` and works on slot ``slots[i]``.  Decode rows (1 token), draft rows (k tokens) and the
+        next chunk of a long prompt (hundreds) run in one call whose cost follows T.  Each sequence is attended as
+        ``extend_attention_dyn`` of its own chunk at its slot's state; with ``commit`` its tokens are stored and its
+        state row advances by its length (``extend_step_dyn``).  Rows of an inactive sequence (slot -1), and rows behind
+        ``cu_q[-1]`` (padding of a step captured at a fixed T) come back as zeros and change nothing.  ``cu_q`` and
+        ``slots``: device int32 tensors (never read on the host: the call is graph-capturable and a captured step replays
+        at any mix of lengths by rewriting them in place) or host lists, which are checked.  The first chunk of a prompt
+        is still a ``prefill_slots`` (it writes the sinks); this call continues an admitted sequence."""
+        import math
+        from . import _native as N
+        dev_state = self._require_pool("ragged_step_dyn")
+        N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
+        if q.dim() != 4 or q.shape[0] != 1:
+            raise ValueError(f"q must be a packed [1, H_q, T, D] tensor, got {tuple(q.shape)}")
+        _one, H_q, T, D = q.shape
+        H_kv = self.sink_k.shape[1]
+        if k_new.shape != (1, H_kv, T, D) or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be [1, H_kv, T, D] = {(1, H_kv, T, D)}, got {tuple(k_new.shape)}")
+        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
+            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+        if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
+            raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
+        cu = self._cu_arg(cu_q, T, q.device)
+        n_seq = cu.numel() - 1
+        slots = self._slots_arg(slots, n_seq, writes=bool(commit))
+        N.require_gpu(slots)
+        st = getattr(self, "_ragged_state", None)
+        key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype)
+        if st is None or st["key"] != key:
+            lib = N.lib()
+            ws_bytes = lib.sfa_decode_ragged_workspace_bytes(n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D,
+                                                             N.SFA_DTYPE[q.dtype])
+            if ws_bytes == 0:
+                raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB (H_q = {H_q} a multiple "
+                                 f"of H_kv = {H_kv}, T >= 1)")
+            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
+                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
+                      ws=torch.empty((int(ws_bytes),), device=q.device, dtype=torch.uint8))
+            self._ragged_state = st
+        q, k_new, v_new = self._rows16(q), self._rows16(k_new), self._rows16(v_new)
+        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        if out is None:
+            out = torch.empty((1, H_q, T, D), device=q.device, dtype=q.dtype)
+        sk, sv, wk, wv = st["descs"]
+        with torch.cuda.device(q.device):
+            rc = st["lib"].sfa_decode_ring_ragged_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
+                                                        N.desc(out),
+                                                        s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                        1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
+                                                        cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
+                                                        st["scale"], 0, N.stream_ptr(q.device))
+        N.check(rc, "sfa_decode_ring_ragged_slots")
+        return out
+
+    def packed_positions(self, cu_q, slots, T: int) -> torch.Tensor:
+        """RoPE positions of a packed step: for packed row ``cu_q[i] + t`` of sequence i, ``seen[slots[i]] + t``; -1 for
+        rows behind ``cu_q[-1]`` (padding) and for rows of inactive sequences.  ``[T]`` int64, built from torch ops on
+        the tensors' device (``bucketize`` over ``arange(T)``: no sync, capturable); call it before the committing
+        ``ragged_step_dyn`` of the step, which moves ``seen``."""
+        dev_state = self._require_pool("packed_positions")
+        cu = cu_q if isinstance(cu_q, torch.Tensor) else torch.tensor([int(x) for x in cu_q], device=dev_state.device)
+        sl = slots if isinstance(slots, torch.Tensor) else torch.tensor([int(x) for x in slots], device=dev_state.device)
+        if cu.dim() != 1 or cu.numel() < 2 or sl.dim() != 1 or sl.numel() != cu.numel() - 1:
+            raise ValueError("cu_q must hold n_seq + 1 >= 2 offsets and slots n_seq entries")
+        cu, sl = cu.to(dev_state.device).long(), sl.to(dev_state.device).long()
+        n_seq, S = sl.numel(), dev_state.shape[0]
+        rows = torch.arange(int(T), device=cu.device)
+        # the last sequence that starts at or before the row (empty sequences share a start with their successor)
+        seq = (torch.bucketize(rows, cu[:n_seq], right=True) - 1).clamp(0, n_seq - 1)
+        slot = sl[seq]
+        ok = (rows >= cu[seq]) & (rows < cu[seq + 1]) & (slot >= 0) & (slot < S)
+        pos = dev_state[slot.clamp(0, S - 1), 3].long() + rows - cu[seq]
+        return torch.where(ok, pos, torch.full_like(pos, -1))
+
     # ------------------------------------------------------- HF layer surface
     def get_seq_length(self, *_, **__) -> int:
         self._refuse_per_seq("get_seq_length")
@@ -938,6 +1024,16 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     def prefill_slots(self, key_states, value_states, cu_seqlens, slots, layer_idx: int) -> torch.Tensor:
         """``SinkCacheLayer.prefill_slots`` of one layer: packed sequences into the named slots of its pool."""
         return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
+
+    def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
+                        commit=True):
+        """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count."""
+        return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
+                                                      commit=commit)
+
+    def packed_positions(self, cu_q, slots, T: int, layer_idx: int = 0) -> torch.Tensor:
+        """``SinkCacheLayer.packed_positions`` of one layer: the RoPE position of every packed row (-1: no row)."""
+        return self._layer(layer_idx).packed_positions(cu_q, slots, T)
 
     def release_slots(self, slots) -> None:
         """``SinkCacheLayer.release_slots`` of every layer that holds a pool (layers without one are skipped)."""

@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""Micro-bench of the packed ragged step (exploration tool, not the contract bench), gpt-oss attention geometry
+(H_q=64, H_kv=8, D=64, num_sink=4, s_aux, bf16), a pool of 8 slots, every ring full and wrapped.  All variants commit
+(attend + store + advance), so the rings stay full and every call does the same work.
+
+Steps:
+    dec7_pre256 / dec7_pre512   7 decode rows (1 token) + 1 prefill chunk of 256 / 512 tokens
+    dec4_draft4                 4 decode rows + 4 draft rows of 8 tokens
+Variants per (W, step), alternating in one process:
+    ragged     one ragged_step_dyn over the pack (skipped where the library lacks it: a parent build)
+    per_len    what was possible before (a): one extend_step_dyn(slots=) per distinct length
+    padded     what was possible before (b): one extend_step_dyn(slots=) with every row padded to the longest chunk.
+               Timing only: a padded row commits its padding too, which a real caller would have to undo.
+--mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
+--mode kernels: --calls calls of each variant after 5 warm-up calls, in the order above, for a kernel trace of its own:
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o rstep -- python tools/kbench_ragged_step.py --mode kernels
+--summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
+  reduce / advance kernel times (the trace is cut into blocks in issue order).
+usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]"""
+import argparse
+import csv
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT]
+
+S, HQ, HKV, D, NS = 8, 64, 8, 64, 4
+WARM = 5
+STEPS = {"dec7_pre256": [1] * 7 + [256], "dec7_pre512": [1] * 7 + [512], "dec4_draft4": [1] * 4 + [8] * 4}
+VARIANTS = ("ragged", "per_len", "padded")
+KINDS = ("prep", "split", "reduce", "advance")
+
+
+def _pool(torch, W, dev, dt):
+    from sink_attention import SinkCacheLayer
+    layer = SinkCacheLayer(NS, W)
+    layer.init_pool(S, HKV, D, dt, dev)
+    pre = NS + W + 37                          # full ring, wrapped
+    k = torch.randn(1, HKV, S * pre, D, device=dev, dtype=dt)
+    layer.prefill_slots(k, torch.randn_like(k), [pre * i for i in range(S + 1)], list(range(S)))
+    return layer
+
+
+def _variants(torch, W, lengths, dev, dt, have_ragged):
+    sa = torch.randn(HQ, device=dev) * 0.5
+    mk = lambda rows, h, n: torch.randn(rows, h, n, D, device=dev, dtype=dt)
+    out = {}
+    if have_ragged:
+        T = sum(lengths)
+        q, k, v = mk(1, HQ, T), mk(1, HKV, T), mk(1, HKV, T)
+        cu = torch.tensor([sum(lengths[:i]) for i in range(S + 1)], dtype=torch.int32, device=dev)
+        slots = torch.arange(S, dtype=torch.int32, device=dev)
+        pool, o = _pool(torch, W, dev, dt), torch.empty_like(q)
+        out["ragged"] = lambda: pool.ragged_step_dyn(q, k, v, cu, slots, s_aux=sa, out=o, commit=True)
+    groups = []
+    for n in sorted(set(lengths)):
+        idx = [i for i, x in enumerate(lengths) if x == n]
+        q = mk(len(idx), HQ, n)
+        groups.append((q, mk(len(idx), HKV, n), mk(len(idx), HKV, n), torch.empty_like(q),
+                       torch.tensor(idx, dtype=torch.int32, device=dev)))
+    pool2 = _pool(torch, W, dev, dt)
+
+    def per_len():
+        for q, k, v, o, sl in groups:
+            pool2.extend_step_dyn(q, k, v, s_aux=sa, out=o, slots=sl)
+
+    out["per_len"] = per_len
+    n = max(lengths)
+    qp, kp, vp = mk(S, HQ, n), mk(S, HKV, n), mk(S, HKV, n)
+    pool3, op, sl_all = _pool(torch, W, dev, dt), torch.empty_like(qp), torch.arange(S, dtype=torch.int32, device=dev)
+    out["padded"] = lambda: pool3.extend_step_dyn(qp, kp, vp, s_aux=sa, out=op, slots=sl_all)
+    return out
+
+
+def _setup(args):
+    import torch
+    import sink_attention
+    from sink_attention import SinkCacheLayer
+    have = hasattr(SinkCacheLayer, "ragged_step_dyn") and hasattr(sink_attention._native.lib(), "sfa_decode_ring_ragged_slots")
+    names = [v for v in args.variants.split(",") if have or v != "ragged"]
+    return torch, names, have
+
+
+def wall(args):
+    torch, names, have = _setup(args)
+    dev, dt = "cuda", torch.bfloat16
+    print(f"gpt-oss geometry H_q={HQ} H_kv={HKV} D={D} num_sink={NS} s_aux bf16, pool of {S}, rings full; device us per "
+          f"step, median of {args.rounds} rounds of {args.calls} calls (events), variants alternating", flush=True)
+    for W in [int(x) for x in args.W.split(",")]:
+        for step in args.steps.split(","):
+            torch.manual_seed(0)
+            fns = _variants(torch, W, STEPS[step], dev, dt, have)
+            res = {v: [] for v in names}
+            for v in names:
+                for _ in range(WARM):
+                    fns[v]()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for v in names:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _c in range(args.calls):
+                        fns[v]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    res[v].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+            med = {v: sorted(x)[len(x) // 2] for v, x in res.items()}
+            spread = {v: max(x) - min(x) for v, x in res.items()}
+            print(f"  W={W:5d} {step:12s} T={sum(STEPS[step]):4d}  " +
+                  "  ".join(f"{v} {med[v]:8.2f} (+-{spread[v] / 2:5.2f})" for v in names), flush=True)
+            del fns
+
+
+def kernels(args):
+    torch, names, have = _setup(args)
+    dev, dt = "cuda", torch.bfloat16
+    for W in [int(x) for x in args.W.split(",")]:
+        for step in args.steps.split(","):
+            torch.manual_seed(0)
+            fns = _variants(torch, W, STEPS[step], dev, dt, have)
+            torch.cuda.synchronize()
+            for v in names:
+                for _ in range(WARM + args.calls):
+                    fns[v]()
+                torch.cuda.synchronize()
+            print(f"W={W} {step}: {WARM} + {args.calls} calls of each of {', '.join(names)}", flush=True)
+            del fns
+
+
+def summarize(args):
+    rows = list(csv.DictReader(open(args.summarize)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    names = args.variants.split(",")
+    per = WARM + args.calls
+    ev = []
+    for r in rows:
+        name = r["Kernel_Name"]
+        kind = "prep" if "ragged_prep_kernel" in name else "split" if "multi_split_" in name else \
+            "reduce" if "multi_reduce_kernel" in name else "advance" if "ring_advance_" in name else None
+        if kind:
+            ev.append((kind, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    print(f"# gpt-oss geometry; summed kernel us per step (prep + split + reduce + advance), median of {args.calls} steps "
+          f"after {WARM} warm-up")
+    pos = 0
+    for W in [int(x) for x in args.W.split(",")]:
+        for step in args.steps.split(","):
+            cells = []
+            for v in names:
+                launches = 1 if v != "per_len" else len(set(STEPS[step]))      # split launches per step
+                steps = []
+                for _ in range(per):
+                    tot = dict.fromkeys(KINDS, 0.0)
+                    seen = 0
+                    while pos < len(ev):
+                        kind, us = ev[pos]
+                        if kind == "split":
+                            if seen == launches:
+                                break
+                            seen += 1
+                        elif kind == "prep" and seen:
+                            break
+                        tot[kind] += us
+                        pos += 1
+                    steps.append(tot)
+                body = steps[WARM:]
+                cells.append(f"{v} " + " + ".join(f"{med([s[k] for s in body]):.2f}" for k in KINDS) +
+                             f" = {med([sum(s.values()) for s in body]):.2f}")
+            print(f"  W={W:5d} {step:12s}  " + "   ".join(cells))
+    assert pos == len(ev), (pos, len(ev))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="wall", choices=["wall", "kernels"])
+    ap.add_argument("--W", default="128,4096")
+    ap.add_argument("--steps", default=",".join(STEPS))
+    ap.add_argument("--variants", default=",".join(VARIANTS))
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
+    args = ap.parse_args()
+    if args.summarize:
+        summarize(args)
+    elif args.mode == "kernels":
+        kernels(args)
+    else:
+        wall(args)
+
+
+if __name__ == "__main__":
+    main()
