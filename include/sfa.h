@@ -84,6 +84,19 @@ extern "C" {
 #define SFA_FLAG_BWD_DKDV_ASM 0x10u
 #define SFA_FLAG_BWD_DKDV_WS 0x20u
 
+/* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
+ * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.
+ *   stride[0] (batch, or slot of a pool): any int64 value.  Every kernel family forms `index * stride[0]` in 64 bits, so
+ *     a batch or slot may start past 2^31 elements / 4 GiB (a slot pool at Hkv 8, W 4096, D 128 does from slot 512 on).
+ *   stride[1] (head): generic (fp32-math), decode and cache kernels: any int64 value.  The MFMA prefill paths
+ *     (sfa_fwd / sfa_bwd and the packed forms, 16-bit dtypes) need stride[1] * 2 < 2^32 bytes on every operand: their
+ *     hand-placed kernels carry the head stride as a 32-bit byte count.
+ *   stride[2] (row): the MFMA prefill paths address rows through 32-bit buffer offsets and need
+ *     (N + 320) * stride[2] * 2 + 512 < 2^32 - 65536 in the forward, (N + 1280) * ... in the backward (N = shape[2]).
+ * An operand outside the MFMA limits (or with rows not 16-byte aligned) is not an error for sfa_fwd / sfa_bwd with
+ * N_q == N_kv: the call runs the generic kernels (sfa_last_path() says "fwd_generic_f32math" / "bwd_generic_f32math").
+ * The packed calls and N_q != N_kv have no generic form: they return SFA_ERR_UNSUPPORTED before anything is launched
+ * (no output, lse, ds_aux or workspace byte is written). */
 typedef struct sfa_tensor {
     void* ptr;         /* device pointer to element [0,0,0,0]                    */
     int64_t shape[4];  /* B, H, N, D                                             */

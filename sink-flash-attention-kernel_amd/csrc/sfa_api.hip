@@ -180,6 +180,7 @@ int sfa_bwd(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const
     SFA_CHECK_ARG(lse != nullptr, "lse: null pointer");
     SFA_CHECK_ARG((s_aux == nullptr) == (ds_aux == nullptr), "ds_aux must be given iff s_aux is");
     const bool use_mfma = !(flags & SFA_FLAG_FORCE_GENERIC) && bwd_mfma_supported(q->dtype, p.D);
+    if (use_mfma && (st = bwd_mfma_refused(q, k, v, d_o, dq, dk, dv, p))) return st;     // before the preprocess: nothing written
     const BwdWorkspace w = bwd_layout(p, q->dtype, use_mfma, flags);
     if (workspace == nullptr || workspace_bytes < w.total || ((uintptr_t)workspace & 255) != 0) {
         set_error("bwd workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", w.total, workspace_bytes,
@@ -266,6 +267,7 @@ int sfa_bwd_varlen(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v
     if (p.Hq == 0 || p.N == 0) return SFA_OK;
     SFA_CHECK_ARG(lse != nullptr, "lse: null pointer");
     SFA_CHECK_ARG((s_aux == nullptr) == (ds_aux == nullptr), "ds_aux must be given iff s_aux is");
+    if ((st = bwd_mfma_refused(q, k, v, d_o, dq, dk, dv, run))) return st;                // before the preprocess: nothing written
     const BwdWorkspace w = bwd_layout(p, q->dtype, true, 0);      // same carving as sfa_bwd with B = 1, N = total rows
     if (workspace == nullptr || workspace_bytes < w.total || ((uintptr_t)workspace & 255) != 0) {
         set_error("bwd workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", w.total, workspace_bytes,

@@ -31,6 +31,9 @@ int bwd_mfma(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, cons
              const float* lse, const float* delta, const sfa_tensor* dq, const sfa_tensor* dk,
              const sfa_tensor* dv, void* workspace, const Problem& p, unsigned flags, hipStream_t stream,
              bool consts_ready = false);
+// SFA_ERR_UNSUPPORTED (message set) for a call bwd_mfma would refuse, SFA_OK otherwise: asked before anything is launched
+int bwd_mfma_refused(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* d_o,
+                     const sfa_tensor* dq, const sfa_tensor* dk, const sfa_tensor* dv, const Problem& p);
 bool bwd_mfma_wants_consts();   // the default dK/dV kernels read the row constants from the head of the workspace
 float bwd_mfma_lse_factor(const Problem& p, unsigned flags);   // ... whose first row is -LSE * this factor (follows the dK/dV kernel choice)
 

@@ -9,11 +9,12 @@ import torch
 
 from oracle import sink_oracle as O
 from test_decode_multi_host import history_keys
-from util import maxdiff, rand
+from util import DECODE_TOL, maxdiff, rand
+from util import chunk_oracle_rows as _oracle_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-TOL = {torch.float32: 2e-5, torch.float16: 2e-3, torch.bfloat16: 1.6e-2}
+TOL = DECODE_TOL
 
 
 def _path():
@@ -44,16 +45,6 @@ def _assert_same_state(a, b, what):
     assert a[:4] == b[:4], (what, a[:4], b[:4])
     for x, y in zip(a[4], b[4]):
         assert torch.equal(x, y), what
-
-
-def _oracle_rows(q, k, v, sa, prefill, ns, W, n, batches):
-    """fp64 decode_dense per chunk row over the keys of the chronological history it may see."""
-    rows = []
-    for t in range(n):
-        keep = torch.tensor(history_keys(prefill, ns, W, t))
-        pos = prefill + t
-        rows.append(O.decode_dense(q[batches, :, pos:pos + 1], k[batches][:, :, keep], v[batches][:, :, keep], sa))
-    return torch.cat(rows, dim=2)
 
 
 def _check_case(dtype, B, Hq, Hkv, D, ns, W, prefill, n, aux, seed=7):

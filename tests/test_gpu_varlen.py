@@ -4,24 +4,10 @@ import torch
 
 from oracle import sink_oracle as O
 from util import dkdv_kernel_name, maxdiff, rand
+from util import per_seq_oracle as _per_seq_oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _per_seq_oracle(q, k, v, do, cu, ns, W, sa):
-    o = torch.zeros(q.shape, dtype=torch.float64)
-    dq, dk, dv = torch.zeros(q.shape, dtype=torch.float64), torch.zeros(k.shape, dtype=torch.float64), torch.zeros(
-        v.shape, dtype=torch.float64)
-    dsa = torch.zeros(q.shape[1], dtype=torch.float64)
-    for a, b in zip(cu[:-1], cu[1:]):
-        sl = (slice(None), slice(None), slice(a, b))
-        o[sl], _ = O.sink_attention_dense(q[sl], k[sl], v[sl], ns, W, sa)
-        g = O.sink_attention_bwd_dense(q[sl], k[sl], v[sl], do[sl], ns, W, sa)
-        dq[sl], dk[sl], dv[sl] = g[0], g[1], g[2]
-        if sa is not None:
-            dsa += g[3]
-    return o, dq, dk, dv, dsa
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])

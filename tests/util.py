@@ -74,3 +74,34 @@ def dkdv_kernel_name(mode, B, Hkv, Nq, Nk, D, window, packed=False, dtype=torch.
     dense = (not packed) and Nq == Nk      # row split available: the hand-placed kernel fills the chip whatever the grid
     fills = -(-Nk // 256) * Hkv * B >= n_cu
     return "dkdvasm4x64" if (dense or fills) else "dkdvws8"
+
+
+# max |error| of the decode kernels against the fp64 oracle, per dtype (shared by the decode test modules)
+DECODE_TOL = {torch.float32: 2e-5, torch.float16: 2e-3, torch.bfloat16: 1.6e-2}
+
+
+def per_seq_oracle(q, k, v, do, cu, ns, W, sa):
+    """fp64 oracle of a packed batch [1, H, T, D]: the dense oracle applied to every sequence cu[i] : cu[i + 1]."""
+    o = torch.zeros(q.shape, dtype=torch.float64)
+    dq, dk, dv = torch.zeros(q.shape, dtype=torch.float64), torch.zeros(k.shape, dtype=torch.float64), torch.zeros(
+        v.shape, dtype=torch.float64)
+    dsa = torch.zeros(q.shape[1], dtype=torch.float64)
+    for a, b in zip(cu[:-1], cu[1:]):
+        sl = (slice(None), slice(None), slice(a, b))
+        o[sl], _ = O.sink_attention_dense(q[sl], k[sl], v[sl], ns, W, sa)
+        g = O.sink_attention_bwd_dense(q[sl], k[sl], v[sl], do[sl], ns, W, sa)
+        dq[sl], dk[sl], dv[sl] = g[0], g[1], g[2]
+        if sa is not None:
+            dsa += g[3]
+    return o, dq, dk, dv, dsa
+
+
+def chunk_oracle_rows(q, k, v, sa, prefill, ns, W, n, batches):
+    """fp64 decode_dense per chunk row over the keys of the chronological history it may see."""
+    from test_decode_multi_host import history_keys
+    rows = []
+    for t in range(n):
+        keep = torch.tensor(history_keys(prefill, ns, W, t))
+        pos = prefill + t
+        rows.append(O.decode_dense(q[batches, :, pos:pos + 1], k[batches][:, :, keep], v[batches][:, :, keep], sa))
+    return torch.cat(rows, dim=2)
