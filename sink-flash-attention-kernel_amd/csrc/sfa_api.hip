@@ -2,6 +2,7 @@
 // validation, kernel-family choice, workspace carving.  No allocation, no sync.
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 
 #include "sfa_common.hpp"
 #include "sfa_internal.hpp"
@@ -300,16 +301,79 @@ size_t sfa_decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nk
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ sink + ring cache
+// Every entry point below fills a RingCall (sfa_internal.hpp) with what its signature provides and hands it to its
+// family: ring_step, ring_multi / ring_tree, ring_ragged, ring_commit / ring_commit_path, fill_varlen.  The family
+// runs the checks, the empty-shape returns, the workspace test and the launch.
 namespace {
 
-// shared by sfa_decode (one contiguous key segment) and sfa_decode_ring (sink buffer + window ring)
-int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, int64_t n1, const sfa_tensor* k2,
-                  const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
-                  size_t workspace_bytes, float scale, void* stream, const sfa_tensor* k_new = nullptr,
-                  const sfa_tensor* v_new = nullptr, int64_t new_slot = -1, int* dyn_state = nullptr,
-                  unsigned flags = 0, bool state_rows = false, const int32_t* slots = nullptr, bool pool = false) {
+#define SFA_NEED(p, what) SFA_CHECK_ARG((p) != nullptr, what ": null device pointer")
+
+// rows of every tensor 16-byte aligned (base and batch / head / row strides).  skip: bit i = a tensor with
+// shape[i] == 0 is empty and not looked at (the rule differs between the families); a null tensor never is
+int check_rows16(std::initializer_list<const sfa_tensor*> ts, int es, unsigned skip, const char* msg) {
+    for (const sfa_tensor* t : ts) {
+        if (!t || ((skip & 1) && t->shape[0] == 0) || ((skip & 2) && t->shape[1] == 0) || ((skip & 4) && t->shape[2] == 0))
+            continue;
+        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
+                          (t->stride[2] * es) % 16 == 0,
+                      "%s", msg);
+    }
+    return SFA_OK;
+}
+
+// sized: `need` is a size (a workspace query that refuses the shape gives 0)
+int check_workspace(const char* name, size_t need, bool sized, void* workspace, size_t workspace_bytes) {
+    if (!sized || workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
+        set_error("%s workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", name, need, workspace_bytes, workspace);
+        return SFA_ERR_WORKSPACE;
+    }
+    return SFA_OK;
+}
+
+// the fields every attention entry point provides, in the order of its signature
+RingCall attend_call(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                     const sfa_tensor* window_v, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                     const float* s_aux, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                     void* stream) {
+    RingCall c{};
+    c.q = q, c.sink_k = sink_k, c.sink_v = sink_v, c.window_k = window_k, c.window_v = window_v;
+    c.k_new = k_new, c.v_new = v_new, c.o = o, c.s_aux = s_aux;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes;
+    c.scale = scale, c.flags = flags, c.stream = (hipStream_t)stream;
+    return c;
+}
+
+RingCall& host_state(RingCall& c, int64_t sink_len, int64_t window_len, int64_t write_pos) {
+    c.mode = RingState::Host, c.sink_len = sink_len, c.window_len = window_len, c.write_pos = write_pos;
+    return c;
+}
+
+// launch geometry and workspace are those of the FULL cache (every sink row, every ring slot)
+RingCall& device_state(RingCall& c, RingState mode, int32_t* state, const int32_t* slots) {
+    c.mode = mode, c.state = state, c.slots = slots;
+    c.sink_len = c.sink_k ? c.sink_k->shape[2] : 0, c.window_len = c.window_k ? c.window_k->shape[2] : 0;
+    return c;
+}
+
+// the null checks every device-state call shares (a *_slots entry point has checked `slots` in between)
+int check_device_state(const RingCall& c) {
+    if (c.mode == RingState::Host) return SFA_OK;
+    SFA_NEED(c.state, "state");
+    SFA_CHECK_ARG(c.sink_k != nullptr && c.window_k != nullptr, "cache buffers: null tensor descriptor");
+    return SFA_OK;
+}
+
+// sfa_decode (one contiguous key segment: the "sink" buffers, no ring) and sfa_decode_ring*: one query per row.  With
+// slots the cache buffers hold S >= 1 slots, q / k_new / v_new / o the B batch rows
+int ring_step(const RingCall& c) {
     g_err[0] = 0;
     int st;
+    if ((st = check_device_state(c))) return st;
+    const sfa_tensor *q = c.q, *k = c.sink_k, *v = c.sink_v, *k2 = c.window_k, *v2 = c.window_v, *o = c.o;
+    const sfa_tensor *k_new = c.k_new, *v_new = c.v_new;
+    const int64_t n1 = c.sink_len, n2 = c.window_len;
+    const bool pool = c.slots != nullptr;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")) ||
         (st = check_tensor(o, "o")))
         return st;
@@ -317,14 +381,13 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
     SFA_CHECK_ARG(q->dtype == k->dtype, "q and k differ in dtype");
     // decode_kernel.py:146-147
     SFA_CHECK_ARG(q->shape[2] == 1, "sink_decode_attention requires N_q=1, got %lld", (long long)q->shape[2]);
-    // pool (sfa_decode_ring_step_slots): the cache buffers hold S >= 1 slots, q / k_new / v_new / o the B batch rows
     if (pool)
         SFA_CHECK_ARG(k->shape[0] >= 1 && k->shape[0] < (1ll << 30),
                       "pool: the cache buffers need shape[0] = S slots, 1 <= S < 2^30 (got %lld)", (long long)k->shape[0]);
     SFA_CHECK_ARG((pool || q->shape[0] == k->shape[0]) && q->shape[3] == k->shape[3], "q/k batch or head-dim mismatch");
     SFA_CHECK_ARG(k->shape[1] > 0 && q->shape[1] % k->shape[1] == 0, "H_q (%lld) must be divisible by H_kv (%lld)",
                   (long long)q->shape[1], (long long)k->shape[1]);
-    SFA_CHECK_ARG(std::isfinite(scale), "scale must be finite");
+    SFA_CHECK_ARG(std::isfinite(c.scale), "scale must be finite");
     SFA_CHECK_ARG(n1 >= 0 && n1 <= k->shape[2], "first key segment: %lld valid rows of %lld", (long long)n1,
                   (long long)k->shape[2]);
     if (k2 || v2 || n2) {
@@ -341,7 +404,7 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
                       (long long)k2->shape[2]);
     }
     SFA_CHECK_ARG(n1 + n2 < (1ll << 31) - 4096, "N_kv too large");
-    if (k_new || v_new) {       // fused cache step: the new token's K/V, stored into ring slot new_slot by the kernel
+    if (k_new || v_new) {       // fused cache step: the new token's K/V, stored into ring slot write_pos by the kernel
         SFA_CHECK_ARG(k_new && v_new && k2 && v2, "fused step needs k_new, v_new and the window ring");
         if ((st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")) ||
             (st = same_shape(k_new, v_new, "k_new", "v_new")))
@@ -352,112 +415,28 @@ int decode_common(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v,
         SFA_CHECK_ARG(k_new->dtype == k2->dtype && (pool || k_new->shape[0] == k2->shape[0]) && k_new->shape[1] == k2->shape[1] &&
                           k_new->shape[2] == 1 && k_new->shape[3] == k2->shape[3],
                       "k_new / v_new must be [B, H_kv, 1, D] in the ring's dtype");
-        SFA_CHECK_ARG(dyn_state || (new_slot >= 0 && new_slot < n2), "write slot %lld outside the %lld valid ring slots",
-                      (long long)new_slot, (long long)n2);
+        SFA_CHECK_ARG(c.mode != RingState::Host || (c.write_pos >= 0 && c.write_pos < n2),
+                      "write slot %lld outside the %lld valid ring slots", (long long)c.write_pos, (long long)n2);
     }
     if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;
     DecodePlan pl;
     st = decode_plan(q->shape[0], q->shape[1], k->shape[1], n1 + n2, q->shape[3], q->dtype, &pl);
     if (st) return st;
-    const int es = dtype_size(q->dtype);
-    const sfa_tensor* ts[7] = {q, k, v, k2, v2, k_new, v_new};
-    for (const sfa_tensor* t : ts) {
-        if (!t || t->shape[2] == 0) continue;
-        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
-                          (t->stride[2] * es) % 16 == 0,
-                      "decode: q/k/v rows must be 16-byte aligned");
-    }
+    if ((st = check_rows16({q, k, v, k2, v2, k_new, v_new}, dtype_size(q->dtype), 4, "decode: q/k/v rows must be 16-byte aligned")))
+        return st;
     const size_t need = sfa_decode_workspace_bytes(q->shape[0], q->shape[1], k->shape[1], n1 + n2, q->shape[3], q->dtype);
-    if (workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
-        set_error("decode workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
-                  workspace);
-        return SFA_ERR_WORKSPACE;
-    }
-    return decode_launch(q, k, v, n1, n2 ? k2 : nullptr, n2 ? v2 : nullptr, n2, o, s_aux, workspace, scale, pl,
-                         (hipStream_t)stream, k_new, v_new, (int)new_slot, dyn_state,
-                         (flags & SFA_FLAG_DECODE_ONE_PASS) != 0, state_rows, slots);
+    if ((st = check_workspace("decode", need, true, c.workspace, c.workspace_bytes))) return st;
+    return decode_launch(c, pl);
 }
 
-}  // namespace
-
-extern "C" {
-
-int sfa_decode(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* o,
-               const float* s_aux, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
-               void* stream) {
-    return decode_common(q, k, v, k ? k->shape[2] : 0, nullptr, nullptr, 0, o, s_aux, workspace, workspace_bytes, scale,
-                         stream, nullptr, nullptr, -1, nullptr, flags);
-}
-
-int sfa_decode_ring(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                    const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, const sfa_tensor* o,
-                    const float* s_aux, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
-                    void* stream) {
-    return decode_common(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, o, s_aux, workspace,
-                         workspace_bytes, scale, stream, nullptr, nullptr, -1, nullptr, flags);
-}
-
-int sfa_decode_ring_step(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
-                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
-                         const float* s_aux, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
-                         void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
-    return decode_common(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, o, s_aux, workspace,
-                         workspace_bytes, scale, stream, k_new, v_new, write_pos, nullptr, flags);
-}
-
-int sfa_decode_ring_step_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                             const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                             const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
-                             void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    // launch geometry and workspace are sized for the FULL cache (every sink row, every ring slot)
-    return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
-                         workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags);
-}
-
-int sfa_decode_ring_step_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
-                              void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    // the state rows [B][4] are per batch row of the cache buffers (decode_common checks q / k_new against them)
-    return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
-                         workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags, true);
-}
-
-int sfa_decode_ring_step_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int32_t* state,
-                               const int32_t* slots, void* workspace, size_t workspace_bytes, float scale,
-                               unsigned flags, void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    // plan, grid and workspace are those of the rows call for q's B rows at the full cache; the buffers are the pool
-    return decode_common(q, sink_k, sink_v, sink_k->shape[2], window_k, window_v, window_k->shape[2], o, s_aux,
-                         workspace, workspace_bytes, scale, stream, k_new, v_new, 0, state, flags, true, slots, true);
-}
-
-}  // extern "C"
-
-namespace {
-
-// every host-checkable argument of sfa_decode_ring_multi(_dyn); nothing launches
-int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
-                const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, float scale, bool pool = false) {
+// every host-checkable argument of an attention call over a chunk (sfa_decode_ring_multi*, _tree*, _ragged_slots), at
+// the state of the descriptor (a device-state call: the full cache); nothing launches
+int check_multi(const RingCall& c) {
+    const sfa_tensor *q = c.q, *sink_k = c.sink_k, *sink_v = c.sink_v, *window_k = c.window_k, *window_v = c.window_v;
+    const sfa_tensor *k_new = c.k_new, *v_new = c.v_new, *o = c.o;
+    const int64_t sink_len = c.sink_len, window_len = c.window_len, write_pos = c.write_pos;
     int st;
+    if ((st = check_device_state(c))) return st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k")) ||
         (st = check_tensor(sink_v, "sink_v")) || (st = check_tensor(window_k, "window_k")) ||
         (st = check_tensor(window_v, "window_v")) || (st = check_tensor(k_new, "k_new")) ||
@@ -468,6 +447,7 @@ int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor*
         return st;
     const int64_t B = q->shape[0], Hq = q->shape[1], n = q->shape[2], D = q->shape[3], Hkv = k_new->shape[1];
     const int64_t Wc = window_k->shape[2];
+    const bool pool = c.slots != nullptr;
     SFA_CHECK_ARG(q->dtype == sink_k->dtype && q->dtype == window_k->dtype && q->dtype == k_new->dtype,
                   "q, the cache buffers and k_new / v_new must share one dtype");
     SFA_CHECK_ARG(n >= 1, "decode_multi: the chunk needs at least one token");
@@ -492,255 +472,78 @@ int check_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor*
     SFA_CHECK_ARG(window_len == Wc || write_pos == window_len,
                   "write_pos (%lld) must equal window_len (%lld) until the ring is full", (long long)write_pos,
                   (long long)window_len);
-    SFA_CHECK_ARG(std::isfinite(scale), "scale must be finite");
+    SFA_CHECK_ARG(std::isfinite(c.scale), "scale must be finite");
     SFA_CHECK_ARG(sink_len + window_len + n < (1ll << 30) && B * Hq * n < (1ll << 30) && Wc < (1ll << 30),
                   "problem too large");
     if ((st = decode_multi_check_head_dim(D, q->dtype))) return st;
-    const int es = dtype_size(q->dtype);
-    const sfa_tensor* ts[8] = {q, o, sink_k, sink_v, window_k, window_v, k_new, v_new};
-    for (const sfa_tensor* t : ts) {
-        if (t->shape[0] == 0 || t->shape[1] == 0 || t->shape[2] == 0) continue;
-        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
-                          (t->stride[2] * es) % 16 == 0,
-                      "decode_multi: rows of every tensor must be 16-byte aligned");
-    }
-    return SFA_OK;
+    return check_rows16({q, o, sink_k, sink_v, window_k, window_v, k_new, v_new}, dtype_size(q->dtype), 7,
+                        "decode_multi: rows of every tensor must be 16-byte aligned");
 }
 
-int check_multi_workspace(const sfa_tensor* q, const sfa_tensor* k_new, int64_t Nkv, void* workspace,
-                          size_t workspace_bytes) {
-    const size_t need = decode_multi_workspace(q->shape[0], q->shape[1], k_new->shape[1], q->shape[2], Nkv, q->shape[3],
-                                               q->dtype);
-    if (workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
-        set_error("decode_multi workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
-                  workspace);
-        return SFA_ERR_WORKSPACE;
-    }
-    return SFA_OK;
+int multi_workspace_and_launch(const RingCall& c) {
+    const sfa_tensor* q = c.q;
+    const size_t need = decode_multi_workspace(q->shape[0], q->shape[1], c.k_new->shape[1], q->shape[2],
+                                               c.sink_len + c.window_len + q->shape[2], q->shape[3], q->dtype);
+    const int st = check_workspace("decode_multi", need, true, c.workspace, c.workspace_bytes);
+    return st ? st : decode_multi_launch(c);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
-                                        int dtype) {
-    return decode_multi_workspace(B, Hq, Hkv, n_new, Nkv, D, dtype);
-}
-
-int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
-                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
-                          const float* s_aux, int commit, void* workspace, size_t workspace_bytes, float scale,
-                          unsigned flags, void* stream) {
+// sfa_decode_ring_multi*.  An empty call still commits where there is something to advance: the shared state with
+// B == 0 or H_q == 0, the state rows with H_q == 0 only (no rows: no state to read or advance)
+int ring_multi(const RingCall& c) {
     g_err[0] = 0;
     int st;
-    if ((st = check_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o, scale)))
-        return st;
-    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;
-    if ((st = check_multi_workspace(q, k_new, sink_len + window_len + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o,
-                               s_aux, commit, workspace, scale, flags, (hipStream_t)stream);
+    if ((st = check_multi(c))) return st;
+    const int64_t B = c.q->shape[0], Hq = c.q->shape[1];
+    if (B == 0 && c.mode != RingState::Shared) return SFA_OK;
+    if (B == 0 || Hq == 0) return c.commit && c.mode != RingState::Host ? ring_commit_dyn_launch(c) : SFA_OK;
+    return multi_workspace_and_launch(c);
 }
 
-int sfa_decode_ring_multi_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
-                              int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
-                              void* stream) {
+// sfa_decode_ring_tree*: the tree-specific checks come after those of the chunk; a tree call never commits
+int ring_tree(const RingCall& c) {
     g_err[0] = 0;
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    // every check of the host-state call, at the full cache (the launch geometry and workspace cover every fill level)
-    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
     int st;
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
-    if (q->shape[0] == 0 || q->shape[1] == 0) {
-        if (!commit) return SFA_OK;
-        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream);
-    }
-    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
-                               scale, flags, (hipStream_t)stream, state);
+    if ((st = check_multi(c))) return st;
+    const int64_t n = c.q->shape[2];
+    SFA_CHECK_ARG(n <= 64, "decode_tree: a tree chunk holds at most 64 nodes (got n = %lld)", (long long)n);
+    SFA_NEED(c.parent, "parent");
+    SFA_CHECK_ARG(c.parent_bstride == 0 || (c.parent_bstride >= n && c.parent_bstride < (1ll << 30)),
+                  "parent_bstride %lld: 0 (one tree shared by the batch) or >= n = %lld (one row per sequence)",
+                  (long long)c.parent_bstride, (long long)n);
+    if (c.q->shape[0] == 0 || c.q->shape[1] == 0) return SFA_OK;
+    return multi_workspace_and_launch(c);
 }
 
-int sfa_decode_ring_multi_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
-                               int32_t* state, void* workspace, size_t workspace_bytes, float scale, unsigned flags,
-                               void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
+// sfa_decode_ring_ragged_slots: every check of the slots call at the full cache; q / k_new / v_new / o share
+// shape[0] and T there
+int ring_ragged(const RingCall& c) {
     int st;
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale))) return st;
-    if (q->shape[0] == 0) return SFA_OK;               // no rows: no state to read or advance
-    if (q->shape[1] == 0) {
-        if (!commit) return SFA_OK;
-        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream, true);
-    }
-    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
-                               scale, flags, (hipStream_t)stream, state, true);
-}
-
-int sfa_decode_ring_multi_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                                const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                                const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
-                                int32_t* state, const int32_t* slots, void* workspace, size_t workspace_bytes,
-                                float scale, unsigned flags, void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
-    int st;
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, true))) return st;
-    if (q->shape[0] == 0) return SFA_OK;               // no rows: no state to read or advance
-    if (q->shape[1] == 0) {
-        if (!commit) return SFA_OK;
-        return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, nullptr, state, (hipStream_t)stream, true, nullptr,
-                                      0, slots);
-    }
-    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, commit, workspace,
-                               scale, flags, (hipStream_t)stream, state, true, nullptr, 0, slots);
-}
-
-size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
-                                         int64_t D, int dtype) {
-    return decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
-}
-
-int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                                 const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                                 const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
-                                 int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
-                                 void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
-    SFA_CHECK_ARG(cu_q != nullptr, "cu_q: null device pointer");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
-    int st;
-    // every check of the slots call at the full cache; q / k_new / v_new / o share shape[0] and T there
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, true))) return st;
+    if ((st = check_multi(c))) return st;
+    const sfa_tensor* q = c.q;
     SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
                   (long long)q->shape[0]);
     SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
-    const size_t need = decode_ragged_workspace(n_seq, q->shape[1], k_new->shape[1], q->shape[2], ns + Wc, q->shape[3],
-                                                q->dtype);
-    if (need == 0 || workspace == nullptr || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) {
-        set_error("decode_ragged workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", need, workspace_bytes,
-                  workspace);
-        return SFA_ERR_WORKSPACE;
-    }
-    return decode_ragged_launch(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, commit, state, slots, cu_q,
-                                n_seq, workspace, scale, flags, (hipStream_t)stream);
+    const size_t need = decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
+                                                c.sink_len + c.window_len, q->shape[3], q->dtype);
+    if ((st = check_workspace("decode_ragged", need, need != 0, c.workspace, c.workspace_bytes))) return st;
+    return decode_ragged_launch(c);
 }
 
-}  // extern "C"
-
-namespace {
-
-// the tree-specific checks of sfa_decode_ring_tree*, after check_multi
-int check_tree(const sfa_tensor* q, const int32_t* parent, int64_t parent_bstride) {
-    const int64_t n = q->shape[2];
-    SFA_CHECK_ARG(n <= 64, "decode_tree: a tree chunk holds at most 64 nodes (got n = %lld)", (long long)n);
-    SFA_CHECK_ARG(parent != nullptr, "parent: null device pointer");
-    SFA_CHECK_ARG(parent_bstride == 0 || (parent_bstride >= n && parent_bstride < (1ll << 30)),
-                  "parent_bstride %lld: 0 (one tree shared by the batch) or >= n = %lld (one row per sequence)",
-                  (long long)parent_bstride, (long long)n);
-    return SFA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
-                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
-                         const float* s_aux, const int32_t* parent, int64_t parent_bstride, void* workspace,
-                         size_t workspace_bytes, float scale, unsigned flags, void* stream) {
-    g_err[0] = 0;
-    int st;
-    if ((st = check_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o, scale)))
-        return st;
-    if ((st = check_tree(q, parent, parent_bstride))) return st;
-    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;
-    if ((st = check_multi_workspace(q, k_new, sink_len + window_len + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, write_pos, k_new, v_new, o,
-                               s_aux, 0, workspace, scale, flags, (hipStream_t)stream, nullptr, false, parent,
-                               parent_bstride);
-}
-
-static int tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
-                    const sfa_tensor* window_v, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
-                    const float* s_aux, const int32_t* parent, int64_t parent_bstride, int32_t* state, void* workspace,
-                    size_t workspace_bytes, float scale, unsigned flags, void* stream, bool rows,
-                    const int32_t* slots = nullptr, bool pool = false) {
-    g_err[0] = 0;
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
-    SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
-    SFA_CHECK_ARG(sink_k != nullptr && window_k != nullptr, "cache buffers: null tensor descriptor");
-    const int64_t ns = sink_k->shape[2], Wc = window_k->shape[2];
-    int st;
-    if ((st = check_multi(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, scale, pool))) return st;
-    if ((st = check_tree(q, parent, parent_bstride))) return st;
-    if (q->shape[0] == 0 || q->shape[1] == 0) return SFA_OK;   // nothing to attend; a tree call never commits
-    if ((st = check_multi_workspace(q, k_new, ns + Wc + q->shape[2], workspace, workspace_bytes))) return st;
-    return decode_multi_launch(q, sink_k, sink_v, ns, window_k, window_v, Wc, 0, k_new, v_new, o, s_aux, 0, workspace,
-                               scale, flags, (hipStream_t)stream, state, rows, parent, parent_bstride, slots);
-}
-
-int sfa_decode_ring_tree_dyn(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                             const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                             const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
-                             int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
-                             float scale, unsigned flags, void* stream) {
-    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
-                    workspace, workspace_bytes, scale, flags, stream, false);
-}
-
-int sfa_decode_ring_tree_rows(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                              const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                              const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
-                              int64_t parent_bstride, int32_t* state, void* workspace, size_t workspace_bytes,
-                              float scale, unsigned flags, void* stream) {
-    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
-                    workspace, workspace_bytes, scale, flags, stream, true);
-}
-
-int sfa_decode_ring_tree_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                               const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                               const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, const int32_t* parent,
-                               int64_t parent_bstride, int32_t* state, const int32_t* slots, void* workspace,
-                               size_t workspace_bytes, float scale, unsigned flags, void* stream) {
-    return tree_dyn(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, parent, parent_bstride, state,
-                    workspace, workspace_bytes, scale, flags, stream, true, slots, true);
-}
-
-}  // extern "C"
-
-namespace {
-
-// every host-checkable argument of sfa_ring_commit_dyn / _rows; nothing launches
-int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                 const sfa_tensor* v_new, const int32_t* count, int32_t* state, bool pool = false) {
+// every host-checkable argument of sfa_ring_commit*; nothing launches
+int check_commit(const RingCall& c) {
+    const sfa_tensor *window_k = c.window_k, *window_v = c.window_v, *k_new = c.k_new, *v_new = c.v_new;
     int st;
     if ((st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
         return st;
     if ((st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k_new, v_new, "k_new", "v_new")))
         return st;
-    SFA_CHECK_ARG(count != nullptr, "count: null device pointer");
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_NEED(c.count, "count");
+    SFA_NEED(c.state, "state");
     SFA_CHECK_ARG(k_new->dtype == window_k->dtype, "k_new / v_new and the ring must share one dtype");
     const int64_t n = k_new->shape[2], Wc = window_k->shape[2];
+    const bool pool = c.slots != nullptr;
     SFA_CHECK_ARG(n >= 1, "ring_commit: the chunk needs at least one token");
     SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
     if (pool)
@@ -753,87 +556,39 @@ int check_commit(const sfa_tensor* window_k, const sfa_tensor* window_v, const s
     const int es = dtype_size(k_new->dtype);
     SFA_CHECK_ARG(k_new->shape[3] > 0 && (k_new->shape[3] * es) % 16 == 0,
                   "ring_commit: K/V rows must be a multiple of 16 bytes (head dim %lld)", (long long)k_new->shape[3]);
-    const sfa_tensor* ts[4] = {window_k, window_v, k_new, v_new};
-    for (const sfa_tensor* t : ts) {
-        if (t->shape[0] == 0 || t->shape[1] == 0) continue;
-        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
-                          (t->stride[2] * es) % 16 == 0,
-                      "ring_commit: rows of every tensor must be 16-byte aligned");
-    }
-    return SFA_OK;
+    return check_rows16({window_k, window_v, k_new, v_new}, es, 3, "ring_commit: rows of every tensor must be 16-byte aligned");
 }
 
-}  // namespace
-
-extern "C" {
-
-int sfa_ring_commit_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                        const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
-    g_err[0] = 0;
-    int st;
-    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
-    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream);
+RingCall commit_call(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                     const sfa_tensor* v_new, const int32_t* count, RingState mode, int32_t* state, const int32_t* slots,
+                     void* stream) {
+    RingCall c{};
+    c.window_k = window_k, c.window_v = window_v, c.k_new = k_new, c.v_new = v_new;
+    c.count = count, c.mode = mode, c.state = state, c.slots = slots, c.stream = (hipStream_t)stream;
+    return c;
 }
 
-int sfa_ring_commit_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                         const sfa_tensor* v_new, const int32_t* count, int32_t* state, void* stream) {
-    g_err[0] = 0;
+// sfa_ring_commit_{dyn,rows,slots}.  The shared state is advanced even for B == 0; without rows there is no state
+int ring_commit(const RingCall& c) {
     int st;
-    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state))) return st;
-    if (k_new->shape[0] == 0) return SFA_OK;
-    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, true);
+    if ((st = check_commit(c))) return st;
+    if (c.mode == RingState::Rows && c.k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(c);
 }
 
-static int commit_path(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                       const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
-                       int32_t* state, void* stream, bool rows, const int32_t* slots = nullptr, bool pool = false) {
-    g_err[0] = 0;
+// sfa_ring_commit_path_{dyn,rows,slots}
+int ring_commit_path(RingCall c, const int32_t* path, int64_t path_bstride) {
+    c.path = path, c.path_bstride = path_bstride;
     int st;
-    SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
-    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state, pool))) return st;
-    const int64_t n = k_new->shape[2];
-    SFA_CHECK_ARG(path != nullptr, "path: null device pointer");
+    if ((st = check_commit(c))) return st;
+    const int64_t n = c.k_new->shape[2];
+    SFA_NEED(path, "path");
     SFA_CHECK_ARG(path_bstride == 0 || (path_bstride >= n && path_bstride < (1ll << 30)),
                   "path_bstride %lld: 0 (one path shared by the batch) or >= n = %lld (one row per sequence)",
                   (long long)path_bstride, (long long)n);
-    if (rows && k_new->shape[0] == 0) return SFA_OK;
-    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, rows, path,
-                                  path_bstride, slots);
+    if (c.mode == RingState::Rows && c.k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(c);
 }
-
-int sfa_ring_commit_path_dyn(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                             const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
-                             int32_t* state, void* stream) {
-    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, false);
-}
-
-int sfa_ring_commit_path_rows(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                              const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
-                              int32_t* state, void* stream) {
-    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, true);
-}
-
-int sfa_ring_commit_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                          const sfa_tensor* v_new, const int32_t* count, int32_t* state, const int32_t* slots,
-                          void* stream) {
-    g_err[0] = 0;
-    int st;
-    SFA_CHECK_ARG(slots != nullptr, "slots: null device pointer");
-    if ((st = check_commit(window_k, window_v, k_new, v_new, count, state, true))) return st;
-    if (k_new->shape[0] == 0) return SFA_OK;
-    return ring_commit_dyn_launch(window_k, window_v, k_new, v_new, count, state, (hipStream_t)stream, true, nullptr, 0,
-                                  slots);
-}
-
-int sfa_ring_commit_path_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                               const sfa_tensor* v_new, const int32_t* count, const int32_t* path, int64_t path_bstride,
-                               int32_t* state, const int32_t* slots, void* stream) {
-    return commit_path(window_k, window_v, k_new, v_new, count, path, path_bstride, state, stream, true, slots, true);
-}
-
-}  // extern "C"
-
-namespace {
 
 // sfa_ring_fill_varlen (slots null: sequence i -> cache row i of n_seq) and sfa_ring_fill_varlen_slots (pool)
 int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
@@ -848,8 +603,8 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     if ((st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
         (st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k, v, "k", "v")))
         return st;
-    SFA_CHECK_ARG(cu_seqlens != nullptr, "cu_seqlens: null device pointer");
-    SFA_CHECK_ARG(state != nullptr, "state: null device pointer");
+    SFA_NEED(cu_seqlens, "cu_seqlens");
+    SFA_NEED(state, "state");
     SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
     SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
@@ -871,20 +626,196 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     const int es = dtype_size(k->dtype);
     SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_fill_varlen: K/V rows must be a multiple of 16 bytes (head dim %lld)",
                   (long long)D);
-    const sfa_tensor* ts[6] = {sink_k, sink_v, window_k, window_v, k, v};
-    for (const sfa_tensor* t : ts) {
-        if (t->shape[0] == 0 || t->shape[1] == 0 || t->shape[2] == 0) continue;
-        SFA_CHECK_ARG(((uintptr_t)t->ptr % 16) == 0 && (t->stride[0] * es) % 16 == 0 && (t->stride[1] * es) % 16 == 0 &&
-                          (t->stride[2] * es) % 16 == 0,
-                      "ring_fill_varlen: rows of every tensor must be 16-byte aligned");
-    }
+    if ((st = check_rows16({sink_k, sink_v, window_k, window_v, k, v}, es, 7,
+                           "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
+        return st;
     return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
                                    (hipStream_t)stream, slots);
 }
 
 }  // namespace
 
+// the parameter lists of include/sfa.h and their pass to attend_call / commit_call
+#define SFA_ATTEND_PARAMS                                                                                              \
+    const sfa_tensor *q, const sfa_tensor *sink_k, const sfa_tensor *sink_v, const sfa_tensor *window_k,               \
+        const sfa_tensor *window_v, const sfa_tensor *k_new, const sfa_tensor *v_new, const sfa_tensor *o,             \
+        const float *s_aux
+#define SFA_ATTEND_CALL \
+    attend_call(q, sink_k, sink_v, window_k, window_v, k_new, v_new, o, s_aux, workspace, workspace_bytes, scale, flags, stream)
+#define SFA_TAIL_PARAMS void *workspace, size_t workspace_bytes, float scale, unsigned flags, void *stream
+#define SFA_COMMIT_PARAMS \
+    const sfa_tensor *window_k, const sfa_tensor *window_v, const sfa_tensor *k_new, const sfa_tensor *v_new, const int32_t *count
+
 extern "C" {
+
+int sfa_decode(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* o,
+               const float* s_aux, SFA_TAIL_PARAMS) {
+    RingCall c = attend_call(q, k, v, nullptr, nullptr, nullptr, nullptr, o, s_aux, workspace, workspace_bytes, scale,
+                             flags, stream);
+    return ring_step(host_state(c, k ? k->shape[2] : 0, 0, 0));
+}
+
+int sfa_decode_ring(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                    const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, const sfa_tensor* o,
+                    const float* s_aux, SFA_TAIL_PARAMS) {
+    RingCall c = attend_call(q, sink_k, sink_v, window_k, window_v, nullptr, nullptr, o, s_aux, workspace,
+                             workspace_bytes, scale, flags, stream);
+    return ring_step(host_state(c, sink_len, window_len, 0));
+}
+
+int sfa_decode_ring_step(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                         const float* s_aux, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    RingCall c = SFA_ATTEND_CALL;
+    return ring_step(host_state(c, sink_len, window_len, write_pos));
+}
+
+int sfa_decode_ring_step_dyn(SFA_ATTEND_PARAMS, int32_t* state, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    RingCall c = SFA_ATTEND_CALL;
+    return ring_step(device_state(c, RingState::Shared, state, nullptr));
+}
+
+int sfa_decode_ring_step_rows(SFA_ATTEND_PARAMS, int32_t* state, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    RingCall c = SFA_ATTEND_CALL;
+    return ring_step(device_state(c, RingState::Rows, state, nullptr));
+}
+
+int sfa_decode_ring_step_slots(SFA_ATTEND_PARAMS, int32_t* state, const int32_t* slots, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_CHECK_ARG(k_new != nullptr && v_new != nullptr, "k_new / v_new: null tensor descriptor");
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    RingCall c = SFA_ATTEND_CALL;
+    return ring_step(device_state(c, RingState::Rows, state, slots));
+}
+
+size_t sfa_decode_multi_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D,
+                                        int dtype) {
+    return decode_multi_workspace(B, Hq, Hkv, n_new, Nkv, D, dtype);
+}
+
+int sfa_decode_ring_multi(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                          const float* s_aux, int commit, SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit;
+    return ring_multi(host_state(c, sink_len, window_len, write_pos));
+}
+
+int sfa_decode_ring_multi_dyn(SFA_ATTEND_PARAMS, int commit, int32_t* state, SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit;
+    return ring_multi(device_state(c, RingState::Shared, state, nullptr));
+}
+
+int sfa_decode_ring_multi_rows(SFA_ATTEND_PARAMS, int commit, int32_t* state, SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit;
+    return ring_multi(device_state(c, RingState::Rows, state, nullptr));
+}
+
+int sfa_decode_ring_multi_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, const int32_t* slots, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit;
+    return ring_multi(device_state(c, RingState::Rows, state, slots));
+}
+
+size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                         int64_t D, int dtype) {
+    return decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+}
+
+int sfa_decode_ring_ragged_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, const int32_t* slots,
+                                 const int32_t* cu_q, int n_seq, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
+int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
+                         const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
+                         int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                         const float* s_aux, const int32_t* parent, int64_t parent_bstride, SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.parent = parent, c.parent_bstride = parent_bstride;
+    return ring_tree(host_state(c, sink_len, window_len, write_pos));
+}
+
+int sfa_decode_ring_tree_dyn(SFA_ATTEND_PARAMS, const int32_t* parent, int64_t parent_bstride, int32_t* state,
+                             SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.parent = parent, c.parent_bstride = parent_bstride;
+    return ring_tree(device_state(c, RingState::Shared, state, nullptr));
+}
+
+int sfa_decode_ring_tree_rows(SFA_ATTEND_PARAMS, const int32_t* parent, int64_t parent_bstride, int32_t* state,
+                              SFA_TAIL_PARAMS) {
+    RingCall c = SFA_ATTEND_CALL;
+    c.parent = parent, c.parent_bstride = parent_bstride;
+    return ring_tree(device_state(c, RingState::Rows, state, nullptr));
+}
+
+int sfa_decode_ring_tree_slots(SFA_ATTEND_PARAMS, const int32_t* parent, int64_t parent_bstride, int32_t* state,
+                               const int32_t* slots, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    RingCall c = SFA_ATTEND_CALL;
+    c.parent = parent, c.parent_bstride = parent_bstride;
+    return ring_tree(device_state(c, RingState::Rows, state, slots));
+}
+
+int sfa_ring_commit_dyn(SFA_COMMIT_PARAMS, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    return ring_commit(commit_call(window_k, window_v, k_new, v_new, count, RingState::Shared, state, nullptr, stream));
+}
+
+int sfa_ring_commit_rows(SFA_COMMIT_PARAMS, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    return ring_commit(commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, nullptr, stream));
+}
+
+int sfa_ring_commit_slots(SFA_COMMIT_PARAMS, int32_t* state, const int32_t* slots, void* stream) {
+    g_err[0] = 0;
+    SFA_NEED(slots, "slots");
+    return ring_commit(commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream));
+}
+
+int sfa_ring_commit_path_dyn(SFA_COMMIT_PARAMS, const int32_t* path, int64_t path_bstride, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    return ring_commit_path(commit_call(window_k, window_v, k_new, v_new, count, RingState::Shared, state, nullptr, stream),
+                            path, path_bstride);
+}
+
+int sfa_ring_commit_path_rows(SFA_COMMIT_PARAMS, const int32_t* path, int64_t path_bstride, int32_t* state, void* stream) {
+    g_err[0] = 0;
+    return ring_commit_path(commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, nullptr, stream),
+                            path, path_bstride);
+}
+
+int sfa_ring_commit_path_slots(SFA_COMMIT_PARAMS, const int32_t* path, int64_t path_bstride, int32_t* state,
+                               const int32_t* slots, void* stream) {
+    g_err[0] = 0;
+    SFA_NEED(slots, "slots");
+    return ring_commit_path(commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream),
+                            path, path_bstride);
+}
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                          const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,

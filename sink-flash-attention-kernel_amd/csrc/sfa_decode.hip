@@ -540,28 +540,32 @@ int decode_plan(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nkv, int64_t D, int 
     return SFA_OK;
 }
 
-int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, int64_t n1, const sfa_tensor* k2,
-                  const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
-                  float scale, const DecodePlan& pl, hipStream_t stream, const sfa_tensor* k_new,
-                  const sfa_tensor* v_new, int new_slot, int* dyn_state, bool one_pass, bool state_rows,
-                  const int32_t* slots) {
+int decode_launch(const RingCall& c, const DecodePlan& pl) {
+    const sfa_tensor *q = c.q, *k = c.sink_k, *v = c.sink_v, *o = c.o;
+    const sfa_tensor *k2 = c.window_len ? c.window_k : nullptr, *v2 = c.window_len ? c.window_v : nullptr;
+    const float* s_aux = c.s_aux;
+    void* workspace = c.workspace;
+    const float scale = c.scale;
+    hipStream_t stream = c.stream;
+    int* dyn_state = c.state;
+    const int32_t* slots = c.slots;
     const int B = (int)q->shape[0], Hq = (int)q->shape[1], D = (int)q->shape[3];
-    const int Hkv = (int)k->shape[1], Nkv = (int)(n1 + n2), N1 = (int)n1;
+    const int Hkv = (int)k->shape[1], Nkv = (int)(c.sink_len + c.window_len), N1 = (int)c.sink_len;
     const View kv2 = k2 ? make_view(k2) : make_view(k);
     const View vv2 = v2 ? make_view(v2) : make_view(v);
     const int wsize = k2 ? (int)k2->shape[2] : 0;
-    const int stride = dyn_state && state_rows ? 4 : 0;
+    const int stride = c.mode == RingState::Rows ? 4 : 0;
     const int npool = (int)k->shape[0];      // slot call: the cache is a pool, B = q's rows
     Fresh fr{kv2, vv2, -1, nullptr, wsize, 0};
-    if (k_new && v_new && (new_slot >= 0 || dyn_state))
-        fr = Fresh{make_view(k_new), make_view(v_new), dyn_state ? 0 : new_slot, dyn_state, wsize, stride};
+    if (c.k_new && c.v_new)                  // fused step: write_pos is 0 with a device state
+        fr = Fresh{make_view(c.k_new), make_view(c.v_new), (int)c.write_pos, dyn_state, wsize, stride};
     const int S = pl.splits;
     // counters of the one-pass mode sit at the START of the workspace (their place must not move when the split count
     // changes from one step to the next while a ring fills), the partials behind them
     float* Mp = reinterpret_cast<float*>((char*)workspace + decode_counter_bytes(B, Hkv));
     float* Lp = Mp + (int64_t)B * Hq * S;
     float* Op = Lp + (int64_t)B * Hq * S;
-    one_pass = one_pass && D <= 256;      // the in-kernel fold gives a head to one wave: 64 lanes x 4 columns
+    const bool one_pass = (c.flags & SFA_FLAG_DECODE_ONE_PASS) != 0 && D <= 256;      // the in-kernel fold gives a head to one wave: 64 lanes x 4 columns
     OnePass op1{one_pass ? reinterpret_cast<int*>(workspace) : nullptr, s_aux, make_view(o)};
     dim3 grid(S, Hkv, B);
     int st;

@@ -130,8 +130,7 @@ __global__ __launch_bounds__(1024) void ragged_prep_kernel(RaggedArgs rg, int2* 
         int lo = 0, hi = rg.n_seq - 1;       // the last i with start(i) <= id; sequence 0 starts at 0
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
-            int c = rg.cu_q[mid];
-            c = c < 0 ? 0 : (c > rg.T ? rg.T : c);
+            const int c = ragged_seq(rg, mid).c0;
             const int64_t start = row ? c : (int64_t)G * c / 32 + mid;
             if (start <= id) lo = mid;
             else hi = mid - 1;
@@ -934,10 +933,8 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
         c = slots[b];
         if ((unsigned)c >= (unsigned)npool) return;
     }
-    int c0 = cu[b], c1 = cu[b + 1];
-    c0 = c0 < 0 ? 0 : (c0 > T ? T : c0);
-    c1 = c1 < c0 ? c0 : (c1 > T ? T : c1);
-    const int L = c1 - c0;
+    const RaggedSeq seq = ragged_seq(RaggedArgs{cu, nullptr, nullptr, n_seq, T}, b);
+    const int c0 = seq.c0, L = seq.n;
     const int sl = L < ns ? L : ns;
     const int rem = L - sl;
     if (hk == 0 && j == 0 && ch == 0) {
@@ -967,38 +964,33 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
 
-// the launch after every reader of the state, one thread per state row (`rows` of them, stride `stride`): write_pos += a
-// (mod Wc), window_len = min(window_len + a, Wc); per-sequence rows (stride 4, count [rows]) also seen += a.
-// Plain stores from vector lanes.
-__global__ void ring_advance_kernel(int* state, const int* count, int n, int wc, int rows, int stride) {
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (r >= rows) return;
-    int* st = state + (int64_t)r * stride;
-    const int acc = count ? clamp_count(count + (stride ? r : 0), n) : n;
+// one state row after every reader of it: write_pos += acc (mod Wc), window_len = min(window_len + acc, Wc), and - for a
+// per-sequence row - seen += acc.  Plain stores from vector lanes.
+__device__ __forceinline__ void advance_row(int* st, int acc, int wc, bool seen) {
     int wl = st[1], wp = st[2];
     wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
     wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
     st[1] = wl + acc < wc ? wl + acc : wc;
     st[2] = (int)(((int64_t)wp + acc) % wc);
-    if (stride) st[3] += acc;
+    if (seen) st[3] += acc;
 }
 
-// the same for a slot call: thread r advances state row slots[r] by count[r] (all n without a count); an inactive row
-// moves nothing
+// one thread per state row (`rows` of them, stride `stride`: 0 = the shared state, 4 = per-sequence rows with count
+// [rows]): advance by clamp(count, 0, n), all n without a count
+__global__ void ring_advance_kernel(int* state, const int* count, int n, int wc, int rows, int stride) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= rows) return;
+    advance_row(state + (int64_t)r * stride, count ? clamp_count(count + (stride ? r : 0), n) : n, wc, stride != 0);
+}
+
+// the same for a slot call: thread r advances state row slots[r]; an inactive row moves nothing
 __global__ void ring_advance_slots_kernel(int* state, const int* count, int n, int wc, int rows, const int* slots,
                                           int npool) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (r >= rows) return;
     const int c = slots[r];
     if ((unsigned)c >= (unsigned)npool) return;
-    int* st = state + (int64_t)c * 4;
-    const int acc = count ? clamp_count(count + r, n) : n;
-    int wl = st[1], wp = st[2];
-    wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
-    wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
-    st[1] = wl + acc < wc ? wl + acc : wc;
-    st[2] = (int)(((int64_t)wp + acc) % wc);
-    st[3] += acc;
+    advance_row(state + (int64_t)c * 4, count ? clamp_count(count + r, n) : n, wc, true);
 }
 
 // the same for a packed call: thread r advances state row slots[r] by n_r = the length of sequence r; an inactive or
@@ -1009,28 +1001,24 @@ __global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int wc, co
     const int c = slots[r];
     if ((unsigned)c >= (unsigned)npool) return;
     const int acc = ragged_seq(rg, r).n;
-    if (acc == 0) return;
-    int* st = state + (int64_t)c * 4;
-    int wl = st[1], wp = st[2];
-    wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
-    wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
-    st[1] = wl + acc < wc ? wl + acc : wc;
-    st[2] = (int)(((int64_t)wp + acc) % wc);
-    st[3] += acc;
+    if (acc) advance_row(state + (int64_t)c * 4, acc, wc, true);
 }
 
-// advance every state row after the launches that read it (shared state: one row)
-int launch_advance(int* state, const int* count, int n, int wc, int B, bool rows, hipStream_t stream,
-                   const int* slots = nullptr, int npool = 0) {
-    const int nrow = rows ? B : 1;
+// advance every state row after the launches that read it (shared state: one row); rg: by the lengths of a pack
+int launch_advance(const MultiArgs& a, const int* count, const RaggedArgs* rg, hipStream_t stream) {
+    int* state = const_cast<int*>(a.state);
+    const int nrow = rg ? rg->n_seq : a.sstride ? a.B : 1;
     if (nrow <= 0) return SFA_OK;
-    if (slots) {
-        ring_advance_slots_kernel<<<dim3((unsigned)cdiv64(nrow, 256)), nrow < 256 ? nrow : 256, 0, stream>>>(
-            state, count, n, wc, nrow, slots, npool);
+    const dim3 grid((unsigned)cdiv64(nrow, 256)), block(nrow < 256 ? nrow : 256);
+    if (rg) {
+        ring_advance_ragged_kernel<<<grid, block, 0, stream>>>(state, *rg, a.wc, a.slots, a.npool);
+        return launch_status("ring_advance_ragged");
+    }
+    if (a.slots) {
+        ring_advance_slots_kernel<<<grid, block, 0, stream>>>(state, count, a.n, a.wc, nrow, a.slots, a.npool);
         return launch_status("ring_advance_slots");
     }
-    ring_advance_kernel<<<dim3((unsigned)cdiv64(nrow, 256)), nrow < 256 ? nrow : 256, 0, stream>>>(
-        state, count, n, wc, nrow, rows ? 4 : 0);
+    ring_advance_kernel<<<grid, block, 0, stream>>>(state, count, a.n, a.wc, nrow, a.sstride);
     return launch_status("ring_advance");
 }
 
@@ -1053,72 +1041,123 @@ int64_t max_splits(int64_t B, int64_t Hkv, int64_t nrb, int64_t Nkv) {
 
 bool mfma_head_dim(int D) { return D == 64 || D == 80 || D == 96 || D == 128; }
 
+// The kernel instances that exist, one line per mode of a call: f gets the (Dyn, Tree, Slots, Ragged) of the split
+// kernels (the reduce kernel has no Tree).  A new mode is a new field of RingCall / MultiArgs plus one line here.
+template <bool Dyn_, bool Tree_, bool Slots_, bool Ragged_>
+struct Mode {
+    static constexpr bool Dyn = Dyn_, Tree = Tree_, Slots = Slots_, Ragged = Ragged_;
+};
+
+template <typename F>
+void dispatch_mode(const MultiArgs& a, const RaggedArgs* rg, F&& f) {
+    if (rg) f(Mode<true, false, true, true>{});                                   // packed: slots and device rows
+    else if (a.slots && a.parent) f(Mode<true, true, true, false>{});             // slot calls: device rows
+    else if (a.slots) f(Mode<true, false, true, false>{});
+    else if (a.state && a.parent) f(Mode<true, true, false, false>{});
+    else if (a.state) f(Mode<true, false, false, false>{});
+    else if (a.parent) f(Mode<false, true, false, false>{});
+    else f(Mode<false, false, false, false>{});
+}
+
+// launch_status of a split launch: decode_{multi,tree}_{mfma,f32}[_slots | _ragged]
+int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
+    char tag[40];
+    snprintf(tag, sizeof(tag), "decode_%s_%s%s", a.parent ? "tree" : "multi", kind, rg ? "_ragged" : a.slots ? "_slots" : "");
+    return launch_status(tag);
+}
+
 template <typename T, int D>
-int launch_mfma(const MultiArgs& a, hipStream_t stream) {
-    const int64_t nblk = (int64_t)a.B * a.Hkv * a.Sw * a.nrb;
-    const dim3 grid((unsigned)nblk);
-    if (a.slots) {       // slot calls: dyn instances of their own
-        if (a.parent) multi_split_mfma_kernel<T, D, true, true, true><<<grid, kWaves * 64, 0, stream>>>(a);
-        else multi_split_mfma_kernel<T, D, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a);
-        return launch_status(a.parent ? "decode_tree_mfma_slots" : "decode_multi_mfma_slots");
-    }
-    if (a.parent) {
-        if (a.state) multi_split_mfma_kernel<T, D, true, true><<<grid, kWaves * 64, 0, stream>>>(a);
-        else multi_split_mfma_kernel<T, D, false, true><<<grid, kWaves * 64, 0, stream>>>(a);
-        return launch_status("decode_tree_mfma");
-    }
-    if (a.state) multi_split_mfma_kernel<T, D, true, false><<<grid, kWaves * 64, 0, stream>>>(a);
-    else multi_split_mfma_kernel<T, D, false, false><<<grid, kWaves * 64, 0, stream>>>(a);
-    return launch_status("decode_multi_mfma");
+int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, hipStream_t stream) {
+    const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
+    dispatch_mode(a, rg, [&](auto m) {
+        using M = decltype(m);
+        if constexpr (M::Ragged) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
+        else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots><<<grid, kWaves * 64, 0, stream>>>(a);
+    });
+    return split_status(a, rg, "mfma");
 }
 
 template <typename T>
-int launch_mfma_d(const MultiArgs& a, hipStream_t stream) {
+int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, hipStream_t stream) {
     switch (a.D) {
-        case 64: return launch_mfma<T, 64>(a, stream);
-        case 80: return launch_mfma<T, 80>(a, stream);
-        case 96: return launch_mfma<T, 96>(a, stream);
-        case 128: return launch_mfma<T, 128>(a, stream);
+        case 64: return launch_mfma<T, 64>(a, rg, stream);
+        case 80: return launch_mfma<T, 80>(a, rg, stream);
+        case 96: return launch_mfma<T, 96>(a, rg, stream);
+        case 128: return launch_mfma<T, 128>(a, rg, stream);
     }
     set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
     return SFA_ERR_UNSUPPORTED;
 }
 
+// split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
 template <typename T>
-int launch_rest(const MultiArgs& a, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
-        if (a.slots) {
-            if (a.parent) multi_split_f32_kernel<T, true, true, true><<<grid, 256, 0, stream>>>(a);
-            else multi_split_f32_kernel<T, true, false, true><<<grid, 256, 0, stream>>>(a);
-            st = launch_status(a.parent ? "decode_tree_f32_slots" : "decode_multi_f32_slots");
-        } else if (a.parent) {
-            if (a.state) multi_split_f32_kernel<T, true, true><<<grid, 256, 0, stream>>>(a);
-            else multi_split_f32_kernel<T, false, true><<<grid, 256, 0, stream>>>(a);
-            st = launch_status("decode_tree_f32");
-        } else {
-            if (a.state) multi_split_f32_kernel<T, true, false><<<grid, 256, 0, stream>>>(a);
-            else multi_split_f32_kernel<T, false, false><<<grid, 256, 0, stream>>>(a);
-            st = launch_status("decode_multi_f32");
-        }
+        dispatch_mode(a, rg, [&](auto m) {
+            using M = decltype(m);
+            if constexpr (M::Ragged) multi_split_f32_kernel<T, M::Dyn, M::Tree, M::Slots, true><<<grid, 256, 0, stream>>>(a, *rg);
+            else multi_split_f32_kernel<T, M::Dyn, M::Tree, M::Slots><<<grid, 256, 0, stream>>>(a);
+        });
+        st = split_status(a, rg, "f32");
     }
     if (st) return st;
     const int nred = (int)cdiv64(rows, 4);
     int64_t ncommit = 0;
-    if (a.commit) {
-        const int64_t ncm = a.n < a.wc ? a.n : a.wc;
+    if (a.commit) {      // 16-byte pieces of the stored tokens: every row of a pack, else the last min(n, Wc) of the chunk
+        const int64_t ncm = rg || a.n < a.wc ? a.n : a.wc;
         ncommit = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)sizeof(T) / 16), 256);
     }
-    if (a.slots) multi_reduce_kernel<T, true, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
-    else if (a.state) multi_reduce_kernel<T, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
-    else multi_reduce_kernel<T, false><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred);
-    if ((st = launch_status("decode_multi_reduce"))) return st;
-    if (a.state && a.commit)     // every reader of the state has finished: advance it (each row) by n
-        st = launch_advance(const_cast<int*>(a.state), nullptr, a.n, a.wc, a.B, a.sstride != 0, stream, a.slots, a.npool);
+    const dim3 rgrid((unsigned)(nred + ncommit));
+    dispatch_mode(a, rg, [&](auto m) {
+        using M = decltype(m);
+        if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
+        else multi_reduce_kernel<T, M::Dyn, M::Slots><<<rgrid, 256, 0, stream>>>(a, nred);
+    });
+    if ((st = launch_status(rg ? "decode_multi_reduce_ragged" : "decode_multi_reduce"))) return st;
+    if (a.state && a.commit)     // every reader of the state has finished: advance it (each row) by n (its n_i)
+        st = launch_advance(a, nullptr, rg, stream);
     return st;
+}
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The kernel argument of a call, filled from the descriptor in this one place.  The commit launcher (attend = false)
+// takes the ring, the chunk, the state and the path / slots and leaves the rest zero; an attention launcher adds its
+// plan (want, T0 .. S, Sw) and the partials (Mp, Lp, Op) itself.
+MultiArgs multi_args(const RingCall& c, bool attend) {
+    MultiArgs a{};
+    a.wk = make_view(c.window_k), a.wv = make_view(c.window_v), a.kn = make_view(c.k_new), a.vn = make_view(c.v_new);
+    a.B = (int)c.k_new->shape[0], a.Hkv = (int)c.k_new->shape[1], a.n = (int)c.k_new->shape[2], a.D = (int)c.k_new->shape[3];
+    a.wc = (int)c.window_k->shape[2];
+    a.state = c.state, a.sstride = c.mode == RingState::Rows ? 4 : 0;
+    a.path = c.path, a.pathstride = (int)c.path_bstride;
+    a.slots = c.slots, a.npool = (int)c.window_k->shape[0];
+    if (!attend) return a;
+    a.q = make_view(c.q), a.sk = make_view(c.sink_k), a.sv = make_view(c.sink_v), a.o = make_view(c.o);
+    a.s_aux = c.s_aux;
+    a.G = (int)(c.q->shape[1] / c.k_new->shape[1]);
+    a.R = a.G * a.n;
+    a.nrb = (int)cdiv64(a.R, 32);
+    a.sink_len = (int)c.sink_len, a.wl = (int)c.window_len, a.wp = (int)c.write_pos;
+    a.ns = (int)c.sink_k->shape[2];
+    a.scale_log2 = c.scale * kLog2e;
+    a.commit = c.commit ? 1 : 0;
+    a.parent = c.parent, a.pstride = (int)c.parent_bstride;
+    return a;
+}
+
+// the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
+int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname) {
+    const int dt = c.q->dtype;
+    *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
+    *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
+    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, false, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, *mfma, c.stream);
+    return launch_rest<bf16_t>(a, rg, *mfma, c.stream);
 }
 
 }  // namespace
@@ -1139,66 +1178,38 @@ size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new,
     const int64_t R = Hq / Hkv * n_new;
     const int64_t S = max_splits(B, Hkv, cdiv64(R, 32), Nkv);
     const size_t rows = (size_t)(B * Hkv * R);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return 2 * al(rows * S * sizeof(float)) + al(rows * S * (size_t)D * sizeof(float));
+    return 2 * al256(rows * S * sizeof(float)) + al256(rows * S * (size_t)D * sizeof(float));
 }
 
-int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                        const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
-                        const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
-                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream, int32_t* state,
-                        bool state_rows, const int32_t* parent, int64_t parent_bstride, const int32_t* slots) {
-    MultiArgs a;
-    a.parent = parent, a.pstride = (int)parent_bstride;   // tree call (never with commit)
-    a.path = nullptr, a.pathstride = 0;
-    a.slots = slots, a.npool = (int)sink_k->shape[0];     // slot call (state_rows; B = q's rows, not the pool's)
-    a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
-    a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
-    a.s_aux = s_aux;
-    a.B = (int)q->shape[0];
-    a.Hkv = (int)k_new->shape[1];
-    a.G = (int)(q->shape[1] / k_new->shape[1]);
-    a.n = (int)q->shape[2];
-    a.D = (int)q->shape[3];
-    a.R = a.G * a.n;
-    a.nrb = (int)cdiv64(a.R, 32);
-    a.sink_len = (int)sink_len, a.wl = (int)window_len, a.wp = (int)write_pos, a.wc = (int)window_k->shape[2];
+int decode_multi_launch(const RingCall& c) {
+    MultiArgs a = multi_args(c, true);
     a.want = (int)want_splits(a.B, a.Hkv, a.nrb);
     const MultiPlan p = multi_plan(a.sink_len, a.wl, a.n, a.want);
     a.T0 = p.T0, a.T1 = p.T1, a.T = p.T, a.tps = p.tps, a.S = p.S;
-    // dyn: (sink_len, window_len) = the full cache here; the grid covers the largest plan of any fill level and every
-    // workgroup replans from the device state (workgroups of splits >= its S exit)
-    a.state = state;
-    a.sstride = state && state_rows ? 4 : 0;
-    a.ns = (int)sink_k->shape[2];
-    a.Sw = state ? (int)max_splits(a.B, a.Hkv, a.nrb, sink_len + window_len + a.n) : a.S;
-    a.scale_log2 = scale * kLog2e;
-    a.commit = commit ? 1 : 0;
+    // device state: (sink_len, window_len) = the full cache here; the grid covers the largest plan of any fill level and
+    // every workgroup replans from its state row (workgroups of splits >= its S exit)
+    a.Sw = c.state ? (int)max_splits(a.B, a.Hkv, a.nrb, c.sink_len + c.window_len + a.n) : a.S;
     const size_t rows = (size_t)a.B * a.Hkv * a.R;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    a.Mp = reinterpret_cast<float*>(workspace);
-    a.Lp = reinterpret_cast<float*>((char*)workspace + al(rows * a.Sw * sizeof(float)));
-    a.Op = reinterpret_cast<float*>((char*)workspace + 2 * al(rows * a.Sw * sizeof(float)));
+    a.Mp = reinterpret_cast<float*>(c.workspace);
+    a.Lp = reinterpret_cast<float*>((char*)c.workspace + al256(rows * a.Sw * sizeof(float)));
+    a.Op = reinterpret_cast<float*>((char*)c.workspace + 2 * al256(rows * a.Sw * sizeof(float)));
     if ((int64_t)a.B * a.Hkv * a.Sw * a.nrb >= (1ll << 31) || cdiv64((int64_t)rows, 4) >= (1ll << 31) - 65536) {
         set_error("decode_multi: grid too large");
         return SFA_ERR_UNSUPPORTED;
     }
-    const int dt = q->dtype;
-    const bool mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(flags & SFA_FLAG_FORCE_GENERIC);
-    const char* dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
-    int st;
-    if (dt == SFA_DTYPE_F32) st = launch_rest<float>(a, false, stream);
-    else if (dt == SFA_DTYPE_F16) st = launch_rest<f16_t>(a, mfma, stream);
-    else st = launch_rest<bf16_t>(a, mfma, stream);
+    bool mfma;
+    const char* dname;
+    const int st = launch_dtype(c, a, nullptr, &mfma, &dname);
     if (st) return st;
-    const char* fam = parent ? "tree" : "multi";
-    if (state) {
-        const char* dyn = slots ? "_slots" : state_rows ? "_rows" : "_dyn";
-        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d%s%s", fam, dname, a.D, a.nrb, dyn, commit ? "_commit" : "");
-        else set_path("decode_%s_f32_%s_d%d%s%s", fam, dname, a.D, dyn, commit ? "_commit" : "");
+    const char* fam = c.parent ? "tree" : "multi";
+    const char* cm = c.commit ? "_commit" : "";
+    if (c.state) {
+        const char* dyn = c.slots ? "_slots" : c.mode == RingState::Rows ? "_rows" : "_dyn";
+        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d%s%s", fam, dname, a.D, a.nrb, dyn, cm);
+        else set_path("decode_%s_f32_%s_d%d%s%s", fam, dname, a.D, dyn, cm);
     } else {
-        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_s%d%s", fam, dname, a.D, a.nrb, a.S, commit ? "_commit" : "");
-        else set_path("decode_%s_f32_%s_d%d_s%d%s", fam, dname, a.D, a.S, commit ? "_commit" : "");
+        if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_s%d%s", fam, dname, a.D, a.nrb, a.S, cm);
+        else set_path("decode_%s_f32_%s_d%d_s%d%s", fam, dname, a.D, a.S, cm);
     }
     return SFA_OK;
 }
@@ -1225,41 +1236,6 @@ RaggedGeom ragged_geom(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_
     return g;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <typename T>
-int launch_ragged(const MultiArgs& a, const RaggedArgs& rg, bool mfma, hipStream_t stream) {
-    int st = SFA_OK;
-    const int64_t rows = (int64_t)a.Hkv * rg.T * a.G;
-    if (mfma) {
-        if constexpr (sizeof(T) == 2) {
-            const dim3 grid((unsigned)((int64_t)a.Hkv * a.Sw * a.nrb));
-            switch (a.D) {
-                case 64: multi_split_mfma_kernel<T, 64, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
-                case 80: multi_split_mfma_kernel<T, 80, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
-                case 96: multi_split_mfma_kernel<T, 96, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
-                default: multi_split_mfma_kernel<T, 128, true, false, true, true><<<grid, kWaves * 64, 0, stream>>>(a, rg); break;
-            }
-            st = launch_status("decode_multi_mfma_ragged");
-        }
-    } else {
-        const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
-        multi_split_f32_kernel<T, true, false, true, true><<<grid, 256, 0, stream>>>(a, rg);
-        st = launch_status("decode_multi_f32_ragged");
-    }
-    if (st) return st;
-    const int nred = (int)cdiv64(rows, 4);
-    const int64_t ncommit = a.commit ? cdiv64((int64_t)a.Hkv * rg.T * (a.D * (int64_t)sizeof(T) / 16), 256) : 0;
-    multi_reduce_kernel<T, true, true, true><<<dim3((unsigned)(nred + ncommit)), 256, 0, stream>>>(a, nred, rg);
-    if ((st = launch_status("decode_multi_reduce_ragged"))) return st;
-    if (a.commit) {      // every reader of the state rows has finished: advance each named one by its n_i
-        ring_advance_ragged_kernel<<<dim3((unsigned)cdiv64(rg.n_seq, 256)), rg.n_seq < 256 ? rg.n_seq : 256, 0, stream>>>(
-            const_cast<int*>(a.state), rg, a.wc, a.slots, a.npool);
-        st = launch_status("ring_advance_ragged");
-    }
-    return st;
-}
-
 }  // namespace
 
 size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype) {
@@ -1271,76 +1247,42 @@ size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T
            al256((size_t)g.nrb * sizeof(int2)) + al256((size_t)T * sizeof(int));
 }
 
-int decode_ragged_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                         const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                         const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit, int32_t* state,
-                         const int32_t* slots, const int32_t* cu_q, int n_seq, void* workspace, float scale,
-                         unsigned flags, hipStream_t stream) {
-    const int64_t T = q->shape[2], ns = sink_k->shape[2], Wc = window_k->shape[2];
-    const RaggedGeom g = ragged_geom(n_seq, q->shape[1], k_new->shape[1], T, ns + Wc);
-    MultiArgs a;
-    a.parent = nullptr, a.pstride = 0, a.path = nullptr, a.pathstride = 0;   // no tree form
-    a.slots = slots, a.npool = (int)sink_k->shape[0];
-    a.q = make_view(q), a.sk = make_view(sink_k), a.sv = make_view(sink_v), a.wk = make_view(window_k);
-    a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new), a.o = make_view(o);
-    a.s_aux = s_aux;
-    a.B = 1;
-    a.Hkv = (int)k_new->shape[1];
-    a.G = (int)g.G;
-    a.D = (int)q->shape[3];
-    // n / R: the pack's bounds here; every workgroup (wave) replaces them with its sequence's n_i and G * n_i
-    a.n = (int)T, a.R = (int)(g.G * T);
+int decode_ragged_launch(const RingCall& c) {
+    const int64_t T = c.q->shape[2];
+    const RaggedGeom g = ragged_geom(c.n_seq, c.q->shape[1], c.k_new->shape[1], T, c.sink_len + c.window_len);
+    // B = 1; n / R: the pack's bounds here, every workgroup (wave) replaces them with its sequence's n_i and G * n_i
+    MultiArgs a = multi_args(c, true);
     a.nrb = (int)g.nrb;
-    a.sink_len = (int)ns, a.wl = (int)Wc, a.wp = 0, a.wc = (int)Wc;
     a.want = (int)want_splits(1, a.Hkv, g.nrb);     // one value for the call: a sequence's plan depends on the call's
-    a.T0 = a.T1 = a.T = a.tps = a.S = 0;            // shape and on its own (state row, n_i), not on its neighbours
-    a.state = state, a.sstride = 4, a.ns = (int)ns;
-    a.Sw = (int)g.Sw;
-    a.scale_log2 = scale * kLog2e;
-    a.commit = commit ? 1 : 0;
-    char* ws = (char*)workspace;
+    a.Sw = (int)g.Sw;                               // shape and on its own (state row, n_i), not on its neighbours
+    char* ws = (char*)c.workspace;
     a.Mp = reinterpret_cast<float*>(ws);
     a.Lp = reinterpret_cast<float*>(ws + al256((size_t)g.P * sizeof(float)));
     a.Op = reinterpret_cast<float*>(ws + 2 * al256((size_t)g.P * sizeof(float)));
     char* tab = ws + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)a.D * sizeof(float));
     int2* blk = reinterpret_cast<int2*>(tab);
     int* rowseq = reinterpret_cast<int*>(tab + al256((size_t)g.nrb * sizeof(int2)));
-    const RaggedArgs rg{cu_q, blk, rowseq, n_seq, (int)T};
+    const RaggedArgs rg{c.cu_q, blk, rowseq, c.n_seq, (int)T};
     if ((int64_t)a.Hkv * a.Sw * g.nrb >= (1ll << 31) || cdiv64(g.rows, 4) >= (1ll << 31) - 65536 ||
         cdiv64(g.rows, 4) + cdiv64((int64_t)a.Hkv * T * (a.D * 4 / 16), 256) >= (1ll << 31)) {
         set_error("decode_ragged: grid too large");
         return SFA_ERR_UNSUPPORTED;
     }
-    ragged_prep_kernel<<<1, 1024, 0, stream>>>(rg, blk, rowseq, a.G, a.nrb);
+    ragged_prep_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, a.G, a.nrb);
     int st;
     if ((st = launch_status("ragged_prep"))) return st;
-    const int dt = q->dtype;
-    const bool mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(flags & SFA_FLAG_FORCE_GENERIC);
-    const char* dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
-    if (dt == SFA_DTYPE_F32) st = launch_ragged<float>(a, rg, false, stream);
-    else if (dt == SFA_DTYPE_F16) st = launch_ragged<f16_t>(a, rg, mfma, stream);
-    else st = launch_ragged<bf16_t>(a, rg, mfma, stream);
-    if (st) return st;
-    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s", dname, a.D, a.nrb, commit ? "_commit" : "");
-    else set_path("decode_multi_f32_%s_d%d_ragged%s", dname, a.D, commit ? "_commit" : "");
+    bool mfma;
+    const char* dname;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
+    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s", dname, a.D, a.nrb, c.commit ? "_commit" : "");
+    else set_path("decode_multi_f32_%s_d%d_ragged%s", dname, a.D, c.commit ? "_commit" : "");
     return SFA_OK;
 }
 
-int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream, bool rows,
-                           const int32_t* path, int64_t path_bstride, const int32_t* slots) {
-    MultiArgs a{};
-    a.path = path, a.pathstride = (int)path_bstride;
-    a.slots = slots, a.npool = (int)window_k->shape[0];
-    a.wk = make_view(window_k), a.wv = make_view(window_v), a.kn = make_view(k_new), a.vn = make_view(v_new);
-    a.B = (int)k_new->shape[0];
-    a.Hkv = (int)k_new->shape[1];
-    a.n = (int)k_new->shape[2];
-    a.D = (int)k_new->shape[3];
-    a.wc = (int)window_k->shape[2];
-    a.state = state;
-    a.sstride = rows ? 4 : 0;
-    const int es = dtype_size(k_new->dtype);
+int ring_commit_dyn_launch(const RingCall& c) {
+    const MultiArgs a = multi_args(c, false);
+    const bool rows = c.mode == RingState::Rows;
+    const int es = dtype_size(c.k_new->dtype);
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
     const int64_t nblk = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)es / 16), 256);
     if (nblk >= (1ll << 31)) {
@@ -1349,16 +1291,17 @@ int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_
     }
     int st;
     if (nblk > 0) {
-        if (slots && path) ring_commit_slots_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
-        else if (slots) ring_commit_slots_kernel<false><<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
-        else if (path) ring_commit_path_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
-        else ring_commit_kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(a, count, es);
-        if ((st = launch_status(path ? "ring_commit_path" : "ring_commit"))) return st;
+        const dim3 grid((unsigned)nblk);
+        if (c.slots && c.path) ring_commit_slots_kernel<true><<<grid, 256, 0, c.stream>>>(a, c.count, es);
+        else if (c.slots) ring_commit_slots_kernel<false><<<grid, 256, 0, c.stream>>>(a, c.count, es);
+        else if (c.path) ring_commit_path_kernel<<<grid, 256, 0, c.stream>>>(a, c.count, es);
+        else ring_commit_kernel<<<grid, 256, 0, c.stream>>>(a, c.count, es);
+        if ((st = launch_status(c.path ? "ring_commit_path" : "ring_commit"))) return st;
     }
     // after every reader of the state
-    if ((st = launch_advance(state, count, a.n, a.wc, a.B, rows, stream, slots, a.npool))) return st;
-    if (path) set_path(slots ? "ring_commit_path_slots" : rows ? "ring_commit_path_rows" : "ring_commit_path_dyn");
-    else set_path(slots ? "ring_commit_slots" : rows ? "ring_commit_rows" : "ring_commit_dyn");
+    if ((st = launch_advance(a, c.count, nullptr, c.stream))) return st;
+    if (c.path) set_path(c.slots ? "ring_commit_path_slots" : rows ? "ring_commit_path_rows" : "ring_commit_path_dyn");
+    else set_path(c.slots ? "ring_commit_slots" : rows ? "ring_commit_rows" : "ring_commit_dyn");
     return SFA_OK;
 }
 

@@ -10,8 +10,8 @@ int fwd_generic(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, c
 // consts (optional, 16-bit tensors with 16-byte aligned rows only): [B, Hq, 2, N] row constants of the wave-specialised
 // dK/dV kernel, written in the same pass
 int bwd_preprocess(const sfa_tensor* o, const sfa_tensor* d_o, const float* lse, const float* s_aux, float* delta,
-                   float* dsaux_part, float* ds_aux, const Problem& p, hipStream_t stream, float* consts = nullptr,
-                   float lse_factor = 0.f);
+                   float* dsaux_part, float* ds_aux, const Problem& p, hipStream_t stream, float* consts,
+                   float lse_factor);
 bool bwd_preprocess_vectorised(const sfa_tensor* o, const sfa_tensor* d_o, const Problem& p);   // can it emit consts?
 int64_t bwd_preprocess_nblk(int64_t N);
 int bwd_generic(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* d_o,
@@ -30,12 +30,50 @@ size_t bwd_mfma_workspace_bytes(const Problem& p, int dtype, unsigned flags);
 int bwd_mfma(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* d_o,
              const float* lse, const float* delta, const sfa_tensor* dq, const sfa_tensor* dk,
              const sfa_tensor* dv, void* workspace, const Problem& p, unsigned flags, hipStream_t stream,
-             bool consts_ready = false);
+             bool consts_ready);
 // SFA_ERR_UNSUPPORTED (message set) for a call bwd_mfma would refuse, SFA_OK otherwise: asked before anything is launched
 int bwd_mfma_refused(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, const sfa_tensor* d_o,
                      const sfa_tensor* dq, const sfa_tensor* dk, const sfa_tensor* dv, const Problem& p);
 bool bwd_mfma_wants_consts();   // the default dK/dV kernels read the row constants from the head of the workspace
 float bwd_mfma_lse_factor(const Problem& p, unsigned flags);   // ... whose first row is -LSE * this factor (follows the dK/dV kernel choice)
+
+// One call on the sink + ring cache, as every launcher below takes it: named fields, a part that a call does not have is
+// null / zero.  An entry point of sfa_api.hip fills the fields its signature provides; the arguments are checked there.
+enum class RingState {
+    Host,     // {sink_len, window_len, write_pos} below are the state
+    Shared,   // `state` = device {sink_len, window_len, write_pos}, one row for the whole batch (the *_dyn calls)
+    Rows,     // `state` = device rows [B][4] {sink_len, window_len, write_pos, seen}, one per sequence (*_rows, *_slots)
+};
+struct RingCall {
+    // q / o [B, H_q, n, D], the cache buffers [B or S, H_kv, ns or Wc, D], the chunk k_new / v_new [B, H_kv, n, D].
+    // sfa_decode has one key segment: sink_k / sink_v with window_len = 0
+    const sfa_tensor *q, *sink_k, *sink_v, *window_k, *window_v, *k_new, *v_new, *o;
+    const float* s_aux;
+    float scale;
+    unsigned flags;
+    hipStream_t stream;
+    void* workspace;
+    size_t workspace_bytes;
+    int commit;                  // store the chunk and advance the state after the attention (never with `parent`)
+    RingState mode;
+    // Host: the state.  Shared / Rows: the FULL cache (every sink row, every ring slot, write_pos 0) - launch geometry
+    // and workspace cover every fill level, each workgroup reads its row of `state` and replans
+    int64_t sink_len, window_len, write_pos;
+    int32_t* state;
+    // slot call (Rows): the buffers are a pool of S rows, batch row b (sequence i of a pack) works on cache row and
+    // state row slots[b]; a value outside [0, S) marks an inactive row
+    const int32_t* slots;
+    // tree chunk (n <= 64): parent[b * parent_bstride + u] in [-1, u); stride 0 = one tree shared by the batch
+    const int32_t* parent;
+    int64_t parent_bstride;
+    // path commit: chunk token path[b * path_bstride + j] is the j-th one stored
+    const int32_t* path;
+    int64_t path_bstride;
+    const int32_t* count;        // commit calls: clamp(count, 0, n) tokens are stored (one value; Rows: B); null = all n
+    // packed call: q / k_new / v_new / o are [1, H, T, D], sequence i = rows [cu_q[i], cu_q[i + 1]) on slot slots[i]
+    const int32_t* cu_q;
+    int n_seq;
+};
 
 // sfa_decode.hip
 struct DecodePlan {
@@ -48,45 +86,25 @@ struct DecodePlan {
 // int32 arrival counters of the one-pass decode, at the start of the decode workspace
 inline size_t decode_counter_bytes(int64_t B, int64_t Hkv) { return (((size_t)(B * Hkv + 1) * sizeof(int)) + 255) & ~(size_t)255; }
 int decode_plan(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nkv, int64_t D, int dtype, DecodePlan* plan);
-// keys = rows [0, n1) of (k, v) followed by rows [0, n2) of (k2, v2); k2/v2 may be null when n2 == 0
-int decode_launch(const sfa_tensor* q, const sfa_tensor* k, const sfa_tensor* v, int64_t n1, const sfa_tensor* k2,
-                  const sfa_tensor* v2, int64_t n2, const sfa_tensor* o, const float* s_aux, void* workspace,
-                  float scale, const DecodePlan& plan, hipStream_t stream, const sfa_tensor* k_new = nullptr,
-                  const sfa_tensor* v_new = nullptr, int new_slot = -1, int* dyn_state = nullptr,
-                  bool one_pass = false, bool state_rows = false,    // state_rows: dyn_state = per-sequence rows [B][4]
-                  const int32_t* slots = nullptr);   // slot call: row b of q works on row slots[b] of the cache and the state
+// one query per row: keys = rows [0, sink_len) of the sink buffers followed by rows [0, window_len) of the ring; with
+// k_new / v_new the kernel first stores the token into ring slot write_pos (or the state's)
+int decode_launch(const RingCall& c, const DecodePlan& plan);
 
-// sfa_decode_multi.hip: several new tokens over the sink + ring cache (sfa_decode_ring_multi); arguments already checked
+// sfa_decode_multi.hip: several new tokens over the sink + ring cache; arguments already checked
 int decode_multi_check_head_dim(int64_t D, int dtype);
 size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D, int dtype);
-int decode_multi_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
-                        const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len, int64_t write_pos,
-                        const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
-                        int commit, void* workspace, float scale, unsigned flags, hipStream_t stream,
-                        int32_t* state = nullptr,    // dyn: sink_len / window_len = the full cache, write_pos = 0
-                        bool rows = false,           // state = per-sequence rows [B][4] (sfa_decode_ring_multi_rows)
-                        const int32_t* parent = nullptr,   // tree chunk (sfa_decode_ring_tree*, n <= 64, no commit)
-                        int64_t parent_bstride = 0,
-                        const int32_t* slots = nullptr);   // slot call (rows): the buffers are a pool, B = q's rows
+int decode_multi_launch(const RingCall& c);      // sfa_decode_ring_multi* / sfa_decode_ring_tree*
 
-// sfa_decode_ring_ragged_slots: a packed [1, H, T, D] step over a pool (sequence i = rows [cu_q[i], cu_q[i + 1]) on slot
-// slots[i]); arguments already checked.  Workspace: partials for T packed rows plus the tables of the preparation launch
+// sfa_decode_ring_ragged_slots.  Workspace: partials for T packed rows plus the tables of the preparation launch
 size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
-int decode_ragged_launch(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
-                         const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                         const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit, int32_t* state,
-                         const int32_t* slots, const int32_t* cu_q, int n_seq, void* workspace, float scale,
-                         unsigned flags, hipStream_t stream);
+int decode_ragged_launch(const RingCall& c);
 
-// sfa_ring_commit_dyn / _rows: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
-int ring_commit_dyn_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
-                           const sfa_tensor* v_new, const int32_t* count, int32_t* state, hipStream_t stream,
-                           bool rows = false, const int32_t* path = nullptr,   // path: sfa_ring_commit_path_*
-                           int64_t path_bstride = 0, const int32_t* slots = nullptr);   // slots: sfa_ring_commit*_slots
-// sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows
+// sfa_ring_commit*: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
+int ring_commit_dyn_launch(const RingCall& c);
+// sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows;
+// slots (null: sequence i -> cache row i): sequence i -> row slots[i] of a pool
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream,
-                            const int32_t* slots = nullptr);   // slots: sequence i -> row slots[i] of a pool
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots);
 
 }  // namespace sfa

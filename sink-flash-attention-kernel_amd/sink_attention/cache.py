@@ -18,6 +18,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from .decode_kernel import rows16
+
 try:  # the HF base classes are optional, exactly as in the reference (cache.py:20-26)
     from transformers.cache_utils import Cache as _HFCache, CacheLayerMixin as _HFLayer
     _HAS_HF = True
@@ -143,7 +145,6 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def _ring_step(self, q, k_new, v_new, new_len, pos, s_aux):
         """sfa_decode_ring_step with the per-layer constants (buffer descriptors, workspace) built once: at B=1 the
         step is host-bound, so the Python work per token is kept to the four per-call descriptors."""
-        import math
         from . import _native as N
         st = getattr(self, "_step_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
@@ -153,25 +154,17 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             if q.dtype != self.window_k.dtype or q.dtype not in N.SFA_DTYPE:
                 raise TypeError("q and the cache buffers must share one dtype")
             assert _one == 1 and H_q % H_kv == 0 and (D * q.element_size()) % 16 == 0
-            lib = N.lib()
-            ws_bytes = lib.sfa_decode_workspace_bytes(B, H_q, H_kv, self.num_sink + self.window_size, D,
-                                                      N.SFA_DTYPE[q.dtype])
-            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
-                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
-                      # owned across calls and zeroed once: the one-pass decode keeps its arrival counters there
-                      ws=torch.zeros((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
-            self._step_state = st
+            st = self._step_consts(key, q)
         N.require_gpu(q, k_new, v_new, s_aux)
         if k_new.dtype != q.dtype or v_new.dtype != q.dtype or k_new.shape != v_new.shape:
             raise TypeError("k_new / v_new must be [B, H_kv, 1, D] tensors of q's dtype")
         q, k_new, v_new = N.unit_inner(q.detach()), N.unit_inner(k_new.detach()), N.unit_inner(v_new.detach())
-        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        s_aux_f, aux = self._aux(s_aux)
         out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
             rc = st["lib"].sfa_decode_ring_step(N.desc(q), sk, sv, self.sink_len, wk, wv, new_len, pos, N.desc(k_new),
-                                                N.desc(v_new), N.desc(out),
-                                                s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                N.desc(v_new), N.desc(out), aux,
                                                 st["ws"].data_ptr(), st["ws"].numel(), st["scale"],
                                                 self._decode_flags(N), N.stream_ptr(q.device))
         N.check(rc, "sfa_decode_ring_step")
@@ -202,7 +195,6 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def _ring_multi(self, q, k_new, v_new, s_aux, commit, tree=None):
         """sfa_decode_ring_multi with the per-layer constants (buffer descriptors, workspace for the full cache) built once
         per chunk shape, as _ring_step does."""
-        import math
         from . import _native as N
         if not (self.is_initialized and self.prefilled):
             raise ValueError("extend_attention / extend_step need a prefilled cache: the first chunk is a prefill "
@@ -215,49 +207,73 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                "fallback")
         B, H_q, n, D = q.shape
         H_kv = self.sink_k.shape[1]
-        if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
-            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = {(B, H_kv, n, D)}, got {tuple(k_new.shape)}")
-        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
-            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+        self._check_chunk(N, q, k_new, v_new, None, "[B, H_kv, n, D]")
         st = getattr(self, "_multi_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
         if st is None or st["key"] != key:
-            lib = N.lib()
-            ws_bytes = lib.sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
-                                                            N.SFA_DTYPE[q.dtype])
+            ws_bytes = N.lib().sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
+                                                                N.SFA_DTYPE[q.dtype])
             if ws_bytes == 0:
                 raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB")
-            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
-                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
-                      ws=torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
-            self._multi_state = st
-
-        def rows16(t):
-            t = N.unit_inner(t.detach())
-            es = t.element_size()
-            if t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3)):
-                t = t.contiguous()
-            return t
-
+            st = self._call_consts("_multi_state", key, ws_bytes, False, q)
         q, k_new, v_new = rows16(q), rows16(k_new), rows16(v_new)
-        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        s_aux_f, aux = self._aux(s_aux)
         out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
             if tree is not None:
                 rc = st["lib"].sfa_decode_ring_tree(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
-                                                    self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                                    s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                    self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out), aux,
                                                     tree[0].data_ptr(), tree[1], st["ws"].data_ptr(), st["ws"].numel(),
                                                     st["scale"], 0, N.stream_ptr(q.device))
             else:
                 rc = st["lib"].sfa_decode_ring_multi(N.desc(q), sk, sv, self.sink_len, wk, wv, self.window_len,
-                                                     self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                                     s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                     self.write_pos, N.desc(k_new), N.desc(v_new), N.desc(out), aux,
                                                      1 if commit else 0, st["ws"].data_ptr(), st["ws"].numel(),
                                                      st["scale"], 0, N.stream_ptr(q.device))
         N.check(rc, "sfa_decode_ring_tree" if tree is not None else "sfa_decode_ring_multi")
         return out
+
+    def _call_consts(self, attr, key, ws_bytes, zeroed, q):
+        """The per-layer constants of one family of calls, built once per ``key`` and kept in ``self.<attr>``: the
+        library handle, the softmax scale, the descriptors of the four cache buffers and a workspace of ``ws_bytes``
+        (zero-filled if ``zeroed``) on q's device."""
+        import math
+        from . import _native as N
+        st = dict(key=key, lib=N.lib(), scale=1.0 / math.sqrt(q.shape[3]),
+                  descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
+                  ws=(torch.zeros if zeroed else torch.empty)((max(int(ws_bytes), 256),), device=q.device,
+                                                              dtype=torch.uint8))
+        setattr(self, attr, st)
+        return st
+
+    def _step_consts(self, key, q):
+        """``_step_state``, shared by ``decode_step`` and ``decode_step_dyn``: the workspace is owned across calls and
+        zeroed once, the one-pass decode keeps its arrival counters there."""
+        from . import _native as N
+        B, H_q, _one, D = q.shape
+        ws_bytes = N.lib().sfa_decode_workspace_bytes(B, H_q, self.sink_k.shape[1], self.num_sink + self.window_size, D,
+                                                      N.SFA_DTYPE[q.dtype])
+        return self._call_consts("_step_state", key, ws_bytes, True, q)
+
+    def _check_chunk(self, N, q, k_new, v_new, out, layout):
+        """Shape of ``k_new`` / ``v_new`` against q and the cache (``layout``: how the message spells it), one dtype
+        for all of them, and ``out`` where the caller brings one."""
+        shape = (q.shape[0], self.sink_k.shape[1], q.shape[2], q.shape[3])
+        if k_new.shape != shape or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be {layout} = {shape}, got {tuple(k_new.shape)}")
+        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
+            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
+        if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
+            raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
+
+    @staticmethod
+    def _aux(s_aux):
+        """``s_aux`` as the fp32 tensor the kernels read (the caller holds it across the call) and its pointer."""
+        if s_aux is None:
+            return None, None
+        f = s_aux.detach().contiguous().float()
+        return f, f.data_ptr()
 
     one_pass = False     # opt-in: SFA_FLAG_DECODE_ONE_PASS (last-arriver fold inside the split kernel, one launch)
 
@@ -324,7 +340,6 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         (``sfa_decode_ring_step_rows``): every row stores its token at its own slot and attends over its own keys.
         ``slots`` (``sfa_decode_ring_step_slots``, see ``init_pool``): batch row b works on cache row ``slots[b]``; a row
         with ``slots[b] = -1`` is inactive (zeros in ``out``, nothing stored, no state moves)."""
-        import math
         from . import _native as N
         slots = self._slots_arg(slots, q.shape[0], writes=True)
         st = getattr(self, "_dev_state", None)
@@ -332,41 +347,27 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ss = getattr(self, "_step_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
         if ss is None or ss["key"] != key:
-            B, H_q, _one, D = q.shape
-            lib = N.lib()
-            ws_bytes = lib.sfa_decode_workspace_bytes(B, H_q, self.sink_k.shape[1], self.num_sink + self.window_size, D,
-                                                      N.SFA_DTYPE[q.dtype])
-            ss = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
-                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
-                      # owned across calls and zeroed once: the one-pass decode keeps its arrival counters there
-                      ws=torch.zeros((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
-            self._step_state = ss
+            ss = self._step_consts(key, q)
         N.require_gpu(q, k_new, v_new, s_aux)
         if k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype != self.window_k.dtype:
             raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
         q, k_new, v_new = N.unit_inner(q.detach()), N.unit_inner(k_new.detach()), N.unit_inner(v_new.detach())
-        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        s_aux_f, aux = self._aux(s_aux)
         if out is None:
             out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = ss["descs"]
+        lib = ss["lib"]
         if slots is not None:
             N.require_gpu(slots)
-            with torch.cuda.device(q.device):
-                rc = ss["lib"].sfa_decode_ring_step_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
-                                                          N.desc(out),
-                                                          s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                                          st.data_ptr(), slots.data_ptr(), ss["ws"].data_ptr(),
-                                                          ss["ws"].numel(), ss["scale"], self._decode_flags(N),
-                                                          N.stream_ptr(q.device))
-            N.check(rc, "sfa_decode_ring_step_slots")
-            return out
+            fn, name, tail = lib.sfa_decode_ring_step_slots, "sfa_decode_ring_step_slots", (slots.data_ptr(),)
+        elif self._per_seq:
+            fn, name, tail = lib.sfa_decode_ring_step_rows, "sfa_decode_ring_step_rows", ()
+        else:
+            fn, name, tail = lib.sfa_decode_ring_step_dyn, "sfa_decode_ring_step_dyn", ()
         with torch.cuda.device(q.device):
-            fn = ss["lib"].sfa_decode_ring_step_rows if self._per_seq else ss["lib"].sfa_decode_ring_step_dyn
-            rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                    s_aux_f.data_ptr() if s_aux_f is not None else None, st.data_ptr(),
-                    ss["ws"].data_ptr(), ss["ws"].numel(), ss["scale"],
-                    self._decode_flags(N), N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_step_rows" if self._per_seq else "sfa_decode_ring_step_dyn")
+            rc = fn(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, st.data_ptr(), *tail,
+                    ss["ws"].data_ptr(), ss["ws"].numel(), ss["scale"], self._decode_flags(N), N.stream_ptr(q.device))
+        N.check(rc, name)
         return out
 
     # ---------------------------- several new tokens with the state on the device (capturable speculative step)
@@ -399,49 +400,21 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         return self._commit_dyn(k_new, v_new, count, None, slots)
 
     def _commit_dyn(self, k_new, v_new, count, path, slots=None):
+        """sfa_ring_commit[_path]_{dyn,rows,slots}: one count for the shared state, B of them for per-sequence rows."""
         from . import _native as N
         slots = self._slots_arg(slots, k_new.shape[0], writes=True)
         st = self._require_dyn("commit_path_dyn" if path is not None else "commit_dyn")
         if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
                 or count.dtype == torch.bool:
             raise TypeError("count must be an integer tensor")
-        if self._per_seq:
-            return self._commit_rows(k_new, v_new, count, st, path, slots)
-        if count.numel() != 1:
-            raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
-        N.require_gpu(k_new, v_new, count, self.window_k)
-        B, H_kv, _w, D = self.window_k.shape
-        if k_new.dim() != 4 or k_new.shape[:2] != (B, H_kv) or k_new.shape[3] != D or v_new.shape != k_new.shape \
-                or k_new.shape[2] < 1:
-            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = [{B}, {H_kv}, n, {D}], got {tuple(k_new.shape)}")
-        if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
-            raise TypeError("k_new / v_new must have the cache buffers' dtype")
-        k_new, v_new = self._rows16(k_new), self._rows16(v_new)
-        cnt = count.reshape(1)
-        if cnt.dtype != torch.int32:
-            cnt = cnt.to(torch.int32)      # a cast kernel: capturable
-        wk, wv = self._ring_descs()
-        if path is not None:
-            from .decode_kernel import tree_path_dev
-            pt, pstride = tree_path_dev(path, B, k_new.shape[2], k_new.device)
-            with torch.cuda.device(k_new.device):
-                rc = N.lib().sfa_ring_commit_path_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), pt.data_ptr(),
-                                                      pstride, st.data_ptr(), N.stream_ptr(k_new.device))
-            N.check(rc, "sfa_ring_commit_path_dyn")
-            return
-        with torch.cuda.device(k_new.device):
-            rc = N.lib().sfa_ring_commit_dyn(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
-                                             N.stream_ptr(k_new.device))
-        N.check(rc, "sfa_ring_commit_dyn")
-
-    def _commit_rows(self, k_new, v_new, count, st, path=None, slots=None):
-        from . import _native as N
         B, H_kv, _w, D = self.window_k.shape
         if slots is not None:           # the buffers are the pool: B is the chunk's
             B = slots.numel()
-        if count.numel() != B:
+        if self._per_seq and count.numel() != B:
             raise ValueError(f"count must hold B = {B} values in per-sequence mode (one per sequence), "
                              f"got shape {tuple(count.shape)}")
+        if not self._per_seq and count.numel() != 1:
+            raise ValueError(f"count must hold one value, got shape {tuple(count.shape)}")
         N.require_gpu(k_new, v_new, count, self.window_k, slots)
         if k_new.dim() != 4 or k_new.shape[:2] != (B, H_kv) or k_new.shape[3] != D or v_new.shape != k_new.shape \
                 or k_new.shape[2] < 1:
@@ -449,33 +422,22 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
             raise TypeError("k_new / v_new must have the cache buffers' dtype")
         k_new, v_new = self._rows16(k_new), self._rows16(v_new)
-        cnt = count.reshape(B)
+        cnt = count.reshape(B if self._per_seq else 1)
         if cnt.dtype != torch.int32:
             cnt = cnt.to(torch.int32)      # a cast kernel: capturable
-        cnt = cnt.contiguous()
+        if self._per_seq:
+            cnt = cnt.contiguous()
         wk, wv = self._ring_descs()
+        mode = "slots" if slots is not None else "rows" if self._per_seq else "dyn"
+        name, mid = "sfa_ring_commit_" + mode, ()
         if path is not None:
             from .decode_kernel import tree_path_dev
             pt, pstride = tree_path_dev(path, B, k_new.shape[2], k_new.device)
-            with torch.cuda.device(k_new.device):
-                if slots is not None:
-                    rc = N.lib().sfa_ring_commit_path_slots(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
-                                                            pt.data_ptr(), pstride, st.data_ptr(), slots.data_ptr(),
-                                                            N.stream_ptr(k_new.device))
-                else:
-                    rc = N.lib().sfa_ring_commit_path_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(),
-                                                           pt.data_ptr(), pstride, st.data_ptr(),
-                                                           N.stream_ptr(k_new.device))
-            N.check(rc, "sfa_ring_commit_path_slots" if slots is not None else "sfa_ring_commit_path_rows")
-            return
+            name, mid = "sfa_ring_commit_path_" + mode, (pt.data_ptr(), pstride)
         with torch.cuda.device(k_new.device):
-            if slots is not None:
-                rc = N.lib().sfa_ring_commit_slots(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
-                                                   slots.data_ptr(), N.stream_ptr(k_new.device))
-            else:
-                rc = N.lib().sfa_ring_commit_rows(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), st.data_ptr(),
-                                                  N.stream_ptr(k_new.device))
-        N.check(rc, "sfa_ring_commit_slots" if slots is not None else "sfa_ring_commit_rows")
+            rc = getattr(N.lib(), name)(wk, wv, N.desc(k_new), N.desc(v_new), cnt.data_ptr(), *mid, st.data_ptr(),
+                                        *(() if slots is None else (slots.data_ptr(),)), N.stream_ptr(k_new.device))
+        N.check(rc, name)
 
     # ------------------------------- tree-structured speculative verify (Medusa / EAGLE / SpecInfer draft trees)
     def extend_attention_tree(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, parent,
@@ -724,14 +686,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             raise RuntimeError(f"{what} needs the state on the device: call enable_device_state() first")
         return st
 
-    @staticmethod
-    def _rows16(t):
-        from . import _native as N
-        t = N.unit_inner(t.detach())
-        es = t.element_size()
-        if t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3)):
-            t = t.contiguous()
-        return t
+    _rows16 = staticmethod(rows16)
 
     def _ring_descs(self):
         key = (self.window_k.data_ptr(), self.window_v.data_ptr())
@@ -745,7 +700,6 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def _ring_multi_dyn(self, q, k_new, v_new, s_aux, out, commit, tree=None, slots=None):
         """sfa_decode_ring_multi_dyn with the per-layer constants (buffer descriptors, a workspace for the full cache plus
         the chunk) built once per chunk shape, as _ring_multi does."""
-        import math
         from . import _native as N
         slots = self._slots_arg(slots, q.shape[0], writes=bool(commit))
         dev_state = self._require_dyn("extend_attention_tree_dyn" if tree is not None else
@@ -753,58 +707,29 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k, slots)
         B, H_q, n, D = q.shape
         H_kv = self.sink_k.shape[1]
-        if k_new.shape != (B, H_kv, n, D) or v_new.shape != k_new.shape:
-            raise ValueError(f"k_new / v_new must be [B, H_kv, n, D] = {(B, H_kv, n, D)}, got {tuple(k_new.shape)}")
-        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
-            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
-        if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
-            raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
+        self._check_chunk(N, q, k_new, v_new, out, "[B, H_kv, n, D]")
         st = getattr(self, "_multi_dyn_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, q.dtype)
         if st is None or st["key"] != key:
-            lib = N.lib()
-            ws_bytes = lib.sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
-                                                            N.SFA_DTYPE[q.dtype])
+            ws_bytes = N.lib().sfa_decode_multi_workspace_bytes(B, H_q, H_kv, n, self.num_sink + self.window_size + n, D,
+                                                                N.SFA_DTYPE[q.dtype])
             if ws_bytes == 0:
                 raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB")
-            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
-                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
-                      ws=torch.empty((max(int(ws_bytes), 256),), device=q.device, dtype=torch.uint8))
-            self._multi_dyn_state = st
+            st = self._call_consts("_multi_dyn_state", key, ws_bytes, False, q)
         q, k_new, v_new = self._rows16(q), self._rows16(k_new), self._rows16(v_new)
-        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        s_aux_f, aux = self._aux(s_aux)
         if out is None:
             out = torch.empty((B, H_q, n, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
+        mode = "_slots" if slots is not None else "_rows" if self._per_seq else "_dyn"
+        if tree is not None:
+            name, mid = "sfa_decode_ring_tree" + mode, (tree[0].data_ptr(), tree[1])
+        else:
+            name, mid = "sfa_decode_ring_multi" + mode, (1 if commit else 0,)
         with torch.cuda.device(q.device):
-            if slots is not None and tree is not None:
-                name = "sfa_decode_ring_tree_slots"
-                rc = st["lib"].sfa_decode_ring_tree_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
-                                                          N.desc(out),
-                                                          s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                                          tree[0].data_ptr(), tree[1], dev_state.data_ptr(),
-                                                          slots.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
-                                                          st["scale"], 0, N.stream_ptr(q.device))
-            elif slots is not None:
-                name = "sfa_decode_ring_multi_slots"
-                rc = st["lib"].sfa_decode_ring_multi_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
-                                                           N.desc(out),
-                                                           s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
-                                                           st["ws"].data_ptr(), st["ws"].numel(), st["scale"], 0,
-                                                           N.stream_ptr(q.device))
-            elif tree is not None:
-                name = "sfa_decode_ring_tree_rows" if self._per_seq else "sfa_decode_ring_tree_dyn"
-                rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                              s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                              tree[0].data_ptr(), tree[1], dev_state.data_ptr(), st["ws"].data_ptr(),
-                                              st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
-            else:
-                name = "sfa_decode_ring_multi_rows" if self._per_seq else "sfa_decode_ring_multi_dyn"
-                rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out),
-                                              s_aux_f.data_ptr() if s_aux_f is not None else None,
-                                              1 if commit else 0, dev_state.data_ptr(), st["ws"].data_ptr(),
-                                              st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
+            rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux,
+                                          *mid, dev_state.data_ptr(), *(() if slots is None else (slots.data_ptr(),)),
+                                          st["ws"].data_ptr(), st["ws"].numel(), st["scale"], 0, N.stream_ptr(q.device))
         N.check(rc, name)
         return out
 
@@ -828,7 +753,6 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``slots``: device int32 tensors (never read on the host: the call is graph-capturable and a captured step replays
         at any mix of lengths by rewriting them in place) or host lists, which are checked.  The first chunk of a prompt
         is still a ``prefill_slots`` (it writes the sinks); this call continues an admitted sequence."""
-        import math
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
@@ -836,12 +760,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             raise ValueError(f"q must be a packed [1, H_q, T, D] tensor, got {tuple(q.shape)}")
         _one, H_q, T, D = q.shape
         H_kv = self.sink_k.shape[1]
-        if k_new.shape != (1, H_kv, T, D) or v_new.shape != k_new.shape:
-            raise ValueError(f"k_new / v_new must be [1, H_kv, T, D] = {(1, H_kv, T, D)}, got {tuple(k_new.shape)}")
-        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
-            raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
-        if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
-            raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
+        self._check_chunk(N, q, k_new, v_new, out, "[1, H_kv, T, D]")
         cu = self._cu_arg(cu_q, T, q.device)
         n_seq = cu.numel() - 1
         slots = self._slots_arg(slots, n_seq, writes=bool(commit))
@@ -849,25 +768,20 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         st = getattr(self, "_ragged_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype)
         if st is None or st["key"] != key:
-            lib = N.lib()
-            ws_bytes = lib.sfa_decode_ragged_workspace_bytes(n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D,
-                                                             N.SFA_DTYPE[q.dtype])
+            ws_bytes = N.lib().sfa_decode_ragged_workspace_bytes(n_seq, H_q, H_kv, T, self.num_sink + self.window_size,
+                                                                 D, N.SFA_DTYPE[q.dtype])
             if ws_bytes == 0:
                 raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB (H_q = {H_q} a multiple "
                                  f"of H_kv = {H_kv}, T >= 1)")
-            st = dict(key=key, lib=lib, scale=1.0 / math.sqrt(D),
-                      descs=[N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)],
-                      ws=torch.empty((int(ws_bytes),), device=q.device, dtype=torch.uint8))
-            self._ragged_state = st
+            st = self._call_consts("_ragged_state", key, ws_bytes, False, q)
         q, k_new, v_new = self._rows16(q), self._rows16(k_new), self._rows16(v_new)
-        s_aux_f = s_aux.detach().contiguous().float() if s_aux is not None else None
+        s_aux_f, aux = self._aux(s_aux)
         if out is None:
             out = torch.empty((1, H_q, T, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         with torch.cuda.device(q.device):
             rc = st["lib"].sfa_decode_ring_ragged_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
-                                                        N.desc(out),
-                                                        s_aux_f.data_ptr() if s_aux_f is not None else None,
+                                                        N.desc(out), aux,
                                                         1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
                                                         cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
                                                         st["scale"], 0, N.stream_ptr(q.device))

@@ -14,6 +14,16 @@ import torch
 from . import _native as N
 
 
+def rows16(t):
+    """``t`` as the kernels take it: unit last stride, 16-byte aligned base and batch / head / row strides (copied only
+    if it is not).  The one alignment fix-up of the package (``SinkCacheLayer._rows16``)."""
+    t = N.unit_inner(t.detach())
+    es = t.element_size()
+    if t.numel() and (t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3))):
+        t = t.contiguous()
+    return t
+
+
 def sink_decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                           s_aux: torch.Tensor = None) -> torch.Tensor:
     N.require_gpu(q, k, v, s_aux)
@@ -30,14 +40,7 @@ def sink_decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     assert row_bytes % 16 == 0 and row_bytes <= 1024, f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB"
     scale = 1.0 / math.sqrt(D)
 
-    def rows16(t):
-        t = N.unit_inner(t)
-        es = t.element_size()
-        if t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3)):
-            t = t.contiguous()
-        return t
-
-    q, k, v = rows16(q.detach()), rows16(k.detach()), rows16(v.detach())
+    q, k, v = rows16(q), rows16(k), rows16(v)
     s_aux_f = None
     if s_aux is not None:
         assert s_aux.shape == (H_q,), f"s_aux shape must be [H_q={H_q}], got {s_aux.shape}"
@@ -86,13 +89,6 @@ def sink_decode_attention_ring(q: torch.Tensor, sink_k: torch.Tensor, sink_v: to
         raise TypeError(f"unsupported dtype {q.dtype}")
     row_bytes = D * q.element_size()
     assert row_bytes % 16 == 0 and row_bytes <= 1024, f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB"
-
-    def rows16(t):
-        t = N.unit_inner(t.detach())
-        es = t.element_size()
-        if t.numel() and (t.data_ptr() % 16 or any((t.stride(i) * es) % 16 for i in range(3))):
-            t = t.contiguous()
-        return t
 
     fused = k_new is not None
     if fused:
@@ -235,12 +231,6 @@ def _ring_multi(q, sink_k, sink_v, sink_len, window_k, window_v, window_len, wri
     def aligned(t):
         es = t.element_size()
         return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(3))
-
-    def rows16(t):
-        t = N.unit_inner(t.detach())
-        if t.numel() and not aligned(t):
-            t = t.contiguous()
-        return t
 
     if commit:
         for t in (window_k, window_v):   # the reduce kernel writes the ring in place: no silent copies allowed here
