@@ -142,21 +142,37 @@ def test_dq_body_assembles_for_gfx950(dtype, persist):
     (1, 2, 1, 40, 40, 4, 1, "bf16", False, False),        # window of one key
     (1, 1, 1, 700, 700, 4, 192, "bf16", True, False),     # W >= 128: window-edge and causal-edge tiles take the typed bodies
     (1, 4, 1, 520, 650, 0, 256, "f16", False, False),     # the same with N_q < N_kv and no sinks
+    # tests/range_inputs.py staircase_up: the out-of-line rescale with 2^-16 <= alpha < 2^-8 in every wave, beside rows of
+    # the same wave that keep alpha = 1 (the spike above has ONE row with alpha ~ 2^-49, where O := 0 would pass as well)
+    (1, 4, 1, 300, 300, 4, 100, "bf16", True, "staircase"),
+    (1, 2, 2, 333, 333, 4, 150, "f16", True, "staircase"),
 ])
 def test_fwd_body_in_emulator_matches_oracle(B, Hq, Hkv, N, Nk, ns, W, dtype, aux, spike):
     g = torch.Generator().manual_seed(N + 2)
     td = torch.bfloat16 if dtype == "bf16" else torch.float16
     q = torch.randn(B, Hq, N, 128, generator=g).to(td)
     k, v = (torch.randn(B, Hkv, Nk, 128, generator=g).to(td) for _ in range(2))
-    if spike:    # rule 26 of the CDNA guide: the rescale branch needs an input that takes it (row maximum jumps by > 2^8)
+    if spike is True:    # rule 26 of the CDNA guide: the rescale branch needs an input that takes it (row maximum jumps by > 2^8)
         k[:, :, Nk - 40] = q[:, 0, N - 1] * 3
     sa = torch.randn(Hq, generator=g) * 0.5 if aux else None
+    if spike == "staircase":
+        q, k, v, sa = _staircase(B, Hq, Hkv, N, Nk, 128, ns, W, td, N + 2)
     o_ref, lse_ref = O.sink_attention_dense(q, k, v, ns, W, sa)
     o, lse = run_fwd(_prog(dtype, True, FwdGen), q, k, v, ns, W, sa, dtype, persist=True, n_wg=2)      # the work-list body
     assert (o.double() - o_ref).abs().max().item() < (1e-2 if dtype == "bf16" else 2e-3)
     fin = torch.isfinite(lse_ref)
     assert (lse.double()[fin] - lse_ref[fin]).abs().max().item() < 5e-3
     assert (lse[~fin] == float("-inf")).all()
+
+
+def _staircase(B, Hq, Hkv, N, Nk, D, ns, W, td, seed):
+    """staircase_up inputs of tests/range_inputs.py; the fp64 walk model must show mid-range rescales in every 64-row wave
+    that has a later tile, or the case would not test what it is here for"""
+    import range_inputs as R
+    inp = R.dense_range("staircase_up", B, Hq, Hkv, N, Nk, D, ns, W, td, seed)
+    cov = R.coverage(R.tile_walk(inp["q"], inp["k"], inp["v"], ns, W, inp["s_aux"])[2])
+    assert cov["mid"] >= 64 and cov["waves_mid"] == cov["waves"] > 0 and cov["waves_mixed"] == cov["waves"], cov
+    return inp["q"], inp["k"], inp["v"], inp["s_aux"]
 
 
 @pytest.mark.parametrize("n_wg", [1, 3])
@@ -206,6 +222,8 @@ def test_other_head_dims_in_emulator(D):
     (8, 2, 300, 64, 100, 3, 5, "f16", False, False),      # no s_aux (rows start from m = -inf), window not a tile multiple, two KV heads
     (4, 1, 260, 96, 64, 2, 2, "bf16", True, True),        # two tiles per item; a spiked key forces the out-of-line rescale
     (4, 1, 330, 64, 192, 4, 6, "bf16", True, False),      # four tiles per item (5-slot ring), one strip over the whole sequence
+    (4, 1, 400, 80, 128, 3, 3, "bf16", True, "staircase"),  # tests/range_inputs.py staircase_up: mid-range alpha between blocks
+    (4, 1, 330, 96, 128, 3, 2, "f16", True, "staircase"),
 ])
 def test_short_window_strip_forward_in_emulator(Hq, Hkv, N, D, W, NT, strip, dtype, aux, spike):
     """tools/asmgen/fwd_strip.py: strips of consecutive query tiles over a sliding K / V ring, double-buffered Q fragments,
@@ -217,9 +235,11 @@ def test_short_window_strip_forward_in_emulator(Hq, Hkv, N, D, W, NT, strip, dty
     td = torch.bfloat16 if dtype == "bf16" else torch.float16
     q = torch.randn(1, Hq, N, D, generator=g).to(td)
     k, v = (torch.randn(1, Hkv, N, D, generator=g).to(td) for _ in range(2))
-    if spike:
+    if spike is True:
         k[:, :, N - 30] = q[:, 0, N - 1] * 3
     sa = torch.randn(Hq, generator=g) * 0.5 if aux else None
+    if spike == "staircase":
+        q, k, v, sa = _staircase(1, Hq, Hkv, N, N, D, 0, W, td, N + D)
     prog = FwdStripGen(dtype, D=D, NT=NT).build()
     if os.path.exists(CLANG):
         ok, err = assemble(prog)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Randomised cross-check on the GPU: MFMA kernels against the exact-f32 kernels of the same library (and the
 N_q < N_kv / packed paths against their padded / per-sequence formulations) on random shapes.
-usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe]
+usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe|range]
 (skew: only shapes of the short-window dK/dV kernel - no sink keys, head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or
-packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn)"""
+packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn;
+--inputs=range: a random family of tests/range_inputs.py - logit staircases, a common offset - that moves the softmax reference)"""
 import os
 import random
 import sys
@@ -13,12 +14,13 @@ sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT, os.
 import torch
 
 import probe_inputs
+import range_inputs
 
 from sink_attention.sink_flash_attention import _sink_flash_attention_ex
 from sink_attention.varlen import sink_flash_attention_varlen
 
 inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
-assert inputs in ("randn", "probe"), inputs
+assert inputs in ("randn", "probe", "range"), inputs
 sys.argv = [a for a in sys.argv if not a.startswith("--inputs=")]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -31,6 +33,10 @@ def draw(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, cu=None):
     """q, k, v, dO on the GPU: randn, or the mask-edge probes of the same shapes"""
     if inputs == "probe":
         pr = probe_inputs.dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, rng.randrange(1 << 30), cu=cu)
+        return tuple(pr[x].cuda() for x in ("q", "k", "v", "do"))
+    if inputs == "range":
+        fam = rng.choice(("staircase_up", "staircase_down", "offset"))
+        pr = range_inputs.dense_range(fam, B, Hq, Hkv, Nq, Nk, D, ns, W, dt, rng.randrange(1 << 30), cu=cu)
         return tuple(pr[x].cuda() for x in ("q", "k", "v", "do"))
     return (torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt), torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt),
             torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt), torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
 fused-step / device-state / one-pass variants against the linearised cache.
-usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe] [--slots]   (probe: keys are the +-1 codes of tests/probe_inputs.py and
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots]   (range: keys carry the falling staircase of
+tests/range_inputs.py along a +-1 code, one level per 64 keys, and the queries a gain of 0 / 0.5 / 1 / -1 along it; probe: keys are the +-1 codes of tests/probe_inputs.py and
 every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
 one just evicted or the last sink; --slots: the single-token steps (decode_step_dyn only; the multi-token and commit
 calls are not fuzzed here) also run through a slot pool - the B sequences sit in a random permutation of a larger pool and the
@@ -15,12 +16,13 @@ sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT, os.
 import torch
 
 import probe_inputs
+import range_inputs
 
 from sink_attention import sink_decode_attention
 from sink_attention.cache import SinkCacheLayer
 
 inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
-assert inputs in ("randn", "probe"), inputs
+assert inputs in ("randn", "probe", "range"), inputs
 use_slots = "--slots" in sys.argv
 sys.argv = [a for a in sys.argv if not a.startswith("--inputs=") and a != "--slots"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
@@ -32,11 +34,20 @@ bad = 0
 def keys(B, H, n, D, dt):
     if inputs == "probe":
         return probe_inputs.codes((B, H, n, D), None, dt, device="cuda")
+    if inputs == "range":
+        # one code per call (seeded by D): keys appended later continue the staircase only within their own call
+        u = probe_inputs.codes((1, 1, 1, D), torch.Generator().manual_seed(D), torch.float32).cuda()
+        lvl = -(torch.arange(n, device="cuda") // 64).float() * range_inputs.STEPS[1] / D ** 0.5
+        return (torch.randn(B, H, n, D, device="cuda") + lvl.view(1, 1, n, 1) * u).to(dt)
     return torch.randn(B, H, n, D, device="cuda", dtype=dt)
 
 
 def query(B, Hq, D, dt, hist, ns, W):
     """randn, or amplitude * the code of one edge key of the history hist [B, Hkv, L, D] (the new token is its last row)"""
+    if inputs == "range":
+        u = probe_inputs.codes((1, 1, 1, D), torch.Generator().manual_seed(D), torch.float32).cuda()
+        a = torch.tensor([rng.choice((0.0, 0.5, 1.0, -1.0)) for _ in range(Hq)], device="cuda").view(1, Hq, 1, 1)
+        return (torch.randn(B, Hq, 1, D, device="cuda") + a * u).to(dt)
     if inputs != "probe":
         return torch.randn(B, Hq, 1, D, device="cuda", dtype=dt)
     L = hist.shape[2]
