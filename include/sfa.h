@@ -83,6 +83,12 @@ extern "C" {
  * rule AND with the hand-placed kernel forced. */
 #define SFA_FLAG_BWD_DKDV_ASM 0x10u
 #define SFA_FLAG_BWD_DKDV_WS 0x20u
+/* sfa_decode_ring_ragged_slots: admit new sequences in the call.  A sequence of the pack whose slot is active and whose
+ * state row has seen == 0 (read on the device) is taken from position 0: its cache is empty whatever the other three
+ * state fields hold, the first min(n_i, num_sink) tokens of its chunk are its sinks, and a commit places the chunk as
+ * sfa_ring_fill_varlen_slots does.  Every other sequence of the pack, and every call without the flag, is unchanged.
+ * Other entry points ignore the bit.  See the packed ragged step below. */
+#define SFA_FLAG_RAGGED_ADMIT 0x40u
 
 /* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
  * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.
@@ -508,9 +514,21 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
  *     replays at any mix of lengths and any occupancy.
  *   - commit != 0: after every read of the cache (stream order), token t >= n_i - Wc of sequence i goes to ring slot
  *     (write_pos + t) mod Wc of its slot, and a trailing launch advances each named state row by n_i (seen += n_i).
- *     Buffers and state rows are then bitwise what sfa_ring_commit_slots leaves for the same tokens.  sink_len never
- *     changes: the FIRST chunk of a prompt is still a prefill (sfa_ring_fill_varlen_slots writes the sinks); this call
- *     continues a sequence that has been admitted.
+ *     Buffers and state rows are then bitwise what sfa_ring_commit_slots leaves for the same tokens.  Without
+ *     SFA_FLAG_RAGGED_ADMIT sink_len never changes: the call continues sequences that a prefill
+ *     (sfa_ring_fill_varlen_slots) has admitted.
+ *   - flags & SFA_FLAG_RAGGED_ADMIT: the FIRST chunk of a prompt goes through this call too.  Sequence i is admitting
+ *     iff its slot is active and state[slots[i]].seen == 0, decided on the device; sink_len, window_len and write_pos of
+ *     such a row are taken as 0.  With nsk = min(n_i, num_sink): query t sees chunk token u iff u <= t and (u < nsk or
+ *     t - u <= Wc - 1), the mask of a prefill of these n_i tokens (n_i > Wc + num_sink is legal: the sinks stay visible
+ *     behind the window).  commit != 0 leaves buffers and state row bitwise as sfa_ring_fill_varlen_slots does for the
+ *     sequence: sink row j < nsk holds token j; with rem = n_i - nsk, ring slot s < rem holds token nsk + s if
+ *     rem <= Wc, else slot s holds token n_i - Wc + s; state = {nsk, min(rem, Wc), rem < Wc ? rem : 0, n_i}; rows and
+ *     slots the sequence does not reach keep their content.  commit == 0 computes the output over the empty cache and
+ *     writes nothing.  n_i == 0 on a fresh slot does nothing.  A first chunk shorter than num_sink pins only its own
+ *     tokens as sinks (later tokens go to the ring), so a scheduler gives an admitting chunk at least min(prompt,
+ *     num_sink) tokens.  Sequences that are not admitting are bit for bit what they are without the flag; workspace
+ *     and launches are the same.
  *   - The same slot twice in one call: undefined with commit, allowed without.
  *   - The output rows of a sequence do not depend on where it lies in the pack or on its neighbours: its split plan is
  *     a function of the call's shape (T, n_seq, heads) and its own (state row, n_i).  No atomics.
@@ -520,7 +538,7 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
  * state, slots and cu_q are non-null; n_seq >= 1; strides, alignment, head dim and dtype as for
  * sfa_decode_ring_multi_slots; workspace >= sfa_decode_ragged_workspace_bytes(n_seq, Hq, Hkv, T, num_sink + Wc, D,
  * dtype) bytes, 256-byte aligned (0: unsupported head dim or shape; no GPU needed).  sfa_last_path() names carry
- * "_ragged".
+ * "_ragged", then "_admit" with SFA_FLAG_RAGGED_ADMIT, then "_commit".
  */
 size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                          int64_t D, int dtype);

@@ -98,6 +98,7 @@ struct RaggedArgs {
     const int2* blk;             // [nrb] row-block id -> (sequence, local 32-row block); sequence -1: surplus
     const int* rowseq;           // [T] packed row -> sequence, -1: covered by none (padding)
     int n_seq, T;
+    int admit;                   // SFA_FLAG_RAGGED_ADMIT: a sequence on a fresh slot (state row seen == 0) is admitted
 };
 
 // the second argument of a ragged kernel instance (`RA...` is empty for every other instance: its signature, argument
@@ -174,7 +175,47 @@ inline __host__ __device__ MultiPlan multi_plan(int sink_len, int wl, int n, int
 struct Fill {
     int sink_len, wl, wp;
     int T0, T1, T, tps, S;
+    int nsk;                     // admitting sequence of a packed call: its first nsk chunk tokens are its sinks; else 0
 };
+
+// The prefill placement of SinkCacheLayer._prefill for a sequence of L tokens (ring_fill_varlen_kernel and the
+// admitting sequences of a packed call): sink row j <- token j for j < sl = min(L, ns); with rem = L - sl, ring slot s <-
+// token sl + s for s < rem when rem <= Wc, else token L - Wc + s (the newest Wc, wrapped at slot 0).
+struct FillPlace {
+    int L, ns, wc, sl, rem;
+};
+
+__device__ __forceinline__ FillPlace fill_place(int L, int ns, int wc) {
+    const int sl = L < ns ? L : ns;
+    return FillPlace{L, ns, wc, sl, L - sl};
+}
+
+// destination j of the (ns + Wc) rows of a cache row (j < ns: sink row j, else ring slot j - ns) -> the token stored
+// there, -1: the row keeps its content
+__device__ __forceinline__ int fill_src(const FillPlace& p, int j) {
+    if (j < p.ns) return j < p.sl ? j : -1;
+    const int s = j - p.ns;
+    return p.rem <= p.wc ? (s < p.rem ? p.sl + s : -1) : p.L - p.wc + s;
+}
+
+// token t -> its destination j, -1: not stored.  The inverse of fill_src by construction: the only row that can hold t is
+// tried and fill_src decides.
+__device__ __forceinline__ int fill_dst(const FillPlace& p, int t) {
+    const int j = t < p.sl ? t : p.ns + (p.rem <= p.wc ? t - p.sl : t - (p.L - p.wc));
+    return (j >= 0 && j < p.ns + p.wc && fill_src(p, j) == t) ? j : -1;
+}
+
+// the state row {sink_len, window_len, write_pos, seen} after the placement (rem <= 0: window_len = write_pos = 0)
+__device__ __forceinline__ void fill_state(const FillPlace& p, int* st) {
+    st[0] = p.sl;
+    st[1] = p.rem < p.wc ? p.rem : p.wc;
+    st[2] = p.rem < p.wc ? p.rem : 0;
+    st[3] = p.L;
+}
+
+// a packed call with SFA_FLAG_RAGGED_ADMIT (admit != 0): the sequence whose (active) slot has the state row `row` is
+// admitted iff the slot is fresh.  The one predicate of the split kernels (get_fill), the commit blocks and the advance.
+__device__ __forceinline__ bool admits(int admit, const int* row) { return admit && row[3] == 0; }
 
 // the cache row (and state row) of batch row b: b itself, or slots[b] of a slot call (-1: an inactive row)
 template <bool Slots>
@@ -195,14 +236,17 @@ __device__ __forceinline__ int state_wp(const MultiArgs& a, int c) {
 }
 
 // c: the cache row, wave-uniform (per-sequence state reads row c; a shared state has stride 0)
-// Ragged: the chunk length is n (the sequence's own n_i) in place of a.n
+// Ragged: the chunk length is n (the sequence's own n_i) in place of a.n; admit (the call's flag): a fresh slot
+// (seen == 0) reads as an empty cache whatever the other three fields hold, and the first min(n, ns) chunk tokens are
+// the sequence's sinks
 template <bool Dyn, bool Ragged = false>
-__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0) {
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0, [[maybe_unused]] int admit = 0) {
     if constexpr (!Dyn) {
-        return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S};
+        return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S, 0};
     } else {
         // dyn mode: the cache state from the device (clamped into the buffers, so that a corrupt state cannot address
-        // outside them), replanned.  Wave-uniform: loads of 12 bytes, broadcast from the first lane.
+        // outside them), replanned.  Wave-uniform: loads of 12 bytes (16 with `seen` in an admitting call), broadcast from
+        // the first lane.
         const int* st = a.state + (int64_t)c * a.sstride;
         int sl = __builtin_amdgcn_readfirstlane(st[0]);
         int wl = __builtin_amdgcn_readfirstlane(st[1]);
@@ -210,9 +254,13 @@ __device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0) {
         sl = sl < 0 ? 0 : (sl > a.ns ? a.ns : sl);
         wl = wl < 0 ? 0 : (wl > a.wc ? a.wc : wl);
         wp = wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp);
+        int nsk = 0;
+        if constexpr (Ragged) {
+            if (__builtin_amdgcn_readfirstlane((int)admits(admit, st))) sl = wl = wp = 0, nsk = n < a.ns ? n : a.ns;
+        }
         const MultiPlan p = multi_plan(sl, wl, Ragged ? n : a.n, a.want);
         auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };   // keep the plan in SGPRs
-        return Fill{sl, wl, wp, u(p.T0), u(p.T1), u(p.T), u(p.tps), u(p.S)};
+        return Fill{sl, wl, wp, u(p.T0), u(p.T1), u(p.T), u(p.tps), u(p.S), nsk};
     }
 }
 
@@ -266,8 +314,14 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
 }
 
 // 0 dead (no row of [tmin, tmax] sees a key), 1 full (every row sees every key), 2 edge
-__device__ __forceinline__ int tile_class(const MultiArgs& a, const TileInfo& ti, int tmin, int tmax) {
+// nsk (Fill): chunk keys c < nsk are sinks, visible behind the window.  A chunk tile that holds one is dead only above
+// the diagonal, and full only if its window keys (c >= nsk, if any: nsk is the oldest of them) are in every row's window.
+__device__ __forceinline__ int tile_class(const MultiArgs& a, const TileInfo& ti, int tmin, int tmax, int nsk = 0) {
     if (ti.seg == 0) return ti.count == kTile ? 1 : 2;
+    if (nsk > 0 && ti.seg == 2 && ti.start < nsk) {   // nsk is the constant 0 outside the ragged instances: no code there
+        if (ti.cmin > tmax) return 0;
+        return (ti.count == kTile && ti.cmax <= tmin && (ti.cmax < nsk || nsk >= tmax - a.wc + 1)) ? 1 : 2;
+    }
     if (ti.cmax < tmin - a.wc + 1 || ti.cmin > tmax) return 0;
     return (ti.count == kTile && ti.cmin >= tmax - a.wc + 1 && ti.cmax <= tmin) ? 1 : 2;
 }
@@ -277,6 +331,15 @@ __device__ __forceinline__ bool key_visible(const MultiArgs& a, const Fill& f, c
     if (ti.seg == 0) return true;
     const int c = ti.seg == 2 ? ti.start + kk : ring_chron(a, f, ti.start + kk);
     return c <= t && c >= t - a.wc + 1;
+}
+
+// a chunk tile of an admitting sequence (f.nsk > 0, ti.seg == 2): chunk keys c < nsk are its sinks, visible behind the
+// window.  A separate function so that the loops of every other tile stay the code they were: the callers branch on
+// the (wave-uniform) admitting() once per tile, not per element.
+__device__ __forceinline__ bool admitting(const Fill& f, const TileInfo& ti) { return f.nsk > 0 && ti.seg == 2; }
+__device__ __forceinline__ bool key_visible_admit(const MultiArgs& a, const Fill& f, const TileInfo& ti, int kk, int t) {
+    const int c = ti.start + kk;
+    return kk < ti.count && c <= t && (c >= t - a.wc + 1 || c < f.nsk);
 }
 
 // ---- tree chunks.  Node u sees ring position c iff c >= depth[u] - Wc + 1 and chunk token v iff
@@ -325,12 +388,13 @@ __device__ __forceinline__ TreeNode tree_node(const MultiArgs& a, int b, int lan
 // chunk tiles of a tree call: dead when no row of the block sees a key of the tile (vor = OR of the rows' vis), edge
 // otherwise; sink and ring tiles as the chain's, against the block's depth range [dlo, dhi]
 template <bool Tree>
-__device__ __forceinline__ int tile_class_t(const MultiArgs& a, const TileInfo& ti, int dlo, int dhi, uint64_t vor) {
+__device__ __forceinline__ int tile_class_t(const MultiArgs& a, const TileInfo& ti, int dlo, int dhi, uint64_t vor,
+                                            int nsk = 0) {
     if (Tree && ti.seg == 2) {
         const uint64_t m = ti.count >= 64 ? ~0ull : ((1ull << ti.count) - 1);
         return ((vor >> ti.start) & m) ? 2 : 0;
     }
-    return tile_class(a, ti, dlo, dhi);
+    return tile_class(a, ti, dlo, dhi, nsk);
 }
 
 template <bool Tree>
@@ -402,7 +466,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) return;             // inactive row (whole workgroup): the reduce writes its zeros
     }
-    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn, rg.admit);
     if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -496,7 +560,7 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
             ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
-            cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor);
+            cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
             if (cls != 0) break;
         }
         return i;
@@ -523,7 +587,13 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
 #pragma unroll
             for (int ks = 0; ks < DK; ++ks) s = M::run(kf[ks], qf[ks], s);
         }
-        if (ccls == 2) {
+        if (Ragged && ccls == 2 && admitting(f, cur)) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                s[i] = key_visible_admit(a, f, cur, kk, td) ? s[i] : -INFINITY;
+            }
+        } else if (ccls == 2) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -681,7 +751,7 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA...
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) return;
     }
-    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn, rg.admit);
     if (Dyn && split >= f.S) return;
     const int t = rho / a.G, head = hk * a.G + rho % a.G;
     const int D = a.D;
@@ -708,9 +778,10 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA...
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
         const TileInfo ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
-        if (tile_class_t<Tree>(a, ti, td, td, vis) == 0) continue;
+        if (tile_class_t<Tree>(a, ti, td, td, vis, f.nsk) == 0) continue;
+        const bool adm = Ragged && admitting(f, ti);
         for (int kk = 0; kk < ti.count; ++kk) {
-            if (!key_visible_t<Tree>(a, f, ti, kk, td, vis)) continue;
+            if (!(adm ? key_visible_admit(a, f, ti, kk, td) : key_visible_t<Tree>(a, f, ti, kk, td, vis))) continue;
             const T* kp = reinterpret_cast<const T*>(ti.k + kk * ti.ksn);
             const T* vp = reinterpret_cast<const T*>(ti.v + kk * ti.vsn);
             float x = 0.f;
@@ -788,6 +859,7 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // the commit piece of a packed call: item = (hk * T + packed row) * cpr + ch.  The row is token t of its sequence i
 // (n_i tokens, slot c): stored iff t >= n_i - Wc, into ring slot (write_pos_c + t) mod Wc - what commit_piece<false, true>
 // stores for a batch row of n_i tokens.  Rows of no sequence and of inactive sequences store nothing.
+// An admitting sequence (admits()) takes the prefill placement instead: token t goes to row fill_dst of its slot.
 __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es) {
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
@@ -801,13 +873,22 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
     if (c < 0) return;
     const RaggedSeq s = ragged_seq(rg, seq);
     const int t = tp - s.c0;
-    if (t < s.n - a.wc) return;
-    const int slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
+    const View *dk = &a.wk, *dv = &a.wv;
+    int slot;
+    if (admits(rg.admit, a.state + (int64_t)c * a.sstride)) {
+        const int j = fill_dst(fill_place(s.n, a.ns, a.wc), t);
+        if (j < 0) return;
+        if (j < a.ns) slot = j, dk = &a.sk, dv = &a.sv;
+        else slot = j - a.ns;
+    } else {
+        if (t < s.n - a.wc) return;
+        slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
+    }
     const int64_t so = (int64_t)ch * 16;
     const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + (int64_t)tp * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + (int64_t)tp * a.vn.sn) * es + so;
-    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
-    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)slot * dk->sn) * es + so;
+    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)slot * dv->sn) * es + so;
     *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
@@ -856,7 +937,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
             return;
         }
     }
-    const Fill f = get_fill<Dyn, Ragged>(a, c, rn);
+    const Fill f = get_fill<Dyn, Ragged>(a, c, rn, rg.admit);
     const int S = f.S, D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
     const float* Lr = a.Lp + rowid * a.Sw;
@@ -908,10 +989,10 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
 // K/V, one 16-byte piece per thread.  item = ((b * Hkv + hk) * (ns + Wc) + j) * cpr + ch: j < ns is sink row j, j >= ns
 // ring slot s = j - ns.  Sequence b = rows [cu[b], cu[b + 1]) of length L (offsets clamped into [0, T], so that bad
-// offsets cannot address outside the pack): sink row j <- token j for j < sl = min(L, ns); with rest = L - sl, slot s <-
-// token sl + s for s < rest when rest <= Wc, else token L - Wc + s (the newest Wc, wrapped at slot 0).  Rows and slots
-// the sequence does not reach keep their content.  The first piece of each sequence writes its state row
-// {sl, min(rest, Wc), rest < Wc ? rest : 0, L} (rest <= 0: window_len = write_pos = 0).
+// offsets cannot address outside the pack) is placed by fill_place / fill_src: sink row j <- token j for j < sl =
+// min(L, ns); with rest = L - sl, slot s <- token sl + s for s < rest when rest <= Wc, else token L - Wc + s (the newest
+// Wc, wrapped at slot 0).  Rows and slots the sequence does not reach keep their content.  The first piece of each
+// sequence writes its state row (fill_state): {sl, min(rest, Wc), rest < Wc ? rest : 0, L}.
 // Slots (sfa_ring_fill_varlen_slots): sequence b goes to cache row and state row slots[b] of a pool of npool rows (a
 // value outside [0, npool): the sequence is skipped); every other row of the pool keeps buffers and state.
 template <bool Slots>
@@ -933,28 +1014,14 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
         c = slots[b];
         if ((unsigned)c >= (unsigned)npool) return;
     }
-    const RaggedSeq seq = ragged_seq(RaggedArgs{cu, nullptr, nullptr, n_seq, T}, b);
-    const int c0 = seq.c0, L = seq.n;
-    const int sl = L < ns ? L : ns;
-    const int rem = L - sl;
-    if (hk == 0 && j == 0 && ch == 0) {
-        int* st = state + (int64_t)c * 4;
-        st[0] = sl;
-        st[1] = rem < wc ? rem : wc;
-        st[2] = rem < wc ? rem : 0;
-        st[3] = L;
-    }
-    int src;   // token index within the sequence, -1: nothing to store
-    const View *dk, *dv;
-    int row;
-    if (j < ns) {
-        src = j < sl ? j : -1, row = j, dk = &sk, dv = &sv;
-    } else {
-        const int s = j - ns;
-        src = rem <= wc ? (s < rem ? sl + s : -1) : L - wc + s;
-        row = s, dk = &wk, dv = &wv;
-    }
+    const RaggedSeq seq = ragged_seq(RaggedArgs{cu, nullptr, nullptr, n_seq, T, 0}, b);
+    const int c0 = seq.c0;
+    const FillPlace p = fill_place(seq.n, ns, wc);
+    if (hk == 0 && j == 0 && ch == 0) fill_state(p, state + (int64_t)c * 4);
+    const int src = fill_src(p, j);   // token index within the sequence, -1: nothing to store
     if (src < 0) return;
+    const View *dk = j < ns ? &sk : &wk, *dv = j < ns ? &sv : &wv;
+    const int row = j < ns ? j : j - ns;
     const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src;
     const char* ks = k.ptr + ((int64_t)hk * k.sh + tok * k.sn) * es + so;
     const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
@@ -994,14 +1061,18 @@ __global__ void ring_advance_slots_kernel(int* state, const int* count, int n, i
 }
 
 // the same for a packed call: thread r advances state row slots[r] by n_r = the length of sequence r; an inactive or
-// empty sequence moves nothing
-__global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int wc, const int* slots, int npool) {
+// empty sequence moves nothing.  An admitting sequence (flag, seen == 0: this launch is the first writer of the row)
+// gets the state of its prefill placement.
+__global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int ns, int wc, const int* slots, int npool) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (r >= rg.n_seq) return;
     const int c = slots[r];
     if ((unsigned)c >= (unsigned)npool) return;
     const int acc = ragged_seq(rg, r).n;
-    if (acc) advance_row(state + (int64_t)c * 4, acc, wc, true);
+    if (!acc) return;
+    int* st = state + (int64_t)c * 4;
+    if (admits(rg.admit, st)) fill_state(fill_place(acc, ns, wc), st);
+    else advance_row(st, acc, wc, true);
 }
 
 // advance every state row after the launches that read it (shared state: one row); rg: by the lengths of a pack
@@ -1011,7 +1082,7 @@ int launch_advance(const MultiArgs& a, const int* count, const RaggedArgs* rg, h
     if (nrow <= 0) return SFA_OK;
     const dim3 grid((unsigned)cdiv64(nrow, 256)), block(nrow < 256 ? nrow : 256);
     if (rg) {
-        ring_advance_ragged_kernel<<<grid, block, 0, stream>>>(state, *rg, a.wc, a.slots, a.npool);
+        ring_advance_ragged_kernel<<<grid, block, 0, stream>>>(state, *rg, a.ns, a.wc, a.slots, a.npool);
         return launch_status("ring_advance_ragged");
     }
     if (a.slots) {
@@ -1262,7 +1333,8 @@ int decode_ragged_launch(const RingCall& c) {
     char* tab = ws + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)a.D * sizeof(float));
     int2* blk = reinterpret_cast<int2*>(tab);
     int* rowseq = reinterpret_cast<int*>(tab + al256((size_t)g.nrb * sizeof(int2)));
-    const RaggedArgs rg{c.cu_q, blk, rowseq, c.n_seq, (int)T};
+    const int admit = (c.flags & SFA_FLAG_RAGGED_ADMIT) ? 1 : 0;
+    const RaggedArgs rg{c.cu_q, blk, rowseq, c.n_seq, (int)T, admit};
     if ((int64_t)a.Hkv * a.Sw * g.nrb >= (1ll << 31) || cdiv64(g.rows, 4) >= (1ll << 31) - 65536 ||
         cdiv64(g.rows, 4) + cdiv64((int64_t)a.Hkv * T * (a.D * 4 / 16), 256) >= (1ll << 31)) {
         set_error("decode_ragged: grid too large");
@@ -1274,8 +1346,9 @@ int decode_ragged_launch(const RingCall& c) {
     bool mfma;
     const char* dname;
     if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
-    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s", dname, a.D, a.nrb, c.commit ? "_commit" : "");
-    else set_path("decode_multi_f32_%s_d%d_ragged%s", dname, a.D, c.commit ? "_commit" : "");
+    const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
+    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s%s", dname, a.D, a.nrb, ad, cm);
+    else set_path("decode_multi_f32_%s_d%d_ragged%s%s", dname, a.D, ad, cm);
     return SFA_OK;
 }
 

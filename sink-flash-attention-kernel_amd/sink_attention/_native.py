@@ -23,6 +23,7 @@ FLAG_DECODE_ONE_PASS = 0x4
 FLAG_BWD_OVERLAP = 0x8        # dQ kernel of a small grid on the library's side stream (include/sfa.h)
 FLAG_BWD_DKDV_ASM = 0x10      # dispatch override: hand-placed dK/dV kernel
 FLAG_BWD_DKDV_WS = 0x20       # dispatch override: wave-specialised compiled dK/dV kernel
+FLAG_RAGGED_ADMIT = 0x40      # sfa_decode_ring_ragged_slots: a sequence on a fresh slot (seen == 0) is admitted in the call
 ABI_VERSION = 2
 
 # flags every backward of the ops passes to sfa_bwd / sfa_bwd_varlen (and to the workspace query): the overlap is ON by

@@ -589,8 +589,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         step then names the slots it works on with the ``slots=`` keyword of the dyn methods: a device int32 ``[B]``
         tensor (never read on the host, so a captured step replays at any occupancy by rewriting it in place), or a host
         list, which is checked for range and duplicates and uploaded.  Batch row b works on slot ``slots[b]``; -1 marks
-        an inactive row.  A slot must be prefilled (``prefill_slots``) before it is used: an all-zero state row is not a
-        prefilled cache."""
+        an inactive row.  A slot must be prefilled (``prefill_slots``) before it is used, or admitted by
+        ``ragged_step_dyn(admit=True)``: to every other call an all-zero state row is not a prefilled cache."""
         if self.window_size < 1:
             raise ValueError("init_pool needs a ring of at least one slot (window_size >= 1)")
         if int(num_slots) < 1:
@@ -671,8 +671,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def release_slots(self, slots) -> None:
         """Retire sequences: zero the state rows of ``slots`` (list or integer tensor; -1 entries name nothing) with torch
         ops on the current stream (no sync, capturable).  The buffers keep their stale content, which no kernel reads
-        beyond a row's ``sink_len`` / ``window_len``.  A released slot must be prefilled again (``prefill_slots``) before
-        it is used: an all-zero state is not a prefilled cache."""
+        beyond a row's ``sink_len`` / ``window_len``.  A released slot must be prefilled again (``prefill_slots``), or
+        admitted by ``ragged_step_dyn(admit=True)``, before it is used: an all-zero state is not a prefilled cache."""
         st = self._require_dyn("release_slots")
         idx = self._slots_arg(slots, None, writes=False).to(st.device)
         hit = (torch.arange(st.shape[0], device=st.device, dtype=torch.int32)[:, None] == idx[None, :]).any(dim=1)
@@ -741,7 +741,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                        commit: bool = True) -> torch.Tensor:
+                        commit: bool = True, admit: bool = False) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -751,8 +751,18 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         state row advances by its length (``extend_step_dyn``).  Rows of an inactive sequence (slot -1), and rows behind
         ``cu_q[-1]`` (padding of a step captured at a fixed T) come back as zeros and change nothing.  ``cu_q`` and
         ``slots``: device int32 tensors (never read on the host: the call is graph-capturable and a captured step replays
-        at any mix of lengths by rewriting them in place) or host lists, which are checked.  The first chunk of a prompt
-        is still a ``prefill_slots`` (it writes the sinks); this call continues an admitted sequence."""
+        at any mix of lengths by rewriting them in place) or host lists, which are checked.
+
+        ``admit=False``: the call continues sequences that ``prefill_slots`` has admitted (``sink_len`` never changes).
+        ``admit=True`` (``SFA_FLAG_RAGGED_ADMIT``): a sequence whose slot is fresh - its state row has ``seen == 0``, as
+        after ``init_pool`` or ``release_slots``, read on the device - is admitted by this call: it attends to its own
+        chunk alone with the mask of a prefill (the first ``min(n_i, num_sink)`` tokens stay visible behind the window;
+        ``n_i > window_size + num_sink`` is fine), and with ``commit`` its tokens and state row end bitwise as
+        ``prefill_slots`` of the chunk leaves them.  Every other sequence of the pack is bit for bit what it is with
+        ``admit=False``, so one captured step serves admission, chunked prefill, decode and draft rows:
+        ``release_slots``, ``packed_positions``, then this call.  A first chunk shorter than ``num_sink`` pins only its
+        own tokens as sinks (later tokens go to the ring, as ``append`` after a short prompt does): a scheduler should
+        give an admitting chunk at least ``min(prompt, num_sink)`` tokens."""
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
@@ -784,7 +794,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                                         N.desc(out), aux,
                                                         1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
                                                         cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
-                                                        st["scale"], 0, N.stream_ptr(q.device))
+                                                        st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
+                                                        N.stream_ptr(q.device))
         N.check(rc, "sfa_decode_ring_ragged_slots")
         return out
 
@@ -940,10 +951,11 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
-                        commit=True):
-        """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count."""
+                        commit=True, admit: bool = False):
+        """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
+        ``admit=True`` takes sequences on fresh slots from position 0 in the same call."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
-                                                      commit=commit)
+                                                      commit=commit, admit=admit)
 
     def packed_positions(self, cu_q, slots, T: int, layer_idx: int = 0) -> torch.Tensor:
         """``SinkCacheLayer.packed_positions`` of one layer: the RoPE position of every packed row (-1: no row)."""

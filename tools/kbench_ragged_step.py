@@ -11,6 +11,11 @@ Variants per (W, step), alternating in one process:
     per_len    what was possible before (a): one extend_step_dyn(slots=) per distinct length
     padded     what was possible before (b): one extend_step_dyn(slots=) with every row padded to the longest chunk.
                Timing only: a padded row commits its padding too, which a real caller would have to undo.
+    ragged_admit   the ragged call with admit=True (SFA_FLAG_RAGGED_ADMIT) on the same pool: every sequence continues, so
+               this is the cost of the flag alone (only when named in --variants; skipped where the keyword is missing)
+--admit: the admission mix instead of the variants above.  The longest sequence and the first two decode rows sit on FRESH
+    slots and are admitted by the call; commit is off (a dry run), so that the slots stay fresh and every call does the
+    same work.  Variants: admit_mix (admit=True) and dry (the same pack, every slot full, admit=False, commit off).
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
 --mode kernels: --calls calls of each variant after 5 warm-up calls, in the order above, for a kernel trace of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o rstep -- python tools/kbench_ragged_step.py --mode kernels
@@ -42,17 +47,25 @@ def _pool(torch, W, dev, dt):
     return layer
 
 
-def _variants(torch, W, lengths, dev, dt, have_ragged):
+def _variants(torch, W, lengths, dev, dt, have_ragged, names=()):
     sa = torch.randn(HQ, device=dev) * 0.5
     mk = lambda rows, h, n: torch.randn(rows, h, n, D, device=dev, dtype=dt)
     out = {}
     if have_ragged:
         T = sum(lengths)
-        q, k, v = mk(1, HQ, T), mk(1, HKV, T), mk(1, HKV, T)
+        qr, kr, vr = mk(1, HQ, T), mk(1, HKV, T), mk(1, HKV, T)   # names of their own: q is rebound below
         cu = torch.tensor([sum(lengths[:i]) for i in range(S + 1)], dtype=torch.int32, device=dev)
         slots = torch.arange(S, dtype=torch.int32, device=dev)
-        pool, o = _pool(torch, W, dev, dt), torch.empty_like(q)
-        out["ragged"] = lambda: pool.ragged_step_dyn(q, k, v, cu, slots, s_aux=sa, out=o, commit=True)
+        pool, o = _pool(torch, W, dev, dt), torch.empty_like(qr)
+        out["ragged"] = lambda: pool.ragged_step_dyn(qr, kr, vr, cu, slots, s_aux=sa, out=o, commit=True)
+        if have_ragged > 1:      # the flag on the same pool and inputs: no further draw
+            out["ragged_admit"] = lambda: pool.ragged_step_dyn(qr, kr, vr, cu, slots, s_aux=sa, out=o, commit=True, admit=True)
+        if have_ragged > 1 and ("admit_mix" in names or "dry" in names):
+            fresh = [0, 1, max(range(S), key=lambda i: lengths[i])]
+            pool_f, pool_d = _pool(torch, W, dev, dt), _pool(torch, W, dev, dt)
+            pool_f.release_slots(fresh)
+            out["admit_mix"] = lambda: pool_f.ragged_step_dyn(qr, kr, vr, cu, slots, s_aux=sa, out=o, commit=False, admit=True)
+            out["dry"] = lambda: pool_d.ragged_step_dyn(qr, kr, vr, cu, slots, s_aux=sa, out=o, commit=False)
     groups = []
     for n in sorted(set(lengths)):
         idx = [i for i, x in enumerate(lengths) if x == n]
@@ -74,11 +87,16 @@ def _variants(torch, W, lengths, dev, dt, have_ragged):
 
 
 def _setup(args):
+    import inspect
     import torch
     import sink_attention
     from sink_attention import SinkCacheLayer
     have = hasattr(SinkCacheLayer, "ragged_step_dyn") and hasattr(sink_attention._native.lib(), "sfa_decode_ring_ragged_slots")
-    names = [v for v in args.variants.split(",") if have or v != "ragged"]
+    # 2: the admit keyword too (a library without the flag ignores the bit: such a run times the unflagged kernels)
+    have = int(have) + int(have and "admit" in inspect.signature(SinkCacheLayer.ragged_step_dyn).parameters)
+    want = ["admit_mix", "dry"] if args.admit else args.variants.split(",")
+    need = {"ragged": 1, "ragged_admit": 2, "admit_mix": 2, "dry": 2}
+    names = [v for v in want if have >= need.get(v, 0)]
     return torch, names, have
 
 
@@ -90,7 +108,7 @@ def wall(args):
     for W in [int(x) for x in args.W.split(",")]:
         for step in args.steps.split(","):
             torch.manual_seed(0)
-            fns = _variants(torch, W, STEPS[step], dev, dt, have)
+            fns = _variants(torch, W, STEPS[step], dev, dt, have, names)
             res = {v: [] for v in names}
             for v in names:
                 for _ in range(WARM):
@@ -118,7 +136,7 @@ def kernels(args):
     for W in [int(x) for x in args.W.split(",")]:
         for step in args.steps.split(","):
             torch.manual_seed(0)
-            fns = _variants(torch, W, STEPS[step], dev, dt, have)
+            fns = _variants(torch, W, STEPS[step], dev, dt, have, names)
             torch.cuda.synchronize()
             for v in names:
                 for _ in range(WARM + args.calls):
@@ -179,6 +197,7 @@ def main():
     ap.add_argument("--variants", default=",".join(VARIANTS))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--admit", action="store_true", help="the admission mix: variants admit_mix and dry")
     ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
     args = ap.parse_args()
     if args.summarize:
