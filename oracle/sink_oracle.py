@@ -111,10 +111,25 @@ def sink_attention_dense(
     return o, lse
 
 
+def _sum_bound_terms(p, dp, adelta, qf, dof, scale, m, tiny):
+    """Per-element magnitude sums behind dV and dK (not reference formulas: the yardstick of tests/util.py::
+    assert_within_sum_bound).  p, dp [B,Hq,R,C]; adelta = sum_e |dO_e O_e| [B,Hq,R]; returns per q head
+    A_K [B,Hq,C,D] = scale * sum_i P_ij (|dP_ij| + adelta_i) |q_id| and A_V [B,Hq,C,D] = sum_i P_ij |dO_id|.
+    ``tiny`` > 0 (the smallest normal number of a 16-bit format whose rounding the bound is for): every VISIBLE pair
+    (mask m [R,C]) counts at least ``tiny`` (P_ij -> P_ij + tiny in A_V, P_ij (...) -> P_ij (...) + tiny in A_K), because
+    below ``tiny`` a packed P or dS is rounded to a fixed spacing, not to a relative precision."""
+    floor = tiny * m.to(p.dtype)
+    a_k = torch.matmul((p * (dp.abs() + adelta.unsqueeze(-1)) + floor).transpose(-2, -1), qf.abs()) * scale
+    a_v = torch.matmul((p + floor).transpose(-2, -1), dof.abs())
+    return a_k, a_v
+
+
 def sink_attention_bwd_dense(
-    q, k, v, do, num_sink: int, window: int, s_aux=None, dtype=torch.float64,
+    q, k, v, do, num_sink: int, window: int, s_aux=None, dtype=torch.float64, bounds: bool = False,
+    tiny: float = 0.0,
 ):
-    """Explicit backward (no autograd): returns dQ, dK, dV, ds_aux (or None).
+    """Explicit backward (no autograd): returns dQ, dK, dV, ds_aux (or None); with ``bounds`` also A_K, A_V
+    [B,Hkv,Nk,D], the sums of the magnitudes of the terms of dK / dV (see ``_sum_bound_terms``).
 
     Formulas of sink_flash_attention.py:568-667:
       Delta = rowsum(dO * O); P = exp(S - LSE); dV = P^T dO; dP = dO V^T;
@@ -147,6 +162,9 @@ def sink_attention_bwd_dense(
     if s_aux is not None:
         sink_prob = torch.exp(s_aux.to(dtype).view(1, Hq, 1) - lse)
         ds_aux = -(sink_prob * delta).sum(dim=(0, 2))
+    if bounds:
+        a_k, a_v = _sum_bound_terms(p, dp, (dof * o).abs().sum(-1), qf, dof, scale, m, tiny)
+        return dq, dk, dv, ds_aux, a_k.view(B, Hkv, g, Nk, D).sum(2), a_v.view(B, Hkv, g, Nk, D).sum(2)
     return dq, dk, dv, ds_aux
 
 
@@ -193,9 +211,10 @@ def sink_attention_banded(
 
 
 def sink_attention_bwd_banded(
-    q, k, v, do, num_sink: int, window: int, s_aux=None, dtype=torch.float64, block: int = 256,
+    q, k, v, do, num_sink: int, window: int, s_aux=None, dtype=torch.float64, block: int = 256, bounds: bool = False,
+    tiny: float = 0.0,
 ):
-    """Banded explicit backward; same outputs as ``sink_attention_bwd_dense``."""
+    """Banded explicit backward; same outputs as ``sink_attention_bwd_dense`` (``bounds`` included)."""
     B, Hq, N, D = q.shape
     Hkv = k.shape[1]
     g = Hq // Hkv
@@ -205,6 +224,8 @@ def sink_attention_bwd_banded(
     dk = torch.zeros(B, Hkv, N, D, dtype=dtype)
     dv = torch.zeros(B, Hkv, N, D, dtype=dtype)
     delta = (do.to(dtype) * o).sum(-1)
+    adelta = (do.to(dtype) * o).abs().sum(-1)
+    a_k, a_v = (torch.zeros(B, Hkv, N, D, dtype=dtype) for _ in range(2)) if bounds else (None, None)
     for r0 in range(0, N, block):
         r1 = min(N, r0 + block)
         cols = _row_block_keys(r0, r1, N, num_sink, window)
@@ -225,10 +246,16 @@ def sink_attention_bwd_banded(
         C = cols.numel()
         dk.index_add_(2, cols, dkb.view(B, Hkv, g, C, D).sum(2))
         dv.index_add_(2, cols, dvb.view(B, Hkv, g, C, D).sum(2))
+        if bounds:
+            akb, avb = _sum_bound_terms(p, dp, adelta[:, :, r0:r1], qb, dob, scale, m, tiny)
+            a_k.index_add_(2, cols, akb.view(B, Hkv, g, C, D).sum(2))
+            a_v.index_add_(2, cols, avb.view(B, Hkv, g, C, D).sum(2))
     ds_aux = None
     if s_aux is not None:
         sink_prob = torch.exp(s_aux.to(dtype).view(1, Hq, 1) - lse)
         ds_aux = -(sink_prob * delta).sum(dim=(0, 2))
+    if bounds:
+        return dq, dk, dv, ds_aux, a_k, a_v
     return dq, dk, dv, ds_aux
 
 

@@ -11,8 +11,13 @@ Construction
     one-key mutant does; the one whose dP = dO . v differs most from the target's, because dQ of the row is proportional
     to that difference): q[i] = a * (c_t + c_u), entries in {-2a, 0, +2a}.  Both logits are EQUAL (a * (D + c_t . c_u) / sqrt(D)), so
     if both keys are seen P is 1/2, 1/2 and dQ of the row is O(1); if only one is seen P is 1, 0 and dQ is about 0.  Single
-    rows cannot move a gradient by ten tolerances (a peaked row and a diffuse row both have dS near 0, and the dK / dV
-    tolerances scale with max |ref|); pair rows are what makes condition (2b) hold on dQ;
+    rows cannot move dQ by ten tolerances (a peaked row and a diffuse row both have dS near 0); pair rows are what makes
+    condition (2b) hold on dQ.  dK / dV have a tolerance that scales with max |ref| and sees no single key; they are judged
+    element by element against the bound of their own sum as well (tests/util.py::assert_within_sum_bound), which a single
+    row moves by up to 1 / (4 u) (condition (2d));
+  * sink_cap (the sinkcap_* cases): hundreds of rows per KV head aim at key num_sink - 1, and one contribution missing
+    among n equal ones is invisible at a relative precision of 4 u; with sink_cap only that many rows per (batch, KV head)
+    keep sink_last, as single rows on block edges, and the others aim at diag;
   * v and dO stay randn rounded to the dtype; s_aux is the usual 0.5 * randn.
 
 Kinds (the edges of oracle.sink_oracle.valid_mask; p = position of the row in its sequence, ns = num_sink, W = window):
@@ -129,10 +134,42 @@ def _draw(exist, Hq, Hkv, g, edge_rows):
     return hit.long().argmax(1)
 
 
-def dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dtype, seed, aux=False, cu=None, a=None, pairs=True):
+def _cap_sink_rows(kind, exist, edge, Hkv, cap):
+    """Keep at most `cap` rows per (batch, KV head) aimed at sink_last and re-aim the others at diag (in place, no random
+    draw).  Block-edge rows come first: group s = batch * H_kv + KV head takes the block edges s * cap, s * cap + 1, ... (mod
+    their number) of those on which sink_last exists, on the head that drew sink_last there, else on head (block mod group
+    size), whose kind is overwritten - so that over the groups every block edge beyond the window is kept somewhere; where
+    there are fewer such edges than `cap`, the first other sink_last rows fill up.  Returns keep [B,Hq,R]."""
+    B, Hq, R = kind.shape
+    grp = Hq // Hkv
+    SL, DIAG = KINDS.index("sink_last"), KINDS.index("diag")
+    keep = torch.zeros(B, Hq, R, dtype=torch.bool)
+    edges = torch.nonzero((edge >= 0) & exist[SL]).flatten().tolist()
+    for b in range(B):
+        for hk in range(Hkv):
+            s, h0 = b * Hkv + hk, hk * grp
+            mine = [edges[(s * cap + x) % len(edges)] for x in range(min(cap, len(edges)))]
+            for r in mine:
+                drew = torch.nonzero(kind[b, h0:h0 + grp, r] == SL).flatten()
+                h = h0 + (int(drew[0]) if drew.numel() else int(edge[r]) % grp)
+                kind[b, h, r], keep[b, h, r] = SL, True
+            h, r = torch.nonzero((kind[b, h0:h0 + grp] == SL) & ~keep[b, h0:h0 + grp], as_tuple=True)
+            order = sorted(range(h.numel()), key=lambda x: (int(r[x]), int(h[x])))
+            for x in order[:cap - len(mine)]:
+                keep[b, h0 + int(h[x]), r[x]] = True
+    drop = (kind == SL) & ~keep
+    assert bool(exist[DIAG].view(1, 1, R).expand_as(drop)[drop].all()), "a capped sink_last row without a diagonal key"
+    kind[drop] = DIAG
+    return keep
+
+
+def dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dtype, seed, aux=False, cu=None, a=None, pairs=True, sink_cap=None):
     """Probe inputs of one dense call (or one pack, B = 1 and cu given).  Returns a dict: q [B,Hq,Nq,D], k / v
     [B,Hkv,Nk,D], do, s_aux (or None), kind [B,Hq,Nq] (index into KINDS), target [B,Hq,Nq] (absolute key index),
-    pair [B,Hq,Nq] bool, partner [B,Hq,Nq] (absolute key index, -1 on single rows)."""
+    pair [B,Hq,Nq] bool, partner [B,Hq,Nq] (absolute key index, -1 on single rows).
+    sink_cap (default None: off, every output as before): at most that many rows per (batch, KV head) aim at sink_last, as
+    SINGLE rows; the others are re-aimed at diag.  Hundreds of rows per KV head aim at key num_sink - 1 otherwise, and one
+    contribution missing among n equal ones cannot be seen in dK / dV of that key at a relative precision of a few u."""
     a = amplitude(D) if a is None else a
     g = torch.Generator().manual_seed(seed)
     k = codes((B, Hkv, Nk, D), g, dtype)
@@ -144,6 +181,7 @@ def dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dtype, seed, aux=False, cu=None, a
     edge = torch.where(rows % BLOCK == BLOCK - 1, rows // BLOCK, torch.full_like(rows, -1))
     grp = Hq // Hkv
     kind = torch.stack([_draw(exist, Hq, Hkv, g, edge) for _ in range(B)])              # [B, Hq, Nq]
+    single = _cap_sink_rows(kind, exist, edge, Hkv, sink_cap) if sink_cap is not None else None
     tgt = target.t()[rows.view(1, 1, Nq), kind]                                          # [B, Hq, Nq]
     kq = k.float().repeat_interleave(grp, dim=1)                                         # [B, Hq, Nk, D]
     vq = v.float().repeat_interleave(grp, dim=1)
@@ -167,6 +205,8 @@ def dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dtype, seed, aux=False, cu=None, a
         best_gap[:, :, r] = torch.where(better, gap, best_gap[:, :, r])
     pair = (torch.rand(B, Hq, Nq, generator=g) < 0.5) | (edge >= 0).view(1, 1, Nq)
     pair &= (best >= 0) & bool(pairs)
+    if single is not None:
+        pair &= ~single
     q = a * (take(kq, tgt) + take(kq, best) * pair.unsqueeze(-1))
     partner = torch.where(pair, best, torch.full_like(best, -1))
     return dict(q=q.to(dtype), k=k, v=v, do=do, s_aux=sa, kind=kind, target=tgt, pair=pair, partner=partner, a=a)
@@ -269,6 +309,8 @@ def kind_counts(pr, kinds=KINDS):
 # shape = (B, Hq, Hkv, Nq, Nk, D, ns, W).  fwd / dq: substrings sfa_last_path() must show after the forward / the backward.
 # missing: the kinds the case lacks BY CONSTRUCTION (every other kind of KINDS[:6] must have >= MIN_ROWS rows per q head).
 MIN_ROWS = 8
+SINK_CAP = 4           # rows per (batch, KV head) aimed at sink_last in the sink-edge cases (tests/test_probe_inputs.py: every
+                       # kept row clears ten sum bounds of dV on its own)
 _NO_WINDOW_EDGE = ("win_oldest", "win_behind", "sink_last", "sink_next")     # W >= N: no row is beyond the window
 _NO_SINK = ("sink_last", "sink_next")                                        # num_sink = 0
 DENSE_CASES = [
@@ -316,6 +358,13 @@ DENSE_CASES = [
     dict(id="ns_ge_n", shape=(1, 4, 2, 777, 777, 128, 1000, 16), dtype="bf16", fwd="fwd_mfma", dq="bwd_mfma",
          missing=_NO_WINDOW_EDGE),                      # every key is a sink key
     dict(id="ns0", shape=(1, 4, 2, 777, 777, 128, 0, 100), dtype="bf16", fwd="fwd_mfma", dq="bwd_mfma", missing=_NO_SINK),
+    # the sink edge in dK / dV: SINK_CAP single rows per (batch, KV head) aim at key num_sink - 1 (dense_probe(sink_cap=)), so
+    # that one dropped contribution to that key exceeds the per-element sum bound of tests/util.py; B * H_kv = 4 groups, row
+    # head dim 128, with and without the row split of a small grid
+    dict(id="sinkcap_d128", shape=(1, 4, 4, 2048, 2048, 128, 4, 512), dtype="bf16", fwd="asm4x64pk", dq="dqasm4x64",
+         sink_cap=SINK_CAP),                            # group size 1: too few trips per chunk for the row split, sink tail
+    dict(id="sinkcap_rowsplit", shape=(2, 4, 2, 2048, 2048, 128, 4, 512), dtype="bf16", fwd="asm4x64pk", dq="dqasm4x64",
+         rule_dkdv="dkdvasm4x64rs", sink_cap=SINK_CAP),
 ]
 # packed batches: the nine cu lists of tests/test_gpu_varlen.py::test_varlen_native_kernels_one_launch; W is the window of
 # that table where it is shorter than the pack's sequences, else cut so that the longer sequences have a window edge
@@ -373,7 +422,8 @@ TREE_DTYPE_D = [("bf16", 64), ("fp16", 128), ("fp32", 48)]
 def dense_case_probe(case):
     i = [c["id"] for c in DENSE_CASES].index(case["id"])
     B, Hq, Hkv, Nq, Nk, D, ns, W = case["shape"]
-    return dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, _DT[case["dtype"]], 1000 + i, aux=case.get("aux", False))
+    return dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, _DT[case["dtype"]], 1000 + i, aux=case.get("aux", False),
+                       sink_cap=case.get("sink_cap"))
 
 
 def pack_case_probe(i):

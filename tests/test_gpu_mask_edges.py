@@ -2,6 +2,9 @@
 of the same inputs, one group of cases per code path that decides which (row, key) pairs exist, at windows where randn
 inputs cannot tell a mask that is off by one key from a correct one (tests/test_probe_inputs.py proves both on the CPU).
 Tolerances are those of the neighbouring randn test of the same kernel; every case asserts the kernel path it ran.
+dK and dV of the dense and the packed calls are ALSO judged element by element against the bound of their own sum
+(util.assert_within_sum_bound: |got - ref| <= 4 u A + u |ref|), because their other tolerance scales with max |ref| and
+lets a mask error confined to the dK/dV kernel pass (tests/test_probe_inputs.py, part 2d, proves both).
 A row aimed at its diagonal key meets its maximum in the LAST tile of its walk, a row aimed at a sink key in the FIRST:
 the online-softmax rescale branch is forced both ways."""
 import functools
@@ -15,7 +18,8 @@ from oracle import sink_oracle as O
 from test_gpu_decode_multi import TOL, _expected_path, _oracle_rows
 from test_gpu_tree_verify import TREES, _oracle_tree, _tree_path_name
 from test_tree_host import random_tree
-from util import assert_close, dkdv_kernel_name, maxdiff, oracle_bwd, oracle_fwd
+from util import (UNIT_ROUNDOFF, assert_close, assert_within_sum_bound, dkdv_kernel_name, maxdiff, oracle_bwd, oracle_fwd,
+                  probe_reference, sum_bound_ratio)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -39,9 +43,7 @@ def _dense(case_id):
     case = next(c for c in P.DENSE_CASES if c["id"] == case_id)
     B, Hq, Hkv, Nq, Nk, D, ns, W = case["shape"]
     pr = P.dense_case_probe(case)
-    banded = Nq == Nk and Nq > 1024            # (the banded oracle walks N_q = N_kv only)
-    o_r, _ = oracle_fwd(pr["q"], pr["k"], pr["v"], ns, W, pr["s_aux"], banded=banded)
-    grads = oracle_bwd(pr["q"], pr["k"], pr["v"], pr["do"], ns, W, pr["s_aux"], banded=banded)
+    o_r, _, grads = probe_reference(pr, ns, W)       # (dq, dk, dv, ds_aux and the bound terms A_K, A_V)
     return pr, o_r, grads
 
 
@@ -50,7 +52,7 @@ def _dense(case_id):
 def test_dense_mask_edges(case, dkdv):
     B, Hq, Hkv, Nq, Nk, D, ns, W = case["shape"]
     dt = DT[case["dtype"]]
-    pr, o_r, (dq_r, dk_r, dv_r, dsa_r) = _dense(case["id"])
+    pr, o_r, (dq_r, dk_r, dv_r, dsa_r, ak_r, av_r) = _dense(case["id"])
     if case.get("layout") == "bnhd":           # [B, N, H, D] storage, passed as transposed views
         qd, kd, vd = (pr[x].transpose(1, 2).contiguous().to(DEV).transpose(1, 2).requires_grad_(True) for x in "qkv")
         dod = pr["do"].transpose(1, 2).contiguous().to(DEV).transpose(1, 2)
@@ -80,6 +82,10 @@ def test_dense_mask_edges(case, dkdv):
     assert_close(qd.grad, dq_r, 5e-2, 5e-2, "dq")
     assert_close(kd.grad, dk_r, 5e-2 * max(1.0, dk_r.abs().max().item()), 5e-2, "dk")
     assert_close(vd.grad, dv_r, 5e-2 * max(1.0, dv_r.abs().max().item()), 5e-2, "dv")
+    u = UNIT_ROUNDOFF[dt]
+    print(f"sum bound {case['id']} {dkdv}: dK {sum_bound_ratio(kd.grad, dk_r, ak_r, u):.3f} dV {sum_bound_ratio(vd.grad, dv_r, av_r, u):.3f}")
+    assert_within_sum_bound(kd.grad, dk_r, ak_r, u, "dk")
+    assert_within_sum_bound(vd.grad, dv_r, av_r, u, "dv")
     if sad is not None:
         assert maxdiff(sad.grad, dsa_r) < 5e-2 * max(1.0, dsa_r.abs().max().item())
 
@@ -93,6 +99,7 @@ def _pack(i):
     pr = P.pack_case_probe(i)
     o = torch.zeros(pr["q"].shape, dtype=torch.float64)
     dq, dk, dv = (torch.zeros(pr[x].shape, dtype=torch.float64) for x in "qkv")
+    ak, av = torch.zeros_like(dk), torch.zeros_like(dv)
     dsa = torch.zeros(c["Hq"], dtype=torch.float64)
     for a, b in zip(cu[:-1], cu[1:]):
         if b == a:
@@ -100,10 +107,10 @@ def _pack(i):
         sl = (slice(None), slice(None), slice(a, b))
         args = (pr["q"][sl], pr["k"][sl], pr["v"][sl])
         o[sl], _ = oracle_fwd(*args, ns, W, pr["s_aux"])
-        g = oracle_bwd(*args, pr["do"][sl], ns, W, pr["s_aux"])
-        dq[sl], dk[sl], dv[sl] = g[0], g[1], g[2]
+        g = oracle_bwd(*args, pr["do"][sl], ns, W, pr["s_aux"], bounds=True)
+        dq[sl], dk[sl], dv[sl], ak[sl], av[sl] = g[0], g[1], g[2], g[4], g[5]
         dsa += g[3]
-    return pr, o, dq, dk, dv, dsa
+    return pr, o, dq, dk, dv, dsa, ak, av
 
 
 @pytest.mark.parametrize("dkdv", ["rule", "asm"], indirect=True)     # (so that one cached oracle serves both)
@@ -114,7 +121,7 @@ def test_packed_mask_edges(i, dkdv):
     from sink_attention.varlen import sink_flash_attention_varlen
     c = P.VARLEN_CASES[i]
     cu = c["cu"]
-    pr, o_r, dq_r, dk_r, dv_r, dsa_r = _pack(i)
+    pr, o_r, dq_r, dk_r, dv_r, dsa_r, ak_r, av_r = _pack(i)
     qd, kd, vd = (pr[x].to(DEV).requires_grad_(True) for x in "qkv")
     sad = pr["s_aux"].to(DEV).requires_grad_(True)
     out = sink_flash_attention_varlen(qd, kd, vd, cu, num_sink=c["ns"], window_size=c["W"], s_aux=sad)
@@ -137,6 +144,10 @@ def test_packed_mask_edges(i, dkdv):
           dv_r.abs().max().item())
     assert errs["o"] < 2e-2 and errs["dq"] < 1.5e-1, errs
     assert errs["dk"] < tol["dk"] and errs["dv"] < tol["dv"], (errs, tol)
+    u = UNIT_ROUNDOFF[torch.bfloat16]
+    print(f"sum bound pack {i} {dkdv}: dK {sum_bound_ratio(kd.grad, dk_r, ak_r, u):.3f} dV {sum_bound_ratio(vd.grad, dv_r, av_r, u):.3f}")
+    assert_within_sum_bound(kd.grad, dk_r, ak_r, u, "dk")
+    assert_within_sum_bound(vd.grad, dv_r, av_r, u, "dv")
     assert maxdiff(sad.grad, dsa_r) < 1.5
 
 

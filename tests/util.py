@@ -1,4 +1,6 @@
 """Shared helpers for the GPU parity tests."""
+import math
+
 import torch
 
 from oracle import sink_oracle as O
@@ -27,12 +29,27 @@ def oracle_fwd(q, k, v, ns, W, s_aux=None, banded=None):
     return o, lse
 
 
-def oracle_bwd(q, k, v, do, ns, W, s_aux=None, banded=None):
+def oracle_bwd(q, k, v, do, ns, W, s_aux=None, banded=None, bounds=False):
+    """dQ, dK, dV, ds_aux in fp64; bounds=True: also A_K, A_V, the per-element sums assert_within_sum_bound takes, every
+    visible pair counted at least at the smallest normal number of q.dtype (fp16: 2^-14; bf16: 2^-126, nothing)"""
     N = q.shape[2]
     if banded is None:
         banded = N > 1024
     fn = O.sink_attention_bwd_banded if banded else O.sink_attention_bwd_dense
-    return fn(q.cpu(), k.cpu(), v.cpu(), do.cpu(), ns, W, None if s_aux is None else s_aux.cpu().float())
+    sa = None if s_aux is None else s_aux.cpu().float()
+    if not bounds:
+        return fn(q.cpu(), k.cpu(), v.cpu(), do.cpu(), ns, W, sa)
+    return fn(q.cpu(), k.cpu(), v.cpu(), do.cpu(), ns, W, sa, bounds=True, tiny=torch.finfo(q.dtype).tiny)
+
+
+def probe_reference(pr, ns, W):
+    """fp64 oracle of one dense probe (tests/probe_inputs.py::dense_probe): o, lse, (dq, dk, dv, ds_aux, A_K, A_V).  Shared
+    by tests/test_gpu_mask_edges.py and the CPU proofs of tests/test_probe_inputs.py, so that the bound terms the GPU
+    assertion uses are the ones whose discrimination is proved."""
+    Nq, Nk = pr["q"].shape[2], pr["k"].shape[2]
+    banded = Nq == Nk and Nq > 1024            # (the banded oracle walks N_q = N_kv only)
+    o, lse = oracle_fwd(pr["q"], pr["k"], pr["v"], ns, W, pr["s_aux"], banded=banded)
+    return o, lse, oracle_bwd(pr["q"], pr["k"], pr["v"], pr["do"], ns, W, pr["s_aux"], banded=banded, bounds=True)
 
 
 def maxdiff(a, b):
@@ -49,6 +66,94 @@ def assert_close(actual, expected, atol, rtol, what=""):
     bad = err > tol
     assert not bad.any(), (f"{what}: {int(bad.sum())}/{bad.numel()} elements out of tolerance "
                            f"(atol={atol}, rtol={rtol}); max abs err {err.max().item():.3e}")
+
+
+# unit roundoff of the storage dtype: round-to-nearest moves a value by at most u |value|
+UNIT_ROUNDOFF = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+SUM_BOUND_FACTOR = 4.0
+
+
+def sum_bound_tolerance(ref, A, u, dtype):
+    """4 u A + u max(|ref|, smallest normal number of dtype), per element"""
+    return SUM_BOUND_FACTOR * u * A + u * ref.abs().clamp(min=torch.finfo(dtype).tiny)     # (+ the result's own rounding)
+
+
+def sum_bound_ratio(got, ref, A, u):
+    """largest |got - ref| / sum_bound_tolerance over the elements (the result's dtype: got.dtype)"""
+    g, r, a = (x.detach().double().cpu() for x in (got, ref, A))
+    tol = sum_bound_tolerance(r, a, u, got.dtype)
+    err = (g - r).abs()
+    ratio = torch.where(err > 0, err / tol, torch.zeros_like(err))         # (err > 0 = tol: inf, and it fails)
+    return ratio.max().item() if ratio.numel() else 0.0
+
+
+def assert_within_sum_bound(got, ref, A, u, what=""):
+    """dK / dV element by element against the bound of their OWN sum: |got - ref| <= 4 u A + u |ref|, where A is the sum of
+    the magnitudes of the element's terms (oracle_bwd(bounds=True): A_V = P^T |dO|, A_K = scale sum_i P_ij (|dP_ij| +
+    sum_e |dO_ie O_ie|) |q_id|, over the GQA group) and u the unit roundoff of the dtype (UNIT_ROUNDOFF).
+    Where the 4 comes from (the documented arithmetic, DESIGN.md 3.x: f32 accumulation, P and dS packed to the dtype once,
+    the result rounded once): the packing moves each term by at most u |term|, i.e. the sum by at most u A; Delta is
+    rowsum(dO O) of an O that the forward already rounded, at most u sum_e |dO_e O_e| per row, which enters dS through
+    P - the second part of A_K -, so both parts together stay below u A_K; the result's own rounding is the u |ref| term
+    and |ref| <= A; f32 accumulation (2^-24 per add) is negligible.  fp16 keeps that relative precision down to 2^-14 only
+    (subnormal below, fixed spacing 2^-24): a packed term is moved by at most u max(|term|, 2^-14), which is why A counts
+    every visible pair at 2^-14 at least, and the result's rounding is u max(|ref|, 2^-14).  Worst case below 2 u A + u |ref|; the factor 4 is a
+    twofold margin over that sum and is not fitted to any kernel's output (tests/test_probe_inputs.py keeps a CPU model
+    of this arithmetic within half of the bound).  Returns the largest ratio."""
+    ratio = sum_bound_ratio(got, ref, A, u)
+    assert ratio <= 1.0, (f"{what}: |got - ref| reaches {ratio:.3f} of the sum bound 4 u A + u |ref| (u = 2^{int(math.log2(u))})")
+    return ratio
+
+
+def _rt(x, dtype):
+    """x (fp64) rounded to dtype and back"""
+    return x.to(dtype).double()
+
+
+def rounded_model_bwd(q, k, v, do, ns, W, s_aux=None, block=256):
+    """CPU model of the documented arithmetic of the MFMA kernels on inputs of dtype q.dtype: the forward
+    packs p to the dtype for P V, O is stored in the dtype, LSE in f32; Delta = rowsum(dO O) of that O, f32; the backward
+    takes p = exp2(c s - LSE log2e) in f32, packs p (for dV) and dS = p (dP - Delta) (for dQ / dK) to the dtype,
+    accumulates in f32 and rounds dQ / dK / dV to the dtype.  fp64 stands in for f32 accumulation (its 2^-24 is not
+    modelled).  N_q <= N_kv (rows are the last N_q positions), row blocks over the sink + window key ranges like the
+    banded oracle.  Returns o, dq, dk, dv in the dtype."""
+    dt = q.dtype
+    B, Hq, Nq, D = q.shape
+    Hkv, Nk = k.shape[1], k.shape[2]
+    g = Hq // Hkv
+    scale = 1.0 / math.sqrt(D)
+    o = torch.zeros(B, Hq, Nq, D, dtype=torch.float64)
+    dq = torch.zeros(B, Hq, Nq, D, dtype=torch.float64)
+    dk, dv = (torch.zeros(B, Hkv, Nk, D, dtype=torch.float64) for _ in range(2))
+    dof = do.double()
+    for r0 in range(0, Nq, block):
+        r1 = min(Nq, r0 + block)
+        pos = torch.arange(r0, r1) + (Nk - Nq)
+        p1 = int(pos[-1]) + 1
+        nsb = min(ns, p1)
+        w0 = max(int(pos[0]) - W + 1, nsb, 0)
+        cols = torch.cat([torch.arange(0, nsb), torch.arange(w0, p1) if p1 > w0 else torch.arange(0)])
+        qb, dob = q[:, :, r0:r1].double(), dof[:, :, r0:r1]
+        kb, vb = (x[:, :, cols].double().repeat_interleave(g, dim=1) for x in (k, v))
+        s = (torch.matmul(qb, kb.transpose(-2, -1)) * scale).float().double()
+        s = s.masked_fill(~O.valid_mask(pos, cols, ns, W), float("-inf"))
+        s_all = s if s_aux is None else torch.cat([s, s_aux.double().view(1, Hq, 1, 1).expand(B, Hq, r1 - r0, 1)], -1)
+        m = s_all.max(-1, keepdim=True).values
+        m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+        e = torch.exp(s - m)
+        l = torch.exp(s_all - m).sum(-1, keepdim=True)
+        lse = (m + torch.log(l)).float().double()
+        ob = _rt(torch.nan_to_num(torch.matmul(_rt(e, dt), vb) / l, nan=0.0), dt)      # packed p, f32 row sum, O stored
+        o[:, :, r0:r1] = ob
+        delta = (dob * ob).sum(-1, keepdim=True).float().double()
+        p = torch.nan_to_num(torch.exp(s - lse), nan=0.0).float().double()
+        dp = torch.matmul(dob, vb.transpose(-2, -1))
+        ds = _rt(p * (dp - delta), dt)
+        C = cols.numel()
+        dq[:, :, r0:r1] = torch.matmul(ds, kb) * scale
+        dk.index_add_(2, cols, (torch.matmul(ds.transpose(-2, -1), qb) * scale).view(B, Hkv, g, C, D).sum(2))
+        dv.index_add_(2, cols, torch.matmul(_rt(p, dt).transpose(-2, -1), dob).view(B, Hkv, g, C, D).sum(2))
+    return o.to(dt), dq.to(dt), dk.to(dt), dv.to(dt)
 
 
 def dkdv_kernel_name(mode, B, Hkv, Nq, Nk, D, window, packed=False, dtype=torch.bfloat16, ns=1):

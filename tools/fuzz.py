@@ -3,7 +3,9 @@
 N_q < N_kv / packed paths against their padded / per-sequence formulations) on random shapes.
 usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe|range]
 (skew: only shapes of the short-window dK/dV kernel - no sink keys, head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or
-packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn;
+packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn,
+and dK / dV of the MFMA kernels also judged element by element against the fp64 oracle with the sum bound of tests/util.py
+(4 u A + u |ref|), which a mask error confined to the dK/dV kernel cannot pass;
 --inputs=range: a random family of tests/range_inputs.py - logit staircases, a common offset - that moves the softmax reference)"""
 import os
 import random
@@ -15,6 +17,7 @@ import torch
 
 import probe_inputs
 import range_inputs
+import util
 
 from sink_attention.sink_flash_attention import _sink_flash_attention_ex
 from sink_attention.varlen import sink_flash_attention_varlen
@@ -50,6 +53,25 @@ def run(q, k, v, do, ns, W, sa, generic):
     return [o.detach().float(), qq.grad.float(), kk.grad.float(), vv.grad.float()] + ([ss.grad.float()] if ss is not None else [])
 
 
+def sum_bound_ratios(q, k, v, do, ns, W, sa, cu, dk, dv):
+    """largest |dK - ref| and |dV - ref| over the sum bound of tests/util.py; fp64 oracle on the CPU, one sequence and one
+    (batch, KV head) group at a time (N_q < N_kv has the dense oracle only)"""
+    worst = [0.0, 0.0]
+    cu = cu or [0, k.shape[2]]
+    off = k.shape[2] - q.shape[2]                                       # (N_q < N_kv: one sequence)
+    g, u = q.shape[1] // k.shape[1], util.UNIT_ROUNDOFF[q.dtype]
+    q, k, v, do, dk, dv = (x.cpu() for x in (q, k, v, do, dk.to(q.dtype), dv.to(q.dtype)))
+    for s0, s1 in zip(cu[:-1], cu[1:]):
+        for b in range(q.shape[0] if s1 > s0 else 0):
+            for hk in range(k.shape[1]):
+                bq, bk = (slice(b, b + 1), slice(hk * g, (hk + 1) * g)), (slice(b, b + 1), slice(hk, hk + 1), slice(s0, s1))
+                ref = util.oracle_bwd(q[bq][:, :, s0:s1 - off], k[bk], v[bk], do[bq][:, :, s0:s1 - off], ns, W,
+                                      None if sa is None else sa[bq[1]].cpu(), banded=off == 0 and s1 - s0 > 1024, bounds=True)
+                worst[0] = max(worst[0], util.sum_bound_ratio(dk[bk], ref[1], ref[4], u))
+                worst[1] = max(worst[1], util.sum_bound_ratio(dv[bk], ref[2], ref[5], u))
+    return worst
+
+
 for case in range(n_cases):
     D = rng.choice([32, 64, 80, 96, 128, 128, 256])
     Hkv = rng.choice([1, 2, 4])
@@ -66,6 +88,7 @@ for case in range(n_cases):
         D, ns, W = rng.choice([64, 80, 96]), 0, rng.choice([1, 5, 31, 64, 100, 128, 300, 512])
         mode = rng.choice(["plain", "plain", "varlen"])
     sa = (torch.randn(Hq, device="cuda") * 0.5) if aux else None
+    cu = None
     tol_o, tol_g = (2e-2, 2e-1) if dt == torch.bfloat16 else (5e-3, 6e-2)
     desc = f"{inputs} {mode} B{B} Hq{Hq} Hkv{Hkv} N{N} D{D} ns{ns} W{W} {str(dt)[6:]} aux{int(aux)}"
     try:
@@ -110,6 +133,9 @@ for case in range(n_cases):
         nan = any(torch.isnan(x).any().item() for x in a)
         lim = [tol_o, tol_g, tol_g, tol_g, tol_g * 20]
         ok = not nan and all(e <= l * max(1.0, y.abs().max().item() if y.numel() else 1.0) for e, l, y in zip(errs, lim, b))
+        if inputs == "probe" and not nan:
+            errs += sum_bound_ratios(q, k, v, do, ns, W, sa, cu if mode == "varlen" else None, a[2], a[3])
+            ok = ok and max(errs[-2:]) <= 1.0
     except Exception as e:      # noqa: BLE001 - report and continue
         ok, errs = False, [repr(e)[:200]]
     if not ok:
