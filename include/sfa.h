@@ -549,6 +549,56 @@ int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, 
                                  int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
                                  void* workspace, size_t workspace_bytes, float scale, unsigned flags, void* stream);
 
+/*
+ * Packed ragged step with draft trees and per-sequence commit (speculative decoding inside the packed step).
+ * sfa_decode_ring_ragged_slots with two more device arrays, each of which may be NULL:
+ *   parent      int32 [T], packed like q: parent[cu_q[i] + u] is the parent of node u of sequence i as a LOCAL index
+ *               in [-1, u); any other value reads as -1 (a root hanging off the cache).  Read on the device after the
+ *               clamping of cu_q, at rows [c0_i, c0_i + n_i) only, so a corrupt array cannot leave the pack.
+ *   commit_seq  int32 [n_seq]: sequence i is stored and its state row advanced iff commit != 0 && commit_seq[i] != 0.
+ *   - parent == NULL: the mask, the kernels and the output bits of sfa_decode_ring_ragged_slots.
+ *   - parent != NULL: sequence i is a TREE sequence iff n_i <= 64 and it is not admitting (SFA_FLAG_RAGGED_ADMIT and
+ *     seen == 0), decided on the device per workgroup.  A tree sequence is attended exactly as
+ *     sfa_decode_ring_tree_slots with n = n_i at its slot's state: sinks always; ring position c iff
+ *     c >= depth[u] - Wc + 1; chunk token v iff v is u or an ancestor of u and depth[u] - depth[v] <= Wc - 1.  Every
+ *     other sequence (a prompt chunk longer than 64, an admitting sequence) ignores its parent entries and takes the
+ *     mask of sfa_decode_ring_ragged_slots, so a scheduler writes u - 1 for chains of at most 64 tokens and may leave
+ *     the rest of the array stale.  With parent[t] = local(t) - 1 everywhere o is bit for bit that of
+ *     sfa_decode_ring_ragged_slots, and a sequence's o rows do not depend on its place in the pack or its neighbours.
+ *   - commit_seq == NULL: all sequences or none, by commit.  Otherwise a sequence with commit_seq[i] == 0 leaves its
+ *     buffers and state row untouched (as with commit == 0); a named one is stored with the placement of
+ *     sfa_decode_ring_ragged_slots, the admitting placement included.  Draft rows take 0 (their accepted prefix is
+ *     stored later by sfa_ring_commit_path_ragged_slots), decode rows and prompt chunks 1.  The bit set on a tree
+ *     sequence stores the WHOLE chunk in packed order: defined, and meaningful only for a chain-shaped parent.
+ * Plan, grid, workspace (sfa_decode_ragged_workspace_bytes), launches and host checks are those of
+ * sfa_decode_ring_ragged_slots.  sfa_last_path(): "decode_tree_{mfma,f32}_..._ragged..." with parent, else
+ * "decode_multi_...".
+ */
+int sfa_decode_ring_ragged_tree_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                      const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                      const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
+                                      const int32_t* parent, const int32_t* commit_seq, int commit, int32_t* state,
+                                      const int32_t* slots, const int32_t* cu_q, int n_seq, void* workspace,
+                                      size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
+/*
+ * Packed commit of accepted prefixes / tree paths: k_new / v_new [1, Hkv, T, D] (the pack of the step), count device
+ * int32 [n_seq], path device int32 [T] packed like k_new with sequence-local entries (NULL: the identity), cu_q and
+ * slots as in the packed step.  For sequence i with a = clamp(count[i], 0, n_i) the j-th stored token is packed row
+ * cu_q[i] + clamp(path[cu_q[i] + j], 0, n_i - 1) (row cu_q[i] + j without a path); tokens j in [max(0, a - Wc), a) go
+ * to ring slot (write_pos + j) mod Wc of slot slots[i], and a trailing launch advances the state row by a.  Buffers and
+ * state row are bitwise what sfa_ring_commit_path_slots (NULL path: sfa_ring_commit_slots) leaves for the sequence
+ * passed as a [1, Hkv, n_i, D] chunk.  Nothing happens for inactive slots, empty sequences, a == 0 and rows that no
+ * sequence covers.  Not an admission: sink_len never changes.  One 16-byte piece of K and of V per thread over T rows;
+ * no workspace.  Host checks before anything launches: k_new / v_new have shape[0] = 1 and share T; count, cu_q, state
+ * and slots are non-null; n_seq >= 1; alignment and dtype as for sfa_ring_commit_slots.
+ * sfa_last_path(): "ring_commit_path_ragged_slots".
+ */
+int sfa_ring_commit_path_ragged_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                      const sfa_tensor* v_new, const int32_t* count, const int32_t* path,
+                                      const int32_t* cu_q, int n_seq, int32_t* state, const int32_t* slots,
+                                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -515,8 +515,9 @@ int ring_tree(const RingCall& c) {
     return multi_workspace_and_launch(c);
 }
 
-// sfa_decode_ring_ragged_slots: every check of the slots call at the full cache; q / k_new / v_new / o share
-// shape[0] and T there
+// sfa_decode_ring_ragged_slots / sfa_decode_ring_ragged_tree_slots: every check of the slots call at the full cache;
+// q / k_new / v_new / o share shape[0] and T there.  parent and commit_seq are device arrays that may be null: nothing
+// of them is checkable on the host
 int ring_ragged(const RingCall& c) {
     int st;
     if ((st = check_multi(c))) return st;
@@ -587,6 +588,15 @@ int ring_commit_path(RingCall c, const int32_t* path, int64_t path_bstride) {
                   "path_bstride %lld: 0 (one path shared by the batch) or >= n = %lld (one row per sequence)",
                   (long long)path_bstride, (long long)n);
     if (c.mode == RingState::Rows && c.k_new->shape[0] == 0) return SFA_OK;
+    return ring_commit_dyn_launch(c);
+}
+
+// sfa_ring_commit_path_ragged_slots: the checks of sfa_ring_commit_slots on the pack, then its own
+int ring_commit_ragged(const RingCall& c) {
+    int st;
+    if ((st = check_commit(c))) return st;
+    SFA_CHECK_ARG(c.k_new->shape[0] == 1, "ring_commit_ragged: k_new / v_new must be packed [1, H_kv, T, D] (got shape[0] = %lld)",
+                  (long long)c.k_new->shape[0]);
     return ring_commit_dyn_launch(c);
 }
 
@@ -748,6 +758,20 @@ int sfa_decode_ring_ragged_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, 
     return ring_ragged(device_state(c, RingState::Rows, state, slots));
 }
 
+int sfa_decode_ring_ragged_tree_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
+                                      int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                      SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.parent = parent, c.commit_seq = commit_seq;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
 int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
@@ -815,6 +839,17 @@ int sfa_ring_commit_path_slots(SFA_COMMIT_PARAMS, const int32_t* path, int64_t p
     SFA_NEED(slots, "slots");
     return ring_commit_path(commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream),
                             path, path_bstride);
+}
+
+int sfa_ring_commit_path_ragged_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
+                                      int32_t* state, const int32_t* slots, void* stream) {
+    g_err[0] = 0;
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
+    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
+    return ring_commit_ragged(c);
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

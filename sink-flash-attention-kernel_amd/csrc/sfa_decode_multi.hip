@@ -99,6 +99,9 @@ struct RaggedArgs {
     const int* rowseq;           // [T] packed row -> sequence, -1: covered by none (padding)
     int n_seq, T;
     int admit;                   // SFA_FLAG_RAGGED_ADMIT: a sequence on a fresh slot (state row seen == 0) is admitted
+    // per-sequence commit: with `commit`, sequence i is stored and advanced iff commit_seq[i] != 0 (null: every
+    // sequence).  Read by commit_piece_ragged and ring_advance_ragged_kernel only.
+    const int* commit_seq;       // [n_seq], device, or null
 };
 
 // the second argument of a ragged kernel instance (`RA...` is empty for every other instance: its signature, argument
@@ -360,16 +363,17 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
 // edges from u up to j (to the root when j = -1), anc = u and its ancestors below j; 6 rounds cover depth 63.  When
 // the window clips the chunk (Wc < n), the Wc-th ancestor k is composed from the same jumps (bits of Wc) and
 // vis = anc[u] minus anc[k].  An entry outside [-1, u) reads as -1, so a corrupt tree cannot loop or leave the chunk.
-__device__ __forceinline__ TreeNode tree_node(const MultiArgs& a, int b, int lane) {
-    int p = lane < a.n ? a.parent[(int64_t)b * a.pstride + lane] : -1;
+// parent: the chunk's n entries (batch row b's tree; the n_i entries of a sequence of a pack), wc: the ring capacity
+__device__ __forceinline__ TreeNode tree_node(int n, const int* parent, int wc, int lane) {
+    int p = lane < n ? parent[lane] : -1;
     if (p < -1 || p >= lane) p = -1;
     int j = p, d = p >= 0 ? 1 : 0;
     uint64_t anc = 1ull << lane;
-    const bool clip = a.wc < a.n;        // otherwise depth <= n - 1 <= Wc - 1: every ancestor is in the window
+    const bool clip = wc < n;            // otherwise depth <= n - 1 <= Wc - 1: every ancestor is in the window
     int kth = lane;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-        if (clip && ((a.wc >> r) & 1)) {
+        if (clip && ((wc >> r) & 1)) {
             const int x = __shfl(j, kth < 0 ? lane : kth);
             kth = kth < 0 ? -1 : x;
         }
@@ -383,6 +387,17 @@ __device__ __forceinline__ TreeNode tree_node(const MultiArgs& a, int b, int lan
         if (kth >= 0) anc &= ~ak;
     }
     return TreeNode{d, anc};
+}
+
+__device__ __forceinline__ TreeNode tree_node(const MultiArgs& a, int b, int lane) {
+    return tree_node(a.n, a.parent + (int64_t)b * a.pstride, a.wc, lane);
+}
+
+// packed tree calls (sfa_decode_ring_ragged_tree_slots, the (Tree, Ragged) instances): sequence i of n_i tokens on
+// cache row c is a tree sequence iff n_i <= 64 and it is not admitting; its nodes are parent[c0_i .. c0_i + n_i).  Every
+// other sequence ignores its entries and takes the ragged mask.  Wave-uniform (n and the state row are).
+__device__ __forceinline__ bool ragged_is_tree(const MultiArgs& a, const RaggedArgs& rg, int c, int n) {
+    return n <= 64 && !admits(rg.admit, a.state + (int64_t)c * a.sstride);
 }
 
 // chunk tiles of a tree call: dead when no row of the block sees a key of the tile (vor = OR of the rows' vis), edge
@@ -420,12 +435,17 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-// Ragged (packed calls, with Dyn and Slots, never with Tree): the workgroup's row block comes from the table of
-// ragged_prep_kernel; it belongs to ONE sequence, whose length, first packed row and slot become the workgroup's
-// scalars (n, R, prow below), and everything else runs as for B = 1.
+// Ragged (packed calls, with Dyn and Slots): the workgroup's row block comes from the table of ragged_prep_kernel; it
+// belongs to ONE sequence, whose length, first packed row and slot become the workgroup's scalars (n, R, prow below),
+// and everything else runs as for B = 1.  With Tree the workgroup scalar is_tree (ragged_is_tree) says whether the
+// sequence takes the tree prologue, tile classes and chunk mask, or the code a (Ragged, no Tree) instance runs.
+// waves_per_eu: the (Tree, Ragged) instance of D = 80 asks for the two waves per SIMD of its tree _slots sibling (the
+// allocator then fits it into 226 VGPRs without scratch; left alone it takes 233 + 48 and one wave).  1 = the default of
+// every other instance, whose code does not change.
 template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
-__global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (Tree || !Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+__global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && Ragged && D == 80) ? 2 : 1)))
+void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -480,8 +500,13 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     // tree: the lane's row is node tq at depth td; [tmin, tmax] becomes the block's depth range over its live rows
     int td = tq;
     uint64_t tvis = 0, vor = 0;
-    if constexpr (Tree) {
-        const TreeNode me = tree_node(a, b, lane);
+    // a pack: per sequence (the whole workgroup takes one side)
+    [[maybe_unused]] bool is_tree = Tree;
+    if constexpr (Tree && Ragged) is_tree = __builtin_amdgcn_readfirstlane((int)ragged_is_tree(a, rg, c, rn)) != 0;
+    if (Tree && is_tree) {
+        TreeNode me;
+        if constexpr (Ragged) me = tree_node(rn, a.parent + prow, a.wc, lane);
+        else me = tree_node(a, b, lane);
         // every lane runs the cross-lane reads (a source lane masked off by a branch would read as 0), then selects
         td = __shfl(me.depth, tq);
         const uint64_t v = shfl64(me.vis, tq);
@@ -560,7 +585,8 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
             ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
-            cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
+            if (Tree && Ragged && !is_tree) cls = tile_class(a, ti, tmin, tmax, f.nsk);
+            else cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
             if (cls != 0) break;
         }
         return i;
@@ -592,6 +618,13 @@ __global__ __launch_bounds__(kWaves * 64) void multi_split_mfma_kernel(MultiArgs
             for (int i = 0; i < 16; ++i) {
                 const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
                 s[i] = key_visible_admit(a, f, cur, kk, td) ? s[i] : -INFINITY;
+            }
+        } else if (Tree && Ragged && ccls == 2 && !(is_tree && cur.seg == 2)) {
+            // a tile outside a tree's chunk: the ragged instance's loop (td = the depth for a tree sequence)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                s[i] = key_visible(a, f, cur, kk, td) ? s[i] : -INFINITY;
             }
         } else if (ccls == 2) {
 #pragma unroll
@@ -729,7 +762,7 @@ __device__ __forceinline__ bool ragged_row(const MultiArgs& a, const RaggedArgs&
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
 template <typename T, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (Tree || !Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
@@ -767,8 +800,13 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA...
     float m = -INFINITY, l = 0.f;
     int td = t;   // tree: the row's node t at depth td, chunk keys vis (wave-uniform)
     uint64_t vis = 0;
-    if constexpr (Tree) {
-        const TreeNode me = tree_node(a, b, lane);
+    // a pack: per sequence, so per wave (ragged_is_tree)
+    [[maybe_unused]] bool is_tree = Tree;
+    if constexpr (Tree && Ragged) is_tree = __builtin_amdgcn_readfirstlane((int)ragged_is_tree(a, rg, c, rn)) != 0;
+    if (Tree && is_tree) {
+        TreeNode me;
+        if constexpr (Ragged) me = tree_node(rn, a.parent + prow, a.wc, lane);
+        else me = tree_node(a, b, lane);
         td = __builtin_amdgcn_readfirstlane(__shfl(me.depth, t));
         const uint64_t v = shfl64(me.vis, t);
         vis = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
@@ -778,10 +816,14 @@ __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA...
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     for (int i = tbeg; i < tend; ++i) {
         const TileInfo ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
-        if (tile_class_t<Tree>(a, ti, td, td, vis, f.nsk) == 0) continue;
+        if ((Tree && Ragged && !is_tree ? tile_class(a, ti, td, td, f.nsk) : tile_class_t<Tree>(a, ti, td, td, vis, f.nsk)) == 0) continue;
         const bool adm = Ragged && admitting(f, ti);
+        const bool plain = Tree && Ragged && !is_tree;      // a chain or admitting sequence of a packed tree call
         for (int kk = 0; kk < ti.count; ++kk) {
-            if (!(adm ? key_visible_admit(a, f, ti, kk, td) : key_visible_t<Tree>(a, f, ti, kk, td, vis))) continue;
+            if (!(adm     ? key_visible_admit(a, f, ti, kk, td)
+                  : plain ? key_visible(a, f, ti, kk, td)
+                          : key_visible_t<Tree>(a, f, ti, kk, td, vis)))
+                continue;
             const T* kp = reinterpret_cast<const T*>(ti.k + kk * ti.ksn);
             const T* vp = reinterpret_cast<const T*>(ti.v + kk * ti.vsn);
             float x = 0.f;
@@ -860,6 +902,7 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // (n_i tokens, slot c): stored iff t >= n_i - Wc, into ring slot (write_pos_c + t) mod Wc - what commit_piece<false, true>
 // stores for a batch row of n_i tokens.  Rows of no sequence and of inactive sequences store nothing.
 // An admitting sequence (admits()) takes the prefill placement instead: token t goes to row fill_dst of its slot.
+// A sequence whose commit_seq entry is 0 stores nothing.
 __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es) {
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
@@ -869,6 +912,7 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
     const int hk = (int)(rest / rg.T);
     const int seq = rg.rowseq[tp];
     if (seq < 0) return;
+    if (rg.commit_seq && !rg.commit_seq[seq]) return;
     const int c = cache_row<true>(a, seq);
     if (c < 0) return;
     const RaggedSeq s = ragged_seq(rg, seq);
@@ -986,6 +1030,47 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
     commit_piece<Path, true>(a, (int64_t)blockIdx.x * 256 + threadIdx.x, es, count);
 }
 
+// sfa_ring_commit_path_ragged_slots: the path commit of a pack, item = (hk * T + packed row) * cpr + ch.  The call has
+// no preparation launch: the thread finds its row's sequence i by the binary search of ragged_prep_kernel.  Its row is
+// position j of the sequence: with acc = clamp(count[i], 0, n_i), positions [max(0, acc - Wc), acc) store packed row
+// c0_i + clamp(path[c0_i + j], 0, n_i - 1) (row c0_i + j without a path) into ring slot (write_pos + j) mod Wc of slot
+// slots[i] - the piece commit_piece<Path, true> stores for the sequence passed as a [1, Hkv, n_i, D] chunk.
+__global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es) {
+    const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int cpr = a.D * es / 16;
+    if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
+    const int ch = (int)(item % cpr);
+    const int64_t rest = item / cpr;
+    const int tp = (int)(rest % rg.T);
+    const int hk = (int)(rest / rg.T);
+    int lo = 0, hi = rg.n_seq - 1;           // the last sequence that starts at or before the row
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (ragged_seq(rg, mid).c0 <= tp) lo = mid;
+        else hi = mid - 1;
+    }
+    const RaggedSeq s = ragged_seq(rg, lo);
+    const int j = tp - s.c0;
+    if (j < 0 || j >= s.n) return;           // a row no sequence covers
+    const int c = cache_row<true>(a, lo);
+    if (c < 0) return;
+    const int last = clamp_count(count + lo, s.n);
+    if (j >= last || j < last - a.wc) return;
+    const int slot = (int)(((int64_t)state_wp(a, c) + j) % a.wc);
+    int src = j;
+    if (a.path) {
+        src = a.path[s.c0 + j];
+        src = src < 0 ? 0 : (src >= s.n ? s.n - 1 : src);
+    }
+    const int64_t so = (int64_t)ch * 16, row = (int64_t)s.c0 + src;
+    const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + row * a.kn.sn) * es + so;
+    const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + row * a.vn.sn) * es + so;
+    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
+    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
+    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+}
+
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
 // K/V, one 16-byte piece per thread.  item = ((b * Hkv + hk) * (ns + Wc) + j) * cpr + ch: j < ns is sink row j, j >= ns
 // ring slot s = j - ns.  Sequence b = rows [cu[b], cu[b + 1]) of length L (offsets clamped into [0, T], so that bad
@@ -1062,13 +1147,17 @@ __global__ void ring_advance_slots_kernel(int* state, const int* count, int n, i
 
 // the same for a packed call: thread r advances state row slots[r] by n_r = the length of sequence r; an inactive or
 // empty sequence moves nothing.  An admitting sequence (flag, seen == 0: this launch is the first writer of the row)
-// gets the state of its prefill placement.
-__global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int ns, int wc, const int* slots, int npool) {
+// gets the state of its prefill placement.  commit_seq (per-sequence commit): a sequence whose entry is 0 moves nothing.
+// count (sfa_ring_commit_path_ragged_slots): by clamp(count[r], 0, n_r) in place of n_r.
+__global__ void ring_advance_ragged_kernel(int* state, RaggedArgs rg, int ns, int wc, const int* slots, int npool,
+                                           const int* count) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (r >= rg.n_seq) return;
     const int c = slots[r];
     if ((unsigned)c >= (unsigned)npool) return;
-    const int acc = ragged_seq(rg, r).n;
+    if (rg.commit_seq && !rg.commit_seq[r]) return;
+    const int n = ragged_seq(rg, r).n;
+    const int acc = count ? clamp_count(count + r, n) : n;
     if (!acc) return;
     int* st = state + (int64_t)c * 4;
     if (admits(rg.admit, st)) fill_state(fill_place(acc, ns, wc), st);
@@ -1082,7 +1171,7 @@ int launch_advance(const MultiArgs& a, const int* count, const RaggedArgs* rg, h
     if (nrow <= 0) return SFA_OK;
     const dim3 grid((unsigned)cdiv64(nrow, 256)), block(nrow < 256 ? nrow : 256);
     if (rg) {
-        ring_advance_ragged_kernel<<<grid, block, 0, stream>>>(state, *rg, a.ns, a.wc, a.slots, a.npool);
+        ring_advance_ragged_kernel<<<grid, block, 0, stream>>>(state, *rg, a.ns, a.wc, a.slots, a.npool, count);
         return launch_status("ring_advance_ragged");
     }
     if (a.slots) {
@@ -1121,7 +1210,8 @@ struct Mode {
 
 template <typename F>
 void dispatch_mode(const MultiArgs& a, const RaggedArgs* rg, F&& f) {
-    if (rg) f(Mode<true, false, true, true>{});                                   // packed: slots and device rows
+    if (rg && a.parent) f(Mode<true, true, true, true>{});                        // packed: slots and device rows
+    else if (rg) f(Mode<true, false, true, true>{});
     else if (a.slots && a.parent) f(Mode<true, true, true, false>{});             // slot calls: device rows
     else if (a.slots) f(Mode<true, false, true, false>{});
     else if (a.state && a.parent) f(Mode<true, true, false, false>{});
@@ -1334,7 +1424,8 @@ int decode_ragged_launch(const RingCall& c) {
     int2* blk = reinterpret_cast<int2*>(tab);
     int* rowseq = reinterpret_cast<int*>(tab + al256((size_t)g.nrb * sizeof(int2)));
     const int admit = (c.flags & SFA_FLAG_RAGGED_ADMIT) ? 1 : 0;
-    const RaggedArgs rg{c.cu_q, blk, rowseq, c.n_seq, (int)T, admit};
+    const RaggedArgs rg{c.cu_q, blk, rowseq, c.n_seq, (int)T, admit, c.commit_seq};
+    a.pstride = 0;                                  // parent is packed like q: a tree sequence reads parent + its first row
     if ((int64_t)a.Hkv * a.Sw * g.nrb >= (1ll << 31) || cdiv64(g.rows, 4) >= (1ll << 31) - 65536 ||
         cdiv64(g.rows, 4) + cdiv64((int64_t)a.Hkv * T * (a.D * 4 / 16), 256) >= (1ll << 31)) {
         set_error("decode_ragged: grid too large");
@@ -1347,8 +1438,9 @@ int decode_ragged_launch(const RingCall& c) {
     const char* dname;
     if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
-    if (mfma) set_path("decode_multi_mfma_%s_d%d_rb%d_ragged%s%s", dname, a.D, a.nrb, ad, cm);
-    else set_path("decode_multi_f32_%s_d%d_ragged%s%s", dname, a.D, ad, cm);
+    const char* fam = c.parent ? "tree" : "multi";
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s", fam, dname, a.D, a.nrb, ad, cm);
+    else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }
 
@@ -1356,6 +1448,22 @@ int ring_commit_dyn_launch(const RingCall& c) {
     const MultiArgs a = multi_args(c, false);
     const bool rows = c.mode == RingState::Rows;
     const int es = dtype_size(c.k_new->dtype);
+    if (c.cu_q) {       // the pack: one piece per (KV head, packed row, 16 bytes), the advance by clamp(count[i], 0, n_i)
+        const RaggedArgs rg{c.cu_q, nullptr, nullptr, c.n_seq, a.n, 0, nullptr};
+        const int64_t nb = cdiv64((int64_t)a.Hkv * a.n * (a.D * (int64_t)es / 16), 256);
+        if (nb >= (1ll << 31)) {
+            set_error("ring_commit: grid too large");
+            return SFA_ERR_UNSUPPORTED;
+        }
+        int st;
+        if (nb > 0) {
+            ring_commit_ragged_kernel<<<dim3((unsigned)nb), 256, 0, c.stream>>>(a, rg, c.count, es);
+            if ((st = launch_status("ring_commit_path_ragged"))) return st;
+        }
+        if ((st = launch_advance(a, c.count, &rg, c.stream))) return st;   // after every reader of the state
+        set_path("ring_commit_path_ragged_slots");
+        return SFA_OK;
+    }
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
     const int64_t nblk = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)es / 16), 256);
     if (nblk >= (1ll << 31)) {

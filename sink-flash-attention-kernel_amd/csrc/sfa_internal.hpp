@@ -54,7 +54,7 @@ struct RingCall {
     hipStream_t stream;
     void* workspace;
     size_t workspace_bytes;
-    int commit;                  // store the chunk and advance the state after the attention (never with `parent`)
+    int commit;                  // store the chunk and advance the state after the attention (with `parent`: packed calls only)
     RingState mode;
     // Host: the state.  Shared / Rows: the FULL cache (every sink row, every ring slot, write_pos 0) - launch geometry
     // and workspace cover every fill level, each workgroup reads its row of `state` and replans
@@ -73,6 +73,10 @@ struct RingCall {
     // packed call: q / k_new / v_new / o are [1, H, T, D], sequence i = rows [cu_q[i], cu_q[i + 1]) on slot slots[i]
     const int32_t* cu_q;
     int n_seq;
+    // packed call with per-sequence commit: with `commit`, sequence i is stored and advanced iff commit_seq[i] != 0
+    // (null: every sequence).  In a packed call `parent` is [T], packed like q, with sequence-local entries, and a
+    // packed commit (cu_q set) takes `path` [T] and `count` [n_seq] the same way
+    const int32_t* commit_seq;
 };
 
 // sfa_decode.hip
@@ -95,7 +99,7 @@ int decode_multi_check_head_dim(int64_t D, int dtype);
 size_t decode_multi_workspace(int64_t B, int64_t Hq, int64_t Hkv, int64_t n_new, int64_t Nkv, int64_t D, int dtype);
 int decode_multi_launch(const RingCall& c);      // sfa_decode_ring_multi* / sfa_decode_ring_tree*
 
-// sfa_decode_ring_ragged_slots.  Workspace: partials for T packed rows plus the tables of the preparation launch
+// sfa_decode_ring_ragged_slots / sfa_decode_ring_ragged_tree_slots.  Workspace: partials for T packed rows plus the tables of the preparation launch
 size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
 int decode_ragged_launch(const RingCall& c);
 

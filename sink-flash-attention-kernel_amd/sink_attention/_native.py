@@ -153,6 +153,12 @@ def _bind(lib):
     lib.sfa_decode_ragged_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i32]
     lib.sfa_decode_ring_ragged_slots.restype = i32
     lib.sfa_decode_ring_ragged_slots.argtypes = [P, P, P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp, sz, f32, u32, vp]
+    # ... with draft trees (`parent`) and per-sequence commit (`commit_seq`) before `commit`; the packed path commit
+    lib.sfa_decode_ring_ragged_tree_slots.restype = i32
+    lib.sfa_decode_ring_ragged_tree_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, f32,
+                                                      u32, vp]
+    lib.sfa_ring_commit_path_ragged_slots.restype = i32
+    lib.sfa_ring_commit_path_ragged_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp]
 
 
 def lib():

@@ -741,7 +741,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                        commit: bool = True, admit: bool = False) -> torch.Tensor:
+                        commit: bool = True, admit: bool = False, parent=None, commit_seq=None) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -762,7 +762,16 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``admit=False``, so one captured step serves admission, chunked prefill, decode and draft rows:
         ``release_slots``, ``packed_positions``, then this call.  A first chunk shorter than ``num_sink`` pins only its
         own tokens as sinks (later tokens go to the ring, as ``append`` after a short prompt does): a scheduler should
-        give an admitting chunk at least ``min(prompt, num_sink)`` tokens."""
+        give an admitting chunk at least ``min(prompt, num_sink)`` tokens.
+
+        ``parent`` / ``commit_seq`` (``sfa_decode_ring_ragged_tree_slots``; both None: the call above, unchanged).
+        ``parent`` ``[T]``, packed like ``q``: ``parent[cu_q[i] + u]`` is the parent of node u of sequence i as a local
+        index in [-1, u), anything else reads as -1.  A sequence of at most 64 tokens that is not admitting is then a draft
+        tree, attended as ``extend_attention_tree_dyn(slots=)`` of its chunk; longer and admitting sequences ignore their
+        entries.  Write ``u - 1`` for chains (decode rows, short chunks, chain drafts).  ``commit_seq`` ``[n_seq]``:
+        with ``commit``, sequence i is stored and advanced iff ``commit_seq[i] != 0`` - 1 for decode rows and prompt
+        chunks, 0 for draft rows, whose accepted prefix ``commit_packed_dyn`` stores afterwards.  Device int32 tensors are
+        taken as they are and never read on the host; host lists are checked for their length (T, n_seq)."""
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
@@ -775,6 +784,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         n_seq = cu.numel() - 1
         slots = self._slots_arg(slots, n_seq, writes=bool(commit))
         N.require_gpu(slots)
+        parent = self._packed_i32(parent, T, "parent", "T", q.device)
+        commit_seq = self._packed_i32(commit_seq, n_seq, "commit_seq", "n_seq", q.device)
         st = getattr(self, "_ragged_state", None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype)
         if st is None or st["key"] != key:
@@ -789,21 +800,81 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if out is None:
             out = torch.empty((1, H_q, T, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
+        name, mid = "sfa_decode_ring_ragged_slots", ()
+        if parent is not None or commit_seq is not None:
+            name = "sfa_decode_ring_ragged_tree_slots"
+            mid = (None if parent is None else parent.data_ptr(), None if commit_seq is None else commit_seq.data_ptr())
         with torch.cuda.device(q.device):
-            rc = st["lib"].sfa_decode_ring_ragged_slots(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new),
-                                                        N.desc(out), aux,
-                                                        1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
-                                                        cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
-                                                        st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
-                                                        N.stream_ptr(q.device))
-        N.check(rc, "sfa_decode_ring_ragged_slots")
+            rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
+                                          1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
+                                          cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
+                                          st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
+                                          N.stream_ptr(q.device))
+        N.check(rc, name)
         return out
+
+    @staticmethod
+    def _packed_i32(x, n, what, nname, device):
+        """A per-row / per-sequence int32 array of a packed call (None stays None): a device tensor is passed through
+        unread (a cast / copy kernel at most), a host list / CPU tensor is checked for its length and uploaded."""
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool or x.dim() != 1:
+                raise TypeError(f"{what} must be a 1-D integer tensor")
+            lst = None if x.is_cuda else x.tolist()
+        else:
+            lst = [int(v) for v in x]
+        if (len(lst) if lst is not None else x.numel()) != n:
+            raise ValueError(f"{what} must hold {nname} = {n} entries, got {len(lst) if lst is not None else x.numel()}")
+        if lst is not None:
+            return torch.tensor(lst, dtype=torch.int32, device=device)
+        return x.to(device=device, dtype=torch.int32).contiguous()
+
+    def commit_packed_dyn(self, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots, count, path=None) -> None:
+        """Store the accepted prefixes / tree paths of a packed step (``sfa_ring_commit_path_ragged_slots``): ``k_new`` /
+        ``v_new`` ``[1, H_kv, T, D]`` are the pack of the step, ``count`` ``[n_seq]`` the accepted tokens per sequence,
+        ``path`` ``[T]`` (packed like ``k_new``, sequence-local entries; None: the identity) the order.  For sequence i
+        with ``a = clamp(count[i], 0, n_i)`` the packed rows ``cu_q[i] + path[cu_q[i] : cu_q[i] + a]`` (entries clamped
+        into [0, n_i)) enter the ring of slot ``slots[i]`` in that order and its state row advances by a: buffers and
+        state are what ``commit_path_dyn(slots=)`` (``commit_dyn(slots=)`` without a path) leaves for the sequence's
+        slice.  Inactive and empty sequences, ``a == 0`` and rows behind ``cu_q[-1]`` change nothing; never an admission.
+        No host sync (``spec_tree.greedy_accept_packed`` gives ``path`` and ``count``); device tensors are not read on
+        the host, host lists are checked for their length."""
+        from . import _native as N
+        dev_state = self._require_pool("commit_packed_dyn")
+        N.require_gpu(k_new, v_new, self.window_k)
+        _S, H_kv, _w, D = self.window_k.shape
+        if k_new.dim() != 4 or k_new.shape[0] != 1 or k_new.shape[1] != H_kv or k_new.shape[3] != D or \
+                v_new.shape != k_new.shape or k_new.shape[2] < 1:
+            raise ValueError(f"k_new / v_new must be packed [1, H_kv, T, D] = [1, {H_kv}, T, {D}], got {tuple(k_new.shape)}")
+        if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
+            raise TypeError("k_new / v_new must have the cache buffers' dtype")
+        T = k_new.shape[2]
+        cu = self._cu_arg(cu_q, T, k_new.device)
+        n_seq = cu.numel() - 1
+        slots = self._slots_arg(slots, n_seq, writes=True)
+        count = self._packed_i32(count, n_seq, "count", "n_seq", k_new.device)
+        if count is None:
+            raise TypeError("count must be an integer tensor or list of n_seq entries")
+        path = self._packed_i32(path, T, "path", "T", k_new.device)
+        N.require_gpu(slots)
+        k_new, v_new = self._rows16(k_new), self._rows16(v_new)
+        wk, wv = self._ring_descs()
+        with torch.cuda.device(k_new.device):
+            rc = N.lib().sfa_ring_commit_path_ragged_slots(wk, wv, N.desc(k_new), N.desc(v_new), count.data_ptr(),
+                                                           None if path is None else path.data_ptr(), cu.data_ptr(),
+                                                           n_seq, dev_state.data_ptr(), slots.data_ptr(),
+                                                           N.stream_ptr(k_new.device))
+        N.check(rc, "sfa_ring_commit_path_ragged_slots")
 
     def packed_positions(self, cu_q, slots, T: int) -> torch.Tensor:
         """RoPE positions of a packed step: for packed row ``cu_q[i] + t`` of sequence i, ``seen[slots[i]] + t``; -1 for
         rows behind ``cu_q[-1]`` (padding) and for rows of inactive sequences.  ``[T]`` int64, built from torch ops on
         the tensors' device (``bucketize`` over ``arange(T)``: no sync, capturable); call it before the committing
-        ``ragged_step_dyn`` of the step, which moves ``seen``."""
+        ``ragged_step_dyn`` of the step, which moves ``seen``.  With draft trees in the pack (``parent=``) node u sits
+        at ``seen + depth[u]``: ``pos - spec_tree.packed_local(cu_q, T) + spec_tree.packed_tree_depth(parent, cu_q, T)``
+        for the rows with ``pos >= 0``."""
         dev_state = self._require_pool("packed_positions")
         cu = cu_q if isinstance(cu_q, torch.Tensor) else torch.tensor([int(x) for x in cu_q], device=dev_state.device)
         sl = slots if isinstance(slots, torch.Tensor) else torch.tensor([int(x) for x in slots], device=dev_state.device)
@@ -951,11 +1022,16 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
-                        commit=True, admit: bool = False):
+                        commit=True, admit: bool = False, parent=None, commit_seq=None):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
-        ``admit=True`` takes sequences on fresh slots from position 0 in the same call."""
+        ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
+        draft trees in the pack and per-sequence commit."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
-                                                      commit=commit, admit=admit)
+                                                      commit=commit, admit=admit, parent=parent, commit_seq=commit_seq)
+
+    def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
+        """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""
+        self._layer(layer_idx).commit_packed_dyn(key_states, value_states, cu_q, slots, count, path=path)
 
     def packed_positions(self, cu_q, slots, T: int, layer_idx: int = 0) -> torch.Tensor:
         """``SinkCacheLayer.packed_positions`` of one layer: the RoPE position of every packed row (-1: no row)."""

@@ -9,6 +9,15 @@ host sync (no ``.item()``, no data-dependent shapes), so a whole verify / accept
     out = layer.extend_attention_tree_dyn(q, k, v, parent)      # every layer
     path, count = greedy_accept(parent, draft_tokens, target_tokens)
     layer.commit_path_dyn(k, v, path, count)                    # every layer
+
+Packed steps (``SinkCacheLayer.ragged_step_dyn(parent=, commit_seq=)``): ``parent`` is one ``[T]`` array packed like q
+with sequence-local entries, and a sequence of at most ``MAX_TREE`` = 64 tokens is a tree.  The ``packed_*`` helpers
+scatter the pack into ``[n_seq, 64]`` rows, run the helpers above and gather back, with the same no-sync rule:
+
+    pos = layer.packed_positions(cu_q, slots, T) - packed_local(cu_q, T) + packed_tree_depth(parent, cu_q, T)
+    out = layer.ragged_step_dyn(q, k, v, cu_q, slots, admit=True, parent=parent, commit_seq=commit_seq)
+    path, count = greedy_accept_packed(parent, draft_tokens, target_tokens, cu_q, n_seq)
+    layer.commit_packed_dyn(k, v, cu_q, slots, count * (1 - commit_seq), path)
 """
 import torch
 
@@ -88,3 +97,70 @@ def greedy_accept(parent: torch.Tensor, draft_tokens: torch.Tensor, target_token
     if squeeze:
         path, count = path[0], count[0]
     return path, count
+
+
+MAX_TREE = 64        # a sequence of a pack with more tokens is a chain (a prompt chunk): the kernels' rule
+
+
+def _packed_rows(cu_q: torch.Tensor, T: int):
+    """Per packed row: (sequence, local index, covered) and per sequence its length, with the kernels' reading of
+    ``cu_q`` (offsets clamped into [0, T], an end before its start reads as the start)."""
+    cu = cu_q.long().clamp(0, int(T))
+    n_seq = cu.numel() - 1
+    c0 = cu[:n_seq]
+    c1 = torch.maximum(cu[1:], c0)
+    rows = torch.arange(int(T), device=cu.device)
+    # the last sequence that starts at or before the row (empty sequences share a start with their successor)
+    seq = (torch.bucketize(rows, c0.contiguous(), right=True) - 1).clamp(0, n_seq - 1)
+    local = rows - c0[seq]
+    covered = (local >= 0) & (rows < c1[seq])
+    return seq, local, covered, c1 - c0
+
+
+def _scatter_rows(x: torch.Tensor, seq, local, tree_row, n_seq: int, fill: int) -> torch.Tensor:
+    """[T] -> [n_seq, MAX_TREE]: row (seq, local) <- x for the rows of tree sequences, ``fill`` elsewhere.  The other
+    rows go to a spare row that is cut off, so that no index depends on the data."""
+    out = torch.full((n_seq + 1, MAX_TREE), fill, dtype=torch.long, device=x.device)
+    out[torch.where(tree_row, seq, torch.full_like(seq, n_seq)), torch.where(tree_row, local, torch.zeros_like(local))] = \
+        torch.where(tree_row, x.long(), torch.full_like(seq, fill))
+    return out[:n_seq]
+
+
+def packed_local(cu_q: torch.Tensor, T: int) -> torch.Tensor:
+    """[T] int64: the index of every packed row within its sequence (0 for rows that no sequence covers)."""
+    _seq, local, covered, _n = _packed_rows(cu_q, T)
+    return torch.where(covered, local, torch.zeros_like(local))
+
+
+def packed_tree_depth(parent: torch.Tensor, cu_q: torch.Tensor, T: int) -> torch.Tensor:
+    """[T] int64 for the ``parent`` [T] of a packed step: the tree depth of a row of a sequence of at most 64 tokens, the
+    local index for a longer sequence (a chain to the kernels, whatever ``parent`` holds) and 0 for rows that no
+    sequence covers.  The RoPE position of a packed row is ``packed_positions(...) - packed_local(cu_q, T) + this``; an
+    admitting sequence (``admit=True`` on a fresh slot) is a chain to the kernels too, so give it a chain ``parent``."""
+    seq, local, covered, n = _packed_rows(cu_q, T)
+    tree_row = covered & (n[seq] <= MAX_TREE)
+    depth = tree_depth(_scatter_rows(parent, seq, local, tree_row, n.numel(), -1))
+    d = depth[seq, local.clamp(0, MAX_TREE - 1)]
+    return torch.where(tree_row, d, torch.where(covered, local, torch.zeros_like(local)))
+
+
+def greedy_accept_packed(parent: torch.Tensor, draft_tokens: torch.Tensor, target_tokens: torch.Tensor,
+                         cu_q: torch.Tensor, n_seq: int):
+    """``greedy_accept`` for every sequence of a pack: ``parent``, ``draft_tokens`` and ``target_tokens`` are [T], packed
+    like q.  Returns ``(path [T], count [n_seq])``, int64, as ``commit_packed_dyn`` takes them: ``path[cu_q[i] + j]`` is
+    the local index of the j-th accepted node of sequence i (root first; entries past ``count[i]`` are unspecified but
+    in [0, n_i)).  A sequence of more than 64 tokens is a chain: ``count = n_i`` and the identity path; an empty one
+    has ``count = 0``.  A sequence that the step itself has stored (``commit_seq[i] = 1``) must not be stored again:
+    pass ``count * (1 - commit_seq)`` to ``commit_packed_dyn``."""
+    T = parent.shape[0]
+    if cu_q.numel() != n_seq + 1:
+        raise ValueError(f"cu_q must hold n_seq + 1 = {n_seq + 1} offsets, got {cu_q.numel()}")
+    seq, local, covered, n = _packed_rows(cu_q, T)
+    tree_row = covered & (n[seq] <= MAX_TREE)
+    rows = [_scatter_rows(x, seq, local, tree_row, n_seq, f) for x, f in ((parent, -1), (draft_tokens, 0),
+                                                                            (target_tokens, 0))]
+    path, count = greedy_accept(*rows)                                       # [n_seq, 64], [n_seq]
+    p = path[seq, local.clamp(0, MAX_TREE - 1)]
+    path_packed = torch.where(tree_row, p, torch.where(covered, local, torch.zeros_like(local)))
+    count = torch.where(n <= MAX_TREE, torch.minimum(count, n), n)
+    return path_packed, count

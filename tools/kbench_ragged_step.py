@@ -16,12 +16,17 @@ Variants per (W, step), alternating in one process:
 --admit: the admission mix instead of the variants above.  The longest sequence and the first two decode rows sit on FRESH
     slots and are admitted by the call; commit is off (a dry run), so that the slots stay fresh and every call does the
     same work.  Variants: admit_mix (admit=True) and dry (the same pack, every slot full, admit=False, commit off).
+--tree: the speculative step instead: 4 decode rows + 4 draft trees of 16 nodes (binary trees, 4 nodes accepted) + one
+    prefill chunk of 256 tokens on a pool of 9 slots.  Variants: packed_tree = one ragged_step_dyn(parent=, commit_seq=)
+    that stores the decode rows and the chunk, plus one commit_packed_dyn for the accepted paths; split_up = what was
+    possible before: a ragged_step_dyn for the 5 sequences that do not speculate, plus extend_attention_tree_dyn(slots=)
+    and commit_path_dyn(slots=) for the 4 trees.  Skipped where the library lacks the packed tree call.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
 --mode kernels: --calls calls of each variant after 5 warm-up calls, in the order above, for a kernel trace of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o rstep -- python tools/kbench_ragged_step.py --mode kernels
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
-usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]"""
+usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...] [--admit | --tree]"""
 import argparse
 import csv
 import os
@@ -37,7 +42,7 @@ VARIANTS = ("ragged", "per_len", "padded")
 KINDS = ("prep", "split", "reduce", "advance")
 
 
-def _pool(torch, W, dev, dt):
+def _pool(torch, W, dev, dt, S=S):
     from sink_attention import SinkCacheLayer
     layer = SinkCacheLayer(NS, W)
     layer.init_pool(S, HKV, D, dt, dev)
@@ -45,6 +50,52 @@ def _pool(torch, W, dev, dt):
     k = torch.randn(1, HKV, S * pre, D, device=dev, dtype=dt)
     layer.prefill_slots(k, torch.randn_like(k), [pre * i for i in range(S + 1)], list(range(S)))
     return layer
+
+
+TREE_STEP = [1] * 4 + [16] * 4 + [256]          # --tree: decode rows, draft trees, one prompt chunk
+TREE_N, TREE_ACCEPT = 16, 4
+
+
+def _tree_variants(torch, W, dev, dt):
+    """--tree: the packed speculative step against the same step split into the calls that existed before"""
+    sa = torch.randn(HQ, device=dev) * 0.5
+    mk = lambda rows, h, n: torch.randn(rows, h, n, D, device=dev, dtype=dt)
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)
+    lengths, ns = TREE_STEP, len(TREE_STEP)
+    cu = [sum(lengths[:i]) for i in range(ns + 1)]
+    T = cu[-1]
+    tree = [(u - 1) // 2 if u else -1 for u in range(TREE_N)]              # binary
+    walk = [0, 1, 3, 7] + [0] * (TREE_N - TREE_ACCEPT)                     # its leftmost root-to-depth-3 path
+    is_tree = [n == TREE_N for n in lengths]
+    parent = sum((tree if t else list(range(-1, n - 1)) for n, t in zip(lengths, is_tree)), [])
+    path = sum((walk if t else list(range(n)) for n, t in zip(lengths, is_tree)), [])
+    q, k, v, o = mk(1, HQ, T), mk(1, HKV, T), mk(1, HKV, T), torch.empty(1, HQ, T, D, device=dev, dtype=dt)
+    a = dict(cu=i32(cu), slots=i32(list(range(ns))), parent=i32(parent), path=i32(path),
+             commit_seq=i32([0 if t else 1 for t in is_tree]), count=i32([TREE_ACCEPT if t else 0 for t in is_tree]))
+    pool = _pool(torch, W, dev, dt, ns)
+
+    def packed_tree():
+        pool.ragged_step_dyn(q, k, v, a["cu"], a["slots"], s_aux=sa, out=o, commit=True, parent=a["parent"],
+                             commit_seq=a["commit_seq"])
+        pool.commit_packed_dyn(k, v, a["cu"], a["slots"], a["count"], path=a["path"])
+
+    rest = [i for i in range(ns) if not is_tree[i]]
+    trees = [i for i in range(ns) if is_tree[i]]
+    lr = [lengths[i] for i in rest]
+    Tr = sum(lr)
+    qr, kr, vr, orr = mk(1, HQ, Tr), mk(1, HKV, Tr), mk(1, HKV, Tr), torch.empty(1, HQ, Tr, D, device=dev, dtype=dt)
+    b = dict(cu=i32([sum(lr[:i]) for i in range(len(lr) + 1)]), slots=i32(rest), tslots=i32(trees),
+             parent=i32([tree] * len(trees)), path=i32([walk] * len(trees)), count=i32([TREE_ACCEPT] * len(trees)))
+    qt, kt, vt = mk(len(trees), HQ, TREE_N), mk(len(trees), HKV, TREE_N), mk(len(trees), HKV, TREE_N)
+    ot = torch.empty_like(qt)
+    pool2 = _pool(torch, W, dev, dt, ns)
+
+    def split_up():
+        pool2.ragged_step_dyn(qr, kr, vr, b["cu"], b["slots"], s_aux=sa, out=orr, commit=True)
+        pool2.extend_attention_tree_dyn(qt, kt, vt, b["parent"], s_aux=sa, out=ot, slots=b["tslots"])
+        pool2.commit_path_dyn(kt, vt, b["path"], b["count"], slots=b["tslots"])
+
+    return {"packed_tree": packed_tree, "split_up": split_up}
 
 
 def _variants(torch, W, lengths, dev, dt, have_ragged, names=()):
@@ -94,8 +145,11 @@ def _setup(args):
     have = hasattr(SinkCacheLayer, "ragged_step_dyn") and hasattr(sink_attention._native.lib(), "sfa_decode_ring_ragged_slots")
     # 2: the admit keyword too (a library without the flag ignores the bit: such a run times the unflagged kernels)
     have = int(have) + int(have and "admit" in inspect.signature(SinkCacheLayer.ragged_step_dyn).parameters)
-    want = ["admit_mix", "dry"] if args.admit else args.variants.split(",")
-    need = {"ragged": 1, "ragged_admit": 2, "admit_mix": 2, "dry": 2}
+    # 3: the packed tree call and the packed commit too
+    have += int(have == 2 and hasattr(SinkCacheLayer, "commit_packed_dyn") and
+                hasattr(sink_attention._native.lib(), "sfa_decode_ring_ragged_tree_slots"))
+    want = ["packed_tree", "split_up"] if args.tree else ["admit_mix", "dry"] if args.admit else args.variants.split(",")
+    need = {"ragged": 1, "ragged_admit": 2, "admit_mix": 2, "dry": 2, "packed_tree": 3, "split_up": 3}
     names = [v for v in want if have >= need.get(v, 0)]
     return torch, names, have
 
@@ -103,12 +157,12 @@ def _setup(args):
 def wall(args):
     torch, names, have = _setup(args)
     dev, dt = "cuda", torch.bfloat16
-    print(f"gpt-oss geometry H_q={HQ} H_kv={HKV} D={D} num_sink={NS} s_aux bf16, pool of {S}, rings full; device us per "
+    print(f"gpt-oss geometry H_q={HQ} H_kv={HKV} D={D} num_sink={NS} s_aux bf16, pool of {len(TREE_STEP) if args.tree else S}, rings full; device us per "
           f"step, median of {args.rounds} rounds of {args.calls} calls (events), variants alternating", flush=True)
     for W in [int(x) for x in args.W.split(",")]:
-        for step in args.steps.split(","):
+        for step in (["dec4_tree4_pre256"] if args.tree else args.steps.split(",")):
             torch.manual_seed(0)
-            fns = _variants(torch, W, STEPS[step], dev, dt, have, names)
+            fns = _tree_variants(torch, W, dev, dt) if args.tree else _variants(torch, W, STEPS[step], dev, dt, have, names)
             res = {v: [] for v in names}
             for v in names:
                 for _ in range(WARM):
@@ -125,7 +179,7 @@ def wall(args):
                     res[v].append(e0.elapsed_time(e1) * 1e3 / args.calls)
             med = {v: sorted(x)[len(x) // 2] for v, x in res.items()}
             spread = {v: max(x) - min(x) for v, x in res.items()}
-            print(f"  W={W:5d} {step:12s} T={sum(STEPS[step]):4d}  " +
+            print(f"  W={W:5d} {step:12s} T={sum(TREE_STEP if args.tree else STEPS[step]):4d}  " +
                   "  ".join(f"{v} {med[v]:8.2f} (+-{spread[v] / 2:5.2f})" for v in names), flush=True)
             del fns
 
@@ -198,6 +252,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--admit", action="store_true", help="the admission mix: variants admit_mix and dry")
+    ap.add_argument("--tree", action="store_true", help="the speculative step (wall mode): variants packed_tree and split_up")
     ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
     args = ap.parse_args()
     if args.summarize:
