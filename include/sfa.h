@@ -599,6 +599,41 @@ int sfa_ring_commit_path_ragged_slots(const sfa_tensor* window_k, const sfa_tens
                                       const int32_t* cu_q, int n_seq, int32_t* state, const int32_t* slots,
                                       void* stream);
 
+/*
+ * Copy slots of a pool on the device: the fork of parallel sampling and beam search (one prefilled prompt into n
+ * slots), and parking a sequence in a second pool.  Pair i (n_pairs of them) copies slot s = src_slots[i] of the source
+ * pool into slot d = dst_slots[i] of the destination pool; src_slots / dst_slots are device int32 [n_pairs].
+ *   src_sink_k/v [S_src, Hkv, num_sink, D]   src_window_k/v [S_src, Hkv, Wc, D]   src_state int32 [S_src][4]
+ *   dst_sink_k/v [S_dst, Hkv, num_sink, D]   dst_window_k/v [S_dst, Hkv, Wc, D]   dst_state int32 [S_dst][4]
+ *   - Pools.  Source and destination may be the same pool (all five pointers equal; the kernel takes src_state ==
+ *     dst_state as "the same pool"), or two pools of equal Hkv, num_sink, Wc, D and dtype with S_src and S_dst free.
+ *     Pools that overlap in part are undefined.
+ *   - What is copied.  The rows the attention kernels would read for the state of s, read with their clamps: sink rows
+ *     j < clamp(sink_len, 0, num_sink) and ring slots j < clamp(window_len, 0, Wc) (a ring that is not full copies only
+ *     its live slots, a full ring all Wc), all KV heads, and the state row verbatim (4 ints).  Every row keeps its
+ *     position, so write_pos means in d what it means in s: any later call on d is bitwise the same call on s.  Rows
+ *     and ring slots the source does not reach keep what d held, as sfa_ring_fill_varlen_slots documents for its
+ *     placement.  A source with seen == 0 makes d fresh.
+ *   - Skipped pairs, decided on the device: s outside [0, S_src), d outside [0, S_dst), s == d in the same pool (the
+ *     slots = -1 rule of the slot calls: a launch captured at a fixed n_pairs replays with any number of live pairs).
+ *   - Aliasing.  One source may feed many destinations in one call.  Undefined, and the device arrays are not
+ *     validated: a destination named twice; in the same pool, a destination that is also a live source.  Beam
+ *     reordering therefore never permutes in place: it forks into free slots and releases the dead ones.
+ * One launch on `stream`, capturable; no workspace, no allocation, nothing read on the host.  The grid covers the
+ * capacity (n_pairs * Hkv * (num_sink + Wc) rows); workgroups past the live rows of their pair leave after the state
+ * read, so the bytes moved follow the fill.  Each thread holds several 16-byte pieces of K and of V in flight before its
+ * first store; exactly one thread writes dst_state[d], and no workgroup of the launch reads that row.
+ * Host checks before anything launches, in this order: null descriptors ("src_sink_k: null tensor descriptor", ...;
+ * unit last stride with them); null src_state / dst_state / src_slots / dst_slots; n_pairs < 0 (n_pairs == 0 returns
+ * SFA_OK here, without a launch); one dtype across the eight buffers; equal Hkv, num_sink, Wc, D between the pools and
+ * one shape[0] >= 1 within each; rows a multiple of 16 bytes and 16-byte aligned.  sfa_last_path(): "ring_copy_slots".
+ */
+int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
+                        const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,
+                        const sfa_tensor* dst_sink_v, const sfa_tensor* dst_window_k, const sfa_tensor* dst_window_v,
+                        int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,7 +303,8 @@ size_t sfa_decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t Nk
 
 // ------------------------------------------------------------------------------------------------ sink + ring cache
 // Every entry point below fills a RingCall (sfa_internal.hpp) with what its signature provides and hands it to its
-// family: ring_step, ring_multi / ring_tree, ring_ragged, ring_commit / ring_commit_path, fill_varlen.  The family
+// family: ring_step, ring_multi / ring_tree, ring_ragged, ring_commit / ring_commit_path, fill_varlen, copy_slots (two
+// pools, no RingCall).  The family
 // runs the checks, the empty-shape returns, the workspace test and the launch.
 namespace {
 
@@ -643,6 +644,54 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
                                    (hipStream_t)stream, slots);
 }
 
+// sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools.  The device arrays (slots,
+// state) are not looked at: skipped pairs are decided by the kernel
+int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
+               int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream) {
+    g_err[0] = 0;
+    static const char* const names[8] = {"src_sink_k", "src_sink_v", "src_window_k", "src_window_v",
+                                         "dst_sink_k", "dst_sink_v", "dst_window_k", "dst_window_v"};
+    int st;
+    for (int i = 0; i < 8; ++i)
+        if ((st = check_tensor(i < 4 ? src[i] : dst[i - 4], names[i]))) return st;
+    SFA_NEED(src_state, "src_state");
+    SFA_NEED(dst_state, "dst_state");
+    SFA_NEED(src_slots, "src_slots");
+    SFA_NEED(dst_slots, "dst_slots");
+    SFA_CHECK_ARG(n_pairs >= 0, "n_pairs must be >= 0 (got %d)", n_pairs);
+    if (n_pairs == 0) return SFA_OK;
+    for (int i = 1; i < 8; ++i)
+        SFA_CHECK_ARG((i < 4 ? src[i] : dst[i - 4])->dtype == src[0]->dtype,
+                      "ring_copy_slots: %s and src_sink_k differ in dtype (the eight buffers must share one)", names[i]);
+    const int64_t Hkv = src[2]->shape[1], ns = src[0]->shape[2], Wc = src[2]->shape[2], D = src[2]->shape[3];
+    for (int i = 0; i < 8; ++i) {      // both pools [S, Hkv, num_sink or Wc, D]: equal geometry, S of each pool free
+        const sfa_tensor* t = i < 4 ? src[i] : dst[i - 4];
+        SFA_CHECK_ARG(t->shape[1] == Hkv && t->shape[2] == ((i & 2) ? Wc : ns) && t->shape[3] == D,
+                      "ring_copy_slots: %s must be [S, H_kv, %s, D] = [S, %lld, %lld, %lld] in both pools (got [%lld, "
+                      "%lld, %lld, %lld])", names[i], (i & 2) ? "Wc" : "num_sink", (long long)Hkv,
+                      (long long)((i & 2) ? Wc : ns), (long long)D, (long long)t->shape[0], (long long)t->shape[1],
+                      (long long)t->shape[2], (long long)t->shape[3]);
+    }
+    for (int p = 0; p < 2; ++p) {
+        const sfa_tensor* const* b = p ? dst : src;
+        const int64_t S = b[0]->shape[0];
+        SFA_CHECK_ARG(S >= 1 && S < (1ll << 30) && b[1]->shape[0] == S && b[2]->shape[0] == S && b[3]->shape[0] == S,
+                      "pool: the %s sink and window buffers must share shape[0] = S >= 1 (sink %lld / %lld, window %lld "
+                      "/ %lld)", p ? "dst" : "src", (long long)S, (long long)b[1]->shape[0], (long long)b[2]->shape[0],
+                      (long long)b[3]->shape[0]);
+    }
+    SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
+    const int es = dtype_size(src[0]->dtype);
+    SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_copy_slots: K/V rows must be a multiple of 16 bytes (head dim %lld)",
+                  (long long)D);
+    SFA_CHECK_ARG(ns + Wc < (1ll << 30) && (ns + Wc) * (D * es / 16) < (1ll << 30) && Hkv < (1ll << 30),
+                  "problem too large");
+    if ((st = check_rows16({src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3]}, es, 7,
+                           "ring_copy_slots: rows of every tensor must be 16-byte aligned")))
+        return st;
+    return ring_copy_slots_launch(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, (hipStream_t)stream);
+}
+
 }  // namespace
 
 // the parameter lists of include/sfa.h and their pass to attend_call / commit_call
@@ -863,6 +912,16 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
                                const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
                                void* stream) {
     return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true);
+}
+
+int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
+                        const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,
+                        const sfa_tensor* dst_sink_v, const sfa_tensor* dst_window_k, const sfa_tensor* dst_window_v,
+                        int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                        void* stream) {
+    const sfa_tensor* const src[4] = {src_sink_k, src_sink_v, src_window_k, src_window_v};
+    const sfa_tensor* const dst[4] = {dst_sink_k, dst_sink_v, dst_window_k, dst_window_v};
+    return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include "sfa_internal.hpp"
 
 #include <climits>
+#include <type_traits>
 
 namespace sfa {
 
@@ -1116,6 +1117,83 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
 }
 
+// sfa_ring_copy_slots: pair i copies slot s = src_slots[i] of the source pool into slot d = dst_slots[i] of the
+// destination pool (the same pool: a fork).  What the readers of s would read is copied in place: sink rows
+// [0, sink_len) and ring slots [0, window_len), both clamped into the buffers as get_fill clamps them, and the state row
+// verbatim (4 ints).  Every live row keeps its position, so write_pos means in d what it means in s; rows beyond the fill
+// keep what d held.  A pair with s or d outside its pool, or with s == d in one pool (`same`), moves nothing.
+// A workgroup is (pair, KV head, block of 256 * kCopyPieces consecutive 16-byte pieces of the live rows of that head:
+// piece p = row * cpr + ch, row < sink_len a sink row, else ring slot row - sink_len); the grid covers the capacity
+// (nblk blocks per head), blocks past the live pieces leave after the state read.  A thread first issues its
+// kCopyPieces loads of K and of V, 256 pieces apart (a wave-instruction reads 1 KiB contiguous), without a branch among
+// them, then stores: 2 * kCopyPieces independent 16-byte loads are in flight per thread.  The first thread of a pair's
+// first block writes the state row; no workgroup of the launch reads that row (it is not a source: the aliasing rule of
+// include/sfa.h).  -DSFA_COPY_PIECES=n: development builds for tools/kbench_fork.py.
+#ifndef SFA_COPY_PIECES
+#define SFA_COPY_PIECES 4
+#endif
+constexpr int kCopyPieces = SFA_COPY_PIECES;
+
+struct CopyPools {
+    View sk, sv, wk, wv;
+    int* state;
+    const int* slots;
+    int S;
+};
+
+__global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, CopyPools dst, int Hkv, int ns, int wc,
+                                                              int cpr, int es, int nblk, int same) {
+    const int blk = (int)(blockIdx.x % (unsigned)nblk);
+    const int rest = (int)(blockIdx.x / (unsigned)nblk);
+    const int hk = rest % Hkv, pair = rest / Hkv;
+    const int s = src.slots[pair], d = dst.slots[pair];
+    if ((unsigned)s >= (unsigned)src.S || (unsigned)d >= (unsigned)dst.S || (same && s == d)) return;
+    const int* st = src.state + (int64_t)s * 4;
+    const int st0 = st[0], st1 = st[1], st2 = st[2], st3 = st[3];
+    const int sl = st0 < 0 ? 0 : (st0 > ns ? ns : st0);
+    const int wl = st1 < 0 ? 0 : (st1 > wc ? wc : st1);
+    if (blk == 0 && hk == 0 && threadIdx.x == 0) {
+        int* dt = dst.state + (int64_t)d * 4;
+        dt[0] = st0, dt[1] = st1, dt[2] = st2, dt[3] = st3;
+    }
+    const int live = (sl + wl) * cpr;            // < 2^30: checked on the host at the capacity
+    const int p0 = blk * (256 * kCopyPieces);
+    if (p0 >= live) return;
+    // the 16 bytes of piece (r, c) in the K (v = false) or V buffer of a pool; slot: the pair's slot of that pool
+    auto at = [&](const CopyPools& pl, int slot, int r, int c, bool v) {
+        const bool sink = r < sl;
+        const View& b = sink ? (v ? pl.sv : pl.sk) : (v ? pl.wv : pl.wk);
+        const int64_t rr = sink ? r : r - sl;
+        return reinterpret_cast<u32x4*>(b.ptr + ((int64_t)slot * b.sb + (int64_t)hk * b.sh + rr * b.sn) * es + (int64_t)c * 16);
+    };
+    // The thread's pieces p0 + tid + 256 u as (row, chunk): one division, then steps of 256 pieces.  full (wave-uniform):
+    // every piece of the block is live, and the loads and stores carry no predicate.  In the last block of a head a
+    // piece past the live ones is loaded from the last live piece (a valid address) and not stored.
+    auto copy = [&](auto full_block) {
+        constexpr bool full = decltype(full_block)::value;
+        int row[kCopyPieces], ch[kCopyPieces];
+        bool ok[kCopyPieces];
+        const int p = p0 + (int)threadIdx.x, rstep = 256 / cpr, cstep = 256 - rstep * cpr;
+        int r = p / cpr, c = p - r * cpr;
+#pragma unroll
+        for (int u = 0; u < kCopyPieces; ++u) {
+            ok[u] = full || p + u * 256 < live;
+            row[u] = ok[u] ? r : sl + wl - 1, ch[u] = ok[u] ? c : cpr - 1;
+            r += rstep, c += cstep;
+            if (c >= cpr) c -= cpr, ++r;
+        }
+        u32x4 kr[kCopyPieces], vr[kCopyPieces];
+#pragma unroll
+        for (int u = 0; u < kCopyPieces; ++u)
+            kr[u] = *at(src, s, row[u], ch[u], false), vr[u] = *at(src, s, row[u], ch[u], true);
+#pragma unroll
+        for (int u = 0; u < kCopyPieces; ++u)
+            if (ok[u]) *at(dst, d, row[u], ch[u], false) = kr[u], *at(dst, d, row[u], ch[u], true) = vr[u];
+    };
+    if (p0 + 256 * kCopyPieces <= live) copy(std::true_type{});
+    else copy(std::false_type{});
+}
+
 // one state row after every reader of it: write_pos += acc (mod Wc), window_len = min(window_len + acc, Wc), and - for a
 // per-sequence row - seen += acc.  Plain stores from vector lanes.
 __device__ __forceinline__ void advance_row(int* st, int acc, int wc, bool seen) {
@@ -1510,6 +1588,33 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
     set_path(slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
+    return SFA_OK;
+}
+
+int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
+                           int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                           hipStream_t stream) {
+    const sfa_tensor *sk = src[0], *wk = src[2];
+    const int es = dtype_size(wk->dtype);
+    const int Hkv = (int)wk->shape[1], ns = (int)sk->shape[2], wc = (int)wk->shape[2];
+    const int cpr = (int)(wk->shape[3] * es / 16);
+    const int64_t nblk = cdiv64((int64_t)(ns + wc) * cpr, 256 * kCopyPieces);
+    const int64_t grid = (int64_t)n_pairs * Hkv * nblk;
+    if (grid >= (1ll << 31)) {
+        set_error("ring_copy_slots: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (grid > 0) {
+        const CopyPools s{make_view(src[0]), make_view(src[1]), make_view(src[2]), make_view(src[3]),
+                          const_cast<int*>(src_state), src_slots, (int)wk->shape[0]};
+        const CopyPools d{make_view(dst[0]), make_view(dst[1]), make_view(dst[2]), make_view(dst[3]),
+                          dst_state, dst_slots, (int)dst[2]->shape[0]};
+        ring_copy_slots_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(s, d, Hkv, ns, wc, cpr, es, (int)nblk,
+                                                                         src_state == dst_state ? 1 : 0);
+        int st;
+        if ((st = launch_status("ring_copy_slots"))) return st;
+    }
+    set_path("ring_copy_slots");
     return SFA_OK;
 }
 

@@ -110,5 +110,10 @@ int ring_commit_dyn_launch(const RingCall& c);
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
                             int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots);
+// sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools (the same pool: a fork); pair i
+// copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i]
+int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
+                           int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                           hipStream_t stream);
 
 }  // namespace sfa

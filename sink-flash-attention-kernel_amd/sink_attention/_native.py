@@ -159,6 +159,9 @@ def _bind(lib):
                                                       u32, vp]
     lib.sfa_ring_commit_path_ragged_slots.restype = i32
     lib.sfa_ring_commit_path_ragged_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp]
+    # slot copy (fork / park): source pool + state, destination pool + state, src_slots, dst_slots, n_pairs, stream
+    lib.sfa_ring_copy_slots.restype = i32
+    lib.sfa_ring_copy_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp]
 
 
 def lib():

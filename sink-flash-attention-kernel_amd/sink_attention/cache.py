@@ -678,6 +678,67 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         hit = (torch.arange(st.shape[0], device=st.device, dtype=torch.int32)[:, None] == idx[None, :]).any(dim=1)
         st.mul_((~hit).to(torch.int32)[:, None])
 
+    def fork_slots(self, src, dst, source: Optional["SinkCacheLayer"] = None) -> None:
+        """Copy slots on the device (``sfa_ring_copy_slots``, one launch, no allocation, capturable): pair i copies slot
+        ``src[i]`` of ``source``'s pool (another pooled layer of equal geometry, dtype and device; default: this layer,
+        a fork) into slot ``dst[i]`` of this layer's pool.  The live sink rows, the live ring slots (each at its
+        position) and the state row are copied, so any later call on ``dst[i]`` gives bitwise what the same call on
+        ``src[i]`` gives; rows the source does not reach keep what the destination held.  One source may feed many
+        destinations: parallel sampling is ``fork_slots([p] * (n - 1), free[:n - 1])``.  A pair with a -1 (or any value
+        outside its pool) on either side, or with ``src[i] == dst[i]`` in one pool, moves nothing, so a captured call
+        replays with any number of live pairs.  Undefined: a destination named twice, and in one pool a destination that
+        is also a live source - a beam step forks into free slots and releases dead ones (``beam_fork_plan``) instead
+        of permuting in place.  ``src`` / ``dst``: device int32 ``[n]`` tensors, passed through unread, or host lists /
+        CPU tensors, which are checked (equal lengths, range, the two undefined cases) and uploaded."""
+        from . import _native as N
+        source = self if source is None else source
+        if not isinstance(source, SinkCacheLayer):
+            raise TypeError("fork_slots: source must be a SinkCacheLayer")
+        dst_state, src_state = self._require_pool("fork_slots"), source._require_pool("fork_slots")
+        if source is not self:
+            if source.window_k.dtype != self.window_k.dtype:
+                raise TypeError(f"fork_slots: the pools differ in dtype ({source.window_k.dtype} / {self.window_k.dtype})")
+            if source.window_k.shape[1:] != self.window_k.shape[1:] or source.sink_k.shape[1:] != self.sink_k.shape[1:]:
+                raise ValueError(f"fork_slots: the pools differ in geometry: source [S, H_kv, num_sink / Wc, D] = "
+                                 f"{tuple(source.sink_k.shape)} / {tuple(source.window_k.shape)}, this layer "
+                                 f"{tuple(self.sink_k.shape)} / {tuple(self.window_k.shape)}")
+            if source.window_k.device != self.window_k.device:
+                raise ValueError("fork_slots: the pools must live on one device")
+        src, dst = self._fork_args(src, dst, source)
+        N.require_gpu(self.window_k, source.window_k, src, dst)
+        if src.numel() == 0:
+            return
+        with torch.cuda.device(self.window_k.device):
+            rc = N.lib().sfa_ring_copy_slots(
+                *(N.desc(t) for t in (source.sink_k, source.sink_v, source.window_k, source.window_v)),
+                src_state.data_ptr(),
+                *(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)), dst_state.data_ptr(),
+                src.data_ptr(), dst.data_ptr(), src.numel(), N.stream_ptr(self.window_k.device))
+        N.check(rc, "sfa_ring_copy_slots")
+
+    def _fork_args(self, src, dst, source):
+        """``src`` / ``dst`` of ``fork_slots`` as int32 tensors on the pool's device: ``_slots_arg`` for each (``src``
+        against ``source``'s pool, ``dst`` against this one), equal lengths, and - where both are host lists - the two
+        cases the kernel leaves undefined.  A pair is live when both entries name a slot and it is not ``s == d`` in one
+        pool."""
+        host = [None if isinstance(x, torch.Tensor) and x.is_cuda else
+                (x.tolist() if isinstance(x, torch.Tensor) else [int(v) for v in x]) for x in (src, dst)]
+        n = [x.numel() if h is None else len(h) for x, h in ((src, host[0]), (dst, host[1]))]
+        if n[0] != n[1]:
+            raise ValueError(f"fork_slots: src and dst must pair up, got {n[0]} and {n[1]} entries")
+        src_t, dst_t = source._slots_arg(src, None, writes=False), self._slots_arg(dst, None, writes=False)
+        if host[0] is not None and host[1] is not None:
+            live = [(s, d) for s, d in zip(*host) if s >= 0 and d >= 0 and not (source is self and s == d)]
+            dsts = [d for _, d in live]
+            if len(set(dsts)) != len(dsts):
+                raise ValueError(f"fork_slots: dst {host[1]} names a destination twice")
+            if source is self:
+                both = sorted(set(dsts) & {s for s, _ in live})
+                if both:
+                    raise ValueError(f"fork_slots: slots {both} are a destination and the source of another pair in one "
+                                     f"call; fork into free slots (beam_fork_plan)")
+        return src_t.to(self.window_k.device), dst_t.to(self.window_k.device)
+
     def _require_dyn(self, what):
         if not (self.is_initialized and self.prefilled):
             raise ValueError(f"{what} needs a prefilled cache: the first chunk is a prefill (sink_flash_attention)")
@@ -1043,6 +1104,19 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
             if layer._pool:
                 layer.release_slots(slots)
 
+    def fork_slots(self, src, dst, source: Optional["SinkAttentionCache"] = None) -> None:
+        """``SinkCacheLayer.fork_slots`` of every layer that holds a pool: slot ``src[i]`` of ``source`` (another
+        ``SinkAttentionCache`` whose layer l holds the pool that layer l here is paired with; default: this cache) into
+        slot ``dst[i]`` of this cache."""
+        if source is not None and not isinstance(source, SinkAttentionCache):
+            raise TypeError("fork_slots: source must be a SinkAttentionCache")
+        for l, layer in enumerate(self.layers):
+            if not layer._pool:
+                continue
+            if source is not None and l >= len(source.layers):
+                raise ValueError(f"fork_slots: source has no layer {l}")
+            layer.fork_slots(src, dst, None if source is None else source.layers[l])
+
     def get_seq_length(self, layer_idx: int = 0, *_, **__) -> int:
         return self.layers[layer_idx].get_seq_length() if layer_idx < len(self.layers) else 0
 
@@ -1056,3 +1130,35 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     @property
     def seen_tokens(self) -> int:
         return self._seen_tokens
+
+
+def beam_fork_plan(beam_idx, slots, free_slots):
+    """Slot bookkeeping of one beam-search step over a pool, on host lists (no GPU).  Row b of the next step continues
+    the sequence that row ``beam_idx[b]`` held in slot ``slots[beam_idx[b]]``.  Returns ``(new_slots, src, dst,
+    freed)``: the first row that continues a beam keeps that beam's slot; every further row that continues it takes a
+    slot from ``free_slots`` (in order) and contributes a pair ``(src[i], dst[i])``; the slots of beams that nobody
+    continues are ``freed``.  Raises ``ValueError`` when ``free_slots`` runs out.  A beam step is then
+    ``fork_slots(src, dst)``, ``release_slots(freed)`` and an in-place rewrite of the step's ``slots`` tensor with
+    ``new_slots``: no destination is a source, so nothing is permuted in place.  A freed slot is free from the next
+    step on (it may still be a source of this one only if somebody continues it, and then it is not freed)."""
+    beam_idx, slots, free = [int(x) for x in beam_idx], [int(x) for x in slots], [int(x) for x in free_slots]
+    B = len(slots)
+    if len(beam_idx) != B:
+        raise ValueError(f"beam_idx must hold one entry per row: {len(beam_idx)} entries for {B} slots")
+    bad = [p for p in beam_idx if not 0 <= p < B]
+    if bad:
+        raise ValueError(f"beam_idx entries {bad} outside [0, {B})")
+    new_slots, src, dst, kept = [], [], [], set()
+    for p in beam_idx:
+        if p not in kept:
+            kept.add(p)
+            new_slots.append(slots[p])
+            continue
+        if not free:
+            raise ValueError(f"beam_fork_plan: free_slots ran out ({len(dst)} forks placed, more needed)")
+        d = free.pop(0)
+        src.append(slots[p])
+        dst.append(d)
+        new_slots.append(d)
+    freed = [slots[p] for p in range(B) if p not in kept]
+    return new_slots, src, dst, freed
