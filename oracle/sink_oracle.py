@@ -97,7 +97,7 @@ def sink_attention_dense(
     qf, kf, vf = q.to(dtype), _expand_kv(k.to(dtype), g), _expand_kv(v.to(dtype), g)
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale                  # [B,Hq,N,Nk]
     Nk = k.shape[2]
-    m = valid_mask(torch.arange(N) + (Nk - N), torch.arange(Nk), num_sink, window)
+    m = valid_mask(torch.arange(N, device=q.device) + (Nk - N), torch.arange(Nk, device=q.device), num_sink, window)
     s = s.masked_fill(~m, NEG_INF)
     if s_aux is not None:
         col = s_aux.to(dtype).view(1, Hq, 1, 1).expand(B, Hq, N, 1)
@@ -146,7 +146,7 @@ def sink_attention_bwd_dense(
     dof = do.to(dtype)
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
     Nk = k.shape[2]
-    m = valid_mask(torch.arange(N) + (Nk - N), torch.arange(Nk), num_sink, window)
+    m = valid_mask(torch.arange(N, device=q.device) + (Nk - N), torch.arange(Nk, device=q.device), num_sink, window)
     p = torch.exp(s.masked_fill(~m, NEG_INF) - lse.unsqueeze(-1))
     p = torch.nan_to_num(p, nan=0.0)
     delta = (dof * o).sum(-1)                                           # [B,Hq,N]
@@ -168,13 +168,13 @@ def sink_attention_bwd_dense(
     return dq, dk, dv, ds_aux
 
 
-def _row_block_keys(r0: int, r1: int, N: int, num_sink: int, window: int) -> torch.Tensor:
+def _row_block_keys(r0: int, r1: int, N: int, num_sink: int, window: int, device=None) -> torch.Tensor:
     """Key positions any row of [r0, r1) can see: sink range then window range
     (the two-range walk of sink_flash_attention.py:151-180)."""
     ns = min(num_sink, r1)
     w0 = max(r0 - window + 1, ns, 0)
-    sink = torch.arange(0, ns)
-    win = torch.arange(w0, r1) if r1 > w0 else torch.arange(0)
+    sink = torch.arange(0, ns, device=device)
+    win = torch.arange(w0, r1, device=device) if r1 > w0 else torch.arange(0, device=device)
     return torch.cat([sink, win])
 
 
@@ -186,12 +186,12 @@ def sink_attention_banded(
     Hkv = k.shape[1]
     g = Hq // Hkv
     scale = 1.0 / math.sqrt(D)
-    o = torch.zeros(B, Hq, N, D, dtype=dtype)
-    lse = torch.full((B, Hq, N), NEG_INF, dtype=dtype)
+    o = torch.zeros(B, Hq, N, D, dtype=dtype, device=q.device)
+    lse = torch.full((B, Hq, N), NEG_INF, dtype=dtype, device=q.device)
     for r0 in range(0, N, block):
         r1 = min(N, r0 + block)
-        cols = _row_block_keys(r0, r1, N, num_sink, window)
-        rows = torch.arange(r0, r1)
+        cols = _row_block_keys(r0, r1, N, num_sink, window, q.device)
+        rows = torch.arange(r0, r1, device=q.device)
         qb = q[:, :, r0:r1].to(dtype)
         kb = _expand_kv(k[:, :, cols].to(dtype), g)
         vb = _expand_kv(v[:, :, cols].to(dtype), g)
@@ -220,16 +220,16 @@ def sink_attention_bwd_banded(
     g = Hq // Hkv
     scale = 1.0 / math.sqrt(D)
     o, lse = sink_attention_banded(q, k, v, num_sink, window, s_aux, dtype, block)
-    dq = torch.zeros(B, Hq, N, D, dtype=dtype)
-    dk = torch.zeros(B, Hkv, N, D, dtype=dtype)
-    dv = torch.zeros(B, Hkv, N, D, dtype=dtype)
+    dq = torch.zeros(B, Hq, N, D, dtype=dtype, device=q.device)
+    dk = torch.zeros(B, Hkv, N, D, dtype=dtype, device=q.device)
+    dv = torch.zeros(B, Hkv, N, D, dtype=dtype, device=q.device)
     delta = (do.to(dtype) * o).sum(-1)
     adelta = (do.to(dtype) * o).abs().sum(-1)
-    a_k, a_v = (torch.zeros(B, Hkv, N, D, dtype=dtype) for _ in range(2)) if bounds else (None, None)
+    a_k, a_v = (torch.zeros(B, Hkv, N, D, dtype=dtype, device=q.device) for _ in range(2)) if bounds else (None, None)
     for r0 in range(0, N, block):
         r1 = min(N, r0 + block)
-        cols = _row_block_keys(r0, r1, N, num_sink, window)
-        rows = torch.arange(r0, r1)
+        cols = _row_block_keys(r0, r1, N, num_sink, window, q.device)
+        rows = torch.arange(r0, r1, device=q.device)
         qb = q[:, :, r0:r1].to(dtype)
         dob = do[:, :, r0:r1].to(dtype)
         kb = _expand_kv(k[:, :, cols].to(dtype), g)

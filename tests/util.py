@@ -42,6 +42,39 @@ def oracle_bwd(q, k, v, do, ns, W, s_aux=None, banded=None, bounds=False):
     return fn(q.cpu(), k.cpu(), v.cpu(), do.cpu(), ns, W, sa, bounds=True, tiny=torch.finfo(q.dtype).tiny)
 
 
+def device_oracle(q, k, v, do, ns, W, s_aux, cu=None):
+    """fp64 oracle over the WHOLE tensor on q.device: O, LSE, dQ, dK, dV, ds_aux and the sum-bound terms A_K, A_V
+    (bounds=True, tiny of q.dtype), one (sequence, batch, KV head) unit at a time so that the intermediates stay small.  The
+    same functions as oracle_fwd / oracle_bwd, banded above 1024 rows.  cu: cu_seqlens of a packed batch [1, H, T, D]
+    (LSE comes back as [1, Hq, T]); s_aux [Hq] or None."""
+    dev, f64 = q.device, torch.float64
+    B, Hq, _, D = q.shape
+    Hkv = k.shape[1]
+    g = Hq // Hkv
+    tiny = torch.finfo(q.dtype).tiny
+    o, dq = (torch.zeros(q.shape, dtype=f64, device=dev) for _ in range(2))
+    dk, dv, a_k, a_v = (torch.zeros(k.shape, dtype=f64, device=dev) for _ in range(4))
+    lse = torch.full(q.shape[:3], float("-inf"), dtype=f64, device=dev)
+    dsa = None if s_aux is None else torch.zeros(Hq, dtype=f64, device=dev)
+    seqs = [(0, q.shape[2])] if cu is None else [(int(a), int(b)) for a, b in zip(cu[:-1], cu[1:]) if b > a]
+    for r0, r1 in seqs:
+        banded = r1 - r0 > 1024
+        fwd = O.sink_attention_banded if banded else O.sink_attention_dense
+        bwd = O.sink_attention_bwd_banded if banded else O.sink_attention_bwd_dense
+        for b in range(B):
+            for hk in range(Hkv):
+                hq = slice(hk * g, (hk + 1) * g)
+                uq = (slice(b, b + 1), hq, slice(r0, r1))
+                uk = (slice(b, b + 1), slice(hk, hk + 1), slice(r0, r1))
+                sa = None if s_aux is None else s_aux[hq].float()
+                o[uq], lse[uq] = fwd(q[uq], k[uk], v[uk], ns, W, sa)
+                r = bwd(q[uq], k[uk], v[uk], do[uq], ns, W, sa, bounds=True, tiny=tiny)
+                dq[uq], dk[uk], dv[uk], a_k[uk], a_v[uk] = r[0], r[1], r[2], r[4], r[5]
+                if dsa is not None:
+                    dsa[hq] += r[3]
+    return o, lse, dq, dk, dv, dsa, a_k, a_v
+
+
 def probe_reference(pr, ns, W):
     """fp64 oracle of one dense probe (tests/probe_inputs.py::dense_probe): o, lse, (dq, dk, dv, ds_aux, A_K, A_V).  Shared
     by tests/test_gpu_mask_edges.py and the CPU proofs of tests/test_probe_inputs.py, so that the bound terms the GPU
@@ -59,8 +92,8 @@ def maxdiff(a, b):
 
 
 def assert_close(actual, expected, atol, rtol, what=""):
-    a = actual.detach().double().cpu()
-    e = expected.detach().double().cpu()
+    e = expected.detach().double()                  # compared where the reference lives (device_oracle: on the GPU)
+    a = actual.detach().to(e.device).double()
     err = (a - e).abs()
     tol = atol + rtol * e.abs()
     bad = err > tol
@@ -80,7 +113,7 @@ def sum_bound_tolerance(ref, A, u, dtype):
 
 def sum_bound_ratio(got, ref, A, u):
     """largest |got - ref| / sum_bound_tolerance over the elements (the result's dtype: got.dtype)"""
-    g, r, a = (x.detach().double().cpu() for x in (got, ref, A))
+    g, r, a = (x.detach().to(ref.device).double() for x in (got, ref, A))      # (where the reference lives)
     tol = sum_bound_tolerance(r, a, u, got.dtype)
     err = (g - r).abs()
     ratio = torch.where(err > 0, err / tol, torch.zeros_like(err))         # (err > 0 = tol: inf, and it fails)
