@@ -68,6 +68,39 @@ M0 = Reg("m0", 0, 1)
 SCC = Reg("scc", 0, 1)
 
 
+class Alloc:
+    """Hands out the registers lo .. hi of one kind in ascending order, by name."""
+
+    def __init__(self, kind, lo, hi):
+        self.kind, self.next, self.hi = kind, lo, hi
+        self.names = {}
+
+    def __call__(self, name, n=1, align=1):
+        self.next = (self.next + align - 1) // align * align
+        r = Reg(self.kind, self.next, n)
+        self.next += n
+        assert self.next <= self.hi + 1, "out of %s registers at %s" % (self.kind, name)
+        self.names[name] = r
+        return r
+
+
+class GenBase:
+    """base of every generator (which sets POOL, pool_next, vfirst, sfirst)"""
+
+    def pool(self):
+        """the next of the POOL register quads that streamed MFMA operand fragments pass through (LDS -> here -> MFMA),
+        round robin; a block that starts over sets pool_next = 0"""
+        r = self.POOL[self.pool_next % len(self.POOL)]
+        self.pool_next += 1
+        return r
+
+    def clobbers(self):
+        """clobber list of the asm statement: every register the allocators may hand out"""
+        c = ["v%d" % i for i in range(self.vfirst, 256)] + ["a%d" % i for i in range(256)]
+        c += ["s%d" % i for i in range(self.sfirst, 100)] + ["vcc", "scc", "memory"]
+        return c
+
+
 class Imm:
     """Integer immediate (printed in decimal or hex) or float literal (printed as its bit pattern unless inline)."""
     __slots__ = ("val", "is_float")
@@ -162,7 +195,7 @@ class Instr:
             return "s_setprio %d" % m["n"]
         if self.op == "s_memtime":
             return "s_memtime %s" % self.dst[0].text()
-        if self.op in ("v_permlane32_swap_b32", "v_permlane16_swap_b32"):
+        if self.op == "v_permlane32_swap_b32":
             return "%s %s, %s" % (self.op, self.dst[0].text(), self.dst[1].text())
         if k in ("ds_read", "ds_write"):
             ops = [d.text() for d in self.dst] + [s.text() for s in self.src]
@@ -346,10 +379,6 @@ class Prog:
     def v_permlane32_swap(self, a, b, note=""):
         """lanes 32..63 of a swap with lanes 0..31 of b"""
         return self.add(Instr("v_permlane32_swap_b32", [a, b], [a, b], kind="valu", note=note))
-
-    def v_permlane16_swap(self, a, b, note=""):
-        """16-lane rows 1 and 3 of a swap with rows 0 and 2 of b (lanes 16..31 <-> 0..15, 48..63 <-> 32..47)"""
-        return self.add(Instr("v_permlane16_swap_b32", [a, b], [a, b], kind="valu", note=note))
 
     def v_readfirstlane(self, d, a, note=""):
         return self.add(Instr("v_readfirstlane_b32", [d], [a], kind="valu", note=note))

@@ -34,7 +34,7 @@ reads, 2 + 2 address registers): off(row, ch) = 2048 (row >> 3) + 512 (ch >> 2) 
 """
 from __future__ import annotations
 
-from .core import A, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, fimm, imm
+from .core import A, Alloc, GenBase, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, fimm, imm
 from .sched import finish_block, fix_hazards, insert_waits, schedule
 
 CST_BASE = 0
@@ -57,21 +57,7 @@ PARAMS = [
 # nrows = query rows of the sequence; cdelta = byte offset of the -Delta row of a head behind its -LSE/scale row.
 
 
-class Alloc:
-    def __init__(self, kind, lo, hi):
-        self.kind, self.next, self.hi = kind, lo, hi
-        self.names = {}
-
-    def __call__(self, name, n=1, align=1):
-        self.next = (self.next + align - 1) // align * align
-        r = Reg(self.kind, self.next, n)
-        self.next += n
-        assert self.next <= self.hi + 1, "out of %s registers at %s" % (self.kind, name)
-        self.names[name] = r
-        return r
-
-
-class DkdvGen:
+class DkdvGen(GenBase):
     def __init__(self, dtype="bf16", sched=True, vfirst=4, sfirst=56, npool=12, stamps=False, ablate=(), dma_t0=40, dma_dt=125, D=128, ahead=3, dead=True, half_edges=True):
         assert dtype in ("bf16", "f16") and D in (64, 80, 96, 128)
         self.dtype = dtype
@@ -166,11 +152,6 @@ class DkdvGen:
         p.s_mov(self.s_tb[0], self.s_ta[0])
 
     # ------------------------------------------------------------------ helpers
-    def pool(self):
-        r = self.POOL[self.pool_next % len(self.POOL)]
-        self.pool_next += 1
-        return r
-
     # LDS-DMA of one slice (Q, dO, row constants) into ring stage s_std / s_cstd, with the running source offsets
     def emit_dma_issue(self, p: Prog, spread: bool = False):
         """`spread`: inside a trip the five pieces get early, staggered deadlines (dma_t0 + i dma_dt cycles), so that the
@@ -844,8 +825,3 @@ class DkdvGen:
         items += finish_block(self.out_of_line().items)
         items += finish_block(self.epilogue().items)
         return items
-
-    def clobbers(self):
-        c = ["v%d" % i for i in range(self.vfirst, 256)] + ["a%d" % i for i in range(256)]
-        c += ["s%d" % i for i in range(self.sfirst, 100)] + ["vcc", "scc", "memory"]
-        return c

@@ -43,9 +43,8 @@ PARAMS = [
 
 
 class DkdvSkewGen(DkdvGen):
-    def __init__(self, dtype="bf16", D=80, sched=True, npool=12, dma_t0=40, dma_dt=None, ablate=(), halves=True):
+    def __init__(self, dtype="bf16", D=80, sched=True, npool=12, dma_t0=40, dma_dt=None, ablate=()):
         assert D in (64, 80, 96)
-        self.halves = halves            # trip bodies for slices that touch only one of the wave's two 32-key blocks
         if dma_dt is None:          # ten pieces per trip above head dim 64: spread over the whole trip (C4: -4 % against 100)
             dma_dt = 140 if D > 64 else 100
         super().__init__(dtype, sched=sched, sfirst=48, npool=npool, dma_t0=dma_t0, dma_dt=dma_dt, D=D, ablate=ablate, dead=False, half_edges=False)
@@ -159,31 +158,30 @@ class DkdvSkewGen(DkdvGen):
         p.s_cmp("gt_i32", self.s_kww, t1)
         p.s_cselect(t1, 1, 0)
         p.s_and_b32(self.s_full, t0, t1)
-        if self.halves:
-            # second block (keys kw63 - 31 .. kw63) dead: behind every row (kw63 - 31 > q0p + 31) or out of every window
-            # (q0p - kw63 >= W: q0p >= kww + 63); first block (kw63 - 63 .. kw63 - 32): kw63 - 63 > q0p + 31, q0p >= kww + 31
-            p.s_add_u32(t1, q0p, 62)
-            p.s_cmp("gt_i32", self.s_kw63, t1)
-            p.s_cselect(t0, 1, 0)
-            p.s_add_u32(t1, self.s_kww, 63)
-            p.s_cmp("ge_i32", q0p, t1)
-            p.s_cselect(t1, 1, 0)
-            p.s_or_b32(t0, t0, t1)                             # second block dead
-            p.s_add_u32(t1, q0p, 94)
-            p.s_cmp("gt_i32", self.s_kw63, t1)
-            p.s_cselect(t2, 1, 0)
-            p.s_add_u32(t1, self.s_kww, 31)
-            p.s_cmp("ge_i32", q0p, t1)
-            p.s_cselect(t1, 1, 0)
-            p.s_or_b32(t2, t2, t1)                             # first block dead
-            p.s_cmp("lg_u32", t0, t2)                          # exactly one of them (both: the masks make zeros of it)
-            p.s_cselect(t1, 1, 0)
-            p.s_and_b32(t0, t0, t1)
-            p.s_and_b32(t2, t2, t1)
-            p.s_cmp("lg_u32", t0, 0)
-            p.s_cselect(self.s_full, 3, self.s_full)
-            p.s_cmp("lg_u32", t2, 0)
-            p.s_cselect(self.s_full, 4, self.s_full)
+        # second block (keys kw63 - 31 .. kw63) dead: behind every row (kw63 - 31 > q0p + 31) or out of every window
+        # (q0p - kw63 >= W: q0p >= kww + 63); first block (kw63 - 63 .. kw63 - 32): kw63 - 63 > q0p + 31, q0p >= kww + 31
+        p.s_add_u32(t1, q0p, 62)
+        p.s_cmp("gt_i32", self.s_kw63, t1)
+        p.s_cselect(t0, 1, 0)
+        p.s_add_u32(t1, self.s_kww, 63)
+        p.s_cmp("ge_i32", q0p, t1)
+        p.s_cselect(t1, 1, 0)
+        p.s_or_b32(t0, t0, t1)                             # second block dead
+        p.s_add_u32(t1, q0p, 94)
+        p.s_cmp("gt_i32", self.s_kw63, t1)
+        p.s_cselect(t2, 1, 0)
+        p.s_add_u32(t1, self.s_kww, 31)
+        p.s_cmp("ge_i32", q0p, t1)
+        p.s_cselect(t1, 1, 0)
+        p.s_or_b32(t2, t2, t1)                             # first block dead
+        p.s_cmp("lg_u32", t0, t2)                          # exactly one of them (both: the masks make zeros of it)
+        p.s_cselect(t1, 1, 0)
+        p.s_and_b32(t0, t0, t1)
+        p.s_and_b32(t2, t2, t1)
+        p.s_cmp("lg_u32", t0, 0)
+        p.s_cselect(self.s_full, 3, self.s_full)
+        p.s_cmp("lg_u32", t2, 0)
+        p.s_cselect(self.s_full, 4, self.s_full)
 
     # ------------------------------------------------------------------ prologue
     def prologue(self) -> Prog:
@@ -364,18 +362,16 @@ class DkdvSkewGen(DkdvGen):
         p.s_barrier()
         p.s_waitcnt(lgkmcnt=0, note="S-chain operands of this trip (fetched at the end of the last one)")
         p.s_cbranch("scc0", "L_edge%=")
-        if self.halves:
-            p.s_cmp("eq_u32", self.s_full, 3)
-            p.s_cbranch("scc1", "L_e0%=")
-            p.s_cmp("eq_u32", self.s_full, 4)
-            p.s_cbranch("scc1", "L_e1%=")
+        p.s_cmp("eq_u32", self.s_full, 3)
+        p.s_cbranch("scc1", "L_e0%=")
+        p.s_cmp("eq_u32", self.s_full, 4)
+        p.s_cbranch("scc1", "L_e1%=")
         return p
 
     def trip_bodies(self):
-        b = [(None, self.trip_body(False)), ("L_edge%=", self.trip_body(True))]
-        if self.halves:
-            b += [("L_e0%=", self.trip_body(True, live=(0,))), ("L_e1%=", self.trip_body(True, live=(1,)))]
-        return b
+        # (L_e0 / L_e1: slices that touch only one of the wave's two 32-key blocks)
+        return [(None, self.trip_body(False)), ("L_edge%=", self.trip_body(True)),
+                ("L_e0%=", self.trip_body(True, live=(0,))), ("L_e1%=", self.trip_body(True, live=(1,)))]
 
     def out_of_line(self) -> Prog:
         p = Prog()

@@ -21,8 +21,7 @@ layout of dkdv.py.
 """
 from __future__ import annotations
 
-from .core import A, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, imm
-from .dkdv import Alloc
+from .core import A, Alloc, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, imm
 from .sched import finish_block, fix_hazards, insert_waits, schedule
 from .worklist import WorkList
 
@@ -56,23 +55,14 @@ PARAMS = [
 class DqGen(WorkList):
     DESC, DESC_BASE = DESC, DESC_BASE
 
-    def __init__(self, dtype="bf16", sched=True, vfirst=4, sfirst=None, npool=12, D=128, ablate=(), dma_t0=40, dma_dt=120, persist=True, stamps=False, dead=True, wide64=False, sinkfar=True, edge_subs=True):
+    def __init__(self, dtype="bf16", sched=True, vfirst=4, sfirst=None, npool=12, D=128, ablate=(), dma_t0=40, dma_dt=120, persist=True, stamps=False, sinkfar=True):
         assert dtype in ("bf16", "f16") and D in (64, 80, 96, 128)
         self.dtype, self.do_sched = dtype, sched
         self.persist = persist
         if sfirst is None:
             sfirst = (44 if stamps else 48) if persist else 56
         self.ablate = set(ablate)         # timing-only knock-out builds (wrong results)
-        self.dead = dead                  # tile class 3 and its body
         self.sinkfar = sinkfar and persist   # class 4: a sink tile whose second key half nobody sees (set at item init)
-        self.edge_subs = edge_subs        # edge tiles: a 32-key x 32-row sub-block that no row sees is left out (classes 5, 6)
-        # the bodies compute "full or not" only (one compare), the selector the rest: measured no faster (C3 dQ 1.861 vs 1.857,
-        # 1.845 vs 1.852 ms, same box), off
-        self.range_cls = False
-        # row stores of 64 contiguous bytes (4 lanes per row, 16 rows per instruction): an experiment that did not pay - C3 dQ
-        # 1.9181 vs 1.9195 ms, W = 512 0.4831 vs 0.4858, bitwise equal (profiles/r03_ab_dq_wide64.log): the stores of an item
-        # transition are not bound by the cache lines an instruction touches
-        self.wide64 = wide64 and persist
         self.dma_t0, self.dma_dt = dma_t0, dma_dt   # deadlines of the eight LDS-DMA pieces inside a trip (cycles of the model)
         # head dim: DK k-steps of 16, DB 32-wide output blocks, NCH valid 16-byte chunks per row (LDS rows stay 256 bytes:
         # chunks beyond the head dim are fetched as zeros or, when a whole 128-byte half is padding, not at all)
@@ -110,15 +100,11 @@ class DqGen(WorkList):
         self.d_k, self.d_v, self.d_x = sa("d_k", 4, 4), sa("d_v", 4, 4), sa("d_x", 4, 4)
         self.s_wave, self.s_hh, self.s_rgi = sa("s_wave"), sa("s_hh"), sa("s_rgi")
         self.s_pw0, self.s_pwhi = sa("s_pw0"), sa("s_pwhi")
-        self.s_flo, self.s_frng = sa("s_flo"), sa("s_frng")        # tiles starting in [flo, flo + frng) are "full" for this wave
         self.s_it, self.s_k0 = sa("s_it"), sa("s_k0")
         self.s_st, self.s_stn, self.s_std = sa("s_st"), sa("s_stn"), sa("s_std")
         self.s_koff, self.s_voff = sa("s_koff"), sa("s_voff")
         self.s_wofs = sa("s_wofs")
         self.s_cls = sa("s_cls")
-        # offsets of the 64-byte row stores: rows l and l + 16 of the two row blocks (the mask scratch of the tile bodies is
-        # idle at a transition)
-        self.vo64, self.vo64b = self.v_d, [self.v_nsh, self.v_weff]
         self.s_tmp = [sa("s_tmp%d" % i) for i in range(5)]
         if persist:
             self.wl_alloc(sa)
@@ -148,70 +134,13 @@ class DqGen(WorkList):
             p.s_sub_u32(self.s_tmp[0], self.s_tt[0], self.s_T0)
             p.s_add_u32(self.s_acc[k], self.s_acc[k], self.s_tmp[0])
 
-    def pool(self):
-        r = self.POOL[self.pool_next % len(self.POOL)]
-        self.pool_next += 1
-        return r
-
     # ------------------------------------------------------------------ pieces
-    def emit_tile_of(self, p: Prog, dst, it):
-        """dst = key-tile index of iteration `it` (sink tiles first, then the window tiles)"""
-        p.s_add_u32(dst, it, self.r_tw_off)
-        p.s_cmp("lt_u32", it, self.r_ts_hi)
-        p.s_cselect(dst, it, dst)
-
-    def emit_dma_tile(self, p: Prog, it_reg, spread=False):
-        """LDS-DMA of the K and V images of iteration it_reg's tile into stage s_std: this wave's 4 + 4 pieces (row
-        groups 2 wave, 2 wave + 1; two 128-byte halves each).  Iterations past the last tile fetch through zero-record
-        descriptors (nothing is read)."""
-        t = self.s_tmp
-        self.emit_tile_of(p, t[0], it_reg)
-        p.s_lshl_b32(t[0], t[0], 6)                        # first key of the tile
-        p.s_mul_i32(self.s_koff, t[0], P("k_sn"))
-        p.s_mul_i32(self.s_voff, t[0], P("v_sn"))
-        p.s_cmp("lt_u32", it_reg, P("nt"))
-        p.s_cselect(self.d_k[2], P("k_rng"), 0)
-        p.s_cselect(self.d_v[2], P("v_rng"), 0)
-        k = 0
-        for img, desc, off, col in ((0, self.d_k, self.s_koff, 0), (16384, self.d_v, self.s_voff, 1)):
-            for e in range(2):
-                for half in range(self.HALVES):
-                    vt = self.vt[k & 1]
-                    if half and self.l_dma1 is not None:
-                        p.v_add_u32(vt, off, self.l_dma1[e][col])
-                    else:
-                        p.v_add_u32(vt, off, self.l_dma[e][col])
-                        if half:
-                            p.v_add_u32(vt, 128, vt)
-                    if k == 0:
-                        p.s_add_u32(t[1], self.s_std, self.s_wofs)
-                        p.s_mov_m0(t[1])
-                    else:
-                        p.s_add_m0(t[1], img + 2048 * e + 1024 * half)
-                    ins = p.buffer_load_lds(16, vt, desc, 0, mem=("dma_stage",))
-                    if spread:
-                        ins.mods["alap"] = self.dma_t0 + self.dma_dt * k
-                    k += 1
-
-    def emit_k_prefetch(self, p: Prog, e, o, deadline=None):
-        """first four K row fragments (key half 0, k-steps 0..3) of the next tile, into pool slots 0..3"""
-        for ks in range(4):      # (DK >= 4 for every supported head dim)
-            base = o if ks & 1 else e
-            ins = p.ds_read_b128(self.POOL[ks], base, 512 * (ks >> 1), mem=("stage_r",))
-            if deadline is not None:
-                ins.mods["alap"] = deadline + 6 * ks
-
+    # (pool, emit_tile_of, emit_dma_tile, emit_k_prefetch: the tile ring shared with fwd.py, worklist.py)
     def emit_class(self, p: Prog):
         """s_cls: 0 full, 1 edge (no sink key in the tile), 2 edge with sink keys.  full <=> k0 + 63 <= pw0 and
-        (k0 + 63 < ns or k0 >= pw_hi - W + 1)"""
+        (k0 + 63 < ns or k0 >= pw_hi - W + 1).  The selector behind the loop head (edge_selector) finds the dead tiles
+        (class 3) and the sub-block classes 5 / 6 among the edge tiles."""
         t = self.s_tmp
-        if self.range_cls:
-            # full <=> pwhi - W + 1 <= k0 <= pw0 - 63 (every key causal for and inside the window of every row): one unsigned
-            # compare against two per-item constants; the selector behind the loop head sorts out the tiles that are not full
-            p.s_sub_u32(t[0], self.s_k0, self.s_flo)
-            p.s_cmp("lt_u32", t[0], self.s_frng)
-            p.s_cselect(self.s_cls, 0, 1)
-            return
         p.s_add_u32(t[0], self.s_k0, 63)
         p.s_cmp("le_i32", t[0], self.s_pw0)
         p.s_cselect(t[1], 1, 0)
@@ -227,22 +156,6 @@ class DqGen(WorkList):
         p.s_cselect(t[1], 2, 1)
         p.s_cmp("lg_u32", t[0], 0)
         p.s_cselect(self.s_cls, 0, t[1])
-        if self.dead and not self.edge_subs:       # (with edge_subs the selector behind the loop head finds the dead tiles)
-            # 3: no row of the wave sees any key of the tile - every key lies behind every row (k0 > pwhi), or the tile holds
-            # no sink key and every key has left every row's window (k0 + 63 <= pw0 - W): waves that own different ROWS
-            # (MHA, groups of 2) walk tiles that only the other waves' rows can see (fwd.py, class 4)
-            p.s_cmp("gt_i32", self.s_k0, self.s_pwhi)
-            p.s_cselect(t[0], 1, 0)
-            p.s_sub_i32(t[1], self.s_pw0, P("W"))
-            p.s_add_u32(t[2], self.s_k0, 63)
-            p.s_cmp("le_i32", t[2], t[1])
-            p.s_cselect(t[1], 1, 0)
-            p.s_cmp("ge_i32", self.s_k0, P("ns"))
-            p.s_cselect(t[2], 1, 0)
-            p.s_and_b32(t[1], t[1], t[2])
-            p.s_or_b32(t[0], t[0], t[1])
-            p.s_cmp("lg_u32", t[0], 0)
-            p.s_cselect(self.s_cls, 3, self.s_cls)
 
     # ------------------------------------------------------------------ prologue
     def prologue(self) -> Prog:
@@ -399,10 +312,7 @@ class DqGen(WorkList):
         p.s_cmp("eq_u32", self.s_cls, 0)
         p.s_cbranch("scc1", "L_full%=")
         p.s_cmp("eq_u32", self.s_cls, 1)
-        p.s_cbranch("scc1", "L_edgesel%=" if self.edge_subs else "L_edge%=")
-        if self.dead and not self.edge_subs:
-            p.s_cmp("eq_u32", self.s_cls, 3)
-            p.s_cbranch("scc1", "L_dead%=")
+        p.s_cbranch("scc1", "L_edgesel%=")
         if self.sinkfar:
             p.s_cmp("eq_u32", self.s_cls, 4)
             p.s_cbranch("scc1", "L_sinkfar%=")
@@ -533,27 +443,15 @@ class DqGen(WorkList):
         p = Prog()
         t = self.s_tmp
         p.label("L_edgesel%=")
-        if self.range_cls:
-            # a tile with sink keys: all of them sinks and causal for every row - full after all; else the sink-edge body
-            p.s_cmp("lt_i32", self.s_k0, P("ns"))
-            p.s_cbranch("scc0", "L_selns%=")
-            p.s_add_u32(t[2], self.s_k0, 63)
-            p.s_cmp("lt_i32", t[2], P("ns"))
-            p.s_cbranch("scc0", "L_sink%=")
-            p.s_cmp("le_i32", t[2], self.s_pw0)
-            p.s_cbranch("scc1", "L_full%=")
-            p.s_branch("L_sink%=")
-            p.label("L_selns%=")
-        if self.dead:
-            # no row of the wave sees any key of the tile: every key lies behind every row (k0 > pwhi), or every key has left
-            # every row's window (k0 + 63 <= pw0 - W; class 1 tiles hold no sink key) - waves that own different ROWS (MHA,
-            # groups of 2) walk tiles that only the other waves' rows can see
-            p.s_cmp("gt_i32", self.s_k0, self.s_pwhi)
-            p.s_cbranch("scc1", "L_dead%=")
-            p.s_sub_i32(t[1], self.s_pw0, P("W"))
-            p.s_add_u32(t[2], self.s_k0, 63)
-            p.s_cmp("le_i32", t[2], t[1])
-            p.s_cbranch("scc1", "L_dead%=")
+        # no row of the wave sees any key of the tile: every key lies behind every row (k0 > pwhi), or every key has left
+        # every row's window (k0 + 63 <= pw0 - W; class 1 tiles hold no sink key) - waves that own different ROWS (MHA,
+        # groups of 2) walk tiles that only the other waves' rows can see
+        p.s_cmp("gt_i32", self.s_k0, self.s_pwhi)
+        p.s_cbranch("scc1", "L_dead%=")
+        p.s_sub_i32(t[1], self.s_pw0, P("W"))
+        p.s_add_u32(t[2], self.s_k0, 63)
+        p.s_cmp("le_i32", t[2], t[1])
+        p.s_cbranch("scc1", "L_dead%=")
         p.s_cmp("ge_i32", self.s_k0, self.s_pw0)
         p.s_cselect(t[0], 1, 0)
         p.s_sub_i32(t[1], self.s_pw0, P("W"))
@@ -582,7 +480,6 @@ class DqGen(WorkList):
     # ------------------------------------------------------------------ epilogue
     def epilogue(self) -> Prog:
         p = Prog()
-        dt = self.dtype
         t0, t1, t2, t3 = self.tmp
         st = self.s_tmp
         p.label("L_done%=")
@@ -600,29 +497,7 @@ class DqGen(WorkList):
         p.v_lshl_add_u32(self.vo[0], t2, 4, t1)               # + 16 h bytes
         p.s_lshl_b32(st[1], P("dq_sn"), 5)
         p.v_add_u32(self.vo[1], st[1], self.vo[0])
-        # groups k / k+1 exchanged between the half-waves: 16 contiguous bytes per lane, one dwordx4 store per pair (as
-        # the forward's epilogue)
-        npair = 0
-        for rb in range(2):
-            for db in range(self.DB):
-                for gp in range(2):
-                    if 32 * db + 16 * gp >= self.D:
-                        continue                              # padding columns of the last block
-                    X, Y = self.POOL[(2 * npair) % 8], self.POOL[(2 * npair + 1) % 8]
-                    npair += 1
-                    for e in range(4):
-                        p.v_accvgpr_read(X[e], self.DQ[rb][db][8 * gp + e])
-                        p.v_accvgpr_read(Y[e], self.DQ[rb][db][8 * gp + 4 + e])
-                    for e in range(4):
-                        p.v_mul_f32(X[e], P("scale"), X[e])
-                        p.v_mul_f32(Y[e], P("scale"), Y[e])
-                    p.v_cvt_pk(dt, X[0], X[0], X[1])
-                    p.v_cvt_pk(dt, X[1], X[2], X[3])
-                    p.v_cvt_pk(dt, X[2], Y[0], Y[1])
-                    p.v_cvt_pk(dt, X[3], Y[2], Y[3])
-                    p.v_permlane32_swap(X[0], X[2])
-                    p.v_permlane32_swap(X[1], X[3])
-                    p.buffer_store(X[0:4], self.vo[rb], self.d_x, 0, offset=64 * db + 32 * gp)
+        self.emit_stores(p)
         p.s_waitcnt(vmcnt=0)
         return p
 
@@ -712,12 +587,6 @@ class DqGen(WorkList):
         p.s_sub_u32(st[2], st[4], 1)
         p.s_min_i32(st[1], st[1], st[2])
         p.s_add_u32(self.s_pwhi, st[1], P("pos0"))
-        if self.range_cls:
-            p.s_sub_i32(self.s_flo, self.s_pwhi, P("W"))
-            p.s_add_i32(self.s_flo, self.s_flo, 1)
-            p.s_sub_i32(st[1], self.s_pw0, self.s_flo)
-            p.s_sub_i32(st[1], st[1], 62)
-            p.s_max_i32(self.s_frng, st[1], 0)
         p.v_add_u32(t0, st[0], self.lane31)                   # row, rb = 0
         p.v_add_u32(self.v_pos[0], P("pos0"), t0)
         p.v_add_u32(self.v_pos[1], 32, self.v_pos[0])
@@ -830,70 +699,42 @@ class DqGen(WorkList):
         p.v_lshl_add_u32(self.vo[0], t2, 4, t1)               # + 16 h bytes
         p.s_lshl_b32(st[1], P("dq_sn"), 5)
         p.v_add_u32(self.vo[1], st[1], self.vo[0])
-        if self.wide64:
-            # 64-byte row pieces: lane = 16 g + l writes bytes 16 g .. of row (first row of the block) + l; the second store of
-            # a pair the rows 16 further
-            p.v_and(t2, 15, self.lane)
-            p.v_sub_u32(t0, self.v_pos[0], P("pos0"))
-            p.v_and(t3, 31, self.lane)
-            p.v_sub_u32(t0, t0, t3)                               # first row of row block 0
-            p.v_add_u32(t0, t0, t2)
-            p.v_mul_lo_u32(t1, t0, P("dq_sn"))
-            p.v_lshrrev(t2, 4, self.lane)
-            p.v_lshl_add_u32(self.vo64[0], t2, 4, t1)
-            p.v_add_u32(self.vo64[1], st[1], self.vo64[0])
-            p.s_lshl_b32(st[1], P("dq_sn"), 4)
-            p.v_add_u32(self.vo64b[0], st[1], self.vo64[0])
-            p.v_add_u32(self.vo64b[1], st[1], self.vo64[1])
 
     def emit_stores(self, p: Prog):
-        """dQ[row, d] = scale * dQ^T[d, row] (as the one-item epilogue).  wide64: the two 16-column groups of a 32-column block
-        are exchanged once more between the 16-lane rows (v_permlane32_swap + v_permlane16_swap), so that four lanes hold 64
-        contiguous bytes of one row and a store instruction touches 16 rows instead of 32 (the stores of an item transition
-        are bound by the cache lines an instruction touches)"""
+        """dQ[row, d] = scale * dQ^T[d, row] of the finished item: groups k / k+1 exchanged between the half-waves, 16
+        contiguous bytes per lane, one dwordx4 store per pair (as the forward's)"""
         dt = self.dtype
         npair = 0
-
-        def quad(rb, db, gp, X, Y):
-            for e in range(4):
-                p.v_accvgpr_read(X[e], self.DQ[rb][db][8 * gp + e])
-                p.v_accvgpr_read(Y[e], self.DQ[rb][db][8 * gp + 4 + e])
-            for e in range(4):
-                p.v_mul_f32(X[e], P("scale"), X[e])
-                p.v_mul_f32(Y[e], P("scale"), Y[e])
-            p.v_cvt_pk(dt, X[0], X[0], X[1])
-            p.v_cvt_pk(dt, X[1], X[2], X[3])
-            p.v_cvt_pk(dt, X[2], Y[0], Y[1])
-            p.v_cvt_pk(dt, X[3], Y[2], Y[3])
-            p.v_permlane32_swap(X[0], X[2])
-            p.v_permlane32_swap(X[1], X[3])
-
         for rb in range(2):
             for db in range(self.DB):
-                if self.wide64 and 32 * db + 32 <= self.D:
-                    X0, Y0, X1, Y1 = (self.POOL[(4 * npair + i) % 8] for i in range(4))
-                    npair += 1
-                    quad(rb, db, 0, X0, Y0)
-                    quad(rb, db, 1, X1, Y1)
-                    for e in range(4):
-                        p.v_permlane32_swap(X0[e], X1[e])
-                        p.v_permlane16_swap(X0[e], X1[e])
-                    p.buffer_store(X0[0:4], self.vo64[rb], self.d_x, 0, offset=64 * db)
-                    p.buffer_store(X1[0:4], self.vo64b[rb], self.d_x, 0, offset=64 * db)
-                    continue
                 for gp in range(2):
                     if 32 * db + 16 * gp >= self.D:
-                        continue
+                        continue                              # padding columns of the last block
                     X, Y = self.POOL[(2 * npair) % 8], self.POOL[(2 * npair + 1) % 8]
                     npair += 1
-                    quad(rb, db, gp, X, Y)
+                    for e in range(4):
+                        p.v_accvgpr_read(X[e], self.DQ[rb][db][8 * gp + e])
+                        p.v_accvgpr_read(Y[e], self.DQ[rb][db][8 * gp + 4 + e])
+                    for e in range(4):
+                        p.v_mul_f32(X[e], P("scale"), X[e])
+                        p.v_mul_f32(Y[e], P("scale"), Y[e])
+                    p.v_cvt_pk(dt, X[0], X[0], X[1])
+                    p.v_cvt_pk(dt, X[1], X[2], X[3])
+                    p.v_cvt_pk(dt, X[2], Y[0], Y[1])
+                    p.v_cvt_pk(dt, X[3], Y[2], Y[3])
+                    p.v_permlane32_swap(X[0], X[2])
+                    p.v_permlane32_swap(X[1], X[3])
                     p.buffer_store(X[0:4], self.vo[rb], self.d_x, 0, offset=64 * db + 32 * gp)
 
-    def build_pk(self):
-        items = []
-        items += finish_block(self.prologue_pk().items)
-        items += insert_waits(self.loop_top().items)
-        for cls, lbl in ((0, "L_full%="), (1, "L_edge%="), (2, "L_sink%=")) + (((3, "L_dead%="),) if self.dead else ()) + (((4, "L_sinkfar%="),) if self.sinkfar else ()) + (((5, "L_edge_d%="), (6, "L_edge_w%=")) if self.edge_subs else ()):
+    def tile_classes(self):
+        """(class, label) of the tile bodies, see tile_body"""
+        far = ((4, "L_sinkfar%="),) if self.sinkfar else ()
+        return ((0, "L_full%="), (1, "L_edge%="), (2, "L_sink%="), (3, "L_dead%=")) + far + ((5, "L_edge_d%="), (6, "L_edge_w%="))
+
+    def bodies(self):
+        """the loop head, the tile bodies behind it and the edge selector they are entered through"""
+        items = insert_waits(self.loop_top().items)
+        for cls, lbl in self.tile_classes():
             body = self.tile_body(cls).items
             items.append(Instr("label", mods={"label": lbl}, kind="label", cost=0))
             if self.do_sched:
@@ -902,8 +743,13 @@ class DqGen(WorkList):
             body = fix_hazards(body, loop=True)
             items += body
             items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
-        if self.edge_subs:
-            items += finish_block(self.edge_selector().items)
+        items += finish_block(self.edge_selector().items)
+        return items
+
+    def build_pk(self):
+        items = []
+        items += finish_block(self.prologue_pk().items)
+        items += self.bodies()
         # ---- item transition: the next item's requests go out BEFORE the finished item's stores are formed
         p = Prog()
         p.label("L_done%=")
@@ -955,22 +801,6 @@ class DqGen(WorkList):
             return self.build_pk()
         items = []
         items += finish_block(self.prologue().items)
-        items += insert_waits(self.loop_top().items)
-        for cls, lbl in ((0, "L_full%="), (1, "L_edge%="), (2, "L_sink%=")) + (((3, "L_dead%="),) if self.dead else ()) + (((4, "L_sinkfar%="),) if self.sinkfar else ()) + (((5, "L_edge_d%="), (6, "L_edge_w%=")) if self.edge_subs else ()):
-            body = self.tile_body(cls).items
-            items.append(Instr("label", mods={"label": lbl}, kind="label", cost=0))
-            if self.do_sched:
-                body = schedule(body)
-            body = insert_waits(body)
-            body = fix_hazards(body, loop=True)
-            items += body
-            items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
-        if self.edge_subs:
-            items += finish_block(self.edge_selector().items)
+        items += self.bodies()
         items += finish_block(self.epilogue().items)
         return items
-
-    def clobbers(self):
-        c = ["v%d" % i for i in range(self.vfirst, 256)] + ["a%d" % i for i in range(256)]
-        c += ["s%d" % i for i in range(self.sfirst, 100)] + ["vcc", "scc", "memory"]
-        return c

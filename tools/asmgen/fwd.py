@@ -21,8 +21,7 @@ rescale), different machine mapping:
 """
 from __future__ import annotations
 
-from .core import A, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, fimm, imm
-from .dkdv import Alloc
+from .core import A, Alloc, Imm, Instr, M0, P, PV, Prog, Reg, S, V, VCC, fimm, imm
 from .sched import finish_block, fix_hazards, insert_waits, schedule
 from .worklist import STREAM, WorkList
 
@@ -51,13 +50,12 @@ PARAMS = [
 class FwdGen(WorkList):
     DESC, DESC_BASE = DESC, DESC_BASE
 
-    def __init__(self, dtype="bf16", sched=True, vfirst=4, sfirst=None, npool=10, thr=8.0, dma_t0=500, dma_dt=180, D=128, ablate=(), lsum="mfma", kpre=True, kpre_dl=300, persist=True, trans_sched=True, dead=True, sinkfar=False):
+    def __init__(self, dtype="bf16", sched=True, vfirst=4, sfirst=None, npool=10, thr=8.0, dma_t0=500, dma_dt=180, D=128, ablate=(), kpre=True, kpre_dl=300, persist=True):
         assert dtype in ("bf16", "f16") and D in (64, 80, 96, 128)
         self.dtype, self.do_sched, self.thr = dtype, sched, thr
         self.persist = persist
-        self.trans_sched = trans_sched        # item transition placed by the gap scheduler (the pipeline fill's MFMAs beside the store tail)
         if persist:
-            assert lsum == "mfma" and kpre
+            assert kpre
         if sfirst is None:
             sfirst = 44 if persist else 56
         # head dim: DK k-steps of 16, DB 32-wide output blocks, NCH valid 16-byte chunks per row (LDS rows stay 256 bytes:
@@ -67,18 +65,9 @@ class FwdGen(WorkList):
         # LDS-DMA deadlines inside a trip (early and staggered; placing them in the PV half measured 0.8 % slower)
         self.dma_t0, self.dma_dt = dma_t0, dma_dt
         self.ablate = set(ablate)         # timing-only knock-out builds (wrong results)
-        self.dead = dead                  # tile class 4 (emit_class) and the iteration bodies that skip dead tiles
-        self.dead_sel = True              # ... found by a selector behind the loop head that only edge tiles reach, not by every body
-        # ... which can also tell sink tiles from edge tiles, so that the bodies compute "full or not" only (12 scalar
-        # instructions fewer per iteration): measured no faster (C3 forward 1.484 vs 1.477 ms, same box), off
-        self.range_cls = False
-        # an item's sink tile without the exp2 / PV of its second key half when nobody sees it: measured no faster (C3 forward
-        # 1.458 vs 1.445 ms, window 512 0.383 vs 0.383, in-process): off; the dQ kernel's version of it pays (dq.py)
-        self.sinkfar = sinkfar and persist and dead
         # the first four K row fragments of the NEXT iteration's S^T chains are read at the end of the current one (their
         # latency passes under the loop head instead of in front of the first MFMA); needs tile i+2 landed at barrier i
         self.kpre, self.kpre_dl = kpre, kpre_dl
-        self.lsum_valu = lsum == "valu"   # row sums: f32 adds beside the exponentials ("valu") or ones-MFMAs ("mfma")
         self.vfirst, self.sfirst = vfirst, sfirst
         va = self.va = Alloc("v", vfirst, 255)
         sa = self.sa = Alloc("s", sfirst, 99)
@@ -88,8 +77,6 @@ class FwdGen(WorkList):
         self.m = [va("m%d" % rb) for rb in range(2)]          # reference point of the running softmax (log2 domain)
         self.nms = [va("nms%d" % rb) for rb in range(2)]      # -(m, or 0 where m = -inf): the exponent offset
         self.alpha = [va("alpha%d" % rb) for rb in range(2)]
-        # per-lane partial row sums (the lane's own keys; the two half-waves are added in the epilogue)
-        self.lsum = [va("lsum%d" % rb) for rb in range(2)] if self.lsum_valu else None
         self.lane, self.lane31 = va("lane"), va("lane31")
         self.l_row_e, self.l_tr0 = va("l_row_e"), va("l_tr0")
         self.a_k_e, self.a_k_o = va("a_k_e"), va("a_k_o")
@@ -115,7 +102,6 @@ class FwdGen(WorkList):
         self.s_f0 = sa("s_f0", 2, 2)
         self.s_wave, self.s_hh, self.s_rgi = sa("s_wave"), sa("s_hh"), sa("s_rgi")
         self.s_pw0, self.s_pwhi = sa("s_pw0"), sa("s_pwhi")
-        self.s_flo, self.s_frng = sa("s_flo"), sa("s_frng")        # tiles starting in [flo, flo + frng) are "full" for this wave
         self.s_it, self.s_k0n = sa("s_it"), sa("s_k0n")
         self.s_st, self.s_stn, self.s_std = sa("s_st"), sa("s_stn"), sa("s_std")
         self.s_koff, self.s_voff = sa("s_koff"), sa("s_voff")
@@ -133,58 +119,11 @@ class FwdGen(WorkList):
             return list(PARAMS_PK)
         return list(PARAMS)
 
-    def pool(self):
-        r = self.POOL[self.pool_next % len(self.POOL)]
-        self.pool_next += 1
-        return r
-
-    # ------------------------------------------------------------------ shared with dq.py (same tile ring)
-    def emit_tile_of(self, p: Prog, dst, it):
-        p.s_add_u32(dst, it, self.r_tw_off)
-        p.s_cmp("lt_u32", it, self.r_ts_hi)
-        p.s_cselect(dst, it, dst)
-
-    def emit_dma_tile(self, p: Prog, it_reg, spread=False):
-        t = self.s_tmp
-        self.emit_tile_of(p, t[0], it_reg)
-        p.s_lshl_b32(t[0], t[0], 6)
-        p.s_mul_i32(self.s_koff, t[0], P("k_sn"))
-        p.s_mul_i32(self.s_voff, t[0], P("v_sn"))
-        p.s_cmp("lt_u32", it_reg, P("nt"))
-        p.s_cselect(self.d_k[2], P("k_rng"), 0)
-        p.s_cselect(self.d_v[2], P("v_rng"), 0)
-        k = 0
-        for img, desc, off, col in ((0, self.d_k, self.s_koff, 0), (16384, self.d_v, self.s_voff, 1)):
-            for e in range(2):
-                for half in range(self.HALVES):
-                    vt = self.vt[k & 1]
-                    if half and self.l_dma1 is not None:
-                        p.v_add_u32(vt, off, self.l_dma1[e][col])
-                    else:
-                        p.v_add_u32(vt, off, self.l_dma[e][col])
-                        if half:
-                            p.v_add_u32(vt, 128, vt)
-                    if k == 0:
-                        p.s_add_u32(t[1], self.s_std, self.s_wofs)
-                        p.s_mov_m0(t[1])
-                    else:
-                        p.s_add_m0(t[1], img + 2048 * e + 1024 * half)
-                    ins = p.buffer_load_lds(16, vt, desc, 0, mem=("dma_stage",))
-                    if spread:
-                        ins.mods["alap"] = self.dma_t0 + self.dma_dt * k
-                    k += 1
-
+    # (pool, emit_tile_of, emit_dma_tile, emit_k_prefetch: the tile ring shared with dq.py, worklist.py)
     def emit_class(self, p: Prog, k0):
-        """s_cls of the tile starting at key k0: 0 full, 1 edge (no sink key in the tile), 2 edge with sink keys, 4 dead"""
+        """s_cls of the tile starting at key k0: 0 full, 1 edge (no sink key in the tile), 2 edge with sink keys.  Dead tiles
+        (class 4) are edge tiles here; edge_selectors tells them apart behind the loop head."""
         t = self.s_tmp
-        if self.range_cls:
-            # the scheduled bodies only ask "full or not": every key causal for every row and inside every row's window <=>
-            # pwhi - W + 1 <= k0 <= pw0 - 63, one unsigned compare against two per-item constants; the selector behind the loop
-            # head tells the rest apart (edge / sink keys / dead), for the tiles that are not full
-            p.s_sub_u32(t[0], k0, self.s_flo)
-            p.s_cmp("lt_u32", t[0], self.s_frng)
-            p.s_cselect(self.s_cls, 0, 1)
-            return
         p.s_add_u32(t[0], k0, 63)
         p.s_cmp("le_i32", t[0], self.s_pw0)
         p.s_cselect(t[1], 1, 0)
@@ -200,31 +139,8 @@ class FwdGen(WorkList):
         p.s_cselect(t[1], 2, 1)
         p.s_cmp("lg_u32", t[0], 0)
         p.s_cselect(self.s_cls, 0, t[1])
-        if self.dead and not self.dead_sel:
-            # 4: no row of the wave sees any key of the tile - every key lies behind every row (k0 > pwhi), or the tile holds
-            # no sink key and every key has left every row's window (k0 + 63 <= pw0 - W).  Workgroups whose waves own
-            # different ROWS (MHA, groups of 2: 4 / hpw row groups) walk tiles that only the other waves' rows can see.
-            p.s_cmp("gt_i32", k0, self.s_pwhi)
-            p.s_cselect(t[0], 1, 0)
-            p.s_sub_i32(t[1], self.s_pw0, P("W"))
-            p.s_add_u32(t[2], k0, 63)
-            p.s_cmp("le_i32", t[2], t[1])
-            p.s_cselect(t[1], 1, 0)
-            p.s_cmp("ge_i32", k0, P("ns"))
-            p.s_cselect(t[2], 1, 0)
-            p.s_and_b32(t[1], t[1], t[2])
-            p.s_or_b32(t[0], t[0], t[1])
-            p.s_cmp("lg_u32", t[0], 0)
-            p.s_cselect(self.s_cls, 4, self.s_cls)
 
     # ------------------------------------------------------------------ phases
-    def emit_k_prefetch(self, p: Prog, e, o, deadline=None):
-        """first four K row fragments (key half 0, k-steps 0..3) of a tile, into pool slots 0..3"""
-        for ks in range(4):      # (DK >= 4 for every supported head dim)
-            ins = p.ds_read_b128(self.POOL[ks], o if ks & 1 else e, 512 * (ks >> 1), mem=("stage_r",), note="K rows, next trip")
-            if deadline is not None:
-                ins.mods["alap"] = deadline + 6 * ks
-
     # Sub-block classes of a tile (the short-window strip bodies, fwd_strip.py): self.sub = None, or sub[kh][rb] in ("mask",
     # "full", "dead") for key half kh x row block rb - a "dead" sub-block (no row sees any of its keys) is left out of every
     # phase, a "full" one (every row sees every key) gets no mask instructions.
@@ -339,8 +255,6 @@ class FwdGen(WorkList):
                     if "fma" not in self.ablate:
                         p.v_fma_f32(acc[v], acc[v], P("c_log2"), self.nms[rb])
                     p.v_exp_f32(acc[v], acc[v])
-                    if self.lsum_valu:
-                        p.v_add_f32(self.lsum[rb], self.lsum[rb], acc[v])
                 for s in range(2):
                     for j in range(4):
                         p.v_cvt_pk(self.dtype, acc[4 * s + j], acc[8 * s + 2 * j], acc[8 * s + 2 * j + 1])
@@ -353,7 +267,7 @@ class FwdGen(WorkList):
             for s in range(2):
                 pf = [self.SS[par][kh][rb][4 * s:4 * s + 4] for rb in range(2)]
                 for rb in range(2):
-                    if not self.lsum_valu and not self.sub_is(kh, rb, "dead"):
+                    if not self.sub_is(kh, rb, "dead"):
                         p.mfma(dt, self.LACC[rb], self.ONES, pf[rb], self.LACC[rb], tag="l")
                 if self.sub_is(kh, 0, "dead") and self.sub_is(kh, 1, "dead"):
                     continue                                   # nobody takes this key half's V^T fragments
@@ -485,16 +399,10 @@ class FwdGen(WorkList):
         p.s_cselect(st[1], P("m0_2"), st[1])
         p.s_cmp("eq_u32", self.s_hh, 3)
         p.s_cselect(st[1], P("m0_3"), st[1])
-        if self.lsum_valu:
-            p.v_mov(t1, P("l0"))
-            p.v_cmp("gt_u32", 32, lane)
         for rb in range(2):
             p.v_mov(self.m[rb], st[1])
-            if self.lsum_valu:
-                p.v_cndmask(self.lsum[rb], 0, t1)                 # l0 once per row: lanes 0..31
-            else:
-                for i in range(16):
-                    p.v_accvgpr_write(self.LACC[rb][i], P("l0"))
+            for i in range(16):
+                p.v_accvgpr_write(self.LACC[rb][i], P("l0"))
             for db in range(self.DB):
                 for i in range(16):
                     p.v_accvgpr_write(self.OACC[rb][db][i], 0)
@@ -548,17 +456,16 @@ class FwdGen(WorkList):
         else:
             p.s_waitcnt(vmcnt=4 * self.HALVES, note="tile it+1 landed (own pieces); tile it+2 may be in flight")
             p.s_barrier()
-        codes = self.body_codes()
-        if self.dead and self.dead_sel:
-            codes = [c for c in codes if (c & 7) != 4]          # the dead-next bodies are entered through the selectors
+        # (the dead-next bodies, class 4, are entered through the selectors, which the edge-next codes go to)
+        codes = [c for c in self.body_codes() if (c & 7) != 4]
+        target = lambda code: ("L_sel%d%%=" if (code & 7) == 1 else "L_body%d%%=") % code
         for code in codes[:-1]:
             p.s_cmp("eq_u32", self.s_cls, code)
-            p.s_cbranch("scc1", ("L_sel%d%%=" if (self.dead and self.dead_sel and (code & 7) == 1) else "L_body%d%%=") % code)
-        last = codes[-1]
-        p.s_branch(("L_sel%d%%=" if (self.dead and self.dead_sel and (last & 7) == 1) else "L_body%d%%=") % last)
+            p.s_cbranch("scc1", target(code))
+        p.s_branch(target(codes[-1]))
         return p
 
-    def dead_selectors(self) -> Prog:
+    def edge_selectors(self) -> Prog:
         """behind the loop head, for iterations whose NEXT tile is an edge tile without sink keys: is it out of reach of every
         row of the wave - every key behind every row (k0n > pwhi) or past every row's window (k0n + 63 <= pw0 - W)?  Then the
         body without its S^T chains and softmax bookkeeping (class 4), else the edge body.  Waves that own different ROWS (MHA,
@@ -569,18 +476,6 @@ class FwdGen(WorkList):
             if (code & 7) != 1:
                 continue
             p.label("L_sel%d%%=" % code)
-            if self.range_cls:
-                # a tile with sink keys: all of them sinks and causal for every row - full after all; else the sink-edge body
-                l_ns = "L_selns%d%%=" % code
-                p.s_cmp("lt_i32", self.s_k0n, P("ns"))
-                p.s_cbranch("scc0", l_ns)
-                p.s_add_u32(t[2], self.s_k0n, 63)
-                p.s_cmp("lt_i32", t[2], P("ns"))
-                p.s_cbranch("scc0", "L_body%d%%=" % (code + 1))
-                p.s_cmp("le_i32", t[2], self.s_pw0)
-                p.s_cbranch("scc1", "L_body%d%%=" % (code - 1))
-                p.s_branch("L_body%d%%=" % (code + 1))
-                p.label(l_ns)
             p.s_cmp("gt_i32", self.s_k0n, self.s_pwhi)
             p.s_cbranch("scc1", "L_body%d%%=" % (code + 3))
             p.s_sub_i32(t[1], self.s_pw0, P("W"))
@@ -593,12 +488,7 @@ class FwdGen(WorkList):
     def body_codes(self):
         """dispatch codes (2 cur_dead + par) 8 + class of the iteration bodies, the frequent ones first"""
         live = [8 * par + c for c in (0, 1, 3, 2) for par in (0, 1)]
-        if not self.dead:
-            return live
-        codes = live + [8 * par + 4 for par in (0, 1)] + [16 + 8 * par + c for c in (4, 0, 1, 3, 2) for par in (0, 1)]
-        if self.sinkfar:
-            codes += [32 + c for c in (0, 1, 4, 3, 2)]           # the item's first iteration, tile 0 = a far sink tile (parity 0)
-        return codes
+        return live + [8 * par + 4 for par in (0, 1)] + [16 + 8 * par + c for c in (4, 0, 1, 3, 2) for par in (0, 1)]
 
     def rescale(self) -> Prog:
         """out of line: O and l of the rows whose reference point moved are multiplied by alpha (1 elsewhere)"""
@@ -607,11 +497,7 @@ class FwdGen(WorkList):
         t = self.tmp
         k = 0
         for rb in range(2):
-            regs = [self.OACC[rb][db][i] for db in range(self.DB) for i in range(16)]
-            if self.lsum_valu:
-                p.v_mul_f32(self.lsum[rb], self.alpha[rb], self.lsum[rb])
-            else:
-                regs = [self.LACC[rb][i] for i in range(16)] + regs
+            regs = [self.LACC[rb][i] for i in range(16)] + [self.OACC[rb][db][i] for db in range(self.DB) for i in range(16)]
             for a in regs:
                 r = t[k % 4]
                 k += 1
@@ -622,7 +508,7 @@ class FwdGen(WorkList):
         return p
 
     # ------------------------------------------------------------------ one iteration
-    def body(self, par: int, cls_next: int, cur_dead: bool = False, cur_sinkfar: bool = False) -> Prog:
+    def body(self, par: int, cls_next: int, cur_dead: bool = False) -> Prog:
         """par: SS[par] holds tile i (its exp / PV run here), SS[par ^ 1] receives tile i+1; cls_next 0..2, 3 = none, 4 = tile
         i+1 is dead for this wave (no S^T, no softmax bookkeeping); cur_dead: tile i is (nothing to exponentiate or add)"""
         p = Prog()
@@ -641,10 +527,8 @@ class FwdGen(WorkList):
         if cls_next not in (3, 4):
             self.emit_A(p, par ^ 1, self.a_k_e, self.a_k_o, pre=self.kpre)
         if not cur_dead:
-            self.sub = [["mask", "mask"], ["dead", "dead"]] if cur_sinkfar else None      # (sub[kh][rb])
             self.emit_E(p, par)
             self.emit_C(p, par)
-            self.sub = None
         if cls_next not in (3, 4):
             self.emit_M(p, par ^ 1, cls_next, self.s_k0n)
         else:
@@ -693,13 +577,7 @@ class FwdGen(WorkList):
         inv = [self.alpha[0], self.alpha[1]]
         lg = [self.nms[0], self.nms[1]]
         for rb in range(2):
-            if self.lsum_valu:
-                p.v_mov(t3, self.lsum[rb])
-                p.v_mov(t4, t3)
-                p.v_permlane32_swap(t3, t4)
-                p.v_add_f32(t3, t3, t4)
-            else:
-                p.v_accvgpr_read(t3, self.LACC[rb][0])
+            p.v_accvgpr_read(t3, self.LACC[rb][0])
             p.v_mov(t4, fimm(1.0))
             p.v_cmp("eq_f32", 0, t3)
             p.v_cndmask(t3, t3, t4)                           # l = 0 -> 1
@@ -843,12 +721,6 @@ class FwdGen(WorkList):
         p.s_sub_u32(st[2], st[4], 1)
         p.s_min_i32(st[1], st[1], st[2])
         p.s_add_u32(self.s_pwhi, st[1], P("pos0"))
-        if self.range_cls:
-            p.s_sub_i32(self.s_flo, self.s_pwhi, P("W"))
-            p.s_add_i32(self.s_flo, self.s_flo, 1)
-            p.s_sub_i32(st[1], self.s_pw0, self.s_flo)
-            p.s_sub_i32(st[1], st[1], 62)
-            p.s_max_i32(self.s_frng, st[1], 0)
         p.v_add_u32(t0, st[0], self.lane31)                   # row, rb = 0
         p.v_add_u32(self.v_pos[0], P("pos0"), t0)
         p.v_add_u32(self.v_pos[1], 32, self.v_pos[0])
@@ -901,26 +773,6 @@ class FwdGen(WorkList):
         self.emit_M(p, 0, 2, self.s_k0n)
         p.s_mov(self.s_it, 0)
         self.emit_next_class(p, self.s_it)
-        if self.sinkfar:
-            # tile 0 is a sink tile whose second 32-key half holds no sink key and lies outside every row's window (rows far
-            # behind the sinks: every item but the first few): the first iteration skips that half's exp2 / PV / row sums
-            # (dispatch code + 32; its S^T and mask above were computed in full - they are masked to -inf)
-            p.s_mov(st[3], 0)
-            self.emit_tile_of(p, st[4], st[3])
-            p.s_lshl_b32(st[4], st[4], 6)                          # k0 of tile 0
-            p.s_cmp("lt_i32", st[4], P("ns"))
-            p.s_cselect(st[0], 1, 0)
-            p.s_add_u32(st[1], st[4], 32)
-            p.s_cmp("ge_i32", st[1], P("ns"))
-            p.s_cselect(st[1], 1, 0)
-            p.s_and_b32(st[0], st[0], st[1])
-            p.s_sub_i32(st[1], self.s_pw0, P("W"))
-            p.s_add_u32(st[2], st[4], 63)
-            p.s_cmp("le_i32", st[2], st[1])
-            p.s_cselect(st[1], 1, 0)
-            p.s_and_b32(st[0], st[0], st[1])
-            p.s_lshl_b32(st[0], st[0], 5)
-            p.s_add_u32(self.s_cls, self.s_cls, st[0])
         if first:
             p.s_waitcnt(vmcnt=0, note="tiles 1, 2 landed (own pieces)")
             p.s_barrier()
@@ -1025,23 +877,29 @@ class FwdGen(WorkList):
         p.buffer_store(lg[0], self.v_d[0], self.d_x, 0)
         p.buffer_store(lg[1], self.v_d[1], self.d_x, 0)
 
+    def bodies(self):
+        """the loop head, the iteration bodies behind it and what they reach out of line (rescale pass, dead-tile selectors)"""
+        items = insert_waits(self.loop_top().items)
+        for code in self.body_codes():
+            b = self.body((code >> 3) & 1, code & 7, cur_dead=bool(code & 16)).items
+            items.append(Instr("label", mods={"label": "L_body%d%%=" % code}, kind="label", cost=0))
+            if self.do_sched:
+                b = schedule(b)
+            b = insert_waits(b)
+            b = fix_hazards(b, loop=True)
+            # every load into a register is consumed inside the body: nothing outstanding at its end
+            items += b
+            if not self.kpre:
+                items.append(Instr("s_waitcnt", kind="wait", mods={"lgkmcnt": 0}))
+            items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
+        items += finish_block(self.rescale().items)
+        items += finish_block(self.edge_selectors().items)
+        return items
+
     def build_pk(self):
         items = []
         items += finish_block(self.prologue_pk().items)
-        items += insert_waits(self.loop_top().items)
-        for code in self.body_codes():
-            if True:
-                b = self.body((code >> 3) & 1, code & 7, cur_dead=bool(code & 16), cur_sinkfar=bool(code & 32)).items
-                items.append(Instr("label", mods={"label": "L_body%d%%=" % code}, kind="label", cost=0))
-                if self.do_sched:
-                    b = schedule(b)
-                b = insert_waits(b)
-                b = fix_hazards(b, loop=True)
-                items += b
-                items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
-        items += finish_block(self.rescale().items)
-        if self.dead and self.dead_sel:
-            items += finish_block(self.dead_selectors().items)
+        items += self.bodies()
         # ---- item transition: the next item's Q requests go out BEFORE the finished item's stores are formed
         p = Prog()
         p.label("L_done%=")
@@ -1055,7 +913,8 @@ class FwdGen(WorkList):
         self.emit_item_begin(p)
         self.emit_stores(p)
         self.emit_item_init(p)
-        blk = schedule(p.items) if (self.trans_sched and self.do_sched) else p.items
+        # (placed by the gap scheduler: the pipeline fill's MFMAs beside the store tail)
+        blk = schedule(p.items) if self.do_sched else p.items
         items += fix_hazards(insert_waits(blk, strict_tail=True))
         items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
         p = Prog()
@@ -1070,27 +929,6 @@ class FwdGen(WorkList):
             return self.build_pk()
         items = []
         items += finish_block(self.prologue().items)
-        items += insert_waits(self.loop_top().items)
-        for code in self.body_codes():
-            if True:
-                b = self.body((code >> 3) & 1, code & 7, cur_dead=bool(code & 16), cur_sinkfar=bool(code & 32)).items
-                items.append(Instr("label", mods={"label": "L_body%d%%=" % code}, kind="label", cost=0))
-                if self.do_sched:
-                    b = schedule(b)
-                b = insert_waits(b)
-                b = fix_hazards(b, loop=True)
-                # every load into a register is consumed inside the body: nothing outstanding at its end
-                items += b
-                if not self.kpre:
-                    items.append(Instr("s_waitcnt", kind="wait", mods={"lgkmcnt": 0}))
-                items.append(Instr("s_branch", mods={"label": "L_top%="}, kind="branch"))
-        items += finish_block(self.rescale().items)
-        if self.dead and self.dead_sel:
-            items += finish_block(self.dead_selectors().items)
+        items += self.bodies()
         items += finish_block(self.epilogue().items)
         return items
-
-    def clobbers(self):
-        c = ["v%d" % i for i in range(self.vfirst, 256)] + ["a%d" % i for i in range(256)]
-        c += ["s%d" % i for i in range(self.sfirst, 100)] + ["vcc", "scc", "memory"]
-        return c

@@ -577,8 +577,3 @@ class FwdStripGen(FwdGen):
         items += finish_block(p.items)
         items += block(self.tail())
         return items
-
-    def clobbers(self):
-        c = ["v%d" % i for i in range(self.vfirst, 256)] + ["a%d" % i for i in range(256)]
-        c += ["s%d" % i for i in range(self.sfirst, 100)] + ["vcc", "scc", "memory"]
-        return c

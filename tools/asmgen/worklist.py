@@ -1,4 +1,5 @@
-"""Work-list (persistent workgroup) machinery shared by the forward and the dQ generators.
+"""What the forward and the dQ generators share: the K / V tile ring (TileRing) and the work-list (persistent workgroup)
+machinery on top of it (WorkList).
 
 A workgroup no longer owns ONE (batch, KV head, head set, query tile) but walks a list of such work items; the HIP shell
 writes one 128-byte descriptor per item into LDS behind the K / V tile ring and passes their number.  Two cursors run
@@ -22,7 +23,7 @@ VGPRs and moved to SGPRs with v_readfirstlane.
 """
 from __future__ import annotations
 
-from .core import P, Prog
+from .core import GenBase, P, Prog
 
 DESC_BYTES = 128
 DESC_MAX = 256                 # items per asm invocation (32 KB of descriptors: ring + table = the CU's 160 KB)
@@ -30,9 +31,67 @@ DESC_MAX = 256                 # items per asm invocation (32 KB of descriptors:
 STREAM = {"k_lo": 16, "k_hi": 17, "v_lo": 18, "v_hi": 19, "k_rng": 20, "v_rng": 21, "nt": 22, "ts_hi": 23, "tw_off": 24}
 
 
-class WorkList:
-    """mixin of FwdGen / DqGen (persist=True).  The host class provides: DESC (field -> dword), DESC_BASE, s_tmp, vt,
-    POOL, l_dma, l_dma1, d_k, d_v, s_koff, s_voff, s_std, s_wofs, HALVES, dma_t0, dma_dt."""
+class TileRing(GenBase):
+    """The 4-deep K / V tile ring of FwdGen / DqGen, in the one-item and the work-list form alike.  The host class
+    provides: s_tmp, vt, POOL, l_dma, l_dma1, d_k, d_v, s_koff, s_voff, s_std, s_wofs, HALVES, dma_t0, dma_dt, and the
+    tile-list scalars r_ts_hi / r_tw_off of the item being computed (SGPRs of the work-list form, asm inputs otherwise)."""
+
+    def emit_tile_of(self, p: Prog, dst, it, ts_hi=None, tw_off=None):
+        """dst = key-tile index of iteration `it` (sink tiles first, then the window tiles); the tile list is the compute
+        cursor's unless given"""
+        p.s_add_u32(dst, it, self.r_tw_off if tw_off is None else tw_off)
+        p.s_cmp("lt_u32", it, self.r_ts_hi if ts_hi is None else ts_hi)
+        p.s_cselect(dst, it, dst)
+
+    def emit_dma_pieces(self, p: Prog, spread):
+        """the wave's pieces of the K and V images of the tile at source offsets s_koff / s_voff, into stage s_std"""
+        t = self.s_tmp
+        k = 0
+        for img, desc, off, col in ((0, self.d_k, self.s_koff, 0), (16384, self.d_v, self.s_voff, 1)):
+            for e in range(2):
+                for half in range(self.HALVES):
+                    vt = self.vt[k & 1]
+                    if half and self.l_dma1 is not None:
+                        p.v_add_u32(vt, off, self.l_dma1[e][col])
+                    else:
+                        p.v_add_u32(vt, off, self.l_dma[e][col])
+                        if half:
+                            p.v_add_u32(vt, 128, vt)
+                    if k == 0:
+                        p.s_add_u32(t[1], self.s_std, self.s_wofs)
+                        p.s_mov_m0(t[1])
+                    else:
+                        p.s_add_m0(t[1], img + 2048 * e + 1024 * half)
+                    ins = p.buffer_load_lds(16, vt, desc, 0, mem=("dma_stage",))
+                    if spread:
+                        ins.mods["alap"] = self.dma_t0 + self.dma_dt * k
+                    k += 1
+
+    def emit_dma_tile(self, p: Prog, it_reg, spread=False):
+        """LDS-DMA of the K and V images of iteration it_reg's tile into stage s_std: this wave's 4 + 4 pieces (row
+        groups 2 wave, 2 wave + 1; two 128-byte halves each).  Iterations past the last tile fetch through zero-record
+        descriptors (nothing is read)."""
+        t = self.s_tmp
+        self.emit_tile_of(p, t[0], it_reg)
+        p.s_lshl_b32(t[0], t[0], 6)                        # first key of the tile
+        p.s_mul_i32(self.s_koff, t[0], P("k_sn"))
+        p.s_mul_i32(self.s_voff, t[0], P("v_sn"))
+        p.s_cmp("lt_u32", it_reg, P("nt"))
+        p.s_cselect(self.d_k[2], P("k_rng"), 0)
+        p.s_cselect(self.d_v[2], P("v_rng"), 0)
+        self.emit_dma_pieces(p, spread)
+
+    def emit_k_prefetch(self, p: Prog, e, o, deadline=None):
+        """first four K row fragments (key half 0, k-steps 0..3) of the next tile, into pool slots 0..3"""
+        for ks in range(4):      # (DK >= 4 for every supported head dim)
+            ins = p.ds_read_b128(self.POOL[ks], o if ks & 1 else e, 512 * (ks >> 1), mem=("stage_r",), note="K rows, next trip")
+            if deadline is not None:
+                ins.mods["alap"] = deadline + 6 * ks
+
+
+class WorkList(TileRing):
+    """base of FwdGen / DqGen; what follows is used by their work-list form only (persist=True).  The host class provides,
+    beyond what TileRing asks for: DESC (field -> dword), DESC_BASE."""
 
     def wl_alloc(self, sa):
         self.s_item = sa("s_item")                       # compute cursor
@@ -101,40 +160,16 @@ class WorkList:
         p.s_mov(self.s_dit, 0)
         p.label(l_na)
 
-    def emit_tile_of_pk(self, p: Prog, dst, it, ts_hi, tw_off):
-        p.s_add_u32(dst, it, tw_off)
-        p.s_cmp("lt_u32", it, ts_hi)
-        p.s_cselect(dst, it, dst)
-
     def emit_dma_stream_tile(self, p: Prog, spread=False):
         """LDS-DMA of the K and V images of the stream's next tile into stage s_std (this wave's pieces), then the cursor
         moves on.  Behind the last item the stream is empty (s_dnt = 0): zero-record descriptors, nothing is read."""
         t = self.s_tmp
-        self.emit_tile_of_pk(p, t[0], self.s_dit, self.s_dts_hi, self.s_dtw_off)
+        self.emit_tile_of(p, t[0], self.s_dit, self.s_dts_hi, self.s_dtw_off)
         p.s_lshl_b32(t[0], t[0], 6)
         p.s_mul_i32(self.s_koff, t[0], P("k_sn"))
         p.s_mul_i32(self.s_voff, t[0], P("v_sn"))
         p.s_cmp("lt_u32", self.s_dit, self.s_dnt)
         p.s_cselect(self.d_k[2], self.s_krng, 0)
         p.s_cselect(self.d_v[2], self.s_vrng, 0)
-        k = 0
-        for img, desc, off, col in ((0, self.d_k, self.s_koff, 0), (16384, self.d_v, self.s_voff, 1)):
-            for e in range(2):
-                for half in range(self.HALVES):
-                    vt = self.vt[k & 1]
-                    if half and self.l_dma1 is not None:
-                        p.v_add_u32(vt, off, self.l_dma1[e][col])
-                    else:
-                        p.v_add_u32(vt, off, self.l_dma[e][col])
-                        if half:
-                            p.v_add_u32(vt, 128, vt)
-                    if k == 0:
-                        p.s_add_u32(t[1], self.s_std, self.s_wofs)
-                        p.s_mov_m0(t[1])
-                    else:
-                        p.s_add_m0(t[1], img + 2048 * e + 1024 * half)
-                    ins = p.buffer_load_lds(16, vt, desc, 0, mem=("dma_stage",))
-                    if spread:
-                        ins.mods["alap"] = self.dma_t0 + self.dma_dt * k
-                    k += 1
+        self.emit_dma_pieces(p, spread)
         p.s_add_u32(self.s_dit, self.s_dit, 1)
