@@ -51,6 +51,9 @@ extern "C" {
 #define SFA_DTYPE_F32 0
 #define SFA_DTYPE_F16 1
 #define SFA_DTYPE_BF16 2
+/* OCP e4m3fn (not fnuz), one byte per element: legal ONLY on the four cache buffers of the *_fp8_slots calls and on the
+ * eight buffers of sfa_ring_copy_slots; every other entry point answers it with "<name>: unknown dtype 3". */
+#define SFA_DTYPE_FP8_E4M3 3
 
 #define SFA_OK 0
 #define SFA_ERR_INVALID_ARGUMENT (-1)  /* null pointer, shape mismatch, bad stride ...   */
@@ -600,6 +603,67 @@ int sfa_ring_commit_path_ragged_slots(const sfa_tensor* window_k, const sfa_tens
                                       void* stream);
 
 /*
+ * FP8 (OCP e4m3fn) slot pool: the packed calls on a pool whose four cache buffers hold one byte per element
+ * (SFA_DTYPE_FP8_E4M3; rows of D = 64 / 80 / 96 / 128 bytes, 16-byte aligned like every row).  Activations (q, k_new,
+ * v_new, o; k / v of the fill) are bf16 or f16, of one dtype T.  An FP8 pool halves the bytes a step reads and the bytes
+ * a slot holds.
+ *   kv_scale    device float [2][H_kv], row 0 for K and row 1 for V: one static scale per KV head, owned by the caller
+ *               (what a calibrated checkpoint carries).  NULL: all ones.  The kernels read it when they run and it is
+ *               never read on the host, so an in-place update is seen by the next replay of a captured graph.  No scale
+ *               lives in the pool.
+ * Storing a 16-bit element x of KV head h, in f32 with one reciprocal per head:
+ *     r = 1.0f / scale[h] (IEEE division);  code = e4m3fn_rne(clamp(float(x) * r, -448, 448))
+ * The clamp is explicit: overflow saturates to +-448 (codes 0x7e / 0xfe), never NaN.  Inputs are finite; what a NaN
+ * becomes is unspecified.  Reading a code of head h gives T(float(code) * scale[h]): one f32 multiply, rounded to
+ * nearest even into T.  Two bitwise equalities follow and are what the tests hold the calls to:
+ *   - Storage.  Every cache row a storing call writes holds exactly that expression applied to the 16-bit row the same
+ *     call writes into a 16-bit pool; every row the 16-bit call leaves alone keeps its bytes; the state rows are equal.
+ *   - Read.  o of a packed step on an FP8 pool is bit for bit o of the same step on a 16-bit pool whose buffers hold
+ *     T(float(code) * scale): the sink and ring tiles are converted in registers between the global load and the LDS
+ *     store, everything after that is the 16-bit kernel.
+ * The tokens of a step (k_new / v_new) are attended at 16-bit precision inside that step and at FP8 precision from the
+ * next one on, so a prompt admitted in several chunks is not bitwise the prompt admitted in one call.
+ *
+ * sfa_decode_ring_ragged_fp8_slots: the arguments of sfa_decode_ring_ragged_tree_slots plus kv_scale in front of
+ * workspace.  parent == NULL: the plain ragged mask; commit_seq == NULL, commit and SFA_FLAG_RAGGED_ADMIT as there.  A
+ * commit quantises as it stores, the admitting placement into the sink rows included.  Workspace:
+ * sfa_decode_ragged_workspace_bytes with q's dtype (the partials are f32).  Host checks: those of the 16-bit call in
+ * its order, with "decode_ragged_fp8: the cache buffers must be FP8 (e4m3)" (SFA_ERR_INVALID_ARGUMENT) where it
+ * compares the dtypes; fp32 activations and head dims outside 64 / 80 / 96 / 128 are SFA_ERR_UNSUPPORTED (there is no
+ * exact-f32 instance for an FP8 pool, and SFA_FLAG_FORCE_GENERIC is refused the same way).  sfa_last_path(): the name of
+ * the 16-bit call plus "_kvfp8".
+ */
+int sfa_decode_ring_ragged_fp8_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                     const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                     const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
+                                     const int32_t* parent, const int32_t* commit_seq, int commit, int32_t* state,
+                                     const int32_t* slots, const int32_t* cu_q, int n_seq, const float* kv_scale,
+                                     void* workspace, size_t workspace_bytes, float scale, unsigned flags,
+                                     void* stream);
+
+/*
+ * sfa_ring_commit_path_ragged_slots into an FP8 ring: the same arguments plus kv_scale in front of stream; k_new /
+ * v_new are bf16 or f16, window_k / window_v FP8.  Slots, order and state advance are those of the 16-bit call; each
+ * stored row is quantised by the storing rule above (a thread reads 16 bytes = 8 elements and writes 8 bytes).
+ * "ring_commit_ragged_fp8: the cache buffers must be FP8 (e4m3)"; sfa_last_path(): "ring_commit_path_ragged_slots_kvfp8".
+ */
+int sfa_ring_commit_path_ragged_fp8_slots(const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                          const sfa_tensor* k_new, const sfa_tensor* v_new, const int32_t* count,
+                                          const int32_t* path, const int32_t* cu_q, int n_seq, int32_t* state,
+                                          const int32_t* slots, const float* kv_scale, void* stream);
+
+/*
+ * sfa_ring_fill_varlen_slots into an FP8 pool: the same arguments plus kv_scale in front of stream; k / v are bf16 or
+ * f16, the four pool buffers FP8.  Placement and state rows are those of the 16-bit call, each stored row quantised by
+ * the storing rule.  "ring_fill_varlen_fp8: the cache buffers must be FP8 (e4m3)"; sfa_last_path():
+ * "ring_fill_varlen_slots_kvfp8".
+ */
+int sfa_ring_fill_varlen_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                   const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                   const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                   const float* kv_scale, void* stream);
+
+/*
  * Copy slots of a pool on the device: the fork of parallel sampling and beam search (one prefilled prompt into n
  * slots), and parking a sequence in a second pool.  Pair i (n_pairs of them) copies slot s = src_slots[i] of the source
  * pool into slot d = dst_slots[i] of the destination pool; src_slots / dst_slots are device int32 [n_pairs].
@@ -627,6 +691,8 @@ int sfa_ring_commit_path_ragged_slots(const sfa_tensor* window_k, const sfa_tens
  * unit last stride with them); null src_state / dst_state / src_slots / dst_slots; n_pairs < 0 (n_pairs == 0 returns
  * SFA_OK here, without a launch); one dtype across the eight buffers; equal Hkv, num_sink, Wc, D between the pools and
  * one shape[0] >= 1 within each; rows a multiple of 16 bytes and 16-byte aligned.  sfa_last_path(): "ring_copy_slots".
+ * FP8 pools: the eight buffers may all be SFA_DTYPE_FP8_E4M3.  The copy stays a byte copy and takes no scales: the
+ * codes of a slot mean in d what they mean in s only if the caller keeps EQUAL kv_scale on pools that exchange slots.
  */
 int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
                         const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,

@@ -37,9 +37,11 @@ void set_path(const char* fmt, ...) {
 
 namespace {
 
-int check_tensor(const sfa_tensor* t, const char* name) {
+// fp8_ok: a cache buffer of an *_fp8_slots call or of sfa_ring_copy_slots, the only places SFA_DTYPE_FP8_E4M3 is legal
+int check_tensor(const sfa_tensor* t, const char* name, bool fp8_ok = false) {
     SFA_CHECK_ARG(t != nullptr, "%s: null tensor descriptor", name);
-    SFA_CHECK_ARG(t->dtype == SFA_DTYPE_F32 || t->dtype == SFA_DTYPE_F16 || t->dtype == SFA_DTYPE_BF16,
+    SFA_CHECK_ARG(t->dtype == SFA_DTYPE_F32 || t->dtype == SFA_DTYPE_F16 || t->dtype == SFA_DTYPE_BF16 ||
+                      (fp8_ok && t->dtype == SFA_DTYPE_FP8_E4M3),
                   "%s: unknown dtype %d", name, t->dtype);
     for (int i = 0; i < 4; ++i) SFA_CHECK_ARG(t->shape[i] >= 0, "%s: negative shape[%d]", name, i);
     const bool empty = t->shape[0] == 0 || t->shape[1] == 0 || t->shape[2] == 0 || t->shape[3] == 0;
@@ -430,6 +432,27 @@ int ring_step(const RingCall& c) {
     return decode_launch(c, pl);
 }
 
+// The checks an *_fp8_slots call adds (`who`: its name in the messages).  Where the 16-bit call compares the dtypes: the
+// cache buffers are FP8, the activations share one dtype ...
+int check_fp8_dtypes(const char* who, const sfa_tensor* cache_a, const sfa_tensor* cache_b, const sfa_tensor* act_a,
+                     const sfa_tensor* act_b, const char* acts) {
+    SFA_CHECK_ARG(cache_a->dtype == SFA_DTYPE_FP8_E4M3 && cache_b->dtype == SFA_DTYPE_FP8_E4M3,
+                  "%s: the cache buffers must be FP8 (e4m3)", who);
+    SFA_CHECK_ARG(act_a->dtype == act_b->dtype, "%s: %s must share one dtype", who, acts);
+    return SFA_OK;
+}
+
+// ... and where it checks the head dim: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one exists)
+int check_fp8_served(const char* who, int dtype, int64_t D, unsigned flags) {
+    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
+        (flags & SFA_FLAG_FORCE_GENERIC)) {
+        set_error("%s: an FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim "
+                  "%lld%s)", who, dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    return SFA_OK;
+}
+
 // every host-checkable argument of an attention call over a chunk (sfa_decode_ring_multi*, _tree*, _ragged_slots), at
 // the state of the descriptor (a device-state call: the full cache); nothing launches
 int check_multi(const RingCall& c) {
@@ -437,10 +460,11 @@ int check_multi(const RingCall& c) {
     const sfa_tensor *k_new = c.k_new, *v_new = c.v_new, *o = c.o;
     const int64_t sink_len = c.sink_len, window_len = c.window_len, write_pos = c.write_pos;
     int st;
+    const bool kv8 = c.cache_es == 1;       // sfa_decode_ring_ragged_fp8_slots
     if ((st = check_device_state(c))) return st;
-    if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k")) ||
-        (st = check_tensor(sink_v, "sink_v")) || (st = check_tensor(window_k, "window_k")) ||
-        (st = check_tensor(window_v, "window_v")) || (st = check_tensor(k_new, "k_new")) ||
+    if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k", kv8)) ||
+        (st = check_tensor(sink_v, "sink_v", kv8)) || (st = check_tensor(window_k, "window_k", kv8)) ||
+        (st = check_tensor(window_v, "window_v", kv8)) || (st = check_tensor(k_new, "k_new")) ||
         (st = check_tensor(v_new, "v_new")))
         return st;
     if ((st = same_shape(q, o, "q", "o")) || (st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
@@ -449,8 +473,11 @@ int check_multi(const RingCall& c) {
     const int64_t B = q->shape[0], Hq = q->shape[1], n = q->shape[2], D = q->shape[3], Hkv = k_new->shape[1];
     const int64_t Wc = window_k->shape[2];
     const bool pool = c.slots != nullptr;
-    SFA_CHECK_ARG(q->dtype == sink_k->dtype && q->dtype == window_k->dtype && q->dtype == k_new->dtype,
-                  "q, the cache buffers and k_new / v_new must share one dtype");
+    if (kv8) {
+        if ((st = check_fp8_dtypes("decode_ragged_fp8", sink_k, window_k, q, k_new, "q and k_new / v_new"))) return st;
+    } else
+        SFA_CHECK_ARG(q->dtype == sink_k->dtype && q->dtype == window_k->dtype && q->dtype == k_new->dtype,
+                      "q, the cache buffers and k_new / v_new must share one dtype");
     SFA_CHECK_ARG(n >= 1, "decode_multi: the chunk needs at least one token");
     SFA_CHECK_ARG(k_new->shape[0] == B && k_new->shape[2] == n && k_new->shape[3] == D,
                   "k_new / v_new must be [B, H_kv, n, D] with the n = %lld rows of q", (long long)n);
@@ -476,6 +503,13 @@ int check_multi(const RingCall& c) {
     SFA_CHECK_ARG(std::isfinite(c.scale), "scale must be finite");
     SFA_CHECK_ARG(sink_len + window_len + n < (1ll << 30) && B * Hq * n < (1ll << 30) && Wc < (1ll << 30),
                   "problem too large");
+    if (kv8) {      // the activations at 2 bytes per element, the cache rows at 1
+        if ((st = check_fp8_served("decode_ragged_fp8", q->dtype, D, c.flags))) return st;
+        if ((st = check_rows16({q, o, k_new, v_new}, 2, 7, "decode_multi: rows of every tensor must be 16-byte aligned")))
+            return st;
+        return check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
+                            "decode_multi: rows of every tensor must be 16-byte aligned");
+    }
     if ((st = decode_multi_check_head_dim(D, q->dtype))) return st;
     return check_rows16({q, o, sink_k, sink_v, window_k, window_v, k_new, v_new}, dtype_size(q->dtype), 7,
                         "decode_multi: rows of every tensor must be 16-byte aligned");
@@ -536,14 +570,18 @@ int ring_ragged(const RingCall& c) {
 int check_commit(const RingCall& c) {
     const sfa_tensor *window_k = c.window_k, *window_v = c.window_v, *k_new = c.k_new, *v_new = c.v_new;
     int st;
-    if ((st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
+    const bool kv8 = c.cache_es == 1;       // sfa_ring_commit_path_ragged_fp8_slots
+    if ((st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
         return st;
     if ((st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k_new, v_new, "k_new", "v_new")))
         return st;
     SFA_NEED(c.count, "count");
     SFA_NEED(c.state, "state");
-    SFA_CHECK_ARG(k_new->dtype == window_k->dtype, "k_new / v_new and the ring must share one dtype");
+    if (kv8) {
+        if ((st = check_fp8_dtypes("ring_commit_ragged_fp8", window_k, window_v, k_new, v_new, "k_new and v_new"))) return st;
+    } else
+        SFA_CHECK_ARG(k_new->dtype == window_k->dtype, "k_new / v_new and the ring must share one dtype");
     const int64_t n = k_new->shape[2], Wc = window_k->shape[2];
     const bool pool = c.slots != nullptr;
     SFA_CHECK_ARG(n >= 1, "ring_commit: the chunk needs at least one token");
@@ -556,6 +594,11 @@ int check_commit(const RingCall& c) {
                   "k_new / v_new must be [B, H_kv, n, D] like the ring [B, H_kv, Wc, D]");
     SFA_CHECK_ARG(n < (1ll << 30) && Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k_new->dtype);
+    if (kv8) {
+        if ((st = check_fp8_served("ring_commit_ragged_fp8", k_new->dtype, k_new->shape[3], 0))) return st;
+        if ((st = check_rows16({k_new, v_new}, es, 3, "ring_commit: rows of every tensor must be 16-byte aligned"))) return st;
+        return check_rows16({window_k, window_v}, 1, 3, "ring_commit: rows of every tensor must be 16-byte aligned");
+    }
     SFA_CHECK_ARG(k_new->shape[3] > 0 && (k_new->shape[3] * es) % 16 == 0,
                   "ring_commit: K/V rows must be a multiple of 16 bytes (head dim %lld)", (long long)k_new->shape[3]);
     return check_rows16({window_k, window_v, k_new, v_new}, es, 3, "ring_commit: rows of every tensor must be 16-byte aligned");
@@ -604,11 +647,12 @@ int ring_commit_ragged(const RingCall& c) {
 // sfa_ring_fill_varlen (slots null: sequence i -> cache row i of n_seq) and sfa_ring_fill_varlen_slots (pool)
 int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                 const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu_seqlens,
-                int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool) {
+                int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool, bool kv8 = false,
+                const float* kv_scale = nullptr) {
     g_err[0] = 0;
     int st;
-    if ((st = check_tensor(sink_k, "sink_k")) || (st = check_tensor(sink_v, "sink_v")) ||
-        (st = check_tensor(window_k, "window_k")) || (st = check_tensor(window_v, "window_v")) ||
+    if ((st = check_tensor(sink_k, "sink_k", kv8)) || (st = check_tensor(sink_v, "sink_v", kv8)) ||
+        (st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
         (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")))
         return st;
     if ((st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
@@ -619,8 +663,11 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
     SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
-    SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
-                  "k / v and the cache buffers must share one dtype");
+    if (kv8) {      // sfa_ring_fill_varlen_fp8_slots
+        if ((st = check_fp8_dtypes("ring_fill_varlen_fp8", sink_k, window_k, k, v, "k and v"))) return st;
+    } else
+        SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
+                      "k / v and the cache buffers must share one dtype");
     const int64_t Hkv = k->shape[1], D = k->shape[3], Wc = window_k->shape[2];
     if (pool)
         SFA_CHECK_ARG(sink_k->shape[0] >= 1 && sink_k->shape[0] == window_k->shape[0] && sink_k->shape[0] < (1ll << 30),
@@ -635,6 +682,15 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
     SFA_CHECK_ARG(k->shape[2] < (1ll << 30) && sink_k->shape[2] + Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k->dtype);
+    if (kv8) {
+        if ((st = check_fp8_served("ring_fill_varlen_fp8", k->dtype, D, 0))) return st;
+        if ((st = check_rows16({k, v}, es, 7, "ring_fill_varlen: rows of every tensor must be 16-byte aligned")) ||
+            (st = check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
+                               "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
+            return st;
+        return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
+                                       (hipStream_t)stream, slots, kv_scale);
+    }
     SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_fill_varlen: K/V rows must be a multiple of 16 bytes (head dim %lld)",
                   (long long)D);
     if ((st = check_rows16({sink_k, sink_v, window_k, window_v, k, v}, es, 7,
@@ -653,7 +709,7 @@ int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const s
                                          "dst_sink_k", "dst_sink_v", "dst_window_k", "dst_window_v"};
     int st;
     for (int i = 0; i < 8; ++i)
-        if ((st = check_tensor(i < 4 ? src[i] : dst[i - 4], names[i]))) return st;
+        if ((st = check_tensor(i < 4 ? src[i] : dst[i - 4], names[i], true))) return st;      // FP8 pools: a byte copy
     SFA_NEED(src_state, "src_state");
     SFA_NEED(dst_state, "dst_state");
     SFA_NEED(src_slots, "src_slots");
@@ -821,6 +877,21 @@ int sfa_decode_ring_ragged_tree_slots(SFA_ATTEND_PARAMS, const int32_t* parent, 
     return ring_ragged(device_state(c, RingState::Rows, state, slots));
 }
 
+int sfa_decode_ring_ragged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
+                                     int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                     const float* kv_scale, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = SFA_ATTEND_CALL;
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.parent = parent, c.commit_seq = commit_seq;
+    c.kv_scale = kv_scale, c.cache_es = 1;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
 int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
                          const sfa_tensor* window_k, const sfa_tensor* window_v, int64_t window_len,
                          int64_t write_pos, const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
@@ -899,6 +970,26 @@ int sfa_ring_commit_path_ragged_slots(SFA_COMMIT_PARAMS, const int32_t* path, co
     RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
     c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
     return ring_commit_ragged(c);
+}
+
+int sfa_ring_commit_path_ragged_fp8_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
+                                          int32_t* state, const int32_t* slots, const float* kv_scale, void* stream) {
+    g_err[0] = 0;
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
+    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.kv_scale = kv_scale, c.cache_es = 1;
+    return ring_commit_ragged(c);
+}
+
+int sfa_ring_fill_varlen_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                   const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                   const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                   const float* kv_scale, void* stream) {
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true, true,
+                       kv_scale);
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

@@ -113,7 +113,7 @@ __device__ __forceinline__ unsigned seq_range(const int* cu, unsigned whole, int
 }
 #endif
 
-inline int dtype_size(int dt) { return dt == SFA_DTYPE_F32 ? 4 : 2; }
+inline int dtype_size(int dt) { return dt == SFA_DTYPE_F32 ? 4 : dt == SFA_DTYPE_FP8_E4M3 ? 1 : 2; }
 
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -56,6 +56,74 @@ template <> struct Mma<f16_t> {
     }
 };
 
+// ---- FP8 pool (the *_fp8_slots calls).  The cache buffers hold OCP e4m3fn codes, one byte per element;
+// the activations stay 16-bit.  A third kernel argument that only the FP8 instances take (`KA...` / the tail of `RA...`
+// is empty for every other instance, as with RaggedArgs): scale = device float [2][Hkv], row 0 K and row 1 V, null = ones.
+struct Kv8Args {
+    const float* scale;
+};
+__device__ __forceinline__ Kv8Args kv8_of() { return Kv8Args{nullptr}; }
+__device__ __forceinline__ const Kv8Args& kv8_of(const Kv8Args& kv) { return kv; }
+
+// the scale of KV head hk: row 0 for K, 1 for V
+__device__ __forceinline__ float kv8_scale(const Kv8Args& kv, int row, int Hkv, int hk) {
+    return kv.scale ? kv.scale[row * Hkv + hk] : 1.f;
+}
+
+// reading: the 8 codes of one 8-byte piece -> 8 elements of T, each T(float(code) * s): one f32 multiply, then the
+// round-to-nearest-even conversion.  Byte i of the piece is element i.
+template <typename T>
+__device__ __forceinline__ u32x4 kv8_read(unsigned lo, unsigned hi, float s) {
+    using E = typename Mma<T>::elem;
+    typename Mma<T>::frag out;
+    const unsigned w[2] = {lo, hi};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        out[4 * i + 0] = (E)(a[0] * s);
+        out[4 * i + 1] = (E)(a[1] * s);
+        out[4 * i + 2] = (E)(b[0] * s);
+        out[4 * i + 3] = (E)(b[1] * s);
+    }
+    return __builtin_bit_cast(u32x4, out);
+}
+
+// storing: 8 elements of the 16-bit type Q (16 bytes) -> 8 codes, each e4m3fn_rne(clamp(float(x) * r, -448, 448)) with
+// r = 1.0f / scale (the caller's division).  The clamp is explicit: the conversion never sees a value it would overflow on.
+template <typename Q>
+__device__ __forceinline__ uint2 kv8_quant(u32x4 raw, float r) {
+    const typename Mma<Q>::frag e = __builtin_bit_cast(typename Mma<Q>::frag, raw);
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = fminf(fmaxf((float)e[i] * r, -448.f), 448.f);
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    return make_uint2((unsigned)lo, (unsigned)hi);
+}
+
+// one piece (8 elements of K and of V, KV head hk) of a storing kernel.  Q = void: source and destination share the
+// dtype, 16 bytes are copied.  Q = the 16-bit source type of an FP8 pool: 16 bytes read, quantised, 8 bytes written.
+template <typename Q>
+__device__ __forceinline__ void store_piece(char* kd, char* vd, const char* ks, const char* vs,
+                                            [[maybe_unused]] const Kv8Args& kv, [[maybe_unused]] int Hkv,
+                                            [[maybe_unused]] int hk) {
+    if constexpr (std::is_void_v<Q>) {
+        *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
+        *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+    } else {
+        const u32x4 kr = *reinterpret_cast<const u32x4*>(ks), vr = *reinterpret_cast<const u32x4*>(vs);
+        *reinterpret_cast<uint2*>(kd) = kv8_quant<Q>(kr, 1.0f / kv8_scale(kv, 0, Hkv, hk));
+        *reinterpret_cast<uint2*>(vd) = kv8_quant<Q>(vr, 1.0f / kv8_scale(kv, 1, Hkv, hk));
+    }
+}
+// bytes per element of the destination and byte offset of piece ch in a destination row
+template <typename Q> __device__ __forceinline__ int piece_es(int es) { return std::is_void_v<Q> ? es : 1; }
+template <typename Q> __device__ __forceinline__ int64_t piece_off(int ch) { return (int64_t)ch * (std::is_void_v<Q> ? 16 : 8); }
+
 constexpr int kTile = 32;        // keys per tile
 constexpr int kWaves = 4;        // waves per workgroup of the MFMA split kernel
 constexpr int kMinTiles = 4;     // a split gives every wave at least one tile
@@ -109,6 +177,9 @@ struct RaggedArgs {
 // block and code stay those of a kernel without the flag)
 __device__ __forceinline__ RaggedArgs ragged_of() { return RaggedArgs{}; }
 __device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg) { return rg; }
+__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const Kv8Args&) { return rg; }
+__device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&) { return Kv8Args{nullptr}; }
+__device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Args& kv) { return kv; }
 
 // sequence i of the pack: first packed row and length
 struct RaggedSeq {
@@ -286,7 +357,8 @@ __device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int
 }
 
 // Ragged: the chunk is the n rows of k_new / v_new from packed row crow on, in place of the a.n rows of batch row b
-template <bool Ragged = false>
+// KV8: sink and ring tiles are FP8 rows (1 byte per element); the chunk keeps es
+template <bool Ragged = false, bool KV8 = false>
 __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es,
                                               int n = 0, int crow = 0) {
     TileInfo ti;
@@ -300,6 +372,7 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
         ti.seg = 2, ti.start = kTile * (i - f.T1), len = Ragged ? n : a.n, kv = &a.kn, vv = &a.vn, row = b;
     }
     ti.count = len - ti.start < kTile ? len - ti.start : kTile;
+    if constexpr (KV8) es = ti.seg == 2 ? es : 1;
     ti.ksn = kv->sn * es;
     ti.vsn = vv->sn * es;
     ti.k = kv->ptr + ((int64_t)row * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
@@ -443,11 +516,17 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
 // waves_per_eu: the (Tree, Ragged) instance of D = 80 asks for the two waves per SIMD of its tree _slots sibling (the
 // allocator then fits it into 226 VGPRs without scratch; left alone it takes 233 + 48 and one wave).  1 = the default of
 // every other instance, whose code does not change.
-template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
+// KV8 (the FP8 pool, with Ragged): sink and ring tiles are loaded as 8-byte pieces - the tile's kTile * CPR chunks of 8
+// elements, the lane-to-chunk map unchanged - and converted to T in registers on the way into LDS (kv8_read, the scale
+// of head hk: one scalar per workgroup for K and for V); the LDS image and everything behind it are those of the 16-bit
+// instance.  Chunk tiles (k_new / v_new) are 16-bit and keep the 16-byte load.
+template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, bool KV8 = false, typename... RA>
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && Ragged && D == 80) ? 2 : 1)))
 void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged),
+                  "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
+    [[maybe_unused]] const Kv8Args kv = kv8_of(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
@@ -542,7 +621,26 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     char* kl = smem + wave * 2 * TILE_BYTES;
     char* vl = kl + TILE_BYTES;
     u32x4 kst[NLD], vst[NLD];
+    // FP8 pool: the K and V scales of head hk (wave-uniform) and whether the staged tile holds codes (kst / vst [0..1])
+    [[maybe_unused]] float ksc = 1.f, vsc = 1.f;
+    [[maybe_unused]] bool st8 = false;
+    if constexpr (KV8) ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
     auto issue_loads = [&](const TileInfo& ti) {
+        if constexpr (KV8) {
+            st8 = ti.seg != 2;
+            if (st8) {
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    const int c = lane + 64 * j;
+                    const int key = c / CPR, ch = c % CPR;
+                    const int row = key < ti.count ? key : ti.count - 1;
+                    const uint2 k8 = *reinterpret_cast<const uint2*>(ti.k + row * ti.ksn + ch * 8);
+                    const uint2 v8 = *reinterpret_cast<const uint2*>(ti.v + row * ti.vsn + ch * 8);
+                    kst[j][0] = k8.x, kst[j][1] = k8.y, vst[j][0] = v8.x, vst[j][1] = v8.y;
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int c = lane + 64 * j;
@@ -553,6 +651,15 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
         }
     };
     auto write_lds = [&]() {
+        if constexpr (KV8) {
+            if (st8) {                 // the conversion: between the global load and the LDS store
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    kst[j] = kv8_read<T>(kst[j][0], kst[j][1], ksc);
+                    vst[j] = kv8_read<T>(vst[j][0], vst[j][1], vsc);
+                }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int c = lane + 64 * j;
@@ -585,7 +692,7 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info<Ragged>(a, f, i, b, c, hk, es, rn, prow);
+            ti = tile_info<Ragged, KV8>(a, f, i, b, c, hk, es, rn, prow);
             if (Tree && Ragged && !is_tree) cls = tile_class(a, ti, tmin, tmax, f.nsk);
             else cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
             if (cls != 0) break;
@@ -904,7 +1011,11 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // stores for a batch row of n_i tokens.  Rows of no sequence and of inactive sequences store nothing.
 // An admitting sequence (admits()) takes the prefill placement instead: token t goes to row fill_dst of its slot.
 // A sequence whose commit_seq entry is 0 stores nothing.
-__device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es) {
+// Q (store_piece): void, or the chunk's 16-bit type when the pool is FP8 - es stays the chunk's element size, a piece 8
+// elements.
+template <typename Q = void>
+__device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es,
+                                                    const Kv8Args& kv = Kv8Args{nullptr}) {
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
     const int ch = (int)(item % cpr);
@@ -929,13 +1040,13 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
         if (t < s.n - a.wc) return;
         slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
     }
-    const int64_t so = (int64_t)ch * 16;
+    const int64_t so = (int64_t)ch * 16, dso = piece_off<Q>(ch);
+    const int ed = piece_es<Q>(es);
     const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + (int64_t)tp * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + (int64_t)tp * a.vn.sn) * es + so;
-    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)slot * dk->sn) * es + so;
-    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)slot * dv->sn) * es + so;
-    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
-    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)slot * dk->sn) * ed + dso;
+    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)slot * dv->sn) * ed + dso;
+    store_piece<Q>(kd, vd, ks, vs, kv, a.Hkv, hk);
 }
 
 // blocks [0, nred): one wave per partial row folds the S partials and s_aux, writes o.  Blocks [nred, ...) with commit:
@@ -946,13 +1057,16 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
 // Slots: S, write_pos and the ring are those of cache row slots[b]; an inactive row gets zeros in o (no partial of it
 // was written) and stores nothing.
 // Ragged: rows are the packed rows (ragged_row); a row without work gets zeros, the commit is commit_piece_ragged.
-template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, typename... RA>
+// KV8 (the FP8 pool, with Ragged): the commit blocks quantise as they store; the fold is the 16-bit instance's.
+template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, bool KV8 = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, nred, RaggedArgs)");
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged),
+                  "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (MultiArgs, nred, RaggedArgs, Kv8Args)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
+        if constexpr (KV8) commit_piece_ragged<T>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...));
+        else if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
         else commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
         return;
     }
@@ -1036,7 +1150,11 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
 // position j of the sequence: with acc = clamp(count[i], 0, n_i), positions [max(0, acc - Wc), acc) store packed row
 // c0_i + clamp(path[c0_i + j], 0, n_i - 1) (row c0_i + j without a path) into ring slot (write_pos + j) mod Wc of slot
 // slots[i] - the piece commit_piece<Path, true> stores for the sequence passed as a [1, Hkv, n_i, D] chunk.
-__global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es) {
+// Q (store_piece): void, or the pack's 16-bit type when the ring is FP8 (es stays the pack's element size); KA: Kv8Args then
+template <typename Q = void, typename... KA>
+__global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es,
+                                                                 KA... ka) {
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1), "FP8 ring: (..., Kv8Args)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
@@ -1063,13 +1181,13 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
         src = a.path[s.c0 + j];
         src = src < 0 ? 0 : (src >= s.n ? s.n - 1 : src);
     }
-    const int64_t so = (int64_t)ch * 16, row = (int64_t)s.c0 + src;
+    const int64_t so = (int64_t)ch * 16, row = (int64_t)s.c0 + src, dso = piece_off<Q>(ch);
+    const int ed = piece_es<Q>(es);
     const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + row * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + row * a.vn.sn) * es + so;
-    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * es + so;
-    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * es + so;
-    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
-    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * ed + dso;
+    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * ed + dso;
+    store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), a.Hkv, hk);
 }
 
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
@@ -1081,11 +1199,13 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
 // sequence writes its state row (fill_state): {sl, min(rest, Wc), rest < Wc ? rest : 0, L}.
 // Slots (sfa_ring_fill_varlen_slots): sequence b goes to cache row and state row slots[b] of a pool of npool rows (a
 // value outside [0, npool): the sequence is skipped); every other row of the pool keeps buffers and state.
-template <bool Slots>
+// Q (store_piece): void, or the pack's 16-bit type when the pool is FP8 (cpr and es stay those of the pack); KA: Kv8Args then
+template <bool Slots, typename Q = void, typename... KA>
 __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv, View wk, View wv, View k, View v,
                                                                const int* cu, int* state, int n_seq, int Hkv, int ns,
                                                                int wc, int T, int cpr, int es, const int* slots,
-                                                               int npool) {
+                                                               int npool, KA... ka) {
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1), "FP8 pool: (..., Kv8Args)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nj = ns + wc;
     if (item >= (int64_t)n_seq * Hkv * nj * cpr) return;
@@ -1108,13 +1228,13 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     if (src < 0) return;
     const View *dk = j < ns ? &sk : &wk, *dv = j < ns ? &sv : &wv;
     const int row = j < ns ? j : j - ns;
-    const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src;
+    const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src, dso = piece_off<Q>(ch);
+    const int ed = piece_es<Q>(es);
     const char* ks = k.ptr + ((int64_t)hk * k.sh + tok * k.sn) * es + so;
     const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
-    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * es + so;
-    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * es + so;
-    *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
-    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * ed + dso;
+    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * ed + dso;
+    store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), Hkv, hk);
 }
 
 // sfa_ring_copy_slots: pair i copies slot s = src_slots[i] of the source pool into slot d = dst_slots[i] of the
@@ -1305,35 +1425,40 @@ int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
     return launch_status(tag);
 }
 
+// kv (packed calls only): the FP8 pool - the (Dyn, Slots, Ragged) instances with the cache format, Tree on or off
 template <typename T, int D>
-int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, hipStream_t stream) {
+int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, hipStream_t stream) {
     const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
-        if constexpr (M::Ragged) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
+        if constexpr (M::Ragged) {
+            if (kv) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv);
+            else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
+        }
         else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots><<<grid, kWaves * 64, 0, stream>>>(a);
     });
     return split_status(a, rg, "mfma");
 }
 
 template <typename T>
-int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, hipStream_t stream) {
+int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, hipStream_t stream) {
     switch (a.D) {
-        case 64: return launch_mfma<T, 64>(a, rg, stream);
-        case 80: return launch_mfma<T, 80>(a, rg, stream);
-        case 96: return launch_mfma<T, 96>(a, rg, stream);
-        case 128: return launch_mfma<T, 128>(a, rg, stream);
+        case 64: return launch_mfma<T, 64>(a, rg, kv, stream);
+        case 80: return launch_mfma<T, 80>(a, rg, kv, stream);
+        case 96: return launch_mfma<T, 96>(a, rg, kv, stream);
+        case 128: return launch_mfma<T, 128>(a, rg, kv, stream);
     }
     set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
     return SFA_ERR_UNSUPPORTED;
 }
 
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
+// kv: the FP8 pool of a packed call (the API admits it for the MFMA instances only)
 template <typename T>
-int launch_rest(const MultiArgs& a, const RaggedArgs* rg, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, kv, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
         dispatch_mode(a, rg, [&](auto m) {
@@ -1353,7 +1478,15 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, bool mfma, hipStream_t
     const dim3 rgrid((unsigned)(nred + ncommit));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
-        if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
+        if constexpr (M::Ragged) {
+            if constexpr (sizeof(T) == 2) {
+                if (kv) {
+                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *kv);
+                    return;
+                }
+            }
+            multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
+        }
         else multi_reduce_kernel<T, M::Dyn, M::Slots><<<rgrid, 256, 0, stream>>>(a, nred);
     });
     if ((st = launch_status(rg ? "decode_multi_reduce_ragged" : "decode_multi_reduce"))) return st;
@@ -1390,13 +1523,18 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 }
 
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
-int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname) {
+int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
+                 const Kv8Args* kv = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
-    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, *mfma, c.stream);
-    return launch_rest<bf16_t>(a, rg, *mfma, c.stream);
+    if (kv && !*mfma) {         // refused by the API before: no f32-accumulate instance reads an FP8 pool
+        set_error("decode_ragged_fp8: no kernel instance for this call");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, nullptr, false, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, kv, *mfma, c.stream);
+    return launch_rest<bf16_t>(a, rg, kv, *mfma, c.stream);
 }
 
 }  // namespace
@@ -1514,10 +1652,11 @@ int decode_ragged_launch(const RingCall& c) {
     if ((st = launch_status("ragged_prep"))) return st;
     bool mfma;
     const char* dname;
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
+    const Kv8Args kv{c.kv_scale};
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cache_es == 1 ? &kv : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s", fam, dname, a.D, a.nrb, ad, cm);
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? "_kvfp8" : "");
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }
@@ -1535,11 +1674,15 @@ int ring_commit_dyn_launch(const RingCall& c) {
         }
         int st;
         if (nb > 0) {
-            ring_commit_ragged_kernel<<<dim3((unsigned)nb), 256, 0, c.stream>>>(a, rg, c.count, es);
+            const Kv8Args kv{c.kv_scale};
+            const dim3 grid((unsigned)nb);
+            if (c.cache_es != 1) ring_commit_ragged_kernel<<<grid, 256, 0, c.stream>>>(a, rg, c.count, es);
+            else if (c.k_new->dtype == SFA_DTYPE_F16) ring_commit_ragged_kernel<f16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
+            else ring_commit_ragged_kernel<bf16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
             if ((st = launch_status("ring_commit_path_ragged"))) return st;
         }
         if ((st = launch_advance(a, c.count, &rg, c.stream))) return st;   // after every reader of the state
-        set_path("ring_commit_path_ragged_slots");
+        set_path(c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8" : "ring_commit_path_ragged_slots");
         return SFA_OK;
     }
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
@@ -1566,8 +1709,9 @@ int ring_commit_dyn_launch(const RingCall& c) {
 
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots) {
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const float* kv_scale) {
     const int es = dtype_size(k->dtype);
+    const bool kv8 = sink_k->dtype == SFA_DTYPE_FP8_E4M3;       // the API: with slots and 16-bit k / v only
     const int Hkv = (int)k->shape[1], ns = (int)sink_k->shape[2], wc = (int)window_k->shape[2];
     const int cpr = (int)(k->shape[3] * es / 16);
     const int64_t nblk = cdiv64((int64_t)n_seq * Hkv * (ns + wc) * cpr, 256);
@@ -1576,7 +1720,15 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         return SFA_ERR_UNSUPPORTED;
     }
     if (nblk > 0) {
-        if (slots)
+        if (kv8 && k->dtype == SFA_DTYPE_F16)
+            ring_fill_varlen_kernel<true, f16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
+        else if (kv8)
+            ring_fill_varlen_kernel<true, bf16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
+        else if (slots)
             ring_fill_varlen_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
                 make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
                 cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0]);
@@ -1587,7 +1739,7 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         int st;
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
-    set_path(slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
+    set_path(kv8 ? "ring_fill_varlen_slots_kvfp8" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
     return SFA_OK;
 }
 

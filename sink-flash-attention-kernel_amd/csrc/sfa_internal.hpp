@@ -77,6 +77,11 @@ struct RingCall {
     // (null: every sequence).  In a packed call `parent` is [T], packed like q, with sequence-local entries, and a
     // packed commit (cu_q set) takes `path` [T] and `count` [n_seq] the same way
     const int32_t* commit_seq;
+    // FP8 pool (the *_fp8_slots calls): the cache buffers hold e4m3fn codes, cache_es = 1 byte per element against the 2
+    // of the activations (every other call: 0, the cache has q's / k_new's dtype); kv_scale = device float [2][H_kv],
+    // row 0 K and row 1 V, null = all ones.  Read by the kernels only
+    const float* kv_scale;
+    int cache_es;
 };
 
 // sfa_decode.hip
@@ -107,9 +112,11 @@ int decode_ragged_launch(const RingCall& c);
 int ring_commit_dyn_launch(const RingCall& c);
 // sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows;
 // slots (null: sequence i -> cache row i): sequence i -> row slots[i] of a pool
+// kv_scale: with FP8 pool buffers (k / v stay 16-bit) the rows are quantised as they are stored; null = all ones
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots);
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots,
+                            const float* kv_scale = nullptr);
 // sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools (the same pool: a fork); pair i
 // copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i]
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],

@@ -18,6 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFA_LIB_PATH") or os.path.join(_HERE, "libsfa.so")   # env: A/B builds in development
 
 SFA_DTYPE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+SFA_DTYPE_FP8_E4M3 = 3        # OCP e4m3fn: the cache buffers of an FP8 pool only (the *_fp8_slots calls, sfa_ring_copy_slots)
+_DESC_DTYPE = {**SFA_DTYPE, torch.float8_e4m3fn: SFA_DTYPE_FP8_E4M3}
 FLAG_FORCE_GENERIC = 0x1
 FLAG_DECODE_ONE_PASS = 0x4
 FLAG_BWD_OVERLAP = 0x8        # dQ kernel of a small grid on the library's side stream (include/sfa.h)
@@ -159,6 +161,14 @@ def _bind(lib):
                                                       u32, vp]
     lib.sfa_ring_commit_path_ragged_slots.restype = i32
     lib.sfa_ring_commit_path_ragged_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp]
+    # FP8 pool: the packed step, the packed commit and the slot fill plus `kv_scale` (device f32 [2, H_kv]) before the tail
+    lib.sfa_decode_ring_ragged_fp8_slots.restype = i32
+    lib.sfa_decode_ring_ragged_fp8_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, sz,
+                                                     f32, u32, vp]
+    lib.sfa_ring_commit_path_ragged_fp8_slots.restype = i32
+    lib.sfa_ring_commit_path_ragged_fp8_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.sfa_ring_fill_varlen_fp8_slots.restype = i32
+    lib.sfa_ring_fill_varlen_fp8_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, vp]
     # slot copy (fork / park): source pool + state, destination pool + state, src_slots, dst_slots, n_pairs, stream
     lib.sfa_ring_copy_slots.restype = i32
     lib.sfa_ring_copy_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp]
@@ -193,7 +203,7 @@ assert _DESC.size == ctypes.sizeof(SfaTensor)   # descriptor; a backward call bu
 
 def desc(t: torch.Tensor) -> SfaTensor:
     """Describe a 4-D [B,H,N,D] tensor (any B/H/N strides, unit D stride)."""
-    return SfaTensor.from_buffer_copy(_DESC.pack(t.data_ptr(), *t.shape, *t.stride(), SFA_DTYPE[t.dtype], 0))
+    return SfaTensor.from_buffer_copy(_DESC.pack(t.data_ptr(), *t.shape, *t.stride(), _DESC_DTYPE[t.dtype], 0))
 
 
 def check(status: int, what: str):

@@ -262,7 +262,9 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         shape = (q.shape[0], self.sink_k.shape[1], q.shape[2], q.shape[3])
         if k_new.shape != shape or v_new.shape != k_new.shape:
             raise ValueError(f"k_new / v_new must be {layout} = {shape}, got {tuple(k_new.shape)}")
-        if q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
+        if self._kv8:
+            self._act16("q, k_new and v_new", q, k_new, v_new)
+        elif q.dtype != self.window_k.dtype or k_new.dtype != q.dtype or v_new.dtype != q.dtype or q.dtype not in N.SFA_DTYPE:
             raise TypeError("q, k_new, v_new and the cache buffers must share one dtype")
         if out is not None and (out.shape != q.shape or out.dtype != q.dtype):
             raise ValueError(f"out must be a {tuple(q.shape)} tensor of q's dtype")
@@ -341,6 +343,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``slots`` (``sfa_decode_ring_step_slots``, see ``init_pool``): batch row b works on cache row ``slots[b]``; a row
         with ``slots[b] = -1`` is inactive (zeros in ``out``, nothing stored, no state moves)."""
         from . import _native as N
+        self._refuse_fp8("decode_step_dyn")
         slots = self._slots_arg(slots, q.shape[0], writes=True)
         st = getattr(self, "_dev_state", None)
         assert st is not None, "call enable_device_state() first"
@@ -402,6 +405,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def _commit_dyn(self, k_new, v_new, count, path, slots=None):
         """sfa_ring_commit[_path]_{dyn,rows,slots}: one count for the shared state, B of them for per-sequence rows."""
         from . import _native as N
+        self._refuse_fp8("commit_path_dyn" if path is not None else "commit_dyn")
         slots = self._slots_arg(slots, k_new.shape[0], writes=True)
         st = self._require_dyn("commit_path_dyn" if path is not None else "commit_dyn")
         if not isinstance(count, torch.Tensor) or count.dtype.is_floating_point or count.dtype.is_complex \
@@ -463,6 +467,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         outside [-1, u) reads as -1 (a root).  ``slots`` (``sfa_decode_ring_tree_slots``): row b verifies its tree
         against cache row ``slots[b]`` (the same slot may be named twice: nothing is written)."""
         from .decode_kernel import tree_parent_dev
+        self._refuse_fp8("extend_attention_tree_dyn")
         if q.shape[2] > 64:
             raise ValueError(f"a tree chunk holds at most 64 nodes, got n = {q.shape[2]}")
         tree = tree_parent_dev(parent, q.shape[0], q.shape[2], q.device)
@@ -505,6 +510,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     _per_seq = False     # set by prefill_varlen / enable_device_state(per_sequence=True)
 
     def _refuse_per_seq(self, what):
+        self._refuse_fp8(what)
         if self._per_seq:
             raise RuntimeError(f"{what}() works on the host-side state, which a cache in per-sequence mode "
                                "(prefill_varlen / enable_device_state(per_sequence=True)) does not keep: use "
@@ -519,6 +525,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         no sync) or a host list / CPU tensor (checked here).  The prompt attention itself is the caller's
         ``sink_flash_attention_varlen`` call on the same pack."""
         from . import _native as N
+        self._refuse_fp8("prefill_varlen")
         N.require_gpu(k, v)
         if self.window_size < 1:
             raise ValueError("prefill_varlen needs a ring of at least one slot (window_size >= 1)")
@@ -581,6 +588,43 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     # ------------------------------------------------ slot pool (continuous batching)
     _pool = False        # set by init_pool
+    kv_scale = None      # FP8 pool: f32 [2, H_kv] on the device (row 0 K, row 1 V), allocated by init_pool
+
+    @property
+    def _kv8(self) -> bool:
+        return self.window_k is not None and self.window_k.dtype == torch.float8_e4m3fn
+
+    def _refuse_fp8(self, what):
+        if self._kv8:
+            raise TypeError(f"{what}() does not serve an FP8 (float8_e4m3fn) pool: use the packed calls prefill_slots / "
+                            "ragged_step_dyn / commit_packed_dyn (and fork_slots, release_slots, positions, "
+                            "packed_positions)")
+
+    def _act16(self, what, *tensors):
+        """An FP8 pool takes bfloat16 / float16 activations of one dtype."""
+        dt = tensors[0].dtype
+        if dt not in (torch.bfloat16, torch.float16) or any(t.dtype != dt for t in tensors):
+            raise TypeError(f"{what} of an FP8 pool must be bfloat16 or float16 tensors of one dtype, got "
+                            f"{[str(t.dtype) for t in tensors]}")
+
+    def _kv_scale_ptr(self):
+        return None if self.kv_scale is None else self.kv_scale.data_ptr()
+
+    def set_kv_scale(self, k_scale, v_scale) -> None:
+        """Set the static per-KV-head scales of an FP8 pool: ``k_scale`` / ``v_scale`` hold H_kv values each (tensor, list
+        or one number for every head) and are copied IN PLACE into ``kv_scale`` (f32 ``[2, H_kv]``, row 0 K, row 1 V; ones
+        after ``init_pool``).  The kernels read the tensor when they run, never the host: with device tensors as sources
+        the copy is capturable, and a captured step keeps the pointer, so a later in-place update is seen by the next
+        replay.  Codes already in the pool are not rescaled: set the scales of a calibrated checkpoint before the first
+        ``prefill_slots``, and keep equal scales on pools that exchange slots (``fork_slots`` copies bytes)."""
+        if not (self._pool and self._kv8):
+            raise TypeError("set_kv_scale needs an FP8 pool: init_pool(..., dtype=torch.float8_e4m3fn)")
+        for row, x in ((0, k_scale), (1, v_scale)):
+            t = x if isinstance(x, torch.Tensor) else torch.tensor(x, dtype=torch.float32)
+            if t.dim() > 1 or (t.dim() == 1 and t.numel() != self.kv_scale.shape[1]) or t.dtype.is_complex:
+                raise ValueError(f"a scale must hold H_kv = {self.kv_scale.shape[1]} values (or one), got shape "
+                                 f"{tuple(t.shape)}")
+            self.kv_scale[row].copy_(t.to(torch.float32) if t.dim() else t.to(torch.float32).expand(self.kv_scale.shape[1]))
 
     def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda") -> torch.Tensor:
         """Allocate a pool of ``num_slots`` cache rows that lives as long as the server: ``[S, H_kv, num_sink /
@@ -590,16 +634,29 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         tensor (never read on the host, so a captured step replays at any occupancy by rewriting it in place), or a host
         list, which is checked for range and duplicates and uploaded.  Batch row b works on slot ``slots[b]``; -1 marks
         an inactive row.  A slot must be prefilled (``prefill_slots``) before it is used, or admitted by
-        ``ragged_step_dyn(admit=True)``: to every other call an all-zero state row is not a prefilled cache."""
+        ``ragged_step_dyn(admit=True)``: to every other call an all-zero state row is not a prefilled cache.
+
+        ``dtype=torch.float8_e4m3fn``: an FP8 pool - half the bytes per slot and per step.  The buffers hold OCP e4m3fn
+        codes, ``kv_scale`` (f32 ``[2, H_kv]``, ones; ``set_kv_scale``) the static per-KV-head scales.  It is served by
+        ``prefill_slots``, ``ragged_step_dyn``, ``commit_packed_dyn``, ``fork_slots``, ``release_slots``, ``positions``
+        and ``packed_positions`` with bfloat16 / float16 activations; every other method raises ``TypeError``.  A stored
+        element is ``e4m3fn(clamp(x / scale, -448, 448))`` and reads back as ``code * scale`` in the activations' dtype:
+        the tokens of a step are attended at 16-bit precision inside that step and at FP8 precision afterwards, so a
+        prompt admitted in chunks is not bitwise the prompt admitted in one call."""
         if self.window_size < 1:
             raise ValueError("init_pool needs a ring of at least one slot (window_size >= 1)")
         if int(num_slots) < 1:
             raise ValueError(f"init_pool needs at least one slot, got num_slots = {num_slots}")
-        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("the pool's dtype must be float32 / float16 / bfloat16")
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float8_e4m3fn):
+            raise TypeError("the pool's dtype must be float32 / float16 / bfloat16 / float8_e4m3fn")
+        if dtype == torch.float8_e4m3fn and D not in (64, 80, 96, 128):
+            raise ValueError(f"an FP8 pool serves head dims 64 / 80 / 96 / 128, got D = {D}")
         mk = lambda n: torch.zeros(int(num_slots), H_kv, n, D, dtype=dtype, device=device)
         self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
         self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
+        # FP8 (OCP e4m3fn, one byte per element): the pool holds codes, the activations of the packed calls stay 16-bit;
+        # the caller-owned static scales start at one (set_kv_scale)
+        self.kv_scale = torch.ones(2, H_kv, dtype=torch.float32, device=device) if dtype == torch.float8_e4m3fn else None
         self._dev_state = torch.zeros(int(num_slots), 4, dtype=torch.int32, device=device)
         self.sink_len = self.window_len = self.write_pos = self.seen_tokens = 0   # not kept in this mode
         self.is_initialized = self.prefilled = True
@@ -653,19 +710,21 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         n_seq = (cu_seqlens.numel() if isinstance(cu_seqlens, torch.Tensor) else len(cu_seqlens)) - 1
         slots = self._slots_arg(slots, n_seq, writes=True)
         N.require_gpu(k, v, self.window_k, slots)
-        if k.dtype != self.window_k.dtype or v.dtype != k.dtype:
+        if self._kv8:
+            self._act16("k / v", k, v)
+        elif k.dtype != self.window_k.dtype or v.dtype != k.dtype:
             raise TypeError("k / v must have the pool's dtype")
         if k.shape[1] != self.window_k.shape[1] or k.shape[3] != self.window_k.shape[3]:
             raise ValueError(f"k / v must be [1, H_kv, T, D] = [1, {self.window_k.shape[1]}, T, {self.window_k.shape[3]}], "
                              f"got {tuple(k.shape)}")
         cu = self._cu_arg(cu_seqlens, k.shape[2], k.device)
         k, v = self._rows16(k), self._rows16(v)
+        name = "sfa_ring_fill_varlen_fp8_slots" if self._kv8 else "sfa_ring_fill_varlen_slots"
         with torch.cuda.device(k.device):
-            rc = N.lib().sfa_ring_fill_varlen_slots(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k,
-                                                                           self.window_v, k, v)),
-                                                    cu.data_ptr(), n_seq, self._dev_state.data_ptr(), slots.data_ptr(),
-                                                    N.stream_ptr(k.device))
-        N.check(rc, "sfa_ring_fill_varlen_slots")
+            rc = getattr(N.lib(), name)(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v, k, v)),
+                                        cu.data_ptr(), n_seq, self._dev_state.data_ptr(), slots.data_ptr(),
+                                        *((self._kv_scale_ptr(),) if self._kv8 else ()), N.stream_ptr(k.device))
+        N.check(rc, name)
         return self._dev_state
 
     def release_slots(self, slots) -> None:
@@ -762,6 +821,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         """sfa_decode_ring_multi_dyn with the per-layer constants (buffer descriptors, a workspace for the full cache plus
         the chunk) built once per chunk shape, as _ring_multi does."""
         from . import _native as N
+        self._refuse_fp8("extend_attention_tree_dyn" if tree is not None else
+                         "extend_step_dyn" if commit else "extend_attention_dyn")
         slots = self._slots_arg(slots, q.shape[0], writes=bool(commit))
         dev_state = self._require_dyn("extend_attention_tree_dyn" if tree is not None else
                                       "extend_step_dyn" if commit else "extend_attention_dyn")
@@ -861,14 +922,15 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if out is None:
             out = torch.empty((1, H_q, T, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
-        name, mid = "sfa_decode_ring_ragged_slots", ()
-        if parent is not None or commit_seq is not None:
-            name = "sfa_decode_ring_ragged_tree_slots"
+        name, mid, kvs = "sfa_decode_ring_ragged_slots", (), ()
+        if parent is not None or commit_seq is not None or self._kv8:
+            name = "sfa_decode_ring_ragged_fp8_slots" if self._kv8 else "sfa_decode_ring_ragged_tree_slots"
             mid = (None if parent is None else parent.data_ptr(), None if commit_seq is None else commit_seq.data_ptr())
+            kvs = (self._kv_scale_ptr(),) if self._kv8 else ()
         with torch.cuda.device(q.device):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
-                                          cu.data_ptr(), n_seq, st["ws"].data_ptr(), st["ws"].numel(),
+                                          cu.data_ptr(), n_seq, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
                                           st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
                                           N.stream_ptr(q.device))
         N.check(rc, name)
@@ -909,7 +971,9 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         if k_new.dim() != 4 or k_new.shape[0] != 1 or k_new.shape[1] != H_kv or k_new.shape[3] != D or \
                 v_new.shape != k_new.shape or k_new.shape[2] < 1:
             raise ValueError(f"k_new / v_new must be packed [1, H_kv, T, D] = [1, {H_kv}, T, {D}], got {tuple(k_new.shape)}")
-        if k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
+        if self._kv8:
+            self._act16("k_new / v_new", k_new, v_new)
+        elif k_new.dtype != self.window_k.dtype or v_new.dtype != k_new.dtype:
             raise TypeError("k_new / v_new must have the cache buffers' dtype")
         T = k_new.shape[2]
         cu = self._cu_arg(cu_q, T, k_new.device)
@@ -922,12 +986,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.require_gpu(slots)
         k_new, v_new = self._rows16(k_new), self._rows16(v_new)
         wk, wv = self._ring_descs()
+        name = "sfa_ring_commit_path_ragged_fp8_slots" if self._kv8 else "sfa_ring_commit_path_ragged_slots"
         with torch.cuda.device(k_new.device):
-            rc = N.lib().sfa_ring_commit_path_ragged_slots(wk, wv, N.desc(k_new), N.desc(v_new), count.data_ptr(),
-                                                           None if path is None else path.data_ptr(), cu.data_ptr(),
-                                                           n_seq, dev_state.data_ptr(), slots.data_ptr(),
-                                                           N.stream_ptr(k_new.device))
-        N.check(rc, "sfa_ring_commit_path_ragged_slots")
+            rc = getattr(N.lib(), name)(wk, wv, N.desc(k_new), N.desc(v_new), count.data_ptr(),
+                                        None if path is None else path.data_ptr(), cu.data_ptr(), n_seq,
+                                        dev_state.data_ptr(), slots.data_ptr(),
+                                        *((self._kv_scale_ptr(),) if self._kv8 else ()), N.stream_ptr(k_new.device))
+        N.check(rc, name)
 
     def packed_positions(self, cu_q, slots, T: int) -> torch.Tensor:
         """RoPE positions of a packed step: for packed row ``cu_q[i] + t`` of sequence i, ``seen[slots[i]] + t``; -1 for
@@ -1077,6 +1142,10 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
                   layer_idx: int = 0) -> torch.Tensor:
         """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state."""
         return self._layer(layer_idx).init_pool(num_slots, H_kv, D, dtype, device)
+
+    def set_kv_scale(self, k_scale, v_scale, layer_idx: int) -> None:
+        """``SinkCacheLayer.set_kv_scale`` of one layer: the static per-KV-head scales of its FP8 pool, copied in place."""
+        self._layer(layer_idx).set_kv_scale(k_scale, v_scale)
 
     def prefill_slots(self, key_states, value_states, cu_seqlens, slots, layer_idx: int) -> torch.Tensor:
         """``SinkCacheLayer.prefill_slots`` of one layer: packed sequences into the named slots of its pool."""

@@ -21,18 +21,28 @@ Variants per (W, step), alternating in one process:
     that stores the decode rows and the chunk, plus one commit_packed_dyn for the accepted paths; split_up = what was
     possible before: a ragged_step_dyn for the 5 sequences that do not speculate, plus extend_attention_tree_dyn(slots=)
     and commit_path_dyn(slots=) for the 4 trees.  Skipped where the library lacks the packed tree call.
+--pool-dtypes bf16,fp8: the pool format instead (wall mode): a serving geometry (H_q=32, H_kv=8, D=128, num_sink=4, bf16
+    activations, a pool of 64 slots, every ring full), steps dec64 (64 decode rows) and dec63_pre512 (63 decode rows + one
+    512-token chunk), one committing ragged_step_dyn per step on a pool of each named format, alternating in one process.
+    Prints ms per step, the spread, and GB/s against the bytes the format must read (the live cache rows of every named
+    slot at 2 or 1 bytes per element plus the 16-bit chunk K/V).  fp8 is skipped where the library lacks the call.
+--pkg DIR: import sink_attention from DIR/sink-flash-attention-kernel_amd (a checkout of another commit with its own
+    built library), to time two commits' libraries with one tool.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
 --mode kernels: --calls calls of each variant after 5 warm-up calls, in the order above, for a kernel trace of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o rstep -- python tools/kbench_ragged_step.py --mode kernels
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
-usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...] [--admit | --tree]"""
+usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
+       [--admit | --tree | --pool-dtypes bf16,fp8] [--pkg DIR]"""
 import argparse
 import csv
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--pkg" in sys.argv[1:-1]:       # before the first import of sink_attention
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--pkg") + 1])
 sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT]
 
 S, HQ, HKV, D, NS = 8, 64, 8, 64, 4
@@ -184,6 +194,68 @@ def wall(args):
             del fns
 
 
+POOL_S, POOL_HQ, POOL_HKV, POOL_D = 64, 32, 8, 128
+POOL_STEPS = {"dec64": [1] * 64, "dec63_pre512": [1] * 63 + [512]}
+
+
+def pool_dtypes(args):
+    """--pool-dtypes: the same committing packed step on a 16-bit and on an FP8 pool, alternating"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt = "cuda", torch.bfloat16
+    fmt = {"bf16": torch.bfloat16, "fp8": getattr(torch, "float8_e4m3fn", None)}
+    names = [n for n in args.pool_dtypes.split(",")
+             if n != "fp8" or hasattr(_native.lib(), "sfa_decode_ring_ragged_fp8_slots")]
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nserving geometry H_q={POOL_HQ} H_kv={POOL_HKV} D={POOL_D} num_sink={NS} s_aux bf16 "
+          f"activations, pool of {POOL_S}, rings full; device ms per committing step, median of {args.rounds} rounds of "
+          f"{args.calls} calls (events), formats alternating; GB/s = bytes the format must read / median", flush=True)
+    for W in Ws:
+        pools = {}
+        pre = NS + W + 37                          # full ring, wrapped
+        torch.manual_seed(0)
+        k = torch.randn(1, POOL_HKV, POOL_S * pre, POOL_D, device=dev, dtype=dt)
+        v = torch.randn_like(k)
+        for n in names:
+            pools[n] = SinkCacheLayer(NS, W)
+            pools[n].init_pool(POOL_S, POOL_HKV, POOL_D, fmt[n], dev)
+            pools[n].prefill_slots(k, v, [pre * i for i in range(POOL_S + 1)], list(range(POOL_S)))
+        del k, v
+        sa = torch.randn(POOL_HQ, device=dev) * 0.5
+        for step, lengths in POOL_STEPS.items():
+            T = sum(lengths)
+            q = torch.randn(1, POOL_HQ, T, POOL_D, device=dev, dtype=dt)
+            kn, vn = (torch.randn(1, POOL_HKV, T, POOL_D, device=dev, dtype=dt) for _ in range(2))
+            o = torch.empty_like(q)
+            cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
+            slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
+            fns = {n: (lambda p=pools[n]: p.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True)) for n in names}
+            res = {n: [] for n in names}
+            for n in names:
+                for _ in range(WARM):
+                    fns[n]()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for n in names:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _c in range(args.calls):
+                        fns[n]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    res[n].append(e0.elapsed_time(e1) / args.calls)
+            cells = []
+            for n in names:
+                x = sorted(res[n])
+                nbytes = 2 * POOL_HKV * POOL_D * (POOL_S * (NS + W) * (1 if n == "fp8" else 2) + T * 2)
+                cells.append(f"{n} {x[len(x) // 2]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f}) {nbytes / 2 ** 20:7.1f} MiB "
+                             f"{nbytes / x[len(x) // 2] / 1e6:7.1f} GB/s")
+            print(f"  W={W:5d} {step:12s} T={T:4d}  " + "   ".join(cells), flush=True)
+            if len(names) == 2:
+                a, b = (sorted(res[n])[len(res[n]) // 2] for n in names)
+                print(f"        {names[1]} / {names[0]} time {b / a:.3f}", flush=True)
+
+
 def kernels(args):
     torch, names, have = _setup(args)
     dev, dt = "cuda", torch.bfloat16
@@ -254,9 +326,13 @@ def main():
     ap.add_argument("--admit", action="store_true", help="the admission mix: variants admit_mix and dry")
     ap.add_argument("--tree", action="store_true", help="the speculative step (wall mode): variants packed_tree and split_up")
     ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
+    ap.add_argument("--pool-dtypes", default=None, help="bf16,fp8: the packed step on pools of these formats (wall mode)")
+    ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
     if args.summarize:
         summarize(args)
+    elif args.pool_dtypes:
+        pool_dtypes(args)
     elif args.mode == "kernels":
         kernels(args)
     else:
