@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
 fused-step / device-state / one-pass variants against the linearised cache.
-usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots]   (range: keys carry the falling staircase of
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots] [--call=packed]   (range: keys carry the falling staircase of
 tests/range_inputs.py along a +-1 code, one level per 64 keys, and the queries a gain of 0 / 0.5 / 1 / -1 along it; probe: keys are the +-1 codes of tests/probe_inputs.py and
 every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
 one just evicted or the last sink; --slots: the single-token steps (decode_step_dyn only; the multi-token and commit
 calls are not fuzzed here) also run through a slot pool - the B sequences sit in a random permutation of a larger pool and the
-batch carries random inactive rows - and are held to the same reference)"""
+batch carries random inactive rows - and are held to the same reference; --call=packed: random packed serving steps
+instead - ragged_step_dyn over a slot pool with Wc up to 4096, random H_kv, G, T_PAD, fills and chunk lengths, in the plain,
+tree (parent=), admitting and FP8-pool forms - against an fp64 masked attention over each sequence's history, computed on
+the GPU)"""
 import os
 import random
 import sys
@@ -24,7 +27,9 @@ from sink_attention.cache import SinkCacheLayer
 inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
 assert inputs in ("randn", "probe", "range"), inputs
 use_slots = "--slots" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith("--inputs=") and a != "--slots"]
+call = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--call=")] or ["step"])[-1]
+assert call in ("step", "packed"), call
+sys.argv = [a for a in sys.argv if not a.startswith("--inputs=") and not a.startswith("--call=") and a != "--slots"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
@@ -65,6 +70,137 @@ def ref_decode(q, k, v, sa):
     p = torch.softmax(s, -1)
     return (p[..., :kk.shape[2]] @ vv)
 
+
+def packed_case():
+    """one random packed step; returns (description, largest error / tolerance over the live rows, or inf)"""
+    from fp8_ref import FP8, dequant, quant
+    D = rng.choice([64, 80, 96, 128, 48])
+    dt = torch.float32 if D == 48 else rng.choice([torch.bfloat16, torch.float16])
+    Hkv, g = rng.choice([1, 2, 8]), rng.choice([1, 4, 8])
+    Hq, ns = Hkv * g, 4
+    W = rng.choice([48, 320, 1024, 2048, 4096])
+    T = rng.choice([64, 320, 1024])
+    form = rng.choice(["plain", "tree", "admit", "fp8"] if dt != torch.float32 else ["plain", "tree", "admit"])
+    n_seq = rng.randrange(2, 7)
+    lengths, left = [], T
+    for _ in range(n_seq):
+        n = min(rng.choice([0, 1, 1, 3, 8, 33, 64, 70, 160, 300]), left - 8 if left > 8 else 0)
+        lengths.append(n)
+        left -= n
+    S = n_seq + 2
+    slots = rng.sample(range(S), n_seq)
+    if rng.random() < 0.3:
+        slots[rng.randrange(n_seq)] = -1
+    fresh = [form == "admit" and rng.random() < 0.5 for _ in range(n_seq)]
+    hist = [0 if fresh[i] else rng.choice([1, 3, 9, 100, ns + W - 1, ns + W, ns + W + rng.randrange(1, 2 * W)]) for i in range(n_seq)]
+    aux = rng.random() < 0.5
+    sa = torch.randn(Hq, device="cuda") * 0.8 if aux else None
+    # tests/util.py::DECODE_TOL for the 16-bit types; fp32: this tool's own 1e-4 (probe and range rows put a logit of 14 - 30
+    # nat on one key among thousands: the f32 rounding of that dot product alone moves p by 1e-5 relative)
+    tol = {torch.float32: 1e-4, torch.float16: 2e-3, torch.bfloat16: 1.6e-2}[dt]
+    desc = f"packed {inputs} {form} Hkv{Hkv} G{g} D{D} Wc{W} T{T} lengths{lengths} hist{hist} slots{slots} {str(dt)[6:]} aux{int(aux)}"
+    layer = SinkCacheLayer(ns, W)
+    layer.init_pool(S, Hkv, D, FP8 if form == "fp8" else dt, "cuda")
+    sc = None
+    if form == "fp8":
+        sc = ([rng.choice([0.37, 1.0, 2.0]) for _ in range(Hkv)], [rng.choice([0.25, 1.0]) for _ in range(Hkv)])
+        layer.set_kv_scale(*sc)
+    cu = [0]
+    for n in lengths:
+        cu.append(cu[-1] + n)
+    def keys_p(n):
+        """keys of one history: as keys(), but the range staircase is a sawtooth of 12 levels (a history of 12000 keys would
+        otherwise climb to 1600 nat, beyond what an f32 dot product resolves) and fp32 takes range_inputs.FP32_SCALE"""
+        if inputs != "range":
+            return keys(1, Hkv, n, D, dt)
+        u = probe_inputs.codes((1, 1, 1, D), torch.Generator().manual_seed(D), torch.float32).cuda()
+        lvl = -((torch.arange(n, device="cuda") // 64) % 12).float() * range_inputs.STEPS[1] / D ** 0.5
+        lvl = lvl * (range_inputs.FP32_SCALE if dt == torch.float32 else 1.0)
+        return (torch.randn(1, Hkv, n, D, device="cuda") + lvl.view(1, 1, n, 1) * u).to(dt)
+
+    q = torch.randn(1, Hq, T, D, device="cuda").to(dt)
+    k, v = keys_p(T), torch.randn(1, Hkv, T, D, device="cuda").to(dt)
+    full = {}
+    for i, (n, L) in enumerate(zip(lengths, hist)):
+        if slots[i] < 0 or n == 0:
+            continue
+        if inputs == "probe":
+            pr = probe_inputs.chunk_probe(1, Hq, Hkv, D, ns, W, L, n, dt, seed=rng.randrange(1 << 30), aux=False)
+            fk, fv = pr["k"].cuda(), pr["v"].cuda()
+            q[:, :, cu[i]:cu[i] + n] = pr["q"][:, :, L:].cuda()
+        else:
+            fk, fv = keys_p(L + n), torch.randn(1, Hkv, L + n, D, device="cuda").to(dt)
+            if inputs == "range":
+                u = probe_inputs.codes((1, 1, 1, D), torch.Generator().manual_seed(D), torch.float32).cuda()
+                a = torch.tensor([rng.choice((0.0, 0.5, 1.0, -1.0)) for _ in range(Hq)], device="cuda").view(1, Hq, 1, 1)
+                q[:, :, cu[i]:cu[i] + n] = (torch.randn(1, Hq, n, D, device="cuda") + a * u).to(dt)
+        k[:, :, cu[i]:cu[i] + n], v[:, :, cu[i]:cu[i] + n] = fk[:, :, L:], fv[:, :, L:]
+        full[i] = (fk, fv)
+    cont = [i for i in full if hist[i] > 0]
+    if cont:
+        fill = [min(hist[i], ns + W) for i in cont]
+        cat = lambda x, lo, hi: torch.cat([full[i][x][:, :, lo(j):hi(j)] for j, i in enumerate(cont)], dim=2)
+        cum = lambda xs: [sum(xs[:j]) for j in range(len(xs) + 1)]
+        layer.prefill_slots(cat(0, lambda j: 0, lambda j: fill[j]), cat(1, lambda j: 0, lambda j: fill[j]), cum(fill), [slots[i] for i in cont])
+        extra = [hist[i] - f for i, f in zip(cont, fill)]
+        if any(extra):
+            layer.commit_packed_dyn(cat(0, lambda j: fill[j], lambda j: hist[cont[j]]), cat(1, lambda j: fill[j], lambda j: hist[cont[j]]),
+                                    cum(extra), [slots[i] for i in cont], extra)
+    parent = None
+    trees = {}
+    if form == "tree" or (form == "fp8" and rng.random() < 0.5):
+        parent = [-1] * T
+        for i, n in enumerate(lengths):
+            trees[i] = [rng.randrange(-1, u) if rng.random() < 0.7 else u - 1 for u in range(n)]
+            parent[cu[i]:cu[i] + n] = trees[i]
+    o = layer.ragged_step_dyn(q, k, v, cu, slots, s_aux=sa, commit=rng.random() < 0.5, admit=form == "admit", parent=parent)
+    worst = 0.0
+    live = torch.zeros(T, dtype=torch.bool, device="cuda")
+    for i, (fk, fv) in full.items():
+        n, L = lengths[i], hist[i]
+        sl = min(n, ns) if fresh[i] else min(L, ns)
+        par = trees[i] if (i in trees and n <= 64) else list(range(-1, n - 1))
+        depth, anc = [], torch.zeros(n, n, dtype=torch.bool)
+        for u in range(n):
+            depth.append(0 if par[u] < 0 else depth[par[u]] + 1)
+            anc[u, u] = True
+            if par[u] >= 0:
+                anc[u] |= anc[par[u]]
+        d = torch.tensor(depth, device="cuda").view(n, 1)
+        j = torch.arange(L + n, device="cuda").view(1, L + n)
+        mask = (j < sl) | ((j >= L + d - W + 1) & (j < L))
+        dd = torch.tensor(depth, device="cuda")
+        chunk = anc.cuda() & ((d - dd.view(1, n) <= W - 1) | (torch.arange(n, device="cuda").view(1, n) < (sl if fresh[i] else 0)))
+        mask = torch.cat([mask[:, :L], chunk], dim=1) if L else chunk
+        if sc is not None and L:
+            fk = torch.cat([dequant(quant(fk[:, :, :L].cpu(), sc[0]), sc[0], dt).cuda(), fk[:, :, L:]], dim=2)
+            fv = torch.cat([dequant(quant(fv[:, :, :L].cpu(), sc[1]), sc[1], dt).cuda(), fv[:, :, L:]], dim=2)
+        s = (q[:, :, cu[i]:cu[i] + n].double() @ fk.double().repeat_interleave(g, 1).transpose(-1, -2)) / D ** 0.5
+        s = s.masked_fill(~mask, float("-inf"))
+        if sa is not None:
+            s = torch.cat([s, sa.double().view(1, Hq, 1, 1).expand(1, Hq, n, 1)], -1)
+        r = torch.softmax(s, -1)[..., :L + n] @ fv.double().repeat_interleave(g, 1)
+        e = (o[:, :, cu[i]:cu[i] + n].double() - r).abs().max().item()
+        worst = max(worst, e / tol if e == e else float("inf"))
+        live[cu[i]:cu[i] + n] = True
+    if bool(o[:, :, ~live].any()):
+        worst = float("inf")                                      # inactive, empty and padded rows must be zeros
+    return desc, worst
+
+
+if call == "packed":
+    top = 0.0
+    for case in range(n_cases):
+        try:
+            desc, worst = packed_case()
+        except Exception as ex:      # noqa: BLE001
+            desc, worst = "packed " + repr(ex)[:300], float("inf")
+        top = max(top, worst if worst != float("inf") else 0.0)
+        if worst > 1.0:
+            bad += 1
+            print("BAD", desc, "error / tol", worst)
+    print(f"fuzz_decode --call=packed --inputs={inputs}: {n_cases} cases, {bad} bad, largest error / tol {top:.3f}")
+    sys.exit(1 if bad else 0)
 
 for case in range(n_cases):
     D = rng.choice([32, 64, 80, 128, 256])
