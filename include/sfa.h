@@ -700,6 +700,94 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
                         int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
                         void* stream);
 
+/*
+ * Paged slot pool: the packed calls on a pool whose RING memory follows the sequence length.  A contiguous pool holds
+ * [S, Hkv, Wc, D] per ring buffer whether a slot has 40 tokens or Wc; a paged pool holds pages and a table:
+ *   window_k/v  [n_pages, Hkv, P, D]: the ring PAGES, in the pool's dtype (bf16 or f16, head dims 64 / 80 / 96 / 128),
+ *               with the strides of the contiguous buffers and the page index where the slot index was.  P = shape[2] is
+ *               a power of two and at least 32, so that a 32-slot ring tile lies inside one page.
+ *   page_table  device int32 [S][table_stride], owned by the caller like kv_scale.  Entry [s][j] is the page that holds
+ *               ring slots [j P, (j + 1) P) of slot s.  The ring capacity is Wc = table_stride * P (the rule: a table
+ *               whose rows are longer than Wc / P entries is passed with table_stride >= Wc / P and means that larger
+ *               ring; Wc need not be a power of two, Wc = 320 with P = 64 is legal).  The kernels read the table when
+ *               they run and the host never reads it: an in-place update is seen by the next replay of a captured graph.
+ *   sink_k/v [S, Hkv, num_sink, D] and state int32 [S][4] are those of the contiguous pool; S comes from the sink buffers.
+ * Table entries.  An entry e with (unsigned)e >= n_pages is UNMAPPED (-1 by convention):
+ *   - a read of a ring tile whose page is unmapped addresses page 0: in bounds; the output of that sequence is
+ *     unspecified and no other sequence's output changes;
+ *   - a store to a ring slot whose page is unmapped is dropped; the state row still advances as the contiguous call
+ *     advances it;
+ *   - every page and row address is computed in 64-bit arithmetic.
+ * Pages needed are a prefix.  A ring fills from slot 0 upwards until it is full (the prefill placement and the commit
+ * both do), so a slot whose ring has held at most r tokens touches table entries 0 .. ceil(min(r, Wc) / P) - 1 only,
+ * in reads and in stores.  An allocator maps that prefix before the call that makes the ring reach it and nothing else.
+ * Two pages mapped into two live slots at once are undefined for storing calls, as the same slot twice is.
+ * Contract.  Let the TWIN be the contiguous pool with window[s, :, j P : (j + 1) P] = pages[table[s][j]], the same
+ * sinks and the same state.  Two bitwise equalities, which are what the tests hold the calls to:
+ *   - Read.  o of a paged step is bit for bit o of the same call on the twin: a ring tile's address is one wave-uniform
+ *     table lookup plus the twin's arithmetic, everything behind the address is the 16-bit kernel.
+ *   - Storage.  After a storing call on both pools every mapped page row equals the twin's ring slot, every row the
+ *     contiguous call leaves alone keeps its bytes, pages mapped to no slot of the call keep their bytes, and sinks and
+ *     state rows are equal.
+ * Host checks, before those of the contiguous sibling (which then run in their order, reading Wc = table_stride * P and
+ * S for the ring's shape), SFA_ERR_INVALID_ARGUMENT: null page descriptors ("window_k: null tensor descriptor");
+ * "page_table: null device pointer"; "<call>: the page size (window_k shape[2] = P) must be a power of two and at least
+ * 32"; "<call>: table_stride (n) must be at least 1 (Wc = table_stride * P)"; page buffers of unequal shape ("window_k
+ * and window_v differ in shape[i]: ..."); "<call>: the page buffers need shape[0] = n_pages in [1, 2^30) (got n)".  After
+ * the sibling's checks: fp32, head dims outside 64 / 80 / 96 / 128 and SFA_FLAG_FORCE_GENERIC are SFA_ERR_UNSUPPORTED
+ * ("<call>: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 (...)"): there is no exact-f32 instance.
+ * <call> is decode_ragged_paged, ring_commit_ragged_paged, ring_fill_varlen_paged or ring_copy_paged.  FP8 pages are
+ * not served.
+ *
+ * sfa_decode_ring_ragged_paged_slots: the arguments of sfa_decode_ring_ragged_tree_slots plus (page_table,
+ * table_stride) in front of workspace; parent, commit_seq, commit and SFA_FLAG_RAGGED_ADMIT as there.  Workspace:
+ * sfa_decode_ragged_workspace_bytes with Nkv_cache = num_sink + Wc.  sfa_last_path(): the name of the contiguous call
+ * plus "_paged".
+ */
+int sfa_decode_ring_ragged_paged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                       const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                                       const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux,
+                                       const int32_t* parent, const int32_t* commit_seq, int commit, int32_t* state,
+                                       const int32_t* slots, const int32_t* cu_q, int n_seq, const int32_t* page_table,
+                                       int table_stride, void* workspace, size_t workspace_bytes, float scale,
+                                       unsigned flags, void* stream);
+
+/*
+ * sfa_ring_commit_path_ragged_slots into a paged ring: the same arguments plus (page_table, table_stride, n_slots) in
+ * front of stream.  n_slots = S, the rows of `state` and of the table: the contiguous call reads S from the ring buffers,
+ * which here hold pages, and this call takes no sink buffers.  sfa_last_path(): "ring_commit_path_ragged_slots_paged".
+ */
+int sfa_ring_commit_path_ragged_paged_slots(const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                            const sfa_tensor* k_new, const sfa_tensor* v_new, const int32_t* count,
+                                            const int32_t* path, const int32_t* cu_q, int n_seq, int32_t* state,
+                                            const int32_t* slots, const int32_t* page_table, int table_stride,
+                                            int n_slots, void* stream);
+
+/* sfa_ring_fill_varlen_slots into a paged pool: the same arguments plus (page_table, table_stride) in front of stream.
+ * The state row is written whether or not the ring's pages are mapped.  sfa_last_path(): "ring_fill_varlen_slots_paged". */
+int sfa_ring_fill_varlen_paged_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                     const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                     const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                     const int32_t* page_table, int table_stride, void* stream);
+
+/*
+ * sfa_ring_copy_slots between paged pools: the same arguments plus a (page_table, table_stride) pair for each side in
+ * front of stream.  Copies the live sink rows, the live ring slots j < clamp(window_len, 0, Wc) through both tables (slot
+ * j is read from row j mod P of the source's page and stored into row j mod P of the destination's) and the state row.
+ * Source and destination are one pool (all pointers equal, the tables included) or two pools of equal geometry, P
+ * included ("ring_copy_paged: the pools differ in page size (src a, dst b)"); n_pages of each is free.  The caller maps
+ * the destination's pages for the source's fill first (the prefix rule at the source's window_len); a slot whose
+ * destination page is unmapped is dropped, one whose source page is unmapped copies page 0's row.  Pages are copied,
+ * never shared.  Skipped pairs and the aliasing rules are those of sfa_ring_copy_slots.  sfa_last_path():
+ * "ring_copy_slots_paged".
+ */
+int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
+                              const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,
+                              const sfa_tensor* dst_sink_v, const sfa_tensor* dst_window_k, const sfa_tensor* dst_window_v,
+                              int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                              const int32_t* src_page_table, int src_table_stride, const int32_t* dst_page_table,
+                              int dst_table_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -453,6 +453,45 @@ int check_fp8_served(const char* who, int dtype, int64_t D, unsigned flags) {
     return SFA_OK;
 }
 
+// The checks a *_paged_slots call adds (`who`: its name in the messages), made before those of its contiguous sibling:
+// the page buffers are descriptors, the table is there, P = shape[2] is a power of two >= 32 (a 32-key ring tile then
+// lies inside one page), table_stride >= 1 and both page buffers have one shape.  Then `ring` gets the descriptors the
+// sibling's checks and the launchers read: [S, H_kv, Wc = table_stride * P, D] with the pages' pointer and strides.
+struct PagedRing {
+    sfa_tensor k, v;
+    PageTable pt;
+};
+
+int paged_ring(const char* who, const sfa_tensor* page_k, const sfa_tensor* page_v, const int32_t* table, int table_stride,
+               int64_t S, PagedRing* ring) {
+    int st;
+    if ((st = check_tensor(page_k, "window_k")) || (st = check_tensor(page_v, "window_v"))) return st;
+    SFA_CHECK_ARG(table != nullptr, "page_table: null device pointer");
+    const int64_t P = page_k->shape[2];
+    SFA_CHECK_ARG(P >= 32 && (P & (P - 1)) == 0,
+                  "%s: the page size (window_k shape[2] = %lld) must be a power of two and at least 32", who, (long long)P);
+    SFA_CHECK_ARG(table_stride >= 1, "%s: table_stride (%d) must be at least 1 (Wc = table_stride * P)", who, table_stride);
+    if ((st = same_shape(page_k, page_v, "window_k", "window_v"))) return st;
+    SFA_CHECK_ARG(page_k->shape[0] >= 1 && page_k->shape[0] < (1ll << 30),
+                  "%s: the page buffers need shape[0] = n_pages in [1, 2^30) (got %lld)", who, (long long)page_k->shape[0]);
+    ring->k = *page_k, ring->v = *page_v;
+    ring->k.shape[0] = ring->v.shape[0] = S;
+    ring->k.shape[2] = ring->v.shape[2] = (int64_t)table_stride * P;
+    ring->pt = PageTable{table, table_stride, P, page_k->shape[0]};
+    return SFA_OK;
+}
+
+// ... and after them: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one reads a paged pool)
+int check_paged_served(const char* who, int dtype, int64_t D, unsigned flags) {
+    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
+        (flags & SFA_FLAG_FORCE_GENERIC)) {
+        set_error("%s: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim %lld%s)", who,
+                  dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    return SFA_OK;
+}
+
 // every host-checkable argument of an attention call over a chunk (sfa_decode_ring_multi*, _tree*, _ragged_slots), at
 // the state of the descriptor (a device-state call: the full cache); nothing launches
 int check_multi(const RingCall& c) {
@@ -560,6 +599,7 @@ int ring_ragged(const RingCall& c) {
     SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
                   (long long)q->shape[0]);
     SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
+    if (c.pt.table && (st = check_paged_served("decode_ragged_paged", q->dtype, q->shape[3], c.flags))) return st;
     const size_t need = decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                 c.sink_len + c.window_len, q->shape[3], q->dtype);
     if ((st = check_workspace("decode_ragged", need, need != 0, c.workspace, c.workspace_bytes))) return st;
@@ -641,6 +681,7 @@ int ring_commit_ragged(const RingCall& c) {
     if ((st = check_commit(c))) return st;
     SFA_CHECK_ARG(c.k_new->shape[0] == 1, "ring_commit_ragged: k_new / v_new must be packed [1, H_kv, T, D] (got shape[0] = %lld)",
                   (long long)c.k_new->shape[0]);
+    if (c.pt.table && (st = check_paged_served("ring_commit_ragged_paged", c.k_new->dtype, c.k_new->shape[3], 0))) return st;
     return ring_commit_dyn_launch(c);
 }
 
@@ -648,7 +689,7 @@ int ring_commit_ragged(const RingCall& c) {
 int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                 const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu_seqlens,
                 int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool, bool kv8 = false,
-                const float* kv_scale = nullptr) {
+                const float* kv_scale = nullptr, const PageTable* pt = nullptr) {
     g_err[0] = 0;
     int st;
     if ((st = check_tensor(sink_k, "sink_k", kv8)) || (st = check_tensor(sink_v, "sink_v", kv8)) ||
@@ -696,14 +737,16 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     if ((st = check_rows16({sink_k, sink_v, window_k, window_v, k, v}, es, 7,
                            "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
         return st;
+    if (pt && (st = check_paged_served("ring_fill_varlen_paged", k->dtype, D, 0))) return st;
     return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
-                                   (hipStream_t)stream, slots);
+                                   (hipStream_t)stream, slots, nullptr, pt);
 }
 
 // sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools.  The device arrays (slots,
 // state) are not looked at: skipped pairs are decided by the kernel
 int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
-               int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream) {
+               int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream,
+               const PageTable* src_pt = nullptr, const PageTable* dst_pt = nullptr) {
     g_err[0] = 0;
     static const char* const names[8] = {"src_sink_k", "src_sink_v", "src_window_k", "src_window_v",
                                          "dst_sink_k", "dst_sink_v", "dst_window_k", "dst_window_v"};
@@ -745,7 +788,9 @@ int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const s
     if ((st = check_rows16({src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3]}, es, 7,
                            "ring_copy_slots: rows of every tensor must be 16-byte aligned")))
         return st;
-    return ring_copy_slots_launch(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, (hipStream_t)stream);
+    if (src_pt && (st = check_paged_served("ring_copy_paged", src[0]->dtype, D, 0))) return st;
+    return ring_copy_slots_launch(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, (hipStream_t)stream,
+                                  src_pt, dst_pt);
 }
 
 }  // namespace
@@ -990,6 +1035,76 @@ int sfa_ring_fill_varlen_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* s
                                    const float* kv_scale, void* stream) {
     return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true, true,
                        kv_scale);
+}
+
+int sfa_decode_ring_ragged_paged_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
+                                       int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                       const int32_t* page_table, int table_stride, SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("decode_ragged_paged", window_k, window_v, page_table, table_stride, sink_k ? sink_k->shape[0] : 1, &ring)))
+        return st;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = attend_call(q, sink_k, sink_v, &ring.k, &ring.v, k_new, v_new, o, s_aux, workspace, workspace_bytes, scale,
+                             flags, stream);
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.parent = parent, c.commit_seq = commit_seq;
+    c.pt = ring.pt;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
+int sfa_ring_commit_path_ragged_paged_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
+                                            int32_t* state, const int32_t* slots, const int32_t* page_table,
+                                            int table_stride, int n_slots, void* stream) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("ring_commit_ragged_paged", window_k, window_v, page_table, table_stride, n_slots, &ring))) return st;
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = commit_call(&ring.k, &ring.v, k_new, v_new, count, RingState::Rows, state, slots, stream);
+    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.pt = ring.pt;
+    return ring_commit_ragged(c);
+}
+
+int sfa_ring_fill_varlen_paged_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                     const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                     const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                     const int32_t* page_table, int table_stride, void* stream) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("ring_fill_varlen_paged", window_k, window_v, page_table, table_stride, sink_k ? sink_k->shape[0] : 1, &ring)))
+        return st;
+    return fill_varlen(sink_k, sink_v, &ring.k, &ring.v, k, v, cu_seqlens, n_seq, state, stream, slots, true, false, nullptr,
+                       &ring.pt);
+}
+
+int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
+                              const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,
+                              const sfa_tensor* dst_sink_v, const sfa_tensor* dst_window_k, const sfa_tensor* dst_window_v,
+                              int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
+                              const int32_t* src_page_table, int src_table_stride, const int32_t* dst_page_table,
+                              int dst_table_stride, void* stream) {
+    g_err[0] = 0;
+    PagedRing sr, dr;
+    int st;
+    if ((st = paged_ring("ring_copy_paged", src_window_k, src_window_v, src_page_table, src_table_stride,
+                         src_sink_k ? src_sink_k->shape[0] : 1, &sr)) ||
+        (st = paged_ring("ring_copy_paged", dst_window_k, dst_window_v, dst_page_table, dst_table_stride,
+                         dst_sink_k ? dst_sink_k->shape[0] : 1, &dr)))
+        return st;
+    SFA_CHECK_ARG(sr.pt.page_size == dr.pt.page_size, "ring_copy_paged: the pools differ in page size (src %lld, dst %lld)",
+                  (long long)sr.pt.page_size, (long long)dr.pt.page_size);
+    const sfa_tensor* const src[4] = {src_sink_k, src_sink_v, &sr.k, &sr.v};
+    const sfa_tensor* const dst[4] = {dst_sink_k, dst_sink_v, &dr.k, &dr.v};
+    return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream, &sr.pt, &dr.pt);
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

@@ -181,6 +181,34 @@ __device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, con
 __device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&) { return Kv8Args{nullptr}; }
 __device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Args& kv) { return kv; }
 
+// ---- paged pool (the *_paged_slots calls).  The ring buffers are PAGES [n_pages, Hkv, P, D] (the
+// page index where the slot index was, same strides); table[c * stride + j] is the page that holds ring slots
+// [j P, (j + 1) P) of cache row c.  P = 1 << shift >= kTile, Wc = stride * P, so a 32-slot ring tile lies inside one page.
+// A kernel argument that only the paged instances take, like Kv8Args (a pool is FP8 or paged, never both).
+struct PageArgs {
+    const int* table;            // device int32 [S][stride]; read when the kernel runs, never on the host
+    int stride;
+    int shift;
+    int npages;
+};
+__device__ __forceinline__ PageArgs page_of() { return PageArgs{}; }
+__device__ __forceinline__ PageArgs page_of(const Kv8Args&) { return PageArgs{}; }
+__device__ __forceinline__ const PageArgs& page_of(const PageArgs& pg) { return pg; }
+__device__ __forceinline__ PageArgs page_of(const RaggedArgs&) { return PageArgs{}; }
+__device__ __forceinline__ PageArgs page_of(const RaggedArgs&, const Kv8Args&) { return PageArgs{}; }
+__device__ __forceinline__ const PageArgs& page_of(const RaggedArgs&, const PageArgs& pg) { return pg; }
+__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const PageArgs&) { return rg; }
+__device__ __forceinline__ Kv8Args kv8_of(const PageArgs&) { return Kv8Args{nullptr}; }
+__device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&, const PageArgs&) { return Kv8Args{nullptr}; }
+
+// the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
+// of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
+__device__ __forceinline__ int page_at(const PageArgs& pg, int c, int slot) {
+    const int e = pg.table[(int64_t)c * pg.stride + (slot >> pg.shift)];
+    return (unsigned)e < (unsigned)pg.npages ? e : -1;
+}
+__device__ __forceinline__ int page_row(const PageArgs& pg, int slot) { return slot & ((1 << pg.shift) - 1); }
+
 // sequence i of the pack: first packed row and length
 struct RaggedSeq {
     int c0, n;
@@ -358,9 +386,11 @@ __device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int
 
 // Ragged: the chunk is the n rows of k_new / v_new from packed row crow on, in place of the a.n rows of batch row b
 // KV8: sink and ring tiles are FP8 rows (1 byte per element); the chunk keeps es
-template <bool Ragged = false, bool KV8 = false>
+// Paged: a ring tile gets its place inside its page (rows [start mod P, ...) of page 0); tile_page adds the page once
+// the tile is known to be live
+template <bool Ragged = false, bool KV8 = false, bool Paged = false>
 __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es,
-                                              int n = 0, int crow = 0) {
+                                              int n = 0, int crow = 0, [[maybe_unused]] int pshift = 0) {
     TileInfo ti;
     const View *kv, *vv;
     int len, row = c;            // sink and ring: the cache row; the chunk: the batch row
@@ -375,8 +405,12 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
     if constexpr (KV8) es = ti.seg == 2 ? es : 1;
     ti.ksn = kv->sn * es;
     ti.vsn = vv->sn * es;
-    ti.k = kv->ptr + ((int64_t)row * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)ti.start * ti.ksn;
-    ti.v = vv->ptr + ((int64_t)row * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)ti.start * ti.vsn;
+    int first = ti.start;        // the tile's first row in its buffer
+    if constexpr (Paged) {
+        if (ti.seg == 1) row = 0, first = ti.start & ((1 << pshift) - 1);
+    }
+    ti.k = kv->ptr + ((int64_t)row * kv->sb + (int64_t)hk * kv->sh) * es + (int64_t)first * ti.ksn;
+    ti.v = vv->ptr + ((int64_t)row * vv->sb + (int64_t)hk * vv->sh) * es + (int64_t)first * ti.vsn;
     if (ti.seg == 2) {
         if constexpr (Ragged) ti.k += (int64_t)crow * ti.ksn, ti.v += (int64_t)crow * ti.vsn;
         ti.cmin = ti.start, ti.cmax = ti.start + ti.count - 1;
@@ -388,6 +422,16 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
         ti.cmin = ti.cmax = 0;
     }
     return ti;
+}
+
+// a live ring tile of a paged pool: one wave-uniform table lookup (a scalar load, the row and the tile index are in
+// SGPRs) moves the tile from page 0 to its page; an unmapped entry stays on page 0 (in bounds, the output unspecified).
+// The tile index is the PHYSICAL ring slot start / P: a ring tile has a fixed place in the ring.
+__device__ __forceinline__ void tile_page(TileInfo& ti, const MultiArgs& a, const PageArgs& pg, int c, int es) {
+    const int e = __builtin_amdgcn_readfirstlane(page_at(pg, c, ti.start));
+    const int64_t page = e < 0 ? 0 : e;
+    ti.k += page * a.wk.sb * es;
+    ti.v += page * a.wv.sb * es;
 }
 
 // 0 dead (no row of [tmin, tmax] sees a key), 1 full (every row sees every key), 2 edge
@@ -520,13 +564,19 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
 // elements, the lane-to-chunk map unchanged - and converted to T in registers on the way into LDS (kv8_read, the scale
 // of head hk: one scalar per workgroup for K and for V); the LDS image and everything behind it are those of the 16-bit
 // instance.  Chunk tiles (k_new / v_new) are 16-bit and keep the 16-byte load.
-template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, bool KV8 = false, typename... RA>
+// Paged (the paged pool, with Ragged): a live ring tile takes its page from the table (tile_page) before its loads are
+// issued; dead tiles cost no lookup, and everything behind the tile address is the 16-bit instance.
+template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, bool KV8 = false,
+          bool Paged = false, typename... RA>
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && Ragged && D == 80) ? 2 : 1)))
 void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged),
-                  "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args)");
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
+                      !(KV8 && !Ragged) && !(Paged && (!Ragged || KV8)),
+                  "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args); paged pool: (MultiArgs, "
+                  "RaggedArgs, PageArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     [[maybe_unused]] const Kv8Args kv = kv8_of(ra...);
+    [[maybe_unused]] const PageArgs pg = page_of(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
@@ -692,10 +742,13 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info<Ragged, KV8>(a, f, i, b, c, hk, es, rn, prow);
+            ti = tile_info<Ragged, KV8, Paged>(a, f, i, b, c, hk, es, rn, prow, pg.shift);
             if (Tree && Ragged && !is_tree) cls = tile_class(a, ti, tmin, tmax, f.nsk);
             else cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
             if (cls != 0) break;
+        }
+        if constexpr (Paged) {
+            if (i < tend && ti.seg == 1) tile_page(ti, a, pg, c, es);
         }
         return i;
     };
@@ -1013,9 +1066,11 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // A sequence whose commit_seq entry is 0 stores nothing.
 // Q (store_piece): void, or the chunk's 16-bit type when the pool is FP8 - es stays the chunk's element size, a piece 8
 // elements.
-template <typename Q = void>
+// Paged: a ring slot is stored into row slot mod P of its page (page_at); a slot on an unmapped page is dropped.
+template <typename Q = void, bool Paged = false>
 __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es,
-                                                    const Kv8Args& kv = Kv8Args{nullptr}) {
+                                                    const Kv8Args& kv = Kv8Args{nullptr},
+                                                    [[maybe_unused]] const PageArgs& pg = PageArgs{}) {
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
     const int ch = (int)(item % cpr);
@@ -1040,12 +1095,19 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
         if (t < s.n - a.wc) return;
         slot = (int)(((int64_t)state_wp(a, c) + t) % a.wc);
     }
+    int drow = c;                // the destination's row of its buffer: the cache row, or the page of a ring slot
+    if constexpr (Paged) {
+        if (dk == &a.wk) {
+            if ((drow = page_at(pg, c, slot)) < 0) return;
+            slot = page_row(pg, slot);
+        }
+    }
     const int64_t so = (int64_t)ch * 16, dso = piece_off<Q>(ch);
     const int ed = piece_es<Q>(es);
     const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + (int64_t)tp * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + (int64_t)tp * a.vn.sn) * es + so;
-    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)slot * dk->sn) * ed + dso;
-    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)slot * dv->sn) * ed + dso;
+    char* kd = dk->ptr + ((int64_t)drow * dk->sb + (int64_t)hk * dk->sh + (int64_t)slot * dk->sn) * ed + dso;
+    char* vd = dv->ptr + ((int64_t)drow * dv->sb + (int64_t)hk * dv->sh + (int64_t)slot * dv->sn) * ed + dso;
     store_piece<Q>(kd, vd, ks, vs, kv, a.Hkv, hk);
 }
 
@@ -1058,14 +1120,18 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
 // was written) and stores nothing.
 // Ragged: rows are the packed rows (ragged_row); a row without work gets zeros, the commit is commit_piece_ragged.
 // KV8 (the FP8 pool, with Ragged): the commit blocks quantise as they store; the fold is the 16-bit instance's.
-template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, bool KV8 = false, typename... RA>
+// Paged (the paged pool, with Ragged): the commit blocks store through the page table; the fold reads no cache.
+template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, bool KV8 = false, bool Paged = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged),
-                  "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (MultiArgs, nred, RaggedArgs, Kv8Args)");
+    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
+                      !(KV8 && !Ragged) && !(Paged && (!Ragged || KV8)),
+                  "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        if constexpr (KV8) commit_piece_ragged<T>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...));
+        if constexpr (Paged)
+            commit_piece_ragged<void, true>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, Kv8Args{nullptr}, page_of(ra...));
+        else if constexpr (KV8) commit_piece_ragged<T>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...));
         else if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
         else commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
         return;
@@ -1151,10 +1217,12 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
 // c0_i + clamp(path[c0_i + j], 0, n_i - 1) (row c0_i + j without a path) into ring slot (write_pos + j) mod Wc of slot
 // slots[i] - the piece commit_piece<Path, true> stores for the sequence passed as a [1, Hkv, n_i, D] chunk.
 // Q (store_piece): void, or the pack's 16-bit type when the ring is FP8 (es stays the pack's element size); KA: Kv8Args then
-template <typename Q = void, typename... KA>
+// Paged (Q = void): KA = PageArgs, the slot goes to row slot mod P of its page, a slot on an unmapped page is dropped
+template <typename Q = void, bool Paged = false, typename... KA>
 __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es,
                                                                  KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1), "FP8 ring: (..., Kv8Args)");
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !std::is_void_v<Q>),
+                  "FP8 ring: (..., Kv8Args); paged ring: (..., PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
@@ -1175,7 +1243,13 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
     if (c < 0) return;
     const int last = clamp_count(count + lo, s.n);
     if (j >= last || j < last - a.wc) return;
-    const int slot = (int)(((int64_t)state_wp(a, c) + j) % a.wc);
+    int slot = (int)(((int64_t)state_wp(a, c) + j) % a.wc);
+    int drow = c;                // the ring's row of its buffer: the cache row, or the slot's page
+    if constexpr (Paged) {
+        const PageArgs& pg = page_of(ka...);
+        if ((drow = page_at(pg, c, slot)) < 0) return;
+        slot = page_row(pg, slot);
+    }
     int src = j;
     if (a.path) {
         src = a.path[s.c0 + j];
@@ -1185,8 +1259,8 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
     const int ed = piece_es<Q>(es);
     const char* ks = a.kn.ptr + ((int64_t)hk * a.kn.sh + row * a.kn.sn) * es + so;
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + row * a.vn.sn) * es + so;
-    char* kd = a.wk.ptr + ((int64_t)c * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * ed + dso;
-    char* vd = a.wv.ptr + ((int64_t)c * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * ed + dso;
+    char* kd = a.wk.ptr + ((int64_t)drow * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * ed + dso;
+    char* vd = a.wv.ptr + ((int64_t)drow * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * ed + dso;
     store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), a.Hkv, hk);
 }
 
@@ -1200,12 +1274,15 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
 // Slots (sfa_ring_fill_varlen_slots): sequence b goes to cache row and state row slots[b] of a pool of npool rows (a
 // value outside [0, npool): the sequence is skipped); every other row of the pool keeps buffers and state.
 // Q (store_piece): void, or the pack's 16-bit type when the pool is FP8 (cpr and es stay those of the pack); KA: Kv8Args then
-template <bool Slots, typename Q = void, typename... KA>
+// Paged (Slots, Q = void): KA = PageArgs; wc = stride * P, ring slot s goes to row s mod P of its page, a slot on an
+// unmapped page is dropped (the state row is written all the same)
+template <bool Slots, typename Q = void, bool Paged = false, typename... KA>
 __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv, View wk, View wv, View k, View v,
                                                                const int* cu, int* state, int n_seq, int Hkv, int ns,
                                                                int wc, int T, int cpr, int es, const int* slots,
                                                                int npool, KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1), "FP8 pool: (..., Kv8Args)");
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !(std::is_void_v<Q> && Slots)),
+                  "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nj = ns + wc;
     if (item >= (int64_t)n_seq * Hkv * nj * cpr) return;
@@ -1227,13 +1304,21 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     const int src = fill_src(p, j);   // token index within the sequence, -1: nothing to store
     if (src < 0) return;
     const View *dk = j < ns ? &sk : &wk, *dv = j < ns ? &sv : &wv;
-    const int row = j < ns ? j : j - ns;
+    int row = j < ns ? j : j - ns;
+    int drow = c;                // the destination's row of its buffer: the cache row, or the page of a ring slot
+    if constexpr (Paged) {
+        if (j >= ns) {
+            const PageArgs& pg = page_of(ka...);
+            if ((drow = page_at(pg, c, row)) < 0) return;
+            row = page_row(pg, row);
+        }
+    }
     const int64_t so = (int64_t)ch * 16, tok = (int64_t)c0 + src, dso = piece_off<Q>(ch);
     const int ed = piece_es<Q>(es);
     const char* ks = k.ptr + ((int64_t)hk * k.sh + tok * k.sn) * es + so;
     const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
-    char* kd = dk->ptr + ((int64_t)c * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * ed + dso;
-    char* vd = dv->ptr + ((int64_t)c * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * ed + dso;
+    char* kd = dk->ptr + ((int64_t)drow * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * ed + dso;
+    char* vd = dv->ptr + ((int64_t)drow * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * ed + dso;
     store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), Hkv, hk);
 }
 
@@ -1261,8 +1346,13 @@ struct CopyPools {
     int S;
 };
 
+// Paged (sfa_ring_copy_paged_slots): PA = (PageArgs of the source, PageArgs of the destination); wc = stride * P of
+// both.  Ring slot j is read from row j mod P of its source page (an unmapped one: page 0) and stored into row j mod P
+// of its destination page (an unmapped one: the piece is dropped).  Sink rows and the state row as above.
+template <bool Paged = false, typename... PA>
 __global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, CopyPools dst, int Hkv, int ns, int wc,
-                                                              int cpr, int es, int nblk, int same) {
+                                                              int cpr, int es, int nblk, int same, PA... pa) {
+    static_assert(sizeof...(PA) == (Paged ? 2 : 0), "paged pools: (..., PageArgs src, PageArgs dst)");
     const int blk = (int)(blockIdx.x % (unsigned)nblk);
     const int rest = (int)(blockIdx.x / (unsigned)nblk);
     const int hk = rest % Hkv, pair = rest / Hkv;
@@ -1280,11 +1370,30 @@ __global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, Cop
     const int p0 = blk * (256 * kCopyPieces);
     if (p0 >= live) return;
     // the 16 bytes of piece (r, c) in the K (v = false) or V buffer of a pool; slot: the pair's slot of that pool
+    // Paged: `slot` of a ring row is its page instead (pages_of below), the row its place in the page
+    [[maybe_unused]] PageArgs spg{}, dpg{};
+    if constexpr (Paged) {
+        const PageArgs both[2] = {pa...};
+        spg = both[0], dpg = both[1];
+    }
     auto at = [&](const CopyPools& pl, int slot, int r, int c, bool v) {
         const bool sink = r < sl;
         const View& b = sink ? (v ? pl.sv : pl.sk) : (v ? pl.wv : pl.wk);
-        const int64_t rr = sink ? r : r - sl;
+        int64_t rr = sink ? r : r - sl;
+        if constexpr (Paged) rr = sink ? rr : page_row(spg, (int)rr);      // one P for both pools
         return reinterpret_cast<u32x4*>(b.ptr + ((int64_t)slot * b.sb + (int64_t)hk * b.sh + rr * b.sn) * es + (int64_t)c * 16);
+    };
+    // paged pools: the buffer row of piece row r in the source (the slot for a sink row, else the page; unmapped: page 0)
+    // and in the destination (unmapped: -1, the piece is not stored)
+    [[maybe_unused]] auto pages_of = [&](int r, int& srow, int& drow) {
+        srow = s, drow = d;
+        if constexpr (Paged) {
+            if (r >= sl) {
+                const int e = page_at(spg, s, r - sl);
+                srow = e < 0 ? 0 : e;
+                drow = page_at(dpg, d, r - sl);
+            }
+        }
     };
     // The thread's pieces p0 + tid + 256 u as (row, chunk): one division, then steps of 256 pieces.  full (wave-uniform):
     // every piece of the block is live, and the loads and stores carry no predicate.  In the last block of a head a
@@ -1303,6 +1412,18 @@ __global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, Cop
             if (c >= cpr) c -= cpr, ++r;
         }
         u32x4 kr[kCopyPieces], vr[kCopyPieces];
+        if constexpr (Paged) {     // the table entries first (independent loads), then the pieces as below
+            int sr[kCopyPieces], dr[kCopyPieces];
+#pragma unroll
+            for (int u = 0; u < kCopyPieces; ++u) pages_of(row[u], sr[u], dr[u]);
+#pragma unroll
+            for (int u = 0; u < kCopyPieces; ++u)
+                kr[u] = *at(src, sr[u], row[u], ch[u], false), vr[u] = *at(src, sr[u], row[u], ch[u], true);
+#pragma unroll
+            for (int u = 0; u < kCopyPieces; ++u)
+                if (ok[u] && dr[u] >= 0) *at(dst, dr[u], row[u], ch[u], false) = kr[u], *at(dst, dr[u], row[u], ch[u], true) = vr[u];
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < kCopyPieces; ++u)
             kr[u] = *at(src, s, row[u], ch[u], false), vr[u] = *at(src, s, row[u], ch[u], true);
@@ -1426,13 +1547,15 @@ int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
 }
 
 // kv (packed calls only): the FP8 pool - the (Dyn, Slots, Ragged) instances with the cache format, Tree on or off
+// pg (packed calls only): the paged pool - the same instances with the table lookup
 template <typename T, int D>
-int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, hipStream_t stream) {
+int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, hipStream_t stream) {
     const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
         if constexpr (M::Ragged) {
-            if (kv) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv);
+            if (pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *pg);
+            else if (kv) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv);
             else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
         }
         else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots><<<grid, kWaves * 64, 0, stream>>>(a);
@@ -1441,24 +1564,24 @@ int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, hip
 }
 
 template <typename T>
-int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, hipStream_t stream) {
+int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, hipStream_t stream) {
     switch (a.D) {
-        case 64: return launch_mfma<T, 64>(a, rg, kv, stream);
-        case 80: return launch_mfma<T, 80>(a, rg, kv, stream);
-        case 96: return launch_mfma<T, 96>(a, rg, kv, stream);
-        case 128: return launch_mfma<T, 128>(a, rg, kv, stream);
+        case 64: return launch_mfma<T, 64>(a, rg, kv, pg, stream);
+        case 80: return launch_mfma<T, 80>(a, rg, kv, pg, stream);
+        case 96: return launch_mfma<T, 96>(a, rg, kv, pg, stream);
+        case 128: return launch_mfma<T, 128>(a, rg, kv, pg, stream);
     }
     set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
     return SFA_ERR_UNSUPPORTED;
 }
 
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
-// kv: the FP8 pool of a packed call (the API admits it for the MFMA instances only)
+// kv / pg: the FP8 / paged pool of a packed call (the API admits either for the MFMA instances only)
 template <typename T>
-int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, kv, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, kv, pg, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
         dispatch_mode(a, rg, [&](auto m) {
@@ -1480,6 +1603,10 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, boo
         using M = decltype(m);
         if constexpr (M::Ragged) {
             if constexpr (sizeof(T) == 2) {
+                if (pg) {
+                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, false, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *pg);
+                    return;
+                }
                 if (kv) {
                     multi_reduce_kernel<T, M::Dyn, M::Slots, true, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *kv);
                     return;
@@ -1522,9 +1649,16 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
     return a;
 }
 
+// the table argument of a paged call (pt.table set): the API has checked that P is a power of two
+PageArgs page_args(const PageTable& pt) {
+    int shift = 0;
+    while ((1ll << shift) < pt.page_size) ++shift;
+    return PageArgs{pt.table, (int)pt.stride, shift, (int)pt.n_pages};
+}
+
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
 int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
-                 const Kv8Args* kv = nullptr) {
+                 const Kv8Args* kv = nullptr, const PageArgs* pg = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
@@ -1532,9 +1666,13 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
         set_error("decode_ragged_fp8: no kernel instance for this call");
         return SFA_ERR_UNSUPPORTED;
     }
-    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, nullptr, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, kv, *mfma, c.stream);
-    return launch_rest<bf16_t>(a, rg, kv, *mfma, c.stream);
+    if (pg && !*mfma) {         // refused by the API before: no f32-accumulate instance reads a paged pool
+        set_error("decode_ragged_paged: no kernel instance for this call");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, nullptr, nullptr, false, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, kv, pg, *mfma, c.stream);
+    return launch_rest<bf16_t>(a, rg, kv, pg, *mfma, c.stream);
 }
 
 }  // namespace
@@ -1653,10 +1791,11 @@ int decode_ragged_launch(const RingCall& c) {
     bool mfma;
     const char* dname;
     const Kv8Args kv{c.kv_scale};
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cache_es == 1 ? &kv : nullptr))) return st;
+    const PageArgs pg = page_args(c.pt);
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cache_es == 1 ? &kv : nullptr, c.pt.table ? &pg : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? "_kvfp8" : "");
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? "_kvfp8" : c.pt.table ? "_paged" : "");
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }
@@ -1676,13 +1815,16 @@ int ring_commit_dyn_launch(const RingCall& c) {
         if (nb > 0) {
             const Kv8Args kv{c.kv_scale};
             const dim3 grid((unsigned)nb);
-            if (c.cache_es != 1) ring_commit_ragged_kernel<<<grid, 256, 0, c.stream>>>(a, rg, c.count, es);
+            if (c.pt.table) ring_commit_ragged_kernel<void, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, page_args(c.pt));
+            else if (c.cache_es != 1) ring_commit_ragged_kernel<<<grid, 256, 0, c.stream>>>(a, rg, c.count, es);
             else if (c.k_new->dtype == SFA_DTYPE_F16) ring_commit_ragged_kernel<f16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
             else ring_commit_ragged_kernel<bf16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
             if ((st = launch_status("ring_commit_path_ragged"))) return st;
         }
         if ((st = launch_advance(a, c.count, &rg, c.stream))) return st;   // after every reader of the state
-        set_path(c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8" : "ring_commit_path_ragged_slots");
+        set_path(c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8"
+                 : c.pt.table  ? "ring_commit_path_ragged_slots_paged"
+                                 : "ring_commit_path_ragged_slots");
         return SFA_OK;
     }
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
@@ -1709,7 +1851,8 @@ int ring_commit_dyn_launch(const RingCall& c) {
 
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const float* kv_scale) {
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const float* kv_scale,
+                            const PageTable* pt) {
     const int es = dtype_size(k->dtype);
     const bool kv8 = sink_k->dtype == SFA_DTYPE_FP8_E4M3;       // the API: with slots and 16-bit k / v only
     const int Hkv = (int)k->shape[1], ns = (int)sink_k->shape[2], wc = (int)window_k->shape[2];
@@ -1728,6 +1871,10 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
             ring_fill_varlen_kernel<true, bf16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
                 make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
                 cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
+        else if (pt)
+            ring_fill_varlen_kernel<true, void, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], page_args(*pt));
         else if (slots)
             ring_fill_varlen_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
                 make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
@@ -1739,13 +1886,13 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         int st;
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
-    set_path(kv8 ? "ring_fill_varlen_slots_kvfp8" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
+    set_path(kv8 ? "ring_fill_varlen_slots_kvfp8" : pt ? "ring_fill_varlen_slots_paged" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
     return SFA_OK;
 }
 
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
-                           hipStream_t stream) {
+                           hipStream_t stream, const PageTable* src_pt, const PageTable* dst_pt) {
     const sfa_tensor *sk = src[0], *wk = src[2];
     const int es = dtype_size(wk->dtype);
     const int Hkv = (int)wk->shape[1], ns = (int)sk->shape[2], wc = (int)wk->shape[2];
@@ -1761,12 +1908,16 @@ int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_st
                           const_cast<int*>(src_state), src_slots, (int)wk->shape[0]};
         const CopyPools d{make_view(dst[0]), make_view(dst[1]), make_view(dst[2]), make_view(dst[3]),
                           dst_state, dst_slots, (int)dst[2]->shape[0]};
-        ring_copy_slots_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(s, d, Hkv, ns, wc, cpr, es, (int)nblk,
-                                                                         src_state == dst_state ? 1 : 0);
+        if (src_pt)
+            ring_copy_slots_kernel<true><<<dim3((unsigned)grid), 256, 0, stream>>>(
+                s, d, Hkv, ns, wc, cpr, es, (int)nblk, src_state == dst_state ? 1 : 0, page_args(*src_pt), page_args(*dst_pt));
+        else
+            ring_copy_slots_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(s, d, Hkv, ns, wc, cpr, es, (int)nblk,
+                                                                             src_state == dst_state ? 1 : 0);
         int st;
         if ((st = launch_status("ring_copy_slots"))) return st;
     }
-    set_path("ring_copy_slots");
+    set_path(src_pt ? "ring_copy_slots_paged" : "ring_copy_slots");
     return SFA_OK;
 }
 

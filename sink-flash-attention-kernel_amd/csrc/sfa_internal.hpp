@@ -39,6 +39,15 @@ float bwd_mfma_lse_factor(const Problem& p, unsigned flags);   // ... whose firs
 
 // One call on the sink + ring cache, as every launcher below takes it: named fields, a part that a call does not have is
 // null / zero.  An entry point of sfa_api.hip fills the fields its signature provides; the arguments are checked there.
+// A paged pool (the *_paged_slots calls): the ring buffers are pages [n_pages, H_kv, P, D] and table[s * stride + j]
+// (device int32) names the page of ring slots [j P, (j + 1) P) of slot s; Wc = stride * P.  The API passes the launchers
+// ring descriptors that read [S, H_kv, Wc, D] with the pages' pointer and strides, so that every geometry read stays
+// where it is; table == null: a contiguous pool.
+struct PageTable {
+    const int32_t* table;
+    int64_t stride, page_size, n_pages;
+};
+
 enum class RingState {
     Host,     // {sink_len, window_len, write_pos} below are the state
     Shared,   // `state` = device {sink_len, window_len, write_pos}, one row for the whole batch (the *_dyn calls)
@@ -82,6 +91,8 @@ struct RingCall {
     // row 0 K and row 1 V, null = all ones.  Read by the kernels only
     const float* kv_scale;
     int cache_es;
+    // paged pool (the *_paged_slots calls): window_k / window_v are the descriptors described at PageTable
+    PageTable pt;
 };
 
 // sfa_decode.hip
@@ -116,11 +127,12 @@ int ring_commit_dyn_launch(const RingCall& c);
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
                             int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots,
-                            const float* kv_scale = nullptr);
+                            const float* kv_scale = nullptr, const PageTable* pt = nullptr);
 // sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools (the same pool: a fork); pair i
-// copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i]
+// copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i].  src_pt / dst_pt (both or none):
+// paged pools, window_k / window_v as described at PageTable
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
-                           hipStream_t stream);
+                           hipStream_t stream, const PageTable* src_pt = nullptr, const PageTable* dst_pt = nullptr);
 
 }  // namespace sfa

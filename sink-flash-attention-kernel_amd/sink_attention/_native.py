@@ -172,6 +172,17 @@ def _bind(lib):
     # slot copy (fork / park): source pool + state, destination pool + state, src_slots, dst_slots, n_pairs, stream
     lib.sfa_ring_copy_slots.restype = i32
     lib.sfa_ring_copy_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp]
+    # paged pool: the packed step, the packed commit (plus n_slots), the slot fill and the slot copy (a pair per side) plus
+    # (`page_table` device int32 [S, table_stride], `table_stride`) before the tail
+    lib.sfa_decode_ring_ragged_paged_slots.restype = i32
+    lib.sfa_decode_ring_ragged_paged_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp,
+                                                       sz, f32, u32, vp]
+    lib.sfa_ring_commit_path_ragged_paged_slots.restype = i32
+    lib.sfa_ring_commit_path_ragged_paged_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    lib.sfa_ring_fill_varlen_paged_slots.restype = i32
+    lib.sfa_ring_fill_varlen_paged_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp]
+    lib.sfa_ring_copy_paged_slots.restype = i32
+    lib.sfa_ring_copy_paged_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp, i32, vp, i32, vp]
 
 
 def lib():

@@ -29,6 +29,68 @@ except ImportError:  # pragma: no cover
     _HFLayer = ABC
 
 
+def pages_needed(tokens: int, window_size: int, page_size: int) -> int:
+    """Table entries a slot touches once its ring has held at most ``tokens`` tokens: the prefix
+    ``0 .. ceil(min(tokens, Wc) / P) - 1``.  The ring fills from slot 0 upwards until it is full (the prefill placement
+    and the commit both do), so reads and stores stay inside that prefix (include/sfa.h, the paged pool)."""
+    return -(-min(max(int(tokens), 0), window_size) // page_size)
+
+
+class PageAllocator:
+    """Host-side bookkeeping of a paged pool's table: a free list of pages and, per slot, the pages mapped so far.  Pure
+    Python: it launches no kernel and never reads the device; the changed entries are written into ``table`` (device
+    int32 ``[S, Wc / P]``) with torch ops.  It assumes that it alone writes the table it was given (a fresh table is
+    all -1)."""
+
+    def __init__(self, table: torch.Tensor, num_pages: int, page_size: int, window_size: int):
+        self.table, self.num_pages, self.page_size, self.window_size = table, int(num_pages), int(page_size), int(window_size)
+        self.free_list = list(range(self.num_pages - 1, -1, -1))        # pop() hands out page 0 first
+        self.rows = [[] for _ in range(table.shape[0])]                 # slot -> its pages, entry j = table[slot][j]
+
+    def _slots(self, slots):
+        lst = slots.tolist() if isinstance(slots, torch.Tensor) else [int(x) for x in slots]
+        bad = [x for x in lst if not 0 <= x < len(self.rows)]
+        if bad or len(set(lst)) != len(lst):
+            raise ValueError(f"slots {lst}: each must name one slot of the pool of {len(self.rows)}, once")
+        return lst
+
+    def _write(self, rows, cols, vals):
+        if rows:
+            dev = self.table.device
+            self.table[torch.tensor(rows, device=dev), torch.tensor(cols, device=dev)] = \
+                torch.tensor(vals, dtype=torch.int32, device=dev)
+
+    def reserve(self, slots, tokens_after) -> None:
+        lst = self._slots(slots)
+        tok = [tokens_after] * len(lst) if isinstance(tokens_after, int) else \
+            (tokens_after.tolist() if isinstance(tokens_after, torch.Tensor) else [int(x) for x in tokens_after])
+        if len(tok) != len(lst):
+            raise ValueError(f"tokens_after must be one number or one per slot ({len(lst)}), got {len(tok)}")
+        more = [max(pages_needed(t, self.window_size, self.page_size) - len(self.rows[s]), 0) for s, t in zip(lst, tok)]
+        if sum(more) > len(self.free_list):
+            raise RuntimeError(f"out of pages: need {sum(more)}, free {len(self.free_list)}")
+        rows, cols, vals = [], [], []
+        for s, m in zip(lst, more):
+            for _ in range(m):
+                page = self.free_list.pop()
+                rows.append(s), cols.append(len(self.rows[s])), vals.append(page)
+                self.rows[s].append(page)
+        self._write(rows, cols, vals)
+
+    def free(self, slots) -> None:
+        rows, cols = [], []
+        for s in self._slots(slots):
+            for j, page in enumerate(self.rows[s]):
+                rows.append(s), cols.append(j)
+                self.free_list.append(page)
+            self.rows[s] = []
+        self._write(rows, cols, [-1] * len(rows))
+
+    def pool_bytes(self, H_kv: int, D: int, elem_bytes: int) -> int:
+        """Bytes of ring memory (K and V) the mapped pages hold."""
+        return 2 * sum(len(r) for r in self.rows) * H_kv * self.page_size * D * elem_bytes
+
+
 class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     """One layer's cache: ``num_sink`` pinned leading tokens + a ring of the last ``window_size`` others."""
 
@@ -599,6 +661,39 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             raise TypeError(f"{what}() does not serve an FP8 (float8_e4m3fn) pool: use the packed calls prefill_slots / "
                             "ragged_step_dyn / commit_packed_dyn (and fork_slots, release_slots, positions, "
                             "packed_positions)")
+        if self.page_size:       # a paged pool is served by the same calls as an FP8 pool
+            raise TypeError(f"{what}() does not serve a paged pool (init_pool(page_size=...)): use the packed calls "
+                            "prefill_slots / ragged_step_dyn / commit_packed_dyn (and fork_slots, release_slots, "
+                            "positions, packed_positions)")
+
+    # paged pool (init_pool(page_size=...)): window_k / window_v are the ring PAGES [num_pages, H_kv, P, D], page_table
+    # the device int32 [S, Wc / P] map (entry [s][j]: the page of ring slots [j P, (j + 1) P) of slot s, -1 unmapped)
+    page_size = None
+    page_table = None
+    _pages = None        # the host-side allocator behind reserve_pages / free_pages (shared by the layers of a cache)
+
+    def _page_args(self):
+        return (self.page_table.data_ptr(), self.page_table.stride(0))
+
+    def reserve_pages(self, slots, tokens_after) -> None:
+        """Map the ring pages the coming step needs (paged pool; pure host bookkeeping, no kernel, no device read):
+        for each host slot the first ``ceil(min(tokens_after, window_size) / page_size)`` table entries are mapped from
+        the free list; entries already mapped stay.  ``tokens_after`` (one number or one per slot) is an upper bound
+        of the slot's ``seen`` after the step; ``seen`` counts the sink tokens too, so at most one page more than the ring
+        reaches is reserved (``num_sink <= page_size``).  The changed
+        entries are written into ``page_table`` with torch ops on the current stream.  Raises ``RuntimeError("out of
+        pages: need X, free Y")`` before anything changes."""
+        self._require_paged("reserve_pages").reserve(slots, tokens_after)
+
+    def free_pages(self, slots) -> None:
+        """Return the pages of the host ``slots`` to the free list and write -1 into their table rows (a retired
+        sequence).  ``release_slots`` zeroes state rows and frees no pages; call both at retirement."""
+        self._require_paged("free_pages").free(slots)
+
+    def _require_paged(self, what):
+        if self._pages is None:
+            raise TypeError(f"{what} needs a paged pool: init_pool(..., page_size=P)")
+        return self._pages
 
     def _act16(self, what, *tensors):
         """An FP8 pool takes bfloat16 / float16 activations of one dtype."""
@@ -626,7 +721,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                  f"{tuple(t.shape)}")
             self.kv_scale[row].copy_(t.to(torch.float32) if t.dim() else t.to(torch.float32).expand(self.kv_scale.shape[1]))
 
-    def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda") -> torch.Tensor:
+    def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda", page_size=None,
+                  num_pages=None, page_table=None) -> torch.Tensor:
         """Allocate a pool of ``num_slots`` cache rows that lives as long as the server: ``[S, H_kv, num_sink /
         window_size, D]`` buffers and a zeroed int32 ``[S, 4]`` device state ``{sink_len, window_len, write_pos, seen}``
         (returned).  The layer enters per-sequence mode (the host-state methods refuse, as after ``prefill_varlen``).  A
@@ -642,7 +738,37 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         and ``packed_positions`` with bfloat16 / float16 activations; every other method raises ``TypeError``.  A stored
         element is ``e4m3fn(clamp(x / scale, -448, 448))`` and reads back as ``code * scale`` in the activations' dtype:
         the tokens of a step are attended at 16-bit precision inside that step and at FP8 precision afterwards, so a
-        prompt admitted in chunks is not bitwise the prompt admitted in one call."""
+        prompt admitted in chunks is not bitwise the prompt admitted in one call.
+
+        ``page_size=P``: a PAGED pool - the ring memory follows the sequence lengths.  ``window_k`` / ``window_v`` are
+        then ``[num_pages, H_kv, P, D]`` page buffers (default ``num_pages``: the full capacity ``S * Wc / P``; a server
+        passes less) and ``page_table`` a device int32 ``[S, Wc / P]`` map, the given tensor or a new one filled with
+        -1 (unmapped).  P is a power of two >= 32 that divides ``window_size`` (which need not be a power of two).  The
+        kernels read the table when they run, so an in-place update is seen by the next replay of a captured graph.
+        ``reserve_pages`` before a step and ``free_pages`` at retirement keep the table; a store to an unmapped page is
+        dropped and a read of one is in bounds but unspecified.  Served by the calls of an FP8 pool, at bfloat16 /
+        float16 and head dims 64 / 80 / 96 / 128; every other method raises ``TypeError``.  Sinks and state rows are not
+        paged.  The defaults (``page_size=None``) give the contiguous pool."""
+        if page_size is None and (num_pages is not None or page_table is not None):
+            raise ValueError("num_pages / page_table need page_size")
+        if page_size is not None:
+            P = int(page_size)
+            if dtype == torch.float8_e4m3fn:
+                raise TypeError("a paged FP8 pool is not served: init_pool takes dtype=float8_e4m3fn or page_size, not both")
+            if dtype not in (torch.float16, torch.bfloat16) or D not in (64, 80, 96, 128):
+                raise ValueError(f"a paged pool serves bfloat16 / float16 at head dims 64 / 80 / 96 / 128, got {dtype}, D = {D}")
+            if P < 32 or P & (P - 1):
+                raise ValueError(f"page_size must be a power of two and at least 32, got {page_size}")
+            if self.window_size < 1 or self.window_size % P:
+                raise ValueError(f"window_size ({self.window_size}) must be a multiple of page_size ({P})")
+            per_slot = self.window_size // P
+            num_pages = int(num_slots) * per_slot if num_pages is None else int(num_pages)
+            if num_pages < 1:
+                raise ValueError(f"a paged pool needs at least one page, got num_pages = {num_pages}")
+            if page_table is not None and (not isinstance(page_table, torch.Tensor) or page_table.dtype != torch.int32 or
+                                           tuple(page_table.shape) != (int(num_slots), per_slot) or
+                                           not page_table.is_contiguous()):
+                raise ValueError(f"page_table must be a contiguous int32 [S, Wc / P] = [{int(num_slots)}, {per_slot}] tensor")
         if self.window_size < 1:
             raise ValueError("init_pool needs a ring of at least one slot (window_size >= 1)")
         if int(num_slots) < 1:
@@ -653,7 +779,16 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             raise ValueError(f"an FP8 pool serves head dims 64 / 80 / 96 / 128, got D = {D}")
         mk = lambda n: torch.zeros(int(num_slots), H_kv, n, D, dtype=dtype, device=device)
         self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
-        self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
+        self.page_size = self.page_table = self._pages = None
+        if page_size is None:
+            self.window_k, self.window_v = mk(self.window_size), mk(self.window_size)
+        else:
+            pg = lambda: torch.zeros(num_pages, H_kv, P, D, dtype=dtype, device=device)
+            self.window_k, self.window_v = pg(), pg()
+            self.page_size = P
+            self.page_table = page_table if page_table is not None else \
+                torch.full((int(num_slots), per_slot), -1, dtype=torch.int32, device=device)
+            self._pages = PageAllocator(self.page_table, num_pages, P, self.window_size)
         # FP8 (OCP e4m3fn, one byte per element): the pool holds codes, the activations of the packed calls stay 16-bit;
         # the caller-owned static scales start at one (set_kv_scale)
         self.kv_scale = torch.ones(2, H_kv, dtype=torch.float32, device=device) if dtype == torch.float8_e4m3fn else None
@@ -719,11 +854,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                              f"got {tuple(k.shape)}")
         cu = self._cu_arg(cu_seqlens, k.shape[2], k.device)
         k, v = self._rows16(k), self._rows16(v)
-        name = "sfa_ring_fill_varlen_fp8_slots" if self._kv8 else "sfa_ring_fill_varlen_slots"
+        name = "sfa_ring_fill_varlen_fp8_slots" if self._kv8 else \
+            "sfa_ring_fill_varlen_paged_slots" if self.page_size else "sfa_ring_fill_varlen_slots"
         with torch.cuda.device(k.device):
             rc = getattr(N.lib(), name)(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v, k, v)),
                                         cu.data_ptr(), n_seq, self._dev_state.data_ptr(), slots.data_ptr(),
-                                        *((self._kv_scale_ptr(),) if self._kv8 else ()), N.stream_ptr(k.device))
+                                        *((self._kv_scale_ptr(),) if self._kv8 else ()),
+                                        *(self._page_args() if self.page_size else ()), N.stream_ptr(k.device))
         N.check(rc, name)
         return self._dev_state
 
@@ -761,19 +898,24 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                 raise ValueError(f"fork_slots: the pools differ in geometry: source [S, H_kv, num_sink / Wc, D] = "
                                  f"{tuple(source.sink_k.shape)} / {tuple(source.window_k.shape)}, this layer "
                                  f"{tuple(self.sink_k.shape)} / {tuple(self.window_k.shape)}")
+            if source.page_size != self.page_size or source.window_size != self.window_size:
+                raise ValueError(f"fork_slots: the pools differ in paging: source page_size {source.page_size} of a ring "
+                                 f"of {source.window_size}, this layer {self.page_size} of {self.window_size}")
             if source.window_k.device != self.window_k.device:
                 raise ValueError("fork_slots: the pools must live on one device")
         src, dst = self._fork_args(src, dst, source)
         N.require_gpu(self.window_k, source.window_k, src, dst)
         if src.numel() == 0:
             return
+        name = "sfa_ring_copy_paged_slots" if self.page_size else "sfa_ring_copy_slots"
         with torch.cuda.device(self.window_k.device):
-            rc = N.lib().sfa_ring_copy_slots(
+            rc = getattr(N.lib(), name)(
                 *(N.desc(t) for t in (source.sink_k, source.sink_v, source.window_k, source.window_v)),
                 src_state.data_ptr(),
                 *(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v)), dst_state.data_ptr(),
-                src.data_ptr(), dst.data_ptr(), src.numel(), N.stream_ptr(self.window_k.device))
-        N.check(rc, "sfa_ring_copy_slots")
+                src.data_ptr(), dst.data_ptr(), src.numel(),
+                *((*source._page_args(), *self._page_args()) if self.page_size else ()), N.stream_ptr(self.window_k.device))
+        N.check(rc, name)
 
     def _fork_args(self, src, dst, source):
         """``src`` / ``dst`` of ``fork_slots`` as int32 tensors on the pool's device: ``_slots_arg`` for each (``src``
@@ -923,10 +1065,11 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             out = torch.empty((1, H_q, T, D), device=q.device, dtype=q.dtype)
         sk, sv, wk, wv = st["descs"]
         name, mid, kvs = "sfa_decode_ring_ragged_slots", (), ()
-        if parent is not None or commit_seq is not None or self._kv8:
-            name = "sfa_decode_ring_ragged_fp8_slots" if self._kv8 else "sfa_decode_ring_ragged_tree_slots"
+        if parent is not None or commit_seq is not None or self._kv8 or self.page_size:
+            name = "sfa_decode_ring_ragged_fp8_slots" if self._kv8 else \
+                "sfa_decode_ring_ragged_paged_slots" if self.page_size else "sfa_decode_ring_ragged_tree_slots"
             mid = (None if parent is None else parent.data_ptr(), None if commit_seq is None else commit_seq.data_ptr())
-            kvs = (self._kv_scale_ptr(),) if self._kv8 else ()
+            kvs = (self._kv_scale_ptr(),) if self._kv8 else self._page_args() if self.page_size else ()
         with torch.cuda.device(q.device):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
@@ -986,12 +1129,15 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.require_gpu(slots)
         k_new, v_new = self._rows16(k_new), self._rows16(v_new)
         wk, wv = self._ring_descs()
-        name = "sfa_ring_commit_path_ragged_fp8_slots" if self._kv8 else "sfa_ring_commit_path_ragged_slots"
+        name = "sfa_ring_commit_path_ragged_fp8_slots" if self._kv8 else \
+            "sfa_ring_commit_path_ragged_paged_slots" if self.page_size else "sfa_ring_commit_path_ragged_slots"
         with torch.cuda.device(k_new.device):
             rc = getattr(N.lib(), name)(wk, wv, N.desc(k_new), N.desc(v_new), count.data_ptr(),
                                         None if path is None else path.data_ptr(), cu.data_ptr(), n_seq,
                                         dev_state.data_ptr(), slots.data_ptr(),
-                                        *((self._kv_scale_ptr(),) if self._kv8 else ()), N.stream_ptr(k_new.device))
+                                        *((self._kv_scale_ptr(),) if self._kv8 else ()),
+                                        *((*self._page_args(), self.num_slots) if self.page_size else ()),
+                                        N.stream_ptr(k_new.device))
         N.check(rc, name)
 
     def packed_positions(self, cu_q, slots, T: int) -> torch.Tensor:
@@ -1138,10 +1284,41 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         """``SinkCacheLayer.prefill_varlen`` of one layer: a packed ragged batch into per-sequence buffers and state."""
         return self._layer(layer_idx).prefill_varlen(key_states, value_states, cu_seqlens)
 
+    page_table = None    # paged pools: the one table every layer's pool shares (init_pool(page_size=...))
+    _pages = None
+
     def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda",
-                  layer_idx: int = 0) -> torch.Tensor:
-        """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state."""
-        return self._layer(layer_idx).init_pool(num_slots, H_kv, D, dtype, device)
+                  layer_idx: int = 0, page_size=None, num_pages=None, page_table=None) -> torch.Tensor:
+        """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state.  With
+        ``page_size`` the layers' pools are paged and share ONE table tensor (``cache.page_table``: that of the first
+        paged layer, or the given one) and one allocator, so one mapping serves every layer: the layers must agree in
+        ``num_slots``, ``page_size`` and ``num_pages``."""
+        layer = self._layer(layer_idx)
+        if page_size is None:
+            return layer.init_pool(num_slots, H_kv, D, dtype, device)
+        shared = self.page_table if page_table is None else page_table
+        state = layer.init_pool(num_slots, H_kv, D, dtype, device, page_size=page_size, num_pages=num_pages,
+                                page_table=shared)
+        if self._pages is not None and shared is self.page_table:
+            if (self._pages.num_pages, self._pages.page_size) != (layer._pages.num_pages, layer._pages.page_size):
+                raise ValueError("init_pool: the paged layers of a cache share one table and must agree in page_size "
+                                 "and num_pages")
+            layer._pages = self._pages
+        else:
+            self.page_table, self._pages = layer.page_table, layer._pages
+        return state
+
+    def reserve_pages(self, slots, tokens_after) -> None:
+        """``SinkCacheLayer.reserve_pages`` on the table the layers share: one mapping serves every layer."""
+        if self._pages is None:
+            raise TypeError("reserve_pages needs a paged pool: init_pool(..., page_size=P)")
+        self._pages.reserve(slots, tokens_after)
+
+    def free_pages(self, slots) -> None:
+        """``SinkCacheLayer.free_pages`` on the table the layers share."""
+        if self._pages is None:
+            raise TypeError("free_pages needs a paged pool: init_pool(..., page_size=P)")
+        self._pages.free(slots)
 
     def set_kv_scale(self, k_scale, v_scale, layer_idx: int) -> None:
         """``SinkCacheLayer.set_kv_scale`` of one layer: the static per-KV-head scales of its FP8 pool, copied in place."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
 fused-step / device-state / one-pass variants against the linearised cache.
-usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots] [--call=packed]   (range: keys carry the falling staircase of
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots] [--call=packed [--page-size=P]]   (range: keys carry the falling staircase of
 tests/range_inputs.py along a +-1 code, one level per 64 keys, and the queries a gain of 0 / 0.5 / 1 / -1 along it; probe: keys are the +-1 codes of tests/probe_inputs.py and
 every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
 one just evicted or the last sink; --slots: the single-token steps (decode_step_dyn only; the multi-token and commit
@@ -9,7 +9,8 @@ calls are not fuzzed here) also run through a slot pool - the B sequences sit in
 batch carries random inactive rows - and are held to the same reference; --call=packed: random packed serving steps
 instead - ragged_step_dyn over a slot pool with Wc up to 4096, random H_kv, G, T_PAD, fills and chunk lengths, in the plain,
 tree (parent=), admitting and FP8-pool forms - against an fp64 masked attention over each sequence's history, computed on
-the GPU)"""
+the GPU; --page-size=P with it: half of the 16-bit cases whose Wc is a multiple of P run on a paged pool of NaN-filled pages
+behind a shuffled table, reserved slot by slot through the host allocator's prefix rule)"""
 import os
 import random
 import sys
@@ -29,7 +30,8 @@ assert inputs in ("randn", "probe", "range"), inputs
 use_slots = "--slots" in sys.argv
 call = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--call=")] or ["step"])[-1]
 assert call in ("step", "packed"), call
-sys.argv = [a for a in sys.argv if not a.startswith("--inputs=") and not a.startswith("--call=") and a != "--slots"]
+page_size = int(([a.split("=", 1)[1] for a in sys.argv if a.startswith("--page-size=")] or ["0"])[-1])
+sys.argv = [a for a in sys.argv if not a.startswith(("--inputs=", "--call=", "--page-size=")) and a != "--slots"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
@@ -100,7 +102,17 @@ def packed_case():
     tol = {torch.float32: 1e-4, torch.float16: 2e-3, torch.bfloat16: 1.6e-2}[dt]
     desc = f"packed {inputs} {form} Hkv{Hkv} G{g} D{D} Wc{W} T{T} lengths{lengths} hist{hist} slots{slots} {str(dt)[6:]} aux{int(aux)}"
     layer = SinkCacheLayer(ns, W)
-    layer.init_pool(S, Hkv, D, FP8 if form == "fp8" else dt, "cuda")
+    paged = bool(page_size) and form != "fp8" and dt != torch.float32 and W % page_size == 0 and rng.random() < 0.5
+    if paged:
+        # pages in a shuffled order, NaN until stored; every slot gets the prefix its history plus this step can reach
+        desc += f" paged P{page_size}"
+        layer.init_pool(S, Hkv, D, dt, "cuda", page_size=page_size)
+        layer.window_k.fill_(float("nan")), layer.window_v.fill_(float("nan"))
+        rng.shuffle(layer._pages.free_list)
+        live_s = [(s, hist[i] + lengths[i]) for i, s in enumerate(slots) if s >= 0]
+        layer.reserve_pages([s for s, _ in live_s], [t for _, t in live_s])
+    else:
+        layer.init_pool(S, Hkv, D, FP8 if form == "fp8" else dt, "cuda")
     sc = None
     if form == "fp8":
         sc = ([rng.choice([0.37, 1.0, 2.0]) for _ in range(Hkv)], [rng.choice([0.25, 1.0]) for _ in range(Hkv)])

@@ -26,6 +26,10 @@ Variants per (W, step), alternating in one process:
     512-token chunk), one committing ragged_step_dyn per step on a pool of each named format, alternating in one process.
     Prints ms per step, the spread, and GB/s against the bytes the format must read (the live cache rows of every named
     slot at 2 or 1 bytes per element plus the 16-bit chunk K/V).  fp8 is skipped where the library lacks the call.
+--page-size 64,256: the paged pool instead (wall mode): the serving geometry and steps of --pool-dtypes
+    on a contiguous bf16 pool and, per page size P, on two paged pools of the same content - `ident` (slot s owns pages
+    s * Wc / P + j) and `shuf` (a seeded shuffle of the page pool) - all alternating in one process.  Prints ms per step, the
+    spread and each paged time over the contiguous one.  Skipped where the library lacks the call.
 --pkg DIR: import sink_attention from DIR/sink-flash-attention-kernel_amd (a checkout of another commit with its own
     built library), to time two commits' libraries with one tool.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
@@ -34,7 +38,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --pool-dtypes bf16,fp8] [--pkg DIR]"""
+       [--admit | --tree | --pool-dtypes bf16,fp8 | --page-size 64,256] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -256,6 +260,68 @@ def pool_dtypes(args):
                 print(f"        {names[1]} / {names[0]} time {b / a:.3f}", flush=True)
 
 
+def page_sizes(args):
+    """--page-size: the same committing packed step on a contiguous pool and on paged pools, alternating"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt = "cuda", torch.bfloat16
+    if not hasattr(_native.lib(), "sfa_decode_ring_ragged_paged_slots"):
+        print("this library has no paged pool: nothing to time")
+        return
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nserving geometry H_q={POOL_HQ} H_kv={POOL_HKV} D={POOL_D} num_sink={NS} s_aux bf16, "
+          f"pool of {POOL_S}, rings full; device ms per committing step, median of {args.rounds} rounds of {args.calls} calls "
+          f"(events) after {WARM} warm-up calls, pools alternating; ident / shuf: identity / seeded-shuffle page table", flush=True)
+    for W in Ws:
+        pre = NS + W + 37                          # full ring, wrapped
+        torch.manual_seed(0)
+        k = torch.randn(1, POOL_HKV, POOL_S * pre, POOL_D, device=dev, dtype=dt)
+        v = torch.randn_like(k)
+        cu_pre, every = [pre * i for i in range(POOL_S + 1)], list(range(POOL_S))
+        pools = {"contig": SinkCacheLayer(NS, W)}
+        pools["contig"].init_pool(POOL_S, POOL_HKV, POOL_D, dt, dev)
+        for P in [int(x) for x in args.page_size.split(",")]:
+            per = W // P
+            for kind in ("ident", "shuf"):
+                p = pools[f"P{P}_{kind}"] = SinkCacheLayer(NS, W)
+                p.init_pool(POOL_S, POOL_HKV, POOL_D, dt, dev, page_size=P)
+                order = torch.arange(POOL_S * per) if kind == "ident" else \
+                    torch.randperm(POOL_S * per, generator=torch.Generator().manual_seed(P))
+                p.page_table.copy_(order.reshape(POOL_S, per).to(torch.int32))
+        for p in pools.values():
+            p.prefill_slots(k, v, cu_pre, every)
+        del k, v
+        names = list(pools)
+        sa = torch.randn(POOL_HQ, device=dev) * 0.5
+        for step, lengths in POOL_STEPS.items():
+            T = sum(lengths)
+            q = torch.randn(1, POOL_HQ, T, POOL_D, device=dev, dtype=dt)
+            kn, vn = (torch.randn(1, POOL_HKV, T, POOL_D, device=dev, dtype=dt) for _ in range(2))
+            o = torch.empty_like(q)
+            cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
+            slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
+            fns = {n: (lambda p=pools[n]: p.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True)) for n in names}
+            res = {n: [] for n in names}
+            for n in names:
+                for _ in range(WARM):
+                    fns[n]()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for n in names:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _c in range(args.calls):
+                        fns[n]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    res[n].append(e0.elapsed_time(e1) / args.calls)
+            med = {n: sorted(x)[len(x) // 2] for n, x in res.items()}
+            print(f"  W={W:5d} {step:12s} T={T:4d}", flush=True)
+            for n in names:
+                x = sorted(res[n])
+                print(f"      {n:12s} {med[n]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f})  / contig {med[n] / med['contig']:.3f}", flush=True)
+
+
 def kernels(args):
     torch, names, have = _setup(args)
     dev, dt = "cuda", torch.bfloat16
@@ -327,10 +393,13 @@ def main():
     ap.add_argument("--tree", action="store_true", help="the speculative step (wall mode): variants packed_tree and split_up")
     ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
     ap.add_argument("--pool-dtypes", default=None, help="bf16,fp8: the packed step on pools of these formats (wall mode)")
+    ap.add_argument("--page-size", default=None, help="64,256: the packed step on a contiguous and on paged pools (wall mode)")
     ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
     if args.summarize:
         summarize(args)
+    elif args.page_size:
+        page_sizes(args)
     elif args.pool_dtypes:
         pool_dtypes(args)
     elif args.mode == "kernels":
