@@ -542,6 +542,9 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
  * sfa_decode_ring_multi_slots; workspace >= sfa_decode_ragged_workspace_bytes(n_seq, Hq, Hkv, T, num_sink + Wc, D,
  * dtype) bytes, 256-byte aligned (0: unsupported head dim or shape; no GPU needed).  sfa_last_path() names carry
  * "_ragged", then "_admit" with SFA_FLAG_RAGGED_ADMIT, then "_commit".
+ * Strides have no upper limit in the packed calls (this one, the _tree / _fp8 / _paged forms, the packed commit, the
+ * fills and sfa_ring_copy_slots): every offset is formed in 64 bits on the device, so the pack may lie behind a head
+ * stride of 4 GiB or more, a pool behind any slot stride and a page buffer may exceed 4 GiB (n_pages < 2^30).
  */
 size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                          int64_t D, int dtype);

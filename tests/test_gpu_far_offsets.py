@@ -8,7 +8,8 @@ the operands past 2^31 elements, 2^31 bytes or 2^32 bytes ("far", tests/far_view
       generic path behind slice_ok(), or SFA_ERR_UNSUPPORTED with nothing written), exactly that,
   (d) the rest of the arena still holds its sentinel: no store landed at a truncated address.
 
-The problems are small; only their addresses are large.  One arena per module (4.1 GiB), every case re-fills it."""
+The problems are small; only their addresses are large.  One arena per module (4.1 GiB), every case re-fills it.
+The last section runs the serving pool (packed step forms, packed commit, fork; the FP8 pool; the paged pool)."""
 import functools
 import math
 
@@ -41,9 +42,9 @@ def arena16():
     torch.cuda.empty_cache()
 
 
-def _arena(arena16, dtype):
+def _arena(arena16, dtype, sentinel=F.SENTINEL16):
     a = arena16.view(dtype)
-    F.fill_sentinel(a)
+    F.fill_sentinel(a, sentinel)
     return a
 
 
@@ -599,3 +600,660 @@ def test_pool_probe_inputs_far_slot(arena16):
     for a, b in zip(nearb, farb):
         assert torch.equal(a[named], b[named]) and F.is_sentinel(b[[0, 2, 3, 4, 5, 6, 7]])
     F.assert_untouched(arena, list(farb), "pool probe")
+
+
+# ------------------------------------------------------------------------------------------- the serving pool, far
+# The packed serving calls (ragged_step_dyn with admit / parent / commit_seq, commit_packed_dyn, fork_slots) on the
+# contiguous 16-bit and fp32 pool, the FP8 pool and the paged pool.  One script of calls runs on a near pool and on a far
+# one; after EVERY call the output, the path, the state rows and the bytes of every named slot (paged: of every mapped
+# page) are recorded, and the two records must be equal.  Every case asserts from data_ptr() that what it calls far lies
+# at or past its line, and that every storing call changed bytes of every slot it names.  No mutant of a kernel runs
+# here: tests/test_far_views.py proves on the CPU, per case and per operand, that a 32-bit element offset, an unsigned or
+# a signed 32-bit byte offset would move one of these rows onto the sentinel or out of the arena.
+from test_gpu_ragged_tree import _check_rows, _cu, _i32, _oracle_tree          # noqa: E402
+from test_ragged_tree_host import binary, chain, read_as, star                 # noqa: E402
+import paged_ref as PR                                                         # noqa: E402
+from fp8_ref import FP8, dequant                                               # noqa: E402
+
+DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
+NS, WC, PG = 4, 64, 32
+RING = ("window_k", "window_v")
+BUFS = ("sink_k", "sink_v") + RING
+
+
+def _ints(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def _offset(arena, t):
+    """bytes from the arena's first byte to the first byte of t (data_ptr arithmetic on the device tensors)"""
+    return t.data_ptr() - arena.data_ptr()
+
+
+def _pool_layer(W, bufs, S, table=None, scales=None):
+    L = _layer(NS, W, list(bufs), torch.zeros(S, 4, dtype=torch.int32, device=DEV), True, True)
+    if table is not None:
+        L.page_size, L.page_table = bufs[2].shape[2], torch.tensor(table, dtype=torch.int32, device=DEV)
+    if scales is not None:
+        L.kv_scale = torch.ones(2, bufs[0].shape[1], dtype=torch.float32, device=DEV)
+        L.set_kv_scale(*scales)
+    return L
+
+
+def _content(L, named):
+    """bytes of every named slot, cloned: sinks per slot; the ring per slot, or per mapped table entry of a paged pool"""
+    c = {}
+    for name in BUFS:
+        buf = _ints(getattr(L, name))
+        for s in named:
+            if L.page_size and name in RING:
+                for j, e in enumerate(L.page_table[s].tolist()):
+                    if 0 <= e < buf.shape[0]:
+                        c[(name, s, j)] = buf[e].clone()
+            else:
+                c[(name, s)] = buf[s].clone()
+    return c
+
+
+def _play(L, steps, named):
+    rec = [dict(name="start", path=None, o=None, st=L._dev_state.clone(), c=_content(L, named), writes=())]
+    for name, fn, writes in steps:
+        o = fn(L)
+        torch.cuda.synchronize()
+        rec.append(dict(name=name, path=_nat().last_path(), o=None if o is None else o.clone(), st=L._dev_state.clone(),
+                        c=_content(L, named), writes=writes))
+    return rec
+
+
+def _changed(rec, i, s):
+    """did call i of a record change bytes of slot s?"""
+    a, b = rec[i - 1]["c"], rec[i]["c"]
+    return any(k not in a or not torch.equal(a[k], b[k]) for k in b if k[1] == s)
+
+
+def _same_records(near, far, what):
+    assert len(near) == len(far)
+    for i, (a, b) in enumerate(zip(near, far)):
+        w = (what, a["name"])
+        assert a["path"] == b["path"], (w, a["path"], b["path"])                                    # (c)
+        assert torch.equal(a["st"], b["st"]), (w, a["st"].tolist(), b["st"].tolist())               # (b)
+        assert (a["o"] is None) == (b["o"] is None) and (a["o"] is None or torch.equal(a["o"], b["o"])), \
+            (w, "o", None if a["o"] is None else maxdiff(a["o"].float(), b["o"].float()))
+        assert a["c"].keys() == b["c"].keys(), w
+        for k in a["c"]:
+            assert torch.equal(a["c"][k], b["c"][k]), (w, "content of", k)
+        for s in a["writes"]:                       # a storing call moved bytes of every slot it names, in both runs
+            assert _changed(near, i, s) and _changed(far, i, s), (w, "stored nothing into slot", s)
+
+
+def _rows(g, dtype, H, T, D):
+    return rand((1, H, T, D), g, dtype)
+
+
+class _Serving:
+    """The script of the serving sequence over the slots (far, a, b): b is prefilled with 30 tokens (a partly filled
+    ring) and decodes; far is fresh and is admitted with num_sink + Wc + 7 tokens (the ring full, wrapped at slot 0, then
+    moved on by the tree step: write_pos 7); a is fresh and is admitted with 2 < num_sink tokens (a short one).  One
+    sequence of every pack is inactive (-1), every pack has a padded tail.  `hist` replays on the CPU what every slot
+    holds, for the fp64 oracle of every attending call."""
+
+    def __init__(self, dt, D, G, Hkv, W, slots, seed, short=False, place=None):
+        self.dtype, self.D, self.G, self.Hkv, self.W = DT[dt], D, G, Hkv, W
+        self.far, self.a, self.b = slots
+        far, a, b = slots
+        dtype, Hq = self.dtype, G * Hkv
+        g = torch.Generator().manual_seed(seed)
+        self.sa = rand((Hq,), g, torch.float32, 0.5)
+        sad = self.sa.to(DEV)
+        kp, vp = _rows(g, dtype, Hkv, 30, D), _rows(g, dtype, Hkv, 30, D)
+        self.long = NS + W + 7
+        L1, S1 = [3, 40, 2, self.long], [b, -1, a, far]
+        T1 = sum(L1) + 8
+        assert T1 <= 260
+        p1 = [_rows(g, dtype, h, T1, D) for h in (Hq, Hkv, Hkv)]
+        L2, S2 = [7, 16, 1, 3], [far, b, a, -1]
+        T2 = sum(L2) + 5
+        trees = [star(7), binary(16), chain(1), chain(3)]
+        par = sum(trees, []) + [5] * (T2 - sum(L2))
+        seq = [1, 0, 1, 1]                                        # the 16-node tree on b is held back
+        p2 = [_rows(g, dtype, h, T2, D) for h in (Hq, Hkv, Hkv)]
+        path = [6, 9, -2, 3, 0, 1, 2] + [15, 3, 3, 20, 0, -1, 7, 8, 9, 1, 2, 4, 5, 6, 10, 11] + [0] + [2, 1, 0] + [9] * 5
+        cnt_a, cnt_b = [9, -2, 0, 2], [3, 5, 1, 2]                # beyond n_i, negative, zero, an inactive sequence
+        d1, d2 = [t.to(DEV) for t in p1] + [None], [t.to(DEV) for t in p2] + [None]
+        self.views, self.inputs = [], []
+        if place is not None:               # the packs themselves (and their outputs) on views: place(operands, n-th pack)
+            for n, d in enumerate((d1, d2)):
+                vs = place(d[:3] + [tuple(d[0].shape)], n)
+                self.inputs += list(zip(vs[:3], d[:3]))
+                self.views += vs
+                d[:] = vs
+        kpd, vpd = kp.to(DEV), vp.to(DEV)
+
+        def step(L, d, lens, sl, **kw):
+            return L.ragged_step_dyn(d[0], d[1], d[2], _i32(_cu(lens)), _i32(sl), s_aux=sad, out=d[3], **kw)
+
+        def prefill(L):
+            L.prefill_slots(kpd, vpd, [0, 30], [b])
+
+        def commit(L, cnt, pt):
+            L.commit_packed_dyn(d2[1], d2[2], _i32(_cu(L2)), _i32(S2), _i32(cnt), path=None if pt is None else _i32(pt))
+
+        self.steps = [("prefill_slots", prefill, (b,)),
+                      ("admit", lambda L: step(L, d1, L1, S1, admit=True, commit=True), (far, a, b))]
+        self.events = [("store", b, kp, vp), ("attend", "admit", p1, L1, S1, None, True)]
+        self.events += [("store", s, p1[1][:, :, c:c + n], p1[2][:, :, c:c + n])
+                        for s, c, n in zip(S1, _cu(L1), L1) if s >= 0]
+        if not short:
+            self.steps += [("tree", lambda L: step(L, d2, L2, S2, parent=_i32(par), commit_seq=_i32(seq), commit=True), (far, a)),
+                           ("commit_path", lambda L: commit(L, cnt_a, path), (far,)),
+                           ("commit", lambda L: commit(L, cnt_b, None), (far, a, b))]
+            self.events += [("attend", "tree", p2, L2, S2, trees, False)]
+            cu2 = _cu(L2)
+            self.events += [("store", s, p2[1][:, :, c:c + n], p2[2][:, :, c:c + n])
+                            for s, c, n, m in zip(S2, cu2, L2, seq) if s >= 0 and m]
+            for cnt, pt in ((cnt_a, path), (cnt_b, None)):
+                for i, (s, c, n) in enumerate(zip(S2, cu2, L2)):
+                    acc = min(max(cnt[i], 0), n)
+                    if s < 0 or acc == 0:
+                        continue
+                    src = [c + (j if pt is None else min(max(pt[c + j], 0), n - 1)) for j in range(acc)]
+                    self.events.append(("store", s, p2[1][:, :, src], p2[2][:, :, src]))
+        self.plain = lambda L, sl: step(L, d2, L2, sl, commit=False)
+        self.steps.append(("plain", lambda L: self.plain(L, S2), ()))
+        self.events.append(("attend", "plain", p2, L2, S2, None, False))
+        self.short = short
+
+    def check_states(self, rec, what):
+        """the far slot's first committed state, outright: the ring full and wrapped; then write_pos != 0"""
+        by = {r["name"]: r for r in rec}
+        assert by["admit"]["st"][self.far].tolist() == [NS, self.W, 0, self.long], (what, by["admit"]["st"].tolist())
+        assert by["admit"]["st"][self.a].tolist() == [2, 0, 0, 2] and by["admit"]["st"][self.b].tolist() == [NS, 29, 29, 33]
+        if not self.short:
+            assert by["tree"]["st"][self.far].tolist() == [NS, self.W, 7, self.long + 7], (what, by["tree"]["st"].tolist())
+            assert by["commit"]["st"][self.far].tolist() == [NS, self.W, 17, self.long + 17]
+            assert by["commit"]["st"][self.b].tolist() == [NS, 34, 34, 38]
+
+    def check_oracle(self, rec, what):
+        """(a): every attending call of a record against fp64 decode_dense per node over the replayed history"""
+        by = {r["name"]: r for r in rec}
+        hist = {}
+        for ev in self.events:
+            if ev[0] == "store":
+                _, s, k, v = ev
+                if s not in hist:
+                    hist[s] = [k[:, :, :0], v[:, :, :0], min(k.shape[2], NS)]
+                hist[s][0], hist[s][1] = torch.cat([hist[s][0], k], dim=2), torch.cat([hist[s][1], v], dim=2)
+                continue
+            _, name, (q, k, v), lens, sl, trees, admit = ev
+            ref = {}
+            for i, (s, c, n) in enumerate(zip(sl, _cu(lens), lens)):
+                if s < 0 or n == 0:
+                    continue
+                sel = slice(c, c + n)
+                if s not in hist:     # an admission: the mask of a prefill of the chunk alone, its first tokens the sinks
+                    assert admit
+                    rows = []
+                    for u in range(n):
+                        keep = [c + w for w in range(u + 1) if w < min(n, NS) or u - w <= self.W - 1]
+                        rows.append(O.decode_dense(q[:, :, c + u:c + u + 1], k[:, :, keep], v[:, :, keep], self.sa))
+                    ref[i] = torch.cat(rows, dim=2)
+                    continue
+                hk, hv, nsink = hist[s]
+                par = read_as(trees[i], n) if trees is not None else chain(n)
+                ref[i] = _oracle_tree(q[:, :, sel], torch.cat([hk, k[:, :, sel]], dim=2), torch.cat([hv, v[:, :, sel]], dim=2),
+                                      self.sa, hk.shape[2], nsink, self.W, par)
+            assert len(ref) == 3
+            _check_rows(by[name]["o"], ref, lens, TOL[self.dtype], (what, name))
+
+
+# ---- 1. the packed serving forms on far slots of the contiguous pool
+PACKED = [("bf16", 64, 8, 1), ("fp16", 128, 1, 2), ("bf16", 96, 1, 2), ("fp32", 48, 2, 2)]      # dtype, D, G, Hkv
+SLOT_S, SLOT_NAMED = 9, [8, 1, 3]                     # far (fresh, admitted long), a (fresh, short), b (prefilled)
+
+
+def _pool_shapes(S, Hkv, W, D):
+    return [(S, Hkv, NS, D)] * 2 + [(S, Hkv, W, D)] * 2
+
+
+def _far_pool(arena, geom, S, Hkv, W, D, named, sentinel=F.SENTINEL16):
+    bufs = F.views(arena, geom, _pool_shapes(S, Hkv, W, D))
+    for t in bufs:
+        _ints(t)[named] = 0                           # the named slots start as the near pool's: zeros
+    return bufs
+
+
+def _near_pool(S, Hkv, W, D, dtype):
+    return [torch.zeros(s, dtype=torch.uint8 if dtype == FP8 else dtype, device=DEV).view(dtype) for s in _pool_shapes(S, Hkv, W, D)]
+
+
+def _unnamed_keep_the_sentinel(nearb, farb, S, named, sentinel=F.SENTINEL16):
+    rest = [c for c in range(S) if c not in named]
+    for a, b in zip(nearb, farb):
+        assert F.is_sentinel(_ints(b)[rest], sentinel) and not bool(_ints(a)[rest].any())
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", PACKED, ids=[f"{p[0]}-d{p[1]}-g{p[2]}" for p in PACKED])
+def test_packed_serving_calls_far_slot(arena16, dt, D, G, Hkv):
+    """prefill, an admitting committing step, a tree step with commit_seq, commit_packed_dyn with count and path and
+    without a path, a plain step - on a pool whose slot 8 lies at 4 GiB and receives the long admission."""
+    dtype = DT[dt]
+    sv = _Serving(dt, D, G, Hkv, WC, SLOT_NAMED, seed=7700 + D)
+    near = _play(_pool_layer(WC, _near_pool(SLOT_S, Hkv, WC, D, dtype), SLOT_S), sv.steps, SLOT_NAMED)
+    sv.check_states(near, "near")
+    sv.check_oracle(near, (dt, D, G))                                                               # (a)
+    arena = _arena(arena16, dtype)
+    farb = _far_pool(arena, F.far_slot, SLOT_S, Hkv, WC, D, SLOT_NAMED)
+    for t in farb:
+        assert _offset(arena, t[8]) >= F.TWO32 and _offset(arena, t[3, -1, -1]) < F.TWO31
+        assert dtype == torch.float32 or (_offset(arena, t[8]) // t.element_size()) >= F.TWO31
+    far = _play(_pool_layer(WC, farb, SLOT_S), sv.steps, SLOT_NAMED)
+    _same_records(near, far, ("far_slot", dt, D))                                                   # (b), (c)
+    _unnamed_keep_the_sentinel(_near_pool(SLOT_S, Hkv, WC, D, dtype), farb, SLOT_S, SLOT_NAMED)
+    assert "_admit_commit" in far[2]["path"] and "decode_tree_" in far[3]["path"] and \
+        far[4]["path"] == far[5]["path"] == "ring_commit_path_ragged_slots", [r["path"] for r in far]
+    F.assert_untouched(arena, farb, f"packed serving {dt} {D}")                                     # (d)
+
+
+@pytest.mark.parametrize("dt,D", [("bf16", 128), ("fp16", 80), ("fp32", 64)])
+def test_packed_serving_calls_with_the_pack_behind_a_far_head(arena16, dt, D):
+    """q, k_new, v_new and out of every step of the serving script on far_head_skew views (G 1, H_kv 2): head 1 of each
+    lies past 4 GiB, over a near pool.  The library serves the layout (it forms these addresses in 64 bits and documents
+    no limit for them): far == near bitwise, the pool included."""
+    dtype, Hkv, S, named = DT[dt], 2, 4, [2, 1, 3]
+    arena = _arena(arena16, dtype)
+    place = lambda ops, n: F.views(arena[n << 22:], F.far_head_skew, ops)
+    sn_, sf_ = (_Serving(dt, D, 1, Hkv, WC, named, seed=7800 + D, place=pl) for pl in (None, place))
+    for t in sf_.views:
+        assert _offset(arena, t[0, 1]) >= F.TWO32 and _offset(arena, t[0, 0, -1]) < F.TWO31
+        assert dtype == torch.float32 or _offset(arena, t[0, 1]) // 2 >= F.TWO31
+    near = _play(_pool_layer(WC, _near_pool(S, Hkv, WC, D, dtype), S), sn_.steps, named)
+    sn_.check_states(near, "near")
+    sn_.check_oracle(near, ("far-head pack", dt, D))                                                # (a)
+    far = _play(_pool_layer(WC, _near_pool(S, Hkv, WC, D, dtype), S), sf_.steps, named)
+    _same_records(near, far, ("far_head_skew pack", dt, D))                                         # (b), (c)
+    assert far[2]["o"][:, 1].any() and not torch.isnan(far[2]["o"].float()).any()
+    F.assert_untouched(arena, sf_.views, f"far-head pack {dt}", inputs=sf_.inputs)                  # (d)
+
+
+# ---- 2. fork_slots across the 4 GiB line
+FORK = [("bf16", 128, 8, 1), ("fp32", 128, 1, 2)]      # 16 and 32 pieces per row: a full ring spans more than one copy block
+
+
+def _copy_block():
+    """pieces one workgroup of ring_copy_slots_kernel copies: 256 * SFA_COPY_PIECES (csrc/sfa_decode_multi.hip)"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "sink-flash-attention-kernel_amd", "csrc", "sfa_decode_multi.hip")).read()
+    return 256 * int(re.search(r"#define SFA_COPY_PIECES (\d+)", src).group(1))
+
+
+class _Forks:
+    """prefill_slots of a wrapped ring (slot `w`) and a short one (slot `s`), then forks; `step(L, slots)` is a plain step
+    of a [1, 7] pack over two slots, which must give on every pair of forks the bits it gives on the sources."""
+
+    def __init__(self, dt, D, G, Hkv, w, s, seed, W=WC, both_bodies=True):
+        self.dtype, self.w, self.s, self.W = DT[dt], w, s, W
+        dtype, Hq = self.dtype, G * Hkv
+        g = torch.Generator().manual_seed(seed)
+        self.lens = [NS + W + 9, 10]
+        T = sum(self.lens)
+        self.kp, self.vp = _rows(g, dtype, Hkv, T, D), _rows(g, dtype, Hkv, T, D)
+        self.kc, self.vc = _rows(g, dtype, Hkv, 5, D), _rows(g, dtype, Hkv, 5, D)      # 5 more tokens: write_pos 5
+        self.pack = [_rows(g, dtype, h, 8, D) for h in (Hq, Hkv, Hkv)]
+        self.sa = rand((Hq,), g, torch.float32, 0.5)
+        kpd, vpd, sad = self.kp.to(DEV), self.vp.to(DEV), self.sa.to(DEV)
+        d = [t.to(DEV) for t in self.pack]
+        cpr = D * torch.empty((), dtype=dtype).element_size() // 16
+        block = _copy_block()
+        live_w, live_s = (NS + W) * cpr, 10 * cpr
+        # the wrapped source: at least one block whose pieces are all live (the unpredicated body) and a last, partial
+        # one (the predicated body); the short source: less than one block
+        assert not both_bodies or (live_w // block >= 1 and live_w % block and live_s < block), (live_w, live_s, block)
+
+        def prefill(L):
+            L.prefill_slots(kpd, vpd, _cu(self.lens), [w, s])
+            L.commit_packed_dyn(self.kc.to(DEV), self.vc.to(DEV), [0, 5], [w], [5])
+        self.prefill = ("prefill_slots", prefill, (w, s))
+        self.step = lambda L, slots: L.ragged_step_dyn(d[0], d[1], d[2], [0, 1, 8], slots, s_aux=sad, commit=False)
+
+    def fork(self, src, dst, writes, partner=False):
+        return (f"fork {src} -> {dst}", lambda L: L.fork_slots(src, dst, source=L.partner if partner else None), writes)
+
+    def over(self, slots):
+        return (f"step {slots}", lambda L: self.step(L, slots), ())
+
+    def check_oracle(self, o, what):
+        ref, cu = {}, _cu(self.lens)
+        q, k, v = self.pack
+        for i, (c, n) in enumerate(((0, 1), (1, 7))):
+            hk, hv = self.kp[:, :, cu[i]:cu[i + 1]], self.vp[:, :, cu[i]:cu[i + 1]]
+            if i == 0:
+                hk, hv = torch.cat([hk, self.kc], 2), torch.cat([hv, self.vc], 2)
+            ref[i] = _oracle_tree(q[:, :, c:c + n], torch.cat([hk, k[:, :, c:c + n]], 2), torch.cat([hv, v[:, :, c:c + n]], 2),
+                                  self.sa, hk.shape[2], NS, self.W, chain(n))
+        _check_rows(o, ref, [1, 7], TOL[self.dtype], what)
+
+
+def _steps_equal(rec, names, what):
+    outs = [r["o"] for r in rec if r["name"] in names]
+    assert len(outs) == len(names) and all(torch.equal(outs[0], o) for o in outs[1:]), (what, names)
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", FORK, ids=[f"{p[0]}-d{p[1]}" for p in FORK])
+def test_fork_slots_across_the_4_gib_line(arena16, dt, D, G, Hkv):
+    """near -> far (1 -> 8), far -> near (8 -> 2), a short ring (3 -> 5), a self pair and an inactive pair in one call;
+    then source= between a pool of near tensors and the pool of arena views, in both directions."""
+    dtype, S, named = DT[dt], SLOT_S, [1, 3, 8, 5, 2]
+    fk = _Forks(dt, D, G, Hkv, 1, 3, seed=7900 + D)
+    steps = [fk.prefill, fk.fork([1, 3, 4, -1], [8, 5, 4, 6], (8, 5)), fk.fork([8], [2], (2,)),
+             fk.over([1, 3]), fk.over([8, 5]), fk.over([2, 5])]
+    nearb = _near_pool(S, Hkv, WC, D, dtype)
+    Ln = _pool_layer(WC, nearb, S)
+    near = _play(Ln, steps, named)
+    fk.check_oracle(near[4]["o"], ("fork sources", dt, D))                                          # (a)
+    _steps_equal(near, ["step [1, 3]", "step [8, 5]", "step [2, 5]"], "near")
+    arena = _arena(arena16, dtype)
+    farb = _far_pool(arena, F.far_slot, S, Hkv, WC, D, named)
+    for t in farb:
+        assert _offset(arena, t[8]) >= F.TWO32 and _offset(arena, t[5, -1, -1]) < F.TWO32 and _offset(arena, t[3, -1, -1]) < F.TWO31
+    Lf = _pool_layer(WC, farb, S)
+    far = _play(Lf, steps, named)
+    _same_records(near, far, ("fork", dt, D))                                                       # (b), (c)
+    _steps_equal(far, ["step [1, 3]", "step [8, 5]", "step [2, 5]"], "far")
+    assert far[2]["path"] == "ring_copy_slots" and far[2]["st"][8].tolist() == [NS, WC, 5, NS + WC + 14]
+    assert not far[3]["st"][[0, 4, 6, 7]].any()                      # the self pair and the inactive pair moved nothing
+    _unnamed_keep_the_sentinel(nearb, farb, S, named)
+    # source=: out of each pool into a fresh pool of near tensors, and from there back into slots 7 and 8
+    named2 = named + [7]
+    for t in farb:
+        _ints(t)[7] = 0
+    recs = []
+    for L in (Ln, Lf):
+        Z = _pool_layer(WC, _near_pool(S, Hkv, WC, D, dtype), S)
+        Z.partner, L.partner = L, Z
+        rz = _play(Z, [fk.fork([8, 3], [0, 6], (0, 6), partner=True), fk.over([0, 6])], [0, 6])
+        rl = _play(L, [fk.fork([6, 0], [8, 7], (8, 7), partner=True), fk.over([7, 8]), fk.over([1, 3])], named2)
+        recs.append((rz, rl))
+    (rzn, rln), (rzf, rlf) = recs
+    _same_records(rzn, rzf, ("fork out of the pool", dt, D))
+    _same_records(rln, rlf, ("fork into the pool", dt, D))
+    assert torch.equal(rzf[2]["o"], far[4]["o"]) and torch.equal(rlf[2]["o"], rlf[3]["o"]) and torch.equal(rlf[3]["o"], far[4]["o"])
+    assert rlf[1]["st"][8].tolist() == [NS, 6, 6, 10] and rlf[1]["st"][7].tolist() == [NS, WC, 5, NS + WC + 14]
+    _unnamed_keep_the_sentinel(nearb, farb, S, named2)
+    F.assert_untouched(arena, farb, f"fork {dt}")                                                   # (d)
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", FORK, ids=[f"{p[0]}-d{p[1]}" for p in FORK])
+def test_fork_slots_far_to_far(arena16, dt, D, G, Hkv):
+    """far_slot2: 35 slots of which 33 and 34 both lie past 4 GiB; the wrapped ring of 33 is forked into 34."""
+    dtype, S, named = DT[dt], 35, [33, 1, 34, 2]
+    fk = _Forks(dt, D, G, Hkv, 33, 1, seed=7950 + D)
+    steps = [fk.prefill, fk.fork([33, 1], [34, 2], (34, 2)), fk.over([33, 1]), fk.over([34, 2])]
+    nearb = _near_pool(S, Hkv, WC, D, dtype)
+    near = _play(_pool_layer(WC, nearb, S), steps, named)
+    fk.check_oracle(near[3]["o"], ("far to far, sources", dt, D))
+    arena = _arena(arena16, dtype)
+    farb = _far_pool(arena, F.far_slot2, S, Hkv, WC, D, named)
+    for t in farb:
+        assert _offset(arena, t[33]) >= F.TWO32 and _offset(arena, t[34]) >= F.TWO32 and _offset(arena, t[2, -1, -1]) < F.TWO31
+    far = _play(_pool_layer(WC, farb, S), steps, named)
+    _same_records(near, far, ("far to far", dt, D))
+    _steps_equal(far, ["step [33, 1]", "step [34, 2]"], "far")
+    _unnamed_keep_the_sentinel(nearb, farb, S, named)
+    F.assert_untouched(arena, farb, f"fork far to far {dt}")
+
+
+# ---- 3. the FP8 pool: one byte per element, slot 8 at element and byte 2^32, slots 4 .. 7 in [2^31, 2^32)
+from test_gpu_fp8_pool import _row, _snap as _snap8, _stored as _stored8       # noqa: E402
+
+FP8_CASES = [("bf16", 64, 8, 1), ("fp16", 128, 1, 2), ("fp16", 80, 1, 2)]
+FP8_NAMED = [8, 1, 5, 2, 6]           # far (2^32), a (near), b (the band); the forks' destinations: near, the band
+
+
+def _play_fp8(p8, p16, steps, named, scales, dtype):
+    """The near run of an FP8 script with its two contracts (tests/fp8_ref.py) checked at every call: a 16-bit twin pool
+    p16 takes the same calls - every row a call stores is quant(the twin's row), the state rows are equal; and o is bit
+    for bit o of the same call on a 16-bit pool that holds dequant(codes)."""
+    rec = [dict(name="start", path=None, o=None, st=p8._dev_state.clone(), c=_content(p8, named), writes=())]
+    S, W = p8._dev_state.shape[0], p8.window_size
+    for name, fn, writes in steps:
+        s8, s16 = _snap8(p8), _snap8(p16)
+        pd = _pool_layer(W, [dequant(getattr(p8, n).cpu(), _row(scales, n), dtype).to(DEV) for n in BUFS], S)
+        pd._dev_state.copy_(p8._dev_state)
+        o8 = fn(p8)
+        path = _nat().last_path()
+        fn(p16)
+        od = fn(pd)
+        if o8 is not None:
+            assert path.endswith("_kvfp8") and _nat().last_path() == path[:-len("_kvfp8")], (name, path, _nat().last_path())
+            assert torch.equal(o8, od), (name, "o differs from the 16-bit step over the dequantised codes", maxdiff(o8, od))
+            assert not torch.isnan(o8.float()).any() and o8.any()
+        if writes:
+            assert _stored8(p8, p16, s8, s16, scales, name) > 0, name
+        rec.append(dict(name=name, path=path, o=None if o8 is None else o8.clone(), st=p8._dev_state.clone(),
+                        c=_content(p8, named), writes=writes))
+    return rec
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", FP8_CASES, ids=[f"{p[0]}-d{p[1]}-g{p[2]}" for p in FP8_CASES])
+def test_fp8_pool_serving_calls_far_slot(arena16, dt, D, G, Hkv):
+    dtype, S = DT[dt], SLOT_S
+    scales = ([0.37, 2.0][:Hkv], [0.25, 1.0][:Hkv])
+    sv = _Serving(dt, D, G, Hkv, WC, FP8_NAMED[:3], seed=8000 + D)
+    steps = sv.steps[:-1] + [("fork", lambda L: L.fork_slots([8, 1], [2, 6]), (2, 6)), sv.steps[-1]]
+    p8 = _pool_layer(WC, _near_pool(S, Hkv, WC, D, FP8), S, scales=scales)
+    p16 = _pool_layer(WC, _near_pool(S, Hkv, WC, D, dtype), S)
+    near = _play_fp8(p8, p16, steps, FP8_NAMED, scales, dtype)                                      # (a): both contracts
+    sv.check_states(near, "near")
+    arena = _arena(arena16, FP8, F.SENTINEL8)
+    assert bool((arena.view(torch.uint8)[:: 1 << 20] == 0x7F).all())
+    farb = _far_pool(arena, F.far_slot, S, Hkv, WC, D, FP8_NAMED)
+    for t in farb:
+        assert _offset(arena, t[8]) >= F.TWO32 and _offset(arena, t[2, -1, -1]) < F.TWO31
+        assert all(F.TWO31 <= _offset(arena, t[s]) and _offset(arena, t[s, -1, -1]) < F.TWO32 for s in (5, 6))
+    far = _play(_pool_layer(WC, farb, S, scales=scales), steps, FP8_NAMED)
+    _same_records(near, far, ("fp8 far_slot", dt, D))                                               # (b), (c)
+    assert far[2]["path"].endswith("_ragged_admit_commit_kvfp8") and far[4]["path"] == "ring_commit_path_ragged_slots_kvfp8", \
+        [r["path"] for r in far]
+    # a step over the forks (2 <- 8, 6 <- 1) is the plain step over their sources, in the far pool
+    Lf = _pool_layer(WC, farb, S, scales=scales)
+    Lf._dev_state.copy_(far[-1]["st"])
+    o_forks = sv.plain(Lf, [2, 5, 6, -1])
+    assert torch.equal(o_forks, far[-1]["o"])
+    _unnamed_keep_the_sentinel(_near_pool(S, Hkv, WC, D, FP8), farb, S, FP8_NAMED, F.SENTINEL8)
+    F.assert_untouched(arena, farb, f"fp8 {dt} {D}", sentinel=F.SENTINEL8)                          # (d)
+
+
+# ---- 4. the paged pool: far pages behind the table
+PAGED = [("bf16", 128, 1, 2), ("fp16", 80, 8, 2)]
+WP = 96                               # three table entries per slot: one page of every class (deal_pages)
+
+
+def _near_paged(S, Hkv, W, D, dtype, table, n_pages):
+    """init_pool(page_size=32, num_pages=n_pages) with `table`; every page row holds the sentinel (NaN), as the arena's do"""
+    from sink_attention.cache import SinkCacheLayer
+    L = SinkCacheLayer(NS, W)
+    L.init_pool(S, Hkv, D, dtype, DEV, page_size=PG, num_pages=n_pages)
+    L.page_table.copy_(torch.tensor(table, dtype=torch.int32))
+    for name in RING:
+        getattr(L, name).copy_(F.sentinel_full(getattr(L, name).shape, dtype, DEV))
+    return L
+
+
+def _far_paged(S, Hkv, W, D, dtype, table, pages):
+    sinks = [torch.zeros(S, Hkv, NS, D, dtype=dtype, device=DEV) for _ in range(2)]
+    return _pool_layer(W, sinks + list(pages), S, table=table)
+
+
+def _rank_table(tab):
+    """the table with every page index replaced by its rank among the mapped ones, and their number"""
+    pages = sorted(e for r in tab for e in r if e >= 0)
+    return [[pages.index(e) if e >= 0 else e for e in r] for r in tab], len(pages)
+
+
+def _contig_twin(L):
+    """the contiguous twin of a paged pool (tests/paged_ref.py::gather), built before any call"""
+    S, Hkv, _, D = L.sink_k.shape
+    ring = [PR.gather(getattr(L, name), L.page_table.cpu()) for name in RING]
+    tw = _pool_layer(L.window_size, [L.sink_k.clone(), L.sink_v.clone()] + ring, S)
+    tw._dev_state.copy_(L._dev_state)
+    return tw
+
+
+def _paged_is_the_twin(rp, rt, what):
+    """record of a paged run against the record of the same script on its contiguous twin: bitwise"""
+    for a, b in zip(rp, rt):
+        w = (what, a["name"])
+        if a["path"] is not None:
+            assert a["path"].endswith("_paged") and b["path"] == a["path"][:-len("_paged")], (w, a["path"], b["path"])
+        assert torch.equal(a["st"], b["st"]), w
+        assert a["o"] is None or torch.equal(a["o"], b["o"]), (w, "o")
+        for k, x in a["c"].items():
+            y = b["c"][k[:2]]
+            assert torch.equal(x, y if len(k) == 2 else y[:, k[2] * PG:(k[2] + 1) * PG]), (w, k)
+
+
+def _mapped_views(pages, tab):
+    return [buf[e] for buf in pages for r in tab for e in r if 0 <= e < buf.shape[0]]
+
+
+def _page_views(arena, pp, Hkv, D):
+    return [F.far_view(arena, sp.shape, sp.strides, sp.offset) for sp in pp.specs(Hkv, PG, D)]
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", PAGED, ids=[f"{p[0]}-d{p[1]}-g{p[2]}" for p in PAGED])
+def test_paged_pool_on_one_large_page_buffer(arena16, dt, D, G, Hkv):
+    """The production layout: the whole arena is one K / V page buffer (far_views.page_pool), the table of the three
+    named slots holds pages on both sides of 2^31 bytes, of 2^31 elements and of 2^32 bytes, every other page keeps the
+    sentinel.  The far run equals the near twin (init_pool, ranks in the table) and the contiguous twin of gather()."""
+    dtype, S, named = DT[dt], 4, [3, 1, 2]
+    arena = _arena(arena16, dtype)
+    pp = F.page_pool(arena.numel(), Hkv * PG * D, arena.element_size())
+    tab = [[-1] * (WP // PG) for _ in range(S)]
+    for s, row in zip(named, F.deal_pages(pp.picks, 3, WP // PG, pp.p31, pp.p32)):
+        tab[s] = row
+    sv = _Serving(dt, D, G, Hkv, WP, named, seed=8100 + D)
+    rtab, n_map = _rank_table(tab)
+    Ln = _near_paged(S, Hkv, WP, D, dtype, rtab, n_map + 2)
+    tw = _contig_twin(Ln)
+    near = _play(Ln, sv.steps, named)
+    sv.check_states(near, "near")
+    sv.check_oracle(near, ("paged", dt, D))                                                         # (a)
+    twin = _play(tw, sv.steps, named)
+    pages = _page_views(arena, pp, Hkv, D)
+    for s in named:
+        hi, lo, mid = tab[s]
+        for buf in pages:
+            assert _offset(arena, buf[hi]) >= F.TWO32 and _offset(arena, buf[hi]) // arena.element_size() >= F.TWO31
+        assert _offset(arena, pages[0][lo]) < F.TWO31 <= _offset(arena, pages[0][mid]) < F.TWO32    # (a page may straddle its line)
+    assert pp.n_pages - 1 in tab[2] and 0 in tab[2]
+    for v in _mapped_views(pages, tab):           # every row of a mapped page is NaN until a call stores into it
+        assert bool(torch.isnan(v.float()).all())
+    far = _play(_far_paged(S, Hkv, WP, D, dtype, tab, pages), sv.steps, named)
+    _same_records(near, far, ("paged far pages", dt, D))                                            # (b), (c)
+    _paged_is_the_twin(far, twin, ("paged far pages", dt, D))
+    for k in far[-1]["c"]:            # every page of the long admission's slot and the first page of every slot was stored into
+        if k[0] in RING and (k[1] == named[0] or k[2] == 0):
+            assert not torch.equal(far[0]["c"][k], far[-1]["c"][k]), ("never written", k)
+    F.assert_untouched(arena, _mapped_views(pages, tab), f"paged {dt} {D}")                         # (d)
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", PAGED[:1], ids=["bf16-d128"])
+def test_paged_pool_small_entries_times_a_huge_page_stride(arena16, dt, D, G, Hkv):
+    """The other factor large: 9 pages on the far_slot geometry, page 8 at 4 GiB."""
+    dtype, S, named = DT[dt], 3, [0, 1, 2]
+    tab = [[8, 1], [3, 7], [5, 2]]
+    sv = _Serving(dt, D, G, Hkv, WC, named, seed=8200 + D, short=True)
+    Ln = _near_paged(S, Hkv, WC, D, dtype, tab, 9)
+    tw = _contig_twin(Ln)
+    near = _play(Ln, sv.steps, named)
+    sv.check_states(near, "near")
+    sv.check_oracle(near, ("paged far_slot", dt, D))
+    twin = _play(tw, sv.steps, named)
+    arena = _arena(arena16, dtype)
+    pages = F.views(arena, F.far_slot, [(9, Hkv, PG, D)] * 2)
+    for buf in pages:
+        assert _offset(arena, buf[8]) >= F.TWO32 and _offset(arena, buf[7]) < F.TWO32 and buf.stride(0) * 2 >= 1 << 29
+    far = _play(_far_paged(S, Hkv, WC, D, dtype, tab, pages), sv.steps, named)
+    _same_records(near, far, ("paged far_slot", dt, D))
+    _paged_is_the_twin(far, twin, ("paged far_slot", dt, D))
+    assert not torch.equal(far[0]["c"][("window_k", 0, 0)], far[-1]["c"][("window_k", 0, 0)])      # page 8
+    assert F.is_sentinel(pages[0][[0, 4, 6]]) and F.is_sentinel(pages[1][[0, 4, 6]])
+    F.assert_untouched(arena, _mapped_views(pages, tab), f"paged far_slot {dt}")
+
+
+@pytest.mark.parametrize("dt,D,G,Hkv", PAGED, ids=[f"{p[0]}-d{p[1]}-g{p[2]}" for p in PAGED])
+def test_fork_slots_between_paged_pools_and_across_the_lines(arena16, dt, D, G, Hkv):
+    """Inside the large pool from a slot whose pages all lie below 2^31 bytes to one whose pages all lie past 2^32; out
+    of it into an ordinary paged pool and from there back into pages of the band.  The destinations are mapped first."""
+    dtype, S = DT[dt], 4
+    arena = _arena(arena16, dtype)
+    pp = F.page_pool(arena.numel(), Hkv * PG * D, arena.element_size())
+    lo, mid, hi = ([p for p in pp.picks if a <= p < b] for a, b in ((0, pp.p31), (pp.p31, pp.p32), (pp.p32, pp.n_pages)))
+    tab = [[lo[1], lo[2], lo[0]], [hi[2], hi[0], hi[1]], [mid[2], mid[0], mid[1]], [-1, -1, -1]]
+    tab_n = [[-1, -1, -1], [5, 0, 3], [2, 4, 1], [-1, -1, -1]]
+    fk = _Forks(dt, D, G, Hkv, 0, 2, seed=8300 + D, W=WP, both_bodies=False)
+    steps = [fk.prefill, fk.fork([0], [1], (1,)), fk.over([0, 2]), fk.over([1, 2])]
+    steps_n = [fk.fork([1, 2], [1, 2], (1, 2), partner=True), fk.over([1, 2])]
+    steps_back = [fk.fork([1], [2], (2,), partner=True), fk.over([2, -1]), fk.over([0, -1])]
+    pages = _page_views(arena, pp, Hkv, D)
+    assert all(_offset(arena, pages[0][e]) < F.TWO31 for e in tab[0])        # (the page under a line may straddle it)
+    assert all(_offset(arena, buf[e]) >= F.TWO32 for e in tab[1] for buf in pages)
+    assert all(F.TWO31 <= _offset(arena, pages[0][e]) < F.TWO32 for e in tab[2])
+    rtab, n_map = _rank_table(tab)
+    recs = []
+    for A in (_near_paged(S, Hkv, WP, D, dtype, rtab, n_map + 2), _far_paged(S, Hkv, WP, D, dtype, tab, pages)):
+        N = _near_paged(S, Hkv, WP, D, dtype, tab_n, 6)
+        A.partner, N.partner = N, A
+        recs.append((_play(A, steps, [0, 1, 2]), _play(N, steps_n, [1, 2]), _play(A, steps_back, [0, 1, 2])))
+    (a1, n1, b1), (a2, n2, b2) = recs
+    fk.check_oracle(a1[3]["o"], ("paged fork sources", dt, D))
+    for x, y, what in ((a1, a2, "inside the pool"), (n1, n2, "out of the pool"), (b1, b2, "back into the pool")):
+        _same_records(x, y, ("paged fork", what, dt, D))
+    assert a2[2]["path"] == "ring_copy_slots_paged" and a2[2]["st"][1].tolist() == [NS, WP, 5, NS + WP + 14]
+    assert torch.equal(a2[3]["o"], a2[4]["o"]) and torch.equal(n2[2]["o"], a2[3]["o"])             # forks step as their sources
+    assert torch.equal(b2[2]["o"], b2[3]["o"])
+    F.assert_untouched(arena, _mapped_views(pages, tab), f"paged fork {dt} {D}")
+
+
+def test_a_store_to_an_unmapped_entry_of_the_far_pool_is_dropped(arena16):
+    """Entries -1 and n_pages in the row of a slot of the large pool: 40 tokens whose ring slots lie on them are dropped,
+    the state row advances, no word of the arena changes (n_pages times the page stride is an address inside the arena's
+    last pages' neighbourhood, so only the arena check tells a dropped store from a misplaced one); the next tokens reach
+    the third, mapped entry."""
+    dt, D, G, Hkv, S = "bf16", 128, 1, 2, 2
+    dtype = DT[dt]
+    arena = _arena(arena16, dtype)
+    pp = F.page_pool(arena.numel(), Hkv * PG * D, 2)
+    row = F.deal_pages(pp.picks, 3, WP // PG, pp.p31, pp.p32)[0]
+    tab = [row, [-1, -1, -1]]
+    g = torch.Generator().manual_seed(8400)
+    kp, vp = (_rows(g, dtype, Hkv, NS + WP, D).to(DEV) for _ in range(2))
+    kc, vc = (_rows(g, dtype, Hkv, 40, D).to(DEV) for _ in range(2))
+
+    def prefill(L):
+        L.prefill_slots(kp, vp, [0, NS + WP], [0])
+
+    def unmap(L):
+        L.page_table[0, 0], L.page_table[0, 1] = -1, L.window_k.shape[0]
+
+    commit = lambda n: lambda L: L.commit_packed_dyn(kc[:, :, :n], vc[:, :, :n], [0, n], [0], [n])
+    steps = [("prefill_slots", prefill, (0,)), ("unmap", unmap, ()), ("commit 40", commit(40), ()), ("commit 30", commit(30), (0,))]
+    rtab, n_map = _rank_table(tab)
+    near = _play(_near_paged(S, Hkv, WP, D, dtype, rtab, n_map + 2), steps, [0])
+    pages = _page_views(arena, pp, Hkv, D)
+    assert _offset(arena, pages[0][row[0]]) >= F.TWO32
+    Lf = _far_paged(S, Hkv, WP, D, dtype, tab, pages)
+    far = _play(Lf, steps[:2], [0])
+    kept = [(buf, e, buf[e].clone()) for buf in pages for e in row[:2]]
+    far += _play(Lf, steps[2:], [0])[1:]
+    _same_records(near, far, "unmapped entries")
+    assert Lf.page_table[0].tolist() == [-1, pp.n_pages, row[2]]
+    assert far[3]["st"][0].tolist() == [NS, WP, 40, NS + WP + 40] and far[4]["st"][0].tolist() == [NS, WP, 70, NS + WP + 70]
+    assert far[3]["path"] == "ring_commit_path_ragged_slots_paged"
+    for buf, e, t in kept:
+        assert torch.equal(t, buf[e]), ("a dropped store reached page", e)
+    changed = (far[4]["c"][("window_k", 0, 2)] != far[2]["c"][("window_k", 0, 2)]).any(dim=-1)
+    assert changed[:, :6].all() and not changed[:, 6:].any()          # ring slots 64 .. 69: rows 0 .. 5 of the third page
+    F.assert_untouched(arena, _mapped_views(pages, tab), "unmapped entries")
