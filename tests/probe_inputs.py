@@ -40,6 +40,10 @@ Amplitude (tests/test_probe_inputs.py::test_amplitude_is_the_smallest_power_of_t
 power of two for which every mask mutant exceeds the O and dQ tolerances tenfold (smallest factor measured at a = 2: dQ 12.3,
 O 41; at a = 1 and D = 64: 9.0).  Largest scaled logit: a * sqrt(D) = 11.3 / 16 / 17.9 / 19.6 / 22.6 / 32 on a single row at
 D = 32 / 64 / 80 / 96 / 128 / 256, and a * (D + c . c') / sqrt(D), about a * (sqrt(D) + 4) at most, on a pair row.
+
+The single-token decode probes (decode_probe, DECODE_KINDS, at the end of the file) are the same idea over the sink buffer
+and the ring as the fused step reads them: one query per (batch, q head), the edges of the step's key set and of its split
+plan (tests/decode_regime.py), s_aux at the target's logit; tests/test_decode_probes.py holds their CPU proofs.
 """
 import torch
 
@@ -56,7 +60,8 @@ PAIR_OFFSETS_EDGE = 256  # ... and p - 2 .. p - 257 for the last row of a 256-ro
                          # is caught by a handful of rows, each of which has to clear the factor on its own
 
 # head dim -> amplitude (power of two, exact in every dtype)
-AMPLITUDE = {32: 2.0, 40: 2.0, 48: 2.0, 64: 2.0, 80: 2.0, 96: 2.0, 128: 2.0, 256: 2.0}
+AMPLITUDE = {32: 2.0, 40: 2.0, 48: 2.0, 64: 2.0, 80: 2.0, 96: 2.0, 128: 2.0, 256: 2.0,
+             16: 4.0}   # D = 16 (the decode probes only): a sqrt(D) = 16 as at D = 64; a = 2 leaves the target below the other keys' sum
 
 
 def amplitude(D):
@@ -447,3 +452,213 @@ def ragged_case_probes():
     c = RAGGED_CASE
     return [chunk_probe(1, c["Hq"], c["Hkv"], c["D"], c["ns"], c["W"], L, c["n"], _DT[c["dtype"]], 5000 + b)
             for b, L in enumerate(c["lengths"])]
+
+
+# ------------------------------------------------------------------------------------------------ single-token decode
+# One query per (batch, q head) over the sink buffer + ring, aimed at ONE key on an edge of what the step may read
+# (tests/decode_regime.py names the splits; tests/test_decode_probes.py proves on the CPU that every mutant of the key set
+# moves these inputs by ten tolerances).  EVERY row of the four cache buffers holds a +-1 code and a randn value, live or
+# not, so the rows beyond the fill and beyond sink_len are planted by construction, and so is the evicted token (the old
+# bytes of the slot the step overwrites).  s_aux[h] sits at the target's logit a sqrt(D) (+ 0.25 randn): the target of a
+# must-see row holds about half of the softmax mass, so counting it twice moves the row by about |v| / 6, dropping it by
+# |v| / 2; a must-not-see row is about zero and moves by |v| / 2 when its target is read.
+#   kind          target (key index in the kernel's order: sink rows, then ring slots)           must
+#   newest        the token being decoded, N1 + write_pos, read from k_new in the fused step     see
+#   evicted       the OLD content of slot write_pos of a full ring                               not
+#   ring_oldest   slot write_pos + 1 of a full ring                                              see
+#   sink_last     sink row sink_len - 1                                                          see
+#   beyond_fill   ring row window_len + 1 (one past the live rows after the step), ring not full not
+#   beyond_sink   sink row sink_len < num_sink                                                   not
+#   split_first   key k_beg of a split s >= 1                                                    see
+#   split_last    key k_end - 1 of a split s >= 1                                                see
+#   last_key      key N_kv - 1, the one the clamped tail loads repeat                            see, once
+DECODE_KINDS = ("newest", "evicted", "ring_oldest", "sink_last", "beyond_fill", "beyond_sink", "split_first", "split_last",
+                "last_key")
+DECODE_MUST_SEE = {"newest": True, "evicted": False, "ring_oldest": True, "sink_last": True, "beyond_fill": False,
+                   "beyond_sink": False, "split_first": True, "split_last": True, "last_key": True}
+DECODE_AUX_JITTER = 0.25
+
+
+def decode_cache(B, Hkv, D, ns, Wc, dtype, seed):
+    """the four cache buffers, every row written: K rows are codes, V rows randn"""
+    g = torch.Generator().manual_seed(seed)
+    return dict(sink_k=codes((B, Hkv, ns, D), g, dtype), sink_v=_rand((B, Hkv, ns, D), g, dtype),
+                window_k=codes((B, Hkv, Wc, D), g, dtype), window_v=_rand((B, Hkv, Wc, D), g, dtype))
+
+
+def _key_loc(j, N1, slot):
+    return ("sink", j) if j < N1 else ("new", 0) if j - N1 == slot else ("ring", j - N1)
+
+
+def probe_splits(row):
+    """the splits s >= 1 of one regime row that hold keys, in the order the probes take them: the last one (index >= 64 on
+    the many-split grids), one in [32, 64), split 1, then the others"""
+    live = [s for s in range(1, len(row["n_keys"])) if row["n_keys"][s] > 0]
+    mid = [s for s in live if 32 <= s < 64]
+    pref = live[-1:] + ([40] if 40 in mid else mid[:1]) + live[:1]
+    return list(dict.fromkeys(pref + live))
+
+
+def decode_kinds(state, ns, Wc, row):
+    """{kind: [locations]} of one batch row: state = (sink_len, window_len, write_pos) BEFORE the step, row = its entry of
+    decode_regime.regime(step=True).  A location is ("sink", r), ("ring", slot) - the bytes in the buffer before the step -
+    or ("new", 0): k_new / v_new."""
+    sl, wl, wp = state
+    N1, Nkv = row["N1"], row["Nkv"]
+    out = {k: [] for k in DECODE_KINDS}
+    out["newest"] = [("new", 0)]
+    if wl == Wc:
+        out["evicted"] = [("ring", wp)]
+        if Wc >= 2:
+            out["ring_oldest"] = [("ring", (wp + 1) % Wc)]
+    if sl >= 1:
+        out["sink_last"] = [("sink", sl - 1)]
+    if wl + 1 < Wc:
+        out["beyond_fill"] = [("ring", wl + 1)]
+    if sl < ns:
+        out["beyond_sink"] = [("sink", sl)]
+    pref = probe_splits(row)
+    for s, s2 in zip(pref, pref[1:] + pref[:1]):          # (split_last starts one further: the last split may hold one key)
+        out["split_first"].append(_key_loc(row["k_beg"][s], N1, wp))
+        out["split_last"].append(_key_loc(row["k_beg"][s2] + row["n_keys"][s2] - 1, N1, wp))
+    out["last_key"] = [_key_loc(Nkv - 1, N1, wp)]
+    return out
+
+
+def decode_probe(cache, states, Hq, rows, seed, rot=0, a=None):
+    """q / k_new / v_new / s_aux of one fused step over `cache` (decode_cache, or a twin that earlier steps advanced) at the
+    per-row `states`; rows: decode_regime.regime(...)[1].  The heads of a GQA group take consecutive kinds of the row's
+    list (which the (batch, q head) pairs walk on from `rot`), so every head of a group aims at another key as long as the row has as
+    many kinds as the group has heads; further heads take split_first / split_last of further splits where the row has
+    them.  Returns q [B,Hq,1,D], k_new / v_new [B,Hkv,1,D], s_aux [Hq] f32, kind [B,Hq] (index into DECODE_KINDS),
+    loc[b][h] (the target's location), a."""
+    B, Hkv, ns, D = cache["sink_k"].shape
+    Wc = cache["window_k"].shape[2]
+    dtype = cache["sink_k"].dtype
+    a = amplitude(D) if a is None else a
+    g = torch.Generator().manual_seed(seed)
+    k_new, v_new = codes((B, Hkv, 1, D), g, dtype), _rand((B, Hkv, 1, D), g, dtype)
+    s_aux = a * D ** 0.5 + DECODE_AUX_JITTER * torch.randn(Hq, generator=g, dtype=torch.float32)
+    grp = Hq // Hkv
+    q = torch.zeros(B, Hq, 1, D)
+    kind = torch.zeros(B, Hq, dtype=torch.long)
+    loc = [[None] * Hq for _ in range(B)]
+    for b in range(B):
+        cand = decode_kinds(states[b], ns, Wc, rows[b])
+        names = [k for k in DECODE_KINDS if cand[k]]
+        split_kinds = [k for k in ("split_first", "split_last") if cand[k]]
+        used = {k: 0 for k in names}
+        for hk in range(Hkv):
+            r0 = (hk * grp + b * Hq + rot) % len(names)
+            seq = names[r0:] + names[:r0]
+            for i in range(grp):
+                name = seq[i] if i < len(seq) else (split_kinds[i % 2] if split_kinds else seq[i % len(seq)])
+                where = cand[name][used[name] % len(cand[name])]
+                used[name] += 1
+                h = hk * grp + i
+                src = {"sink": cache["sink_k"], "ring": cache["window_k"], "new": k_new}[where[0]]
+                q[b, h, 0] = a * src[b, hk, where[1]].float()
+                kind[b, h], loc[b][h] = DECODE_KINDS.index(name), where
+    return dict(q=q.to(dtype), k_new=k_new, v_new=v_new, s_aux=s_aux, kind=kind, loc=loc, a=a)
+
+
+def decode_kept(cache, state, b, k_new=None, v_new=None):
+    """K, V [Hkv, N_kv, D] of batch row b in the kernel's key order - sink rows [0, sink_len), then ring slots [0,
+    window_len after the step) with slot write_pos taken from k_new / v_new - and the rows a step must NOT read:
+    extras = {"evicted" / "beyond_fill" / "beyond_sink": (K, V) [Hkv, 1, D]} where they exist.  k_new None: no step, the
+    keys of the state as it is."""
+    sl, wl, wp = state
+    Wc = cache["window_k"].shape[2]
+    ns = cache["sink_k"].shape[2]
+    step = k_new is not None
+    wl1 = min(wl + 1, Wc) if step else wl
+    rk, rv = cache["window_k"][b, :, :wl1].clone(), cache["window_v"][b, :, :wl1].clone()
+    extras = {}
+    if step:
+        if wl == Wc:
+            extras["evicted"] = (rk[:, wp:wp + 1].clone(), rv[:, wp:wp + 1].clone())
+        rk[:, wp], rv[:, wp] = k_new[b, :, 0], v_new[b, :, 0]
+        if wl + 1 < Wc:
+            extras["beyond_fill"] = (cache["window_k"][b, :, wl + 1:wl + 2], cache["window_v"][b, :, wl + 1:wl + 2])
+    if sl < ns:
+        extras["beyond_sink"] = (cache["sink_k"][b, :, sl:sl + 1], cache["sink_v"][b, :, sl:sl + 1])
+    return torch.cat([cache["sink_k"][b, :, :sl], rk], 1), torch.cat([cache["sink_v"][b, :, :sl], rv], 1), extras
+
+
+def decode_apply(cache, states, k_new, v_new, active=None):
+    """the CPU twin of a storing step: slot write_pos of every active row takes k_new / v_new IN PLACE, no other byte
+    moves; returns the advanced states"""
+    Wc = cache["window_k"].shape[2]
+    out = []
+    for b, (sl, wl, wp) in enumerate(states):
+        if active is not None and not active[b]:
+            out.append((sl, wl, wp))
+            continue
+        cache["window_k"][b, :, wp] = k_new[b, :, 0]
+        cache["window_v"][b, :, wp] = v_new[b, :, 0]
+        out.append((sl, min(wl + 1, Wc), 0 if wp + 1 == Wc else wp + 1))
+    return out
+
+
+def decode_oracle(cache, states, pr, step=True):
+    """fp64 oracle (oracle.sink_oracle.decode_dense) of every batch row over the tokens the cache keeps"""
+    from oracle import sink_oracle as O
+    rows = []
+    for b, st in enumerate(states):
+        K, V, _ = decode_kept(cache, st, b, pr["k_new"] if step else None, pr["v_new"] if step else None)
+        rows.append(O.decode_dense(pr["q"][b:b + 1], K[None], V[None], pr["s_aux"]))
+    return torch.cat(rows, 0)
+
+
+class DecodeRun:
+    """One sequence of fused steps over a CPU twin of the cache: the probe of every step, its regime and its fp64
+    reference, and the twin's update.  case: a row of decode_regime.MANY / GROUPS / FILLS; states: one (sink_len,
+    window_len, write_pos) per batch row; device_state: the launch is planned for the full cache (decode_step_dyn);
+    active: rows of a slots= call that are not -1 (an inactive row gets zeros and nothing of it moves)."""
+
+    def __init__(self, case, states, device_state, seed, rot=0, active=None):
+        import decode_regime as R
+        self.R, self.case, self.device_state = R, dict(case, B=len(states)), device_state
+        self.states, self.seed, self.rot = list(states), seed, rot
+        self.active = [True] * len(states) if active is None else list(active)
+        self.cache = decode_cache(len(states), case["Hkv"], case["D"], case["ns"], case["Wc"], R.DT[case["dtype"]], seed)
+
+    def probe(self):
+        """dict(pl, rows, pr, ref, states) of the next step; the twin does not move"""
+        pl, rows = self.R.regime(self.case, self.states, step=True, device_state=self.device_state)
+        self.seed, self.rot = self.seed + 1, self.rot + 1
+        pr = decode_probe(self.cache, self.states, self.case["Hq"], rows, self.seed, rot=self.rot)
+        ref = decode_oracle(self.cache, self.states, pr)
+        for b, on in enumerate(self.active):
+            if not on:
+                ref[b] = 0
+        return dict(pl=pl, rows=rows, pr=pr, ref=ref, states=list(self.states), active=self.active)
+
+    def apply(self, pr):
+        self.states = decode_apply(self.cache, self.states, pr["k_new"], pr["v_new"], self.active)
+
+
+FILLS_INACTIVE = 3         # batch row of the slots= form that is inactive (a copy of state 0 nobody stores)
+
+
+def decode_runs(case):
+    """[(name, DecodeRun, steps)] of one case: the launches tests/test_gpu_decode_edges.py makes and
+    tests/test_decode_probes.py proves.  many / groups: one host-state step per state of the case (`step<i>`), many also
+    `dyn` (shared device state at the second state).  fills: `rows` (one batch row per state), `slots` (the same with an
+    inactive row) and `shared<i>` (state i alone, B = 2), three steps each."""
+    import decode_regime as R
+    tables = R.MANY + R.GROUPS + R.FILLS
+    base = 7000 + 100 * [c["id"] for c in tables].index(case["id"])
+    B, st = case["B"], case["states"]
+    if case in R.FILLS:
+        with_off = st[:FILLS_INACTIVE] + [st[0]] + st[FILLS_INACTIVE:]
+        act = [b != FILLS_INACTIVE for b in range(len(with_off))]
+        runs = [("rows", DecodeRun(case, st, True, base, 0), R.FILLS_STEPS),
+                ("slots", DecodeRun(case, with_off, True, base + 10, 3, active=act), R.FILLS_STEPS)]
+        runs += [(f"shared{i}", DecodeRun(case, [s, s], True, base + 20 + 4 * i, 6 + i), R.FILLS_STEPS)
+                 for i, s in enumerate(st)]
+        return runs
+    runs = [(f"step{i}", DecodeRun(case, [s] * B, False, base + 10 * i, i * B * case["Hq"]), 1) for i, s in enumerate(st)]
+    if case in R.MANY:
+        runs.append(("dyn", DecodeRun(case, [st[1]] * B, True, base + 50, 5), 1))
+    return runs

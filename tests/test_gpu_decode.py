@@ -1,7 +1,14 @@
 """GPU parity: sink_decode_attention vs the CPU oracle.  Ports of the reference's
 tests/test_decode_kernel.py (tolerances :76,:181,:223) and the decode rows of
 tests/test_inference.py (fp32 at 1e-4, :86; the cache is out of scope, so the keys it
-would hand over -- sink tokens + last ``window`` tokens -- are gathered directly)."""
+would hand over -- sink tokens + last ``window`` tokens -- are gathered directly).
+
+The randn cases here are ports of the reference's tests, at its shapes and tolerances: they say that the kernels compute
+attention, not that every key is counted once (tests/test_decode_probes.py measures what randn hides at the shape of
+test_long_kv).  The edge coverage - more than 64 splits, the later rounds of the reduce, head loops of several trips, padded
+lane groups, device-state rows at every fill level, one key more or less at every edge of the step - lives in
+tests/test_gpu_decode_edges.py, on the probe inputs of tests/probe_inputs.py and the launch arithmetic of
+tests/decode_regime.py."""
 import pytest
 import torch
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the decode paths on the GPU: plain decode vs a float64 torch reference, and ring /
 fused-step / device-state / one-pass variants against the linearised cache.
-usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots] [--call=packed [--page-size=P]]   (range: keys carry the falling staircase of
+usage: python tools/fuzz_decode.py [n] [seed] [--inputs=randn|probe|range] [--slots] [--call=packed [--page-size=P]] [--call=edge]   (range: keys carry the falling staircase of
 tests/range_inputs.py along a +-1 code, one level per 64 keys, and the queries a gain of 0 / 0.5 / 1 / -1 along it; probe: keys are the +-1 codes of tests/probe_inputs.py and
 every query aims, with that module's amplitude, at one key of the history: the newest, the oldest the ring still holds, the
 one just evicted or the last sink; --slots: the single-token steps (decode_step_dyn only; the multi-token and commit
@@ -10,7 +10,11 @@ batch carries random inactive rows - and are held to the same reference; --call=
 instead - ragged_step_dyn over a slot pool with Wc up to 4096, random H_kv, G, T_PAD, fills and chunk lengths, in the plain,
 tree (parent=), admitting and FP8-pool forms - against an fp64 masked attention over each sequence's history, computed on
 the GPU; --page-size=P with it: half of the 16-bit cases whose Wc is a multiple of P run on a paged pool of NaN-filled pages
-behind a shuffled table, reserved slot by slot through the host allocator's prefix rule)"""
+behind a shuffled table, reserved slot by slot through the host allocator's prefix rule; --call=edge (with --inputs=probe):
+the single-token step on the decode probes of tests/probe_inputs.py::decode_probe - every (batch, q head) aims at one edge key
+of what the step may read, with half of the softmax mass on it - at a ring capacity up to 16384, random per-row fill states, in
+the host-state, shared-state and per-sequence forms, one_pass either way, against probe_inputs.decode_oracle at DECODE_TOL;
+the launch is checked against tests/decode_regime.py and the cache buffers against the CPU twin)"""
 import os
 import random
 import sys
@@ -29,7 +33,8 @@ inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or
 assert inputs in ("randn", "probe", "range"), inputs
 use_slots = "--slots" in sys.argv
 call = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--call=")] or ["step"])[-1]
-assert call in ("step", "packed"), call
+assert call in ("step", "packed", "edge"), call
+assert call != "edge" or inputs == "probe", "--call=edge takes --inputs=probe"
 page_size = int(([a.split("=", 1)[1] for a in sys.argv if a.startswith("--page-size=")] or ["0"])[-1])
 sys.argv = [a for a in sys.argv if not a.startswith(("--inputs=", "--call=", "--page-size=")) and a != "--slots"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
@@ -199,6 +204,65 @@ def packed_case():
         worst = float("inf")                                      # inactive, empty and padded rows must be zeros
     return desc, worst
 
+
+def edge_case():
+    """one random fused step on the decode probes; returns (description, error / tolerance or inf)"""
+    import decode_regime as R
+    from sink_attention import _native
+    from util import DECODE_TOL
+    D, dname = rng.choice([(16, "fp16"), (64, "bf16"), (64, "fp32"), (80, "bf16"), (80, "fp32"), (128, "fp16"), (256, "bf16")])
+    Hkv, g = rng.choice([1, 2, 4]), rng.choice([1, 3, 4, 6, 8, 12, 16])
+    ns, Wc = rng.choice([1, 4]), rng.choice([300, 1020, 2400, 5000, 16381, 16384])
+    form = rng.choice(["host", "dyn", "rows"])
+    B = rng.choice([1, 2, 5])
+    full = lambda: (ns, Wc, rng.randrange(Wc))
+    part = lambda: (lambda wl: (rng.randrange(1, ns + 1) if wl == 0 else ns, wl, wl))(rng.choice([0, 1, 251, 252, 253, Wc // 2, Wc - 1]))
+    states = [rng.choice([full, part])() for _ in range(B)] if form == "rows" else [rng.choice([full, part])()] * B
+    case = dict(id="fuzz", dtype=dname, B=B, Hq=Hkv * g, Hkv=Hkv, D=D, ns=ns, Wc=Wc)
+    one_pass = rng.random() < 0.5
+    desc = f"edge {form} 1pass{int(one_pass)} B{B} Hkv{Hkv} G{g} D{D} ns{ns} Wc{Wc} {dname} states{states}"
+    run = probe_inputs.DecodeRun(case, states, form != "host", rng.randrange(1 << 30), rng.randrange(64))
+    layer = SinkCacheLayer(ns, Wc)
+    for name in ("sink_k", "sink_v", "window_k", "window_v"):
+        setattr(layer, name, run.cache[name].cuda())
+    layer.is_initialized = layer.prefilled = True
+    layer.one_pass = one_pass
+    if form == "rows":
+        layer._dev_state = torch.tensor([[sl, wl, wp, sl + wl] for sl, wl, wp in states], dtype=torch.int32, device="cuda")
+        layer._per_seq = True
+    else:
+        layer.sink_len, layer.window_len, layer.write_pos = states[0]
+        if form == "dyn":
+            layer.enable_device_state()
+    worst = 0.0
+    for step in range(rng.choice([1, 3])):
+        L = run.probe()
+        pr = L["pr"]
+        q, kn, vn, sa = (pr[x].cuda() for x in ("q", "k_new", "v_new", "s_aux"))
+        o = layer.decode_step(q, kn, vn, s_aux=sa) if form == "host" else layer.decode_step_dyn(q, kn, vn, s_aux=sa)
+        path = _native.last_path()
+        e = (o.double().cpu() - L["ref"]).abs().max().item() / DECODE_TOL[q.dtype]
+        worst = max(worst, e if e == e else float("inf"))
+        run.apply(pr)
+        same = all(torch.equal(getattr(layer, n).cpu(), run.cache[n]) for n in ("sink_k", "sink_v", "window_k", "window_v"))
+        if not path.endswith("_" + L["pl"]["suffix"]) or ("1pass" in path) != one_pass or not same:
+            return desc + f" step{step} path {path} plan {L['pl']['suffix']} buffers equal {same}", float("inf")
+    return desc, worst
+
+
+if call == "edge":
+    top = 0.0
+    for case in range(n_cases):
+        try:
+            desc, worst = edge_case()
+        except Exception as ex:      # noqa: BLE001
+            desc, worst = "edge " + repr(ex)[:300], float("inf")
+        top = max(top, worst if worst != float("inf") else 0.0)
+        if worst > 1.0:
+            bad += 1
+            print("BAD", desc, "error / tol", worst)
+    print(f"fuzz_decode --call=edge --inputs=probe: {n_cases} cases, {bad} bad, largest error / tol {top:.3f}")
+    sys.exit(1 if bad else 0)
 
 if call == "packed":
     top = 0.0
