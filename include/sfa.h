@@ -740,7 +740,7 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
  * the sibling's checks: fp32, head dims outside 64 / 80 / 96 / 128 and SFA_FLAG_FORCE_GENERIC are SFA_ERR_UNSUPPORTED
  * ("<call>: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 (...)"): there is no exact-f32 instance.
  * <call> is decode_ragged_paged, ring_commit_ragged_paged, ring_fill_varlen_paged or ring_copy_paged.  FP8 pages are
- * not served.
+ * served by the *_paged_fp8_slots calls below (and copied by sfa_ring_copy_paged_slots); these three calls refuse them.
  *
  * sfa_decode_ring_ragged_paged_slots: the arguments of sfa_decode_ring_ragged_tree_slots plus (page_table,
  * table_stride) in front of workspace; parent, commit_seq, commit and SFA_FLAG_RAGGED_ADMIT as there.  Workspace:
@@ -783,6 +783,9 @@ int sfa_ring_fill_varlen_paged_slots(const sfa_tensor* sink_k, const sfa_tensor*
  * destination page is unmapped is dropped, one whose source page is unmapped copies page 0's row.  Pages are copied,
  * never shared.  Skipped pairs and the aliasing rules are those of sfa_ring_copy_slots.  sfa_last_path():
  * "ring_copy_slots_paged".
+ * FP8 pages: the eight buffers may all be SFA_DTYPE_FP8_E4M3 (a paged FP8 pool, below), as in sfa_ring_copy_slots: a
+ * byte copy through both tables, 16 codes per piece, no scales - the caller keeps EQUAL kv_scale on pools that exchange
+ * slots.  Mixed FP8 / 16-bit buffers are refused with the one-dtype text of sfa_ring_copy_slots.
  */
 int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
                               const sfa_tensor* src_window_v, const int32_t* src_state, const sfa_tensor* dst_sink_k,
@@ -790,6 +793,62 @@ int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* sr
                               int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
                               const int32_t* src_page_table, int src_table_stride, const int32_t* dst_page_table,
                               int dst_table_stride, void* stream);
+
+/*
+ * Paged FP8 slot pool: the two pools above composed - the ring memory follows the sequence length AND holds one byte per
+ * element.  Nothing new is defined here; each rule is the one of the pool it comes from:
+ *   window_k/v  [n_pages, Hkv, P, D] SFA_DTYPE_FP8_E4M3: the ring pages hold e4m3fn codes.  P, page_table, table_stride,
+ *               Wc = table_stride * P, unmapped entries (a read goes to page 0, a store is dropped, the state row still
+ *               advances), the prefix rule and 64-bit page and row addresses are those of the paged pool.  A page is
+ *               Hkv * P * D BYTES: every page and row offset is taken at one byte per element.
+ *   sink_k/v    [S, Hkv, num_sink, D] SFA_DTYPE_FP8_E4M3, not paged.
+ *   kv_scale    device float [2][Hkv] or null, with the storing rule, the clamp and the reading rule of the FP8 pool.
+ *   q / k_new / v_new / o (k / v of the fill) are bf16 or f16, head dims 64 / 80 / 96 / 128.
+ * Contract, bitwise (pages8 = the page buffers, table, scale as above):
+ *   - Read vs the contiguous FP8 twin.  o equals o of the same call of the *_fp8_slots family on the contiguous FP8
+ *     pool window[s, :, j P : (j + 1) P] = pages8[table[s][j]] with the same sinks, state and scales.
+ *   - Read vs the 16-bit paged pool.  o equals o of the same *_paged_slots call on a 16-bit pool with the same table
+ *     whose pages and sinks hold T(float(code) * scale).
+ *   - Storage.  After a storing call every mapped page row holds the storing rule applied to the row the same call
+ *     writes into a 16-bit paged pool with the same table; every other byte of the page buffers keeps its value; stores
+ *     to unmapped pages are dropped; the sinks hold what the *_fp8_slots sibling stores; the state rows are equal.
+ *   - Copy.  After sfa_ring_copy_paged_slots every later call on the destination is bitwise the call on the source,
+ *     within a pool and between two pools of equal scales, geometry and P.
+ * Host checks, in this order: those the paged pool adds (above, with <call> as below); then those of the *_fp8_slots
+ * sibling in their order, "<call>: the cache buffers must be FP8 (e4m3)" where the dtypes are compared (a 16-bit page
+ * buffer ends here); then SFA_ERR_UNSUPPORTED for fp32 activations, other head dims or SFA_FLAG_FORCE_GENERIC: "<call>:
+ * a paged FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 (got dtype d, head dim n[,
+ * SFA_FLAG_FORCE_GENERIC])".  <call> is decode_ragged_paged_fp8, ring_commit_ragged_paged_fp8 or
+ * ring_fill_varlen_paged_fp8.
+ *
+ * sfa_decode_ring_ragged_paged_fp8_slots: the arguments of sfa_decode_ring_ragged_paged_slots plus kv_scale in front of
+ * workspace.  Workspace: sfa_decode_ragged_workspace_bytes with q's dtype and Nkv_cache = num_sink + table_stride * P.
+ * sfa_last_path(): the name of the 16-bit contiguous call plus "_paged_kvfp8".
+ */
+int sfa_decode_ring_ragged_paged_fp8_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                           const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                           const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                                           const float* s_aux, const int32_t* parent, const int32_t* commit_seq,
+                                           int commit, int32_t* state, const int32_t* slots, const int32_t* cu_q,
+                                           int n_seq, const int32_t* page_table, int table_stride,
+                                           const float* kv_scale, void* workspace, size_t workspace_bytes, float scale,
+                                           unsigned flags, void* stream);
+
+/* sfa_ring_commit_path_ragged_paged_slots into FP8 pages: the same arguments plus kv_scale in front of stream; each row
+ * is quantised as it is stored through the table.  sfa_last_path(): "ring_commit_path_ragged_slots_paged_kvfp8". */
+int sfa_ring_commit_path_ragged_paged_fp8_slots(const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                                const sfa_tensor* k_new, const sfa_tensor* v_new, const int32_t* count,
+                                                const int32_t* path, const int32_t* cu_q, int n_seq, int32_t* state,
+                                                const int32_t* slots, const int32_t* page_table, int table_stride,
+                                                int n_slots, const float* kv_scale, void* stream);
+
+/* sfa_ring_fill_varlen_paged_slots into a paged FP8 pool: the same arguments plus kv_scale in front of stream.
+ * sfa_last_path(): "ring_fill_varlen_slots_paged_kvfp8". */
+int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                         const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                         const int32_t* page_table, int table_stride, const float* kv_scale,
+                                         void* stream);
 
 #ifdef __cplusplus
 }

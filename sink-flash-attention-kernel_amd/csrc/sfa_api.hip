@@ -462,10 +462,11 @@ struct PagedRing {
     PageTable pt;
 };
 
+// fp8_ok: the page buffers may hold FP8 codes (the *_paged_fp8_slots calls, sfa_ring_copy_paged_slots)
 int paged_ring(const char* who, const sfa_tensor* page_k, const sfa_tensor* page_v, const int32_t* table, int table_stride,
-               int64_t S, PagedRing* ring) {
+               int64_t S, PagedRing* ring, bool fp8_ok = false) {
     int st;
-    if ((st = check_tensor(page_k, "window_k")) || (st = check_tensor(page_v, "window_v"))) return st;
+    if ((st = check_tensor(page_k, "window_k", fp8_ok)) || (st = check_tensor(page_v, "window_v", fp8_ok))) return st;
     SFA_CHECK_ARG(table != nullptr, "page_table: null device pointer");
     const int64_t P = page_k->shape[2];
     SFA_CHECK_ARG(P >= 32 && (P & (P - 1)) == 0,
@@ -482,11 +483,24 @@ int paged_ring(const char* who, const sfa_tensor* page_k, const sfa_tensor* page
 }
 
 // ... and after them: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one reads a paged pool)
-int check_paged_served(const char* who, int dtype, int64_t D, unsigned flags) {
-    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
+// fp8_ok (sfa_ring_copy_paged_slots): FP8 pages pass too - the copy moves bytes
+int check_paged_served(const char* who, int dtype, int64_t D, unsigned flags, bool fp8_ok = false) {
+    if (dtype == SFA_DTYPE_F32 || (dtype == SFA_DTYPE_FP8_E4M3 && !fp8_ok) || !(D == 64 || D == 80 || D == 96 || D == 128) ||
         (flags & SFA_FLAG_FORCE_GENERIC)) {
         set_error("%s: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim %lld%s)", who,
                   dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    return SFA_OK;
+}
+
+// A *_paged_fp8_slots call (RingCall::pt and cache_es = 1 together): the checks of its FP8 sibling under the call's own
+// name, and this in place of check_fp8_served
+int check_paged_fp8_served(const char* who, int dtype, int64_t D, unsigned flags) {
+    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
+        (flags & SFA_FLAG_FORCE_GENERIC)) {
+        set_error("%s: a paged FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 (got dtype %d, head "
+                  "dim %lld%s)", who, dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
         return SFA_ERR_UNSUPPORTED;
     }
     return SFA_OK;
@@ -499,7 +513,8 @@ int check_multi(const RingCall& c) {
     const sfa_tensor *k_new = c.k_new, *v_new = c.v_new, *o = c.o;
     const int64_t sink_len = c.sink_len, window_len = c.window_len, write_pos = c.write_pos;
     int st;
-    const bool kv8 = c.cache_es == 1;       // sfa_decode_ring_ragged_fp8_slots
+    const bool kv8 = c.cache_es == 1;       // sfa_decode_ring_ragged_fp8_slots, sfa_decode_ring_ragged_paged_fp8_slots
+    const char* who8 = c.pt.table ? "decode_ragged_paged_fp8" : "decode_ragged_fp8";
     if ((st = check_device_state(c))) return st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k", kv8)) ||
         (st = check_tensor(sink_v, "sink_v", kv8)) || (st = check_tensor(window_k, "window_k", kv8)) ||
@@ -513,7 +528,7 @@ int check_multi(const RingCall& c) {
     const int64_t Wc = window_k->shape[2];
     const bool pool = c.slots != nullptr;
     if (kv8) {
-        if ((st = check_fp8_dtypes("decode_ragged_fp8", sink_k, window_k, q, k_new, "q and k_new / v_new"))) return st;
+        if ((st = check_fp8_dtypes(who8, sink_k, window_k, q, k_new, "q and k_new / v_new"))) return st;
     } else
         SFA_CHECK_ARG(q->dtype == sink_k->dtype && q->dtype == window_k->dtype && q->dtype == k_new->dtype,
                       "q, the cache buffers and k_new / v_new must share one dtype");
@@ -543,7 +558,8 @@ int check_multi(const RingCall& c) {
     SFA_CHECK_ARG(sink_len + window_len + n < (1ll << 30) && B * Hq * n < (1ll << 30) && Wc < (1ll << 30),
                   "problem too large");
     if (kv8) {      // the activations at 2 bytes per element, the cache rows at 1
-        if ((st = check_fp8_served("decode_ragged_fp8", q->dtype, D, c.flags))) return st;
+        if ((st = c.pt.table ? check_paged_fp8_served(who8, q->dtype, D, c.flags) : check_fp8_served(who8, q->dtype, D, c.flags)))
+            return st;
         if ((st = check_rows16({q, o, k_new, v_new}, 2, 7, "decode_multi: rows of every tensor must be 16-byte aligned")))
             return st;
         return check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
@@ -599,7 +615,8 @@ int ring_ragged(const RingCall& c) {
     SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
                   (long long)q->shape[0]);
     SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
-    if (c.pt.table && (st = check_paged_served("decode_ragged_paged", q->dtype, q->shape[3], c.flags))) return st;
+    if (c.pt.table && c.cache_es != 1 && (st = check_paged_served("decode_ragged_paged", q->dtype, q->shape[3], c.flags)))
+        return st;
     const size_t need = decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                 c.sink_len + c.window_len, q->shape[3], q->dtype);
     if ((st = check_workspace("decode_ragged", need, need != 0, c.workspace, c.workspace_bytes))) return st;
@@ -610,7 +627,8 @@ int ring_ragged(const RingCall& c) {
 int check_commit(const RingCall& c) {
     const sfa_tensor *window_k = c.window_k, *window_v = c.window_v, *k_new = c.k_new, *v_new = c.v_new;
     int st;
-    const bool kv8 = c.cache_es == 1;       // sfa_ring_commit_path_ragged_fp8_slots
+    const bool kv8 = c.cache_es == 1;       // sfa_ring_commit_path_ragged_fp8_slots and its _paged_fp8 form
+    const char* who8 = c.pt.table ? "ring_commit_ragged_paged_fp8" : "ring_commit_ragged_fp8";
     if ((st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
         return st;
@@ -619,7 +637,7 @@ int check_commit(const RingCall& c) {
     SFA_NEED(c.count, "count");
     SFA_NEED(c.state, "state");
     if (kv8) {
-        if ((st = check_fp8_dtypes("ring_commit_ragged_fp8", window_k, window_v, k_new, v_new, "k_new and v_new"))) return st;
+        if ((st = check_fp8_dtypes(who8, window_k, window_v, k_new, v_new, "k_new and v_new"))) return st;
     } else
         SFA_CHECK_ARG(k_new->dtype == window_k->dtype, "k_new / v_new and the ring must share one dtype");
     const int64_t n = k_new->shape[2], Wc = window_k->shape[2];
@@ -635,7 +653,9 @@ int check_commit(const RingCall& c) {
     SFA_CHECK_ARG(n < (1ll << 30) && Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k_new->dtype);
     if (kv8) {
-        if ((st = check_fp8_served("ring_commit_ragged_fp8", k_new->dtype, k_new->shape[3], 0))) return st;
+        if ((st = c.pt.table ? check_paged_fp8_served(who8, k_new->dtype, k_new->shape[3], 0)
+                             : check_fp8_served(who8, k_new->dtype, k_new->shape[3], 0)))
+            return st;
         if ((st = check_rows16({k_new, v_new}, es, 3, "ring_commit: rows of every tensor must be 16-byte aligned"))) return st;
         return check_rows16({window_k, window_v}, 1, 3, "ring_commit: rows of every tensor must be 16-byte aligned");
     }
@@ -681,7 +701,9 @@ int ring_commit_ragged(const RingCall& c) {
     if ((st = check_commit(c))) return st;
     SFA_CHECK_ARG(c.k_new->shape[0] == 1, "ring_commit_ragged: k_new / v_new must be packed [1, H_kv, T, D] (got shape[0] = %lld)",
                   (long long)c.k_new->shape[0]);
-    if (c.pt.table && (st = check_paged_served("ring_commit_ragged_paged", c.k_new->dtype, c.k_new->shape[3], 0))) return st;
+    if (c.pt.table && c.cache_es != 1 &&
+        (st = check_paged_served("ring_commit_ragged_paged", c.k_new->dtype, c.k_new->shape[3], 0)))
+        return st;
     return ring_commit_dyn_launch(c);
 }
 
@@ -704,8 +726,9 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
     SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
-    if (kv8) {      // sfa_ring_fill_varlen_fp8_slots
-        if ((st = check_fp8_dtypes("ring_fill_varlen_fp8", sink_k, window_k, k, v, "k and v"))) return st;
+    const char* who8 = pt ? "ring_fill_varlen_paged_fp8" : "ring_fill_varlen_fp8";
+    if (kv8) {      // sfa_ring_fill_varlen_fp8_slots, sfa_ring_fill_varlen_paged_fp8_slots
+        if ((st = check_fp8_dtypes(who8, sink_k, window_k, k, v, "k and v"))) return st;
     } else
         SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
                       "k / v and the cache buffers must share one dtype");
@@ -724,13 +747,13 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(k->shape[2] < (1ll << 30) && sink_k->shape[2] + Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k->dtype);
     if (kv8) {
-        if ((st = check_fp8_served("ring_fill_varlen_fp8", k->dtype, D, 0))) return st;
+        if ((st = pt ? check_paged_fp8_served(who8, k->dtype, D, 0) : check_fp8_served(who8, k->dtype, D, 0))) return st;
         if ((st = check_rows16({k, v}, es, 7, "ring_fill_varlen: rows of every tensor must be 16-byte aligned")) ||
             (st = check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
                                "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
             return st;
         return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
-                                       (hipStream_t)stream, slots, kv_scale);
+                                       (hipStream_t)stream, slots, kv_scale, pt);
     }
     SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_fill_varlen: K/V rows must be a multiple of 16 bytes (head dim %lld)",
                   (long long)D);
@@ -788,7 +811,7 @@ int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const s
     if ((st = check_rows16({src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3]}, es, 7,
                            "ring_copy_slots: rows of every tensor must be 16-byte aligned")))
         return st;
-    if (src_pt && (st = check_paged_served("ring_copy_paged", src[0]->dtype, D, 0))) return st;
+    if (src_pt && (st = check_paged_served("ring_copy_paged", src[0]->dtype, D, 0, true))) return st;      // FP8 pages: bytes
     return ring_copy_slots_launch(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, (hipStream_t)stream,
                                   src_pt, dst_pt);
 }
@@ -1096,15 +1119,70 @@ int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* sr
     PagedRing sr, dr;
     int st;
     if ((st = paged_ring("ring_copy_paged", src_window_k, src_window_v, src_page_table, src_table_stride,
-                         src_sink_k ? src_sink_k->shape[0] : 1, &sr)) ||
+                         src_sink_k ? src_sink_k->shape[0] : 1, &sr, true)) ||
         (st = paged_ring("ring_copy_paged", dst_window_k, dst_window_v, dst_page_table, dst_table_stride,
-                         dst_sink_k ? dst_sink_k->shape[0] : 1, &dr)))
+                         dst_sink_k ? dst_sink_k->shape[0] : 1, &dr, true)))
         return st;
     SFA_CHECK_ARG(sr.pt.page_size == dr.pt.page_size, "ring_copy_paged: the pools differ in page size (src %lld, dst %lld)",
                   (long long)sr.pt.page_size, (long long)dr.pt.page_size);
     const sfa_tensor* const src[4] = {src_sink_k, src_sink_v, &sr.k, &sr.v};
     const sfa_tensor* const dst[4] = {dst_sink_k, dst_sink_v, &dr.k, &dr.v};
     return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream, &sr.pt, &dr.pt);
+}
+
+// the *_paged_fp8_slots calls: the descriptor of the paged call with kv_scale and cache_es = 1 set beside pt
+int sfa_decode_ring_ragged_paged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
+                                           int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                           const int32_t* page_table, int table_stride, const float* kv_scale,
+                                           SFA_TAIL_PARAMS) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("decode_ragged_paged_fp8", window_k, window_v, page_table, table_stride,
+                         sink_k ? sink_k->shape[0] : 1, &ring, true)))
+        return st;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = attend_call(q, sink_k, sink_v, &ring.k, &ring.v, k_new, v_new, o, s_aux, workspace, workspace_bytes, scale,
+                             flags, stream);
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.parent = parent, c.commit_seq = commit_seq;
+    c.pt = ring.pt, c.kv_scale = kv_scale, c.cache_es = 1;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
+int sfa_ring_commit_path_ragged_paged_fp8_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
+                                                int32_t* state, const int32_t* slots, const int32_t* page_table,
+                                                int table_stride, int n_slots, const float* kv_scale, void* stream) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("ring_commit_ragged_paged_fp8", window_k, window_v, page_table, table_stride, n_slots, &ring, true)))
+        return st;
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = commit_call(&ring.k, &ring.v, k_new, v_new, count, RingState::Rows, state, slots, stream);
+    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.pt = ring.pt, c.kv_scale = kv_scale, c.cache_es = 1;
+    return ring_commit_ragged(c);
+}
+
+int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                         const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
+                                         const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
+                                         const int32_t* page_table, int table_stride, const float* kv_scale,
+                                         void* stream) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = paged_ring("ring_fill_varlen_paged_fp8", window_k, window_v, page_table, table_stride,
+                         sink_k ? sink_k->shape[0] : 1, &ring, true)))
+        return st;
+    return fill_varlen(sink_k, sink_v, &ring.k, &ring.v, k, v, cu_seqlens, n_seq, state, stream, slots, true, true, kv_scale,
+                       &ring.pt);
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

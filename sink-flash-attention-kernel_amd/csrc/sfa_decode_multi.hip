@@ -184,7 +184,8 @@ __device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Arg
 // ---- paged pool (the *_paged_slots calls).  The ring buffers are PAGES [n_pages, Hkv, P, D] (the
 // page index where the slot index was, same strides); table[c * stride + j] is the page that holds ring slots
 // [j P, (j + 1) P) of cache row c.  P = 1 << shift >= kTile, Wc = stride * P, so a 32-slot ring tile lies inside one page.
-// A kernel argument that only the paged instances take, like Kv8Args (a pool is FP8 or paged, never both).
+// A kernel argument that only the paged instances take, like Kv8Args.  A pool that is FP8 AND paged
+// takes both, Kv8Args first: its pages hold codes, and every page and row offset is in bytes of ONE per element.
 struct PageArgs {
     const int* table;            // device int32 [S][stride]; read when the kernel runs, never on the host
     int stride;
@@ -200,6 +201,12 @@ __device__ __forceinline__ const PageArgs& page_of(const RaggedArgs&, const Page
 __device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const PageArgs&) { return rg; }
 __device__ __forceinline__ Kv8Args kv8_of(const PageArgs&) { return Kv8Args{nullptr}; }
 __device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&, const PageArgs&) { return Kv8Args{nullptr}; }
+// the paged FP8 pool: (RaggedArgs, Kv8Args, PageArgs) behind MultiArgs, (Kv8Args, PageArgs) behind a storing kernel's own
+__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const Kv8Args&, const PageArgs&) { return rg; }
+__device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Args& kv, const PageArgs&) { return kv; }
+__device__ __forceinline__ const PageArgs& page_of(const RaggedArgs&, const Kv8Args&, const PageArgs& pg) { return pg; }
+__device__ __forceinline__ const Kv8Args& kv8_of(const Kv8Args& kv, const PageArgs&) { return kv; }
+__device__ __forceinline__ const PageArgs& page_of(const Kv8Args&, const PageArgs& pg) { return pg; }
 
 // the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
 // of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
@@ -427,6 +434,7 @@ __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f,
 // a live ring tile of a paged pool: one wave-uniform table lookup (a scalar load, the row and the tile index are in
 // SGPRs) moves the tile from page 0 to its page; an unmapped entry stays on page 0 (in bounds, the output unspecified).
 // The tile index is the PHYSICAL ring slot start / P: a ring tile has a fixed place in the ring.
+// es: bytes per element of the RING (tile_info's local one: 1 in a KV8 instance, whatever the activations have).
 __device__ __forceinline__ void tile_page(TileInfo& ti, const MultiArgs& a, const PageArgs& pg, int c, int es) {
     const int e = __builtin_amdgcn_readfirstlane(page_at(pg, c, ti.start));
     const int64_t page = e < 0 ? 0 : e;
@@ -566,14 +574,16 @@ __device__ __forceinline__ int xcd_work_id(int bid, int nblk) {
 // instance.  Chunk tiles (k_new / v_new) are 16-bit and keep the 16-byte load.
 // Paged (the paged pool, with Ragged): a live ring tile takes its page from the table (tile_page) before its loads are
 // issued; dead tiles cost no lookup, and everything behind the tile address is the 16-bit instance.
+// KV8 and Paged (the paged FP8 pool): both of the above - the lookup in front of the tile address, in bytes of one per
+// element, the conversion behind the load.
 template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, bool KV8 = false,
           bool Paged = false, typename... RA>
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && Ragged && D == 80) ? 2 : 1)))
 void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
-                      !(KV8 && !Ragged) && !(Paged && (!Ragged || KV8)),
+                      !(KV8 && !Ragged) && !(Paged && !Ragged),
                   "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args); paged pool: (MultiArgs, "
-                  "RaggedArgs, PageArgs)");
+                  "RaggedArgs, PageArgs); paged FP8 pool: (MultiArgs, RaggedArgs, Kv8Args, PageArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     [[maybe_unused]] const Kv8Args kv = kv8_of(ra...);
     [[maybe_unused]] const PageArgs pg = page_of(ra...);
@@ -748,7 +758,7 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
             if (cls != 0) break;
         }
         if constexpr (Paged) {
-            if (i < tend && ti.seg == 1) tile_page(ti, a, pg, c, es);
+            if (i < tend && ti.seg == 1) tile_page(ti, a, pg, c, KV8 ? 1 : es);
         }
         return i;
     };
@@ -1121,15 +1131,19 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
 // Ragged: rows are the packed rows (ragged_row); a row without work gets zeros, the commit is commit_piece_ragged.
 // KV8 (the FP8 pool, with Ragged): the commit blocks quantise as they store; the fold is the 16-bit instance's.
 // Paged (the paged pool, with Ragged): the commit blocks store through the page table; the fold reads no cache.
+// KV8 and Paged: the commit blocks quantise as they store through the table.
 template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, bool KV8 = false, bool Paged = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred, RA... ra) {
     static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
-                      !(KV8 && !Ragged) && !(Paged && (!Ragged || KV8)),
-                  "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs)");
+                      !(KV8 && !Ragged) && !(Paged && !Ragged),
+                  "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 "
+                  "pool: (..., Kv8Args, PageArgs)");
     [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        if constexpr (Paged)
+        if constexpr (Paged && KV8)
+            commit_piece_ragged<T, true>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...), page_of(ra...));
+        else if constexpr (Paged)
             commit_piece_ragged<void, true>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, Kv8Args{nullptr}, page_of(ra...));
         else if constexpr (KV8) commit_piece_ragged<T>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...));
         else if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
@@ -1217,12 +1231,12 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
 // c0_i + clamp(path[c0_i + j], 0, n_i - 1) (row c0_i + j without a path) into ring slot (write_pos + j) mod Wc of slot
 // slots[i] - the piece commit_piece<Path, true> stores for the sequence passed as a [1, Hkv, n_i, D] chunk.
 // Q (store_piece): void, or the pack's 16-bit type when the ring is FP8 (es stays the pack's element size); KA: Kv8Args then
-// Paged (Q = void): KA = PageArgs, the slot goes to row slot mod P of its page, a slot on an unmapped page is dropped
+// Paged: KA ends in PageArgs, the slot goes to row slot mod P of its page, a slot on an unmapped page is dropped
 template <typename Q = void, bool Paged = false, typename... KA>
 __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es,
                                                                  KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !std::is_void_v<Q>),
-                  "FP8 ring: (..., Kv8Args); paged ring: (..., PageArgs)");
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0),
+                  "FP8 ring: (..., Kv8Args); paged ring: (..., PageArgs); paged FP8 ring: (..., Kv8Args, PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
@@ -1274,15 +1288,15 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
 // Slots (sfa_ring_fill_varlen_slots): sequence b goes to cache row and state row slots[b] of a pool of npool rows (a
 // value outside [0, npool): the sequence is skipped); every other row of the pool keeps buffers and state.
 // Q (store_piece): void, or the pack's 16-bit type when the pool is FP8 (cpr and es stay those of the pack); KA: Kv8Args then
-// Paged (Slots, Q = void): KA = PageArgs; wc = stride * P, ring slot s goes to row s mod P of its page, a slot on an
+// Paged (Slots): KA ends in PageArgs; wc = stride * P, ring slot s goes to row s mod P of its page, a slot on an
 // unmapped page is dropped (the state row is written all the same)
 template <bool Slots, typename Q = void, bool Paged = false, typename... KA>
 __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv, View wk, View wv, View k, View v,
                                                                const int* cu, int* state, int n_seq, int Hkv, int ns,
                                                                int wc, int T, int cpr, int es, const int* slots,
                                                                int npool, KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !(std::is_void_v<Q> && Slots)),
-                  "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs)");
+    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !Slots),
+                  "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 pool: (..., Kv8Args, PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nj = ns + wc;
     if (item >= (int64_t)n_seq * Hkv * nj * cpr) return;
@@ -1548,13 +1562,15 @@ int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
 
 // kv (packed calls only): the FP8 pool - the (Dyn, Slots, Ragged) instances with the cache format, Tree on or off
 // pg (packed calls only): the paged pool - the same instances with the table lookup
+// kv and pg: the paged FP8 pool - the same instances with both
 template <typename T, int D>
 int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, hipStream_t stream) {
     const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
         if constexpr (M::Ragged) {
-            if (pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *pg);
+            if (kv && pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv, *pg);
+            else if (pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *pg);
             else if (kv) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv);
             else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
         }
@@ -1576,7 +1592,7 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, c
 }
 
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
-// kv / pg: the FP8 / paged pool of a packed call (the API admits either for the MFMA instances only)
+// kv / pg: the FP8 / paged pool of a packed call, both for a paged FP8 one (the API admits them for the MFMA instances only)
 template <typename T>
 int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
@@ -1594,7 +1610,7 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, con
     if (st) return st;
     const int nred = (int)cdiv64(rows, 4);
     int64_t ncommit = 0;
-    if (a.commit) {      // 16-byte pieces of the stored tokens: every row of a pack, else the last min(n, Wc) of the chunk
+    if (a.commit) {      // 16-byte pieces of the stored tokens AS THEY ARE READ (T's, whatever the pool stores): every row of a pack, else the last min(n, Wc) of the chunk
         const int64_t ncm = rg || a.n < a.wc ? a.n : a.wc;
         ncommit = cdiv64((int64_t)a.B * a.Hkv * ncm * (a.D * (int64_t)sizeof(T) / 16), 256);
     }
@@ -1603,6 +1619,10 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, con
         using M = decltype(m);
         if constexpr (M::Ragged) {
             if constexpr (sizeof(T) == 2) {
+                if (kv && pg) {
+                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, true, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *kv, *pg);
+                    return;
+                }
                 if (pg) {
                     multi_reduce_kernel<T, M::Dyn, M::Slots, true, false, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *pg);
                     return;
@@ -1663,7 +1683,7 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
     if (kv && !*mfma) {         // refused by the API before: no f32-accumulate instance reads an FP8 pool
-        set_error("decode_ragged_fp8: no kernel instance for this call");
+        set_error("%s: no kernel instance for this call", pg ? "decode_ragged_paged_fp8" : "decode_ragged_fp8");
         return SFA_ERR_UNSUPPORTED;
     }
     if (pg && !*mfma) {         // refused by the API before: no f32-accumulate instance reads a paged pool
@@ -1795,7 +1815,7 @@ int decode_ragged_launch(const RingCall& c) {
     if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cache_es == 1 ? &kv : nullptr, c.pt.table ? &pg : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? "_kvfp8" : c.pt.table ? "_paged" : "");
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? (c.pt.table ? "_paged_kvfp8" : "_kvfp8") : c.pt.table ? "_paged" : "");
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }
@@ -1815,14 +1835,19 @@ int ring_commit_dyn_launch(const RingCall& c) {
         if (nb > 0) {
             const Kv8Args kv{c.kv_scale};
             const dim3 grid((unsigned)nb);
-            if (c.pt.table) ring_commit_ragged_kernel<void, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, page_args(c.pt));
+            if (c.pt.table && c.cache_es == 1 && c.k_new->dtype == SFA_DTYPE_F16)
+                ring_commit_ragged_kernel<f16_t, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv, page_args(c.pt));
+            else if (c.pt.table && c.cache_es == 1)
+                ring_commit_ragged_kernel<bf16_t, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv, page_args(c.pt));
+            else if (c.pt.table) ring_commit_ragged_kernel<void, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, page_args(c.pt));
             else if (c.cache_es != 1) ring_commit_ragged_kernel<<<grid, 256, 0, c.stream>>>(a, rg, c.count, es);
             else if (c.k_new->dtype == SFA_DTYPE_F16) ring_commit_ragged_kernel<f16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
             else ring_commit_ragged_kernel<bf16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
             if ((st = launch_status("ring_commit_path_ragged"))) return st;
         }
         if ((st = launch_advance(a, c.count, &rg, c.stream))) return st;   // after every reader of the state
-        set_path(c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8"
+        set_path(c.cache_es == 1 && c.pt.table ? "ring_commit_path_ragged_slots_paged_kvfp8"
+                 : c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8"
                  : c.pt.table  ? "ring_commit_path_ragged_slots_paged"
                                  : "ring_commit_path_ragged_slots");
         return SFA_OK;
@@ -1863,7 +1888,17 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         return SFA_ERR_UNSUPPORTED;
     }
     if (nblk > 0) {
-        if (kv8 && k->dtype == SFA_DTYPE_F16)
+        if (kv8 && pt && k->dtype == SFA_DTYPE_F16)
+            ring_fill_varlen_kernel<true, f16_t, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale},
+                page_args(*pt));
+        else if (kv8 && pt)
+            ring_fill_varlen_kernel<true, bf16_t, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale},
+                page_args(*pt));
+        else if (kv8 && k->dtype == SFA_DTYPE_F16)
             ring_fill_varlen_kernel<true, f16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
                 make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
                 cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
@@ -1886,7 +1921,7 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         int st;
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
-    set_path(kv8 ? "ring_fill_varlen_slots_kvfp8" : pt ? "ring_fill_varlen_slots_paged" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
+    set_path(kv8 && pt ? "ring_fill_varlen_slots_paged_kvfp8" : kv8 ? "ring_fill_varlen_slots_kvfp8" : pt ? "ring_fill_varlen_slots_paged" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
     return SFA_OK;
 }
 

@@ -92,6 +92,7 @@ struct RingCall {
     const float* kv_scale;
     int cache_es;
     // paged pool (the *_paged_slots calls): window_k / window_v are the descriptors described at PageTable
+    // paged FP8 pool (the *_paged_fp8_slots calls): pt, kv_scale and cache_es = 1 are set together, the pages hold codes
     PageTable pt;
 };
 

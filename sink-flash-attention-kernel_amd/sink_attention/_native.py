@@ -183,6 +183,14 @@ def _bind(lib):
     lib.sfa_ring_fill_varlen_paged_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp]
     lib.sfa_ring_copy_paged_slots.restype = i32
     lib.sfa_ring_copy_paged_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp, i32, vp, i32, vp]
+    # paged FP8 pool: the paged step, commit and fill plus `kv_scale` behind the table arguments (the copy is the paged one)
+    lib.sfa_decode_ring_ragged_paged_fp8_slots.restype = i32
+    lib.sfa_decode_ring_ragged_paged_fp8_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32,
+                                                           vp, vp, sz, f32, u32, vp]
+    lib.sfa_ring_commit_path_ragged_paged_fp8_slots.restype = i32
+    lib.sfa_ring_commit_path_ragged_paged_fp8_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
+    lib.sfa_ring_fill_varlen_paged_fp8_slots.restype = i32
+    lib.sfa_ring_fill_varlen_paged_fp8_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp, vp]
 
 
 def lib():

@@ -675,6 +675,18 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def _page_args(self):
         return (self.page_table.data_ptr(), self.page_table.stride(0))
 
+    def _pool_entry(self, base, fp8, paged):
+        """The entry point of a packed call on this pool: ``base`` on a 16-bit contiguous pool, else the form for an FP8
+        pool, a paged pool, or - both - a paged FP8 pool (``init_pool(page_size=P, kv_dtype=torch.float8_e4m3fn)``)."""
+        return fp8 + "_slots" if self._kv8 and not self.page_size else \
+            paged + "_fp8_slots" if self._kv8 else paged + "_slots" if self.page_size else base
+
+    def _pool_tail(self, n_slots=False):
+        """What those forms take in front of the tail: (page_table, table_stride[, n_slots]) of a paged pool, then
+        kv_scale of an FP8 pool."""
+        pg = (*self._page_args(), *((self.num_slots,) if n_slots else ())) if self.page_size else ()
+        return (*pg, *((self._kv_scale_ptr(),) if self._kv8 else ()))
+
     def reserve_pages(self, slots, tokens_after) -> None:
         """Map the ring pages the coming step needs (paged pool; pure host bookkeeping, no kernel, no device read):
         for each host slot the first ``ceil(min(tokens_after, window_size) / page_size)`` table entries are mapped from
@@ -713,7 +725,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         replay.  Codes already in the pool are not rescaled: set the scales of a calibrated checkpoint before the first
         ``prefill_slots``, and keep equal scales on pools that exchange slots (``fork_slots`` copies bytes)."""
         if not (self._pool and self._kv8):
-            raise TypeError("set_kv_scale needs an FP8 pool: init_pool(..., dtype=torch.float8_e4m3fn)")
+            raise TypeError("set_kv_scale needs an FP8 pool: init_pool(..., dtype=torch.float8_e4m3fn) or, paged, "
+                            "init_pool(..., page_size=P, kv_dtype=torch.float8_e4m3fn)")
         for row, x in ((0, k_scale), (1, v_scale)):
             t = x if isinstance(x, torch.Tensor) else torch.tensor(x, dtype=torch.float32)
             if t.dim() > 1 or (t.dim() == 1 and t.numel() != self.kv_scale.shape[1]) or t.dtype.is_complex:
@@ -722,7 +735,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             self.kv_scale[row].copy_(t.to(torch.float32) if t.dim() else t.to(torch.float32).expand(self.kv_scale.shape[1]))
 
     def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda", page_size=None,
-                  num_pages=None, page_table=None) -> torch.Tensor:
+                  num_pages=None, page_table=None, kv_dtype=None) -> torch.Tensor:
         """Allocate a pool of ``num_slots`` cache rows that lives as long as the server: ``[S, H_kv, num_sink /
         window_size, D]`` buffers and a zeroed int32 ``[S, 4]`` device state ``{sink_len, window_len, write_pos, seen}``
         (returned).  The layer enters per-sequence mode (the host-state methods refuse, as after ``prefill_varlen``).  A
@@ -748,13 +761,27 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``reserve_pages`` before a step and ``free_pages`` at retirement keep the table; a store to an unmapped page is
         dropped and a read of one is in bounds but unspecified.  Served by the calls of an FP8 pool, at bfloat16 /
         float16 and head dims 64 / 80 / 96 / 128; every other method raises ``TypeError``.  Sinks and state rows are not
-        paged.  The defaults (``page_size=None``) give the contiguous pool."""
+        paged.  The defaults (``page_size=None``) give the contiguous pool.
+
+        ``kv_dtype=torch.float8_e4m3fn`` (default None: the buffers have ``dtype``): the cache buffers hold FP8 codes and
+        ``dtype`` (bfloat16 / float16) only names the activations the pool is meant for.  With ``page_size`` this is the
+        PAGED FP8 pool - FP8 sinks ``[S, H_kv, num_sink, D]``, FP8 pages ``[num_pages, H_kv, P, D]``, ``kv_scale`` and
+        ``page_table`` as above, every rule of the two pools unchanged, served by the same calls.  Without ``page_size``
+        it is the contiguous FP8 pool of ``dtype=torch.float8_e4m3fn``.  (``dtype=torch.float8_e4m3fn`` together with
+        ``page_size`` stays refused: the paged FP8 pool is spelled with ``kv_dtype``.)"""
+        if kv_dtype is not None:
+            if kv_dtype != torch.float8_e4m3fn:
+                raise TypeError(f"kv_dtype must be None (the buffers have dtype) or torch.float8_e4m3fn, got {kv_dtype}")
+            if dtype not in (torch.float16, torch.bfloat16):
+                raise TypeError(f"with kv_dtype=float8_e4m3fn, dtype names the activations and must be bfloat16 or float16, "
+                                f"got {dtype}")
         if page_size is None and (num_pages is not None or page_table is not None):
             raise ValueError("num_pages / page_table need page_size")
         if page_size is not None:
             P = int(page_size)
             if dtype == torch.float8_e4m3fn:
-                raise TypeError("a paged FP8 pool is not served: init_pool takes dtype=float8_e4m3fn or page_size, not both")
+                raise TypeError("a paged FP8 pool is not served: init_pool takes dtype=float8_e4m3fn or page_size, not both "
+                                "(the paged FP8 pool is dtype=bfloat16 / float16, page_size=P, kv_dtype=float8_e4m3fn)")
             if dtype not in (torch.float16, torch.bfloat16) or D not in (64, 80, 96, 128):
                 raise ValueError(f"a paged pool serves bfloat16 / float16 at head dims 64 / 80 / 96 / 128, got {dtype}, D = {D}")
             if P < 32 or P & (P - 1):
@@ -769,6 +796,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                            tuple(page_table.shape) != (int(num_slots), per_slot) or
                                            not page_table.is_contiguous()):
                 raise ValueError(f"page_table must be a contiguous int32 [S, Wc / P] = [{int(num_slots)}, {per_slot}] tensor")
+        if kv_dtype is not None:     # from here on `dtype` is what the buffers hold
+            dtype = kv_dtype
         if self.window_size < 1:
             raise ValueError("init_pool needs a ring of at least one slot (window_size >= 1)")
         if int(num_slots) < 1:
@@ -854,13 +883,11 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                              f"got {tuple(k.shape)}")
         cu = self._cu_arg(cu_seqlens, k.shape[2], k.device)
         k, v = self._rows16(k), self._rows16(v)
-        name = "sfa_ring_fill_varlen_fp8_slots" if self._kv8 else \
-            "sfa_ring_fill_varlen_paged_slots" if self.page_size else "sfa_ring_fill_varlen_slots"
+        name = self._pool_entry("sfa_ring_fill_varlen_slots", "sfa_ring_fill_varlen_fp8", "sfa_ring_fill_varlen_paged")
         with torch.cuda.device(k.device):
             rc = getattr(N.lib(), name)(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v, k, v)),
                                         cu.data_ptr(), n_seq, self._dev_state.data_ptr(), slots.data_ptr(),
-                                        *((self._kv_scale_ptr(),) if self._kv8 else ()),
-                                        *(self._page_args() if self.page_size else ()), N.stream_ptr(k.device))
+                                        *self._pool_tail(), N.stream_ptr(k.device))
         N.check(rc, name)
         return self._dev_state
 
@@ -1066,10 +1093,10 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         sk, sv, wk, wv = st["descs"]
         name, mid, kvs = "sfa_decode_ring_ragged_slots", (), ()
         if parent is not None or commit_seq is not None or self._kv8 or self.page_size:
-            name = "sfa_decode_ring_ragged_fp8_slots" if self._kv8 else \
-                "sfa_decode_ring_ragged_paged_slots" if self.page_size else "sfa_decode_ring_ragged_tree_slots"
+            name = self._pool_entry("sfa_decode_ring_ragged_tree_slots", "sfa_decode_ring_ragged_fp8",
+                                    "sfa_decode_ring_ragged_paged")
             mid = (None if parent is None else parent.data_ptr(), None if commit_seq is None else commit_seq.data_ptr())
-            kvs = (self._kv_scale_ptr(),) if self._kv8 else self._page_args() if self.page_size else ()
+            kvs = self._pool_tail()
         with torch.cuda.device(q.device):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
@@ -1129,15 +1156,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.require_gpu(slots)
         k_new, v_new = self._rows16(k_new), self._rows16(v_new)
         wk, wv = self._ring_descs()
-        name = "sfa_ring_commit_path_ragged_fp8_slots" if self._kv8 else \
-            "sfa_ring_commit_path_ragged_paged_slots" if self.page_size else "sfa_ring_commit_path_ragged_slots"
+        name = self._pool_entry("sfa_ring_commit_path_ragged_slots", "sfa_ring_commit_path_ragged_fp8",
+                                "sfa_ring_commit_path_ragged_paged")
         with torch.cuda.device(k_new.device):
             rc = getattr(N.lib(), name)(wk, wv, N.desc(k_new), N.desc(v_new), count.data_ptr(),
                                         None if path is None else path.data_ptr(), cu.data_ptr(), n_seq,
                                         dev_state.data_ptr(), slots.data_ptr(),
-                                        *((self._kv_scale_ptr(),) if self._kv8 else ()),
-                                        *((*self._page_args(), self.num_slots) if self.page_size else ()),
-                                        N.stream_ptr(k_new.device))
+                                        *self._pool_tail(n_slots=True), N.stream_ptr(k_new.device))
         N.check(rc, name)
 
     def packed_positions(self, cu_q, slots, T: int) -> torch.Tensor:
@@ -1288,17 +1313,17 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     _pages = None
 
     def init_pool(self, num_slots: int, H_kv: int, D: int, dtype=torch.bfloat16, device="cuda",
-                  layer_idx: int = 0, page_size=None, num_pages=None, page_table=None) -> torch.Tensor:
+                  layer_idx: int = 0, page_size=None, num_pages=None, page_table=None, kv_dtype=None) -> torch.Tensor:
         """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state.  With
         ``page_size`` the layers' pools are paged and share ONE table tensor (``cache.page_table``: that of the first
         paged layer, or the given one) and one allocator, so one mapping serves every layer: the layers must agree in
         ``num_slots``, ``page_size`` and ``num_pages``."""
         layer = self._layer(layer_idx)
         if page_size is None:
-            return layer.init_pool(num_slots, H_kv, D, dtype, device)
+            return layer.init_pool(num_slots, H_kv, D, dtype, device, kv_dtype=kv_dtype)
         shared = self.page_table if page_table is None else page_table
         state = layer.init_pool(num_slots, H_kv, D, dtype, device, page_size=page_size, num_pages=num_pages,
-                                page_table=shared)
+                                page_table=shared, kv_dtype=kv_dtype)
         if self._pages is not None and shared is self.page_table:
             if (self._pages.num_pages, self._pages.page_size) != (layer._pages.num_pages, layer._pages.page_size):
                 raise ValueError("init_pool: the paged layers of a cache share one table and must agree in page_size "

@@ -30,6 +30,10 @@ Variants per (W, step), alternating in one process:
     on a contiguous bf16 pool and, per page size P, on two paged pools of the same content - `ident` (slot s owns pages
     s * Wc / P + j) and `shuf` (a seeded shuffle of the page pool) - all alternating in one process.  Prints ms per step, the
     spread and each paged time over the contiguous one.  Skipped where the library lacks the call.
+--pool-dtypes bf16,fp8 --page-size 64 together: the same geometry and steps on the contiguous pool of
+    each named format and, per page size, on a paged pool of each (shuffled table) - with fp8 the last one is the paged
+    FP8 pool (init_pool(page_size=P, kv_dtype=float8_e4m3fn)) - all alternating in one process.  Prints ms per step, the
+    spread and each time over the contiguous 16-bit one.  A pool the library lacks is skipped (a parent build).
 --pkg DIR: import sink_attention from DIR/sink-flash-attention-kernel_amd (a checkout of another commit with its own
     built library), to time two commits' libraries with one tool.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
@@ -38,7 +42,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --pool-dtypes bf16,fp8 | --page-size 64,256] [--pkg DIR]"""
+       [--admit | --tree | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -202,6 +206,26 @@ POOL_S, POOL_HQ, POOL_HKV, POOL_D = 64, 32, 8, 128
 POOL_STEPS = {"dec64": [1] * 64, "dec63_pre512": [1] * 63 + [512]}
 
 
+def _alternate(torch, args, fns, names):
+    """ms per call of every variant: WARM calls of each, then args.rounds rounds in which each variant in turn runs
+    args.calls calls between two events"""
+    res = {n: [] for n in names}
+    for n in names:
+        for _ in range(WARM):
+            fns[n]()
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for n in names:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _c in range(args.calls):
+                fns[n]()
+            e1.record()
+            torch.cuda.synchronize()
+            res[n].append(e0.elapsed_time(e1) / args.calls)
+    return res
+
+
 def pool_dtypes(args):
     """--pool-dtypes: the same committing packed step on a 16-bit and on an FP8 pool, alternating"""
     import torch
@@ -234,20 +258,7 @@ def pool_dtypes(args):
             cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
             slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
             fns = {n: (lambda p=pools[n]: p.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True)) for n in names}
-            res = {n: [] for n in names}
-            for n in names:
-                for _ in range(WARM):
-                    fns[n]()
-            torch.cuda.synchronize()
-            for _ in range(args.rounds):
-                for n in names:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _c in range(args.calls):
-                        fns[n]()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    res[n].append(e0.elapsed_time(e1) / args.calls)
+            res = _alternate(torch, args, fns, names)
             cells = []
             for n in names:
                 x = sorted(res[n])
@@ -301,25 +312,71 @@ def page_sizes(args):
             cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
             slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
             fns = {n: (lambda p=pools[n]: p.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True)) for n in names}
-            res = {n: [] for n in names}
-            for n in names:
-                for _ in range(WARM):
-                    fns[n]()
-            torch.cuda.synchronize()
-            for _ in range(args.rounds):
-                for n in names:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _c in range(args.calls):
-                        fns[n]()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    res[n].append(e0.elapsed_time(e1) / args.calls)
+            res = _alternate(torch, args, fns, names)
             med = {n: sorted(x)[len(x) // 2] for n, x in res.items()}
             print(f"  W={W:5d} {step:12s} T={T:4d}", flush=True)
             for n in names:
                 x = sorted(res[n])
                 print(f"      {n:12s} {med[n]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f})  / contig {med[n] / med['contig']:.3f}", flush=True)
+
+
+def paged_dtypes(args):
+    """--pool-dtypes with --page-size: contiguous and paged pools of each format, alternating"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt = "cuda", torch.bfloat16
+    lib, fp8 = _native.lib(), getattr(torch, "float8_e4m3fn", None)
+    have = {"bf16": True, "fp8": hasattr(lib, "sfa_decode_ring_ragged_fp8_slots"),
+            "paged_bf16": hasattr(lib, "sfa_decode_ring_ragged_paged_slots"),
+            "paged_fp8": hasattr(lib, "sfa_decode_ring_ragged_paged_fp8_slots")}
+    fmts = args.pool_dtypes.split(",")
+    if set(fmts) - {"bf16", "fp8"}:
+        sys.exit(f"--pool-dtypes takes bf16 and fp8, got {args.pool_dtypes}")
+    fmts = [n for n in fmts if have[n]]
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nserving geometry H_q={POOL_HQ} H_kv={POOL_HKV} D={POOL_D} num_sink={NS} s_aux bf16 "
+          f"activations, pool of {POOL_S}, rings full; device ms per committing step, median of {args.rounds} rounds of "
+          f"{args.calls} calls (events) after {WARM} warm-up calls, pools alternating; paged pools: seeded-shuffle page table",
+          flush=True)
+    for W in Ws:
+        pre = NS + W + 37                          # full ring, wrapped
+        torch.manual_seed(0)
+        k = torch.randn(1, POOL_HKV, POOL_S * pre, POOL_D, device=dev, dtype=dt)
+        v = torch.randn_like(k)
+        pools = {}
+        for n in fmts:
+            pools[n] = SinkCacheLayer(NS, W)
+            pools[n].init_pool(POOL_S, POOL_HKV, POOL_D, fp8 if n == "fp8" else dt, dev)
+        for P in [int(x) for x in args.page_size.split(",")]:
+            per = W // P
+            for n in fmts:
+                if not have["paged_" + n]:
+                    print(f"  this library has no paged {n} pool: skipped", flush=True)
+                    continue
+                p = pools[f"P{P}_{n}"] = SinkCacheLayer(NS, W)
+                p.init_pool(POOL_S, POOL_HKV, POOL_D, dt, dev, page_size=P, **(dict(kv_dtype=fp8) if n == "fp8" else {}))
+                order = torch.randperm(POOL_S * per, generator=torch.Generator().manual_seed(P))
+                p.page_table.copy_(order.reshape(POOL_S, per).to(torch.int32))
+        for p in pools.values():
+            p.prefill_slots(k, v, [pre * i for i in range(POOL_S + 1)], list(range(POOL_S)))
+        del k, v
+        names = list(pools)
+        sa = torch.randn(POOL_HQ, device=dev) * 0.5
+        for step, lengths in POOL_STEPS.items():
+            T = sum(lengths)
+            q = torch.randn(1, POOL_HQ, T, POOL_D, device=dev, dtype=dt)
+            kn, vn = (torch.randn(1, POOL_HKV, T, POOL_D, device=dev, dtype=dt) for _ in range(2))
+            o = torch.empty_like(q)
+            cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
+            slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
+            fns = {n: (lambda p=pools[n]: p.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True)) for n in names}
+            res = _alternate(torch, args, fns, names)
+            med = {n: sorted(x)[len(x) // 2] for n, x in res.items()}
+            print(f"  W={W:5d} {step:12s} T={T:4d}", flush=True)
+            for n in names:
+                x = sorted(res[n])
+                print(f"      {n:12s} {med[n]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f})  / {names[0]} {med[n] / med[names[0]]:.3f}",
+                      flush=True)
 
 
 def kernels(args):
@@ -398,6 +455,8 @@ def main():
     args = ap.parse_args()
     if args.summarize:
         summarize(args)
+    elif args.page_size and args.pool_dtypes:
+        paged_dtypes(args)
     elif args.page_size:
         page_sizes(args)
     elif args.pool_dtypes:
