@@ -433,7 +433,7 @@ int ring_step(const RingCall& c) {
 }
 
 // The checks an *_fp8_slots call adds (`who`: its name in the messages).  Where the 16-bit call compares the dtypes: the
-// cache buffers are FP8, the activations share one dtype ...
+// cache buffers are FP8, the activations share one dtype (where it checks the head dim: check_pool_served)
 int check_fp8_dtypes(const char* who, const sfa_tensor* cache_a, const sfa_tensor* cache_b, const sfa_tensor* act_a,
                      const sfa_tensor* act_b, const char* acts) {
     SFA_CHECK_ARG(cache_a->dtype == SFA_DTYPE_FP8_E4M3 && cache_b->dtype == SFA_DTYPE_FP8_E4M3,
@@ -442,12 +442,24 @@ int check_fp8_dtypes(const char* who, const sfa_tensor* cache_a, const sfa_tenso
     return SFA_OK;
 }
 
-// ... and where it checks the head dim: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one exists)
-int check_fp8_served(const char* who, int dtype, int64_t D, unsigned flags) {
-    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
+// `who` of a pool call in the messages: the name of its family plus _fp8 / _paged / _paged_fp8
+struct Who {
+    char s[40];
+    Who(const char* base, bool fp8, bool paged) { snprintf(s, sizeof(s), "%s%s%s", base, paged ? "_paged" : "", fp8 ? "_fp8" : ""); }
+    Who(const char* base, const SlotPool& pool) : Who(base, pool.fp8, pool.pt.table != nullptr) {}
+    operator const char*() const { return s; }
+};
+
+// What an FP8 or a paged pool serves: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one reads such a
+// pool).  An FP8 call asks where its 16-bit sibling checks the head dim, a 16-bit paged call after the sibling's checks.
+// fp8_pages_ok (sfa_ring_copy_paged_slots): FP8 pages pass too - the copy moves bytes
+int check_pool_served(const char* who, const SlotPool& pool, int dtype, int64_t D, unsigned flags, bool fp8_pages_ok = false) {
+    if (dtype == SFA_DTYPE_F32 || (dtype == SFA_DTYPE_FP8_E4M3 && !fp8_pages_ok) || !(D == 64 || D == 80 || D == 96 || D == 128) ||
         (flags & SFA_FLAG_FORCE_GENERIC)) {
-        set_error("%s: an FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim "
-                  "%lld%s)", who, dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        set_error("%s: %s at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim %lld%s)", who,
+                  !pool.fp8 ? "a paged pool serves bf16 / f16" : pool.pt.table ? "a paged FP8 pool serves bf16 / f16 activations"
+                                                                               : "an FP8 pool serves bf16 / f16 activations",
+                  dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
         return SFA_ERR_UNSUPPORTED;
     }
     return SFA_OK;
@@ -482,27 +494,24 @@ int paged_ring(const char* who, const sfa_tensor* page_k, const sfa_tensor* page
     return SFA_OK;
 }
 
-// ... and after them: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one reads a paged pool)
-// fp8_ok (sfa_ring_copy_paged_slots): FP8 pages pass too - the copy moves bytes
-int check_paged_served(const char* who, int dtype, int64_t D, unsigned flags, bool fp8_ok = false) {
-    if (dtype == SFA_DTYPE_F32 || (dtype == SFA_DTYPE_FP8_E4M3 && !fp8_ok) || !(D == 64 || D == 80 || D == 96 || D == 128) ||
-        (flags & SFA_FLAG_FORCE_GENERIC)) {
-        set_error("%s: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim %lld%s)", who,
-                  dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
-        return SFA_ERR_UNSUPPORTED;
-    }
-    return SFA_OK;
-}
+// The pool of an entry point as its signature names it: all zero for the 16-bit contiguous calls.  pool_of turns it into
+// the descriptor of the launchers; of a paged call it makes the checks of paged_ring first, under the call's own name
+// (`base` plus the pool's suffix), and replaces the page buffers by the ring descriptors.  S: the slots of the pool
+struct PoolIn {
+    bool fp8;
+    const float* kv_scale;
+    bool paged;
+    const int32_t* table;
+    int table_stride;
+};
 
-// A *_paged_fp8_slots call (RingCall::pt and cache_es = 1 together): the checks of its FP8 sibling under the call's own
-// name, and this in place of check_fp8_served
-int check_paged_fp8_served(const char* who, int dtype, int64_t D, unsigned flags) {
-    if (dtype == SFA_DTYPE_F32 || dtype == SFA_DTYPE_FP8_E4M3 || !(D == 64 || D == 80 || D == 96 || D == 128) ||
-        (flags & SFA_FLAG_FORCE_GENERIC)) {
-        set_error("%s: a paged FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 (got dtype %d, head "
-                  "dim %lld%s)", who, dtype, (long long)D, (flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
-        return SFA_ERR_UNSUPPORTED;
-    }
+int pool_of(const char* base, const PoolIn& in, int64_t S, const sfa_tensor** window_k, const sfa_tensor** window_v,
+            PagedRing* ring, SlotPool* pool) {
+    *pool = SlotPool{in.fp8, in.kv_scale, PageTable{}};
+    if (!in.paged) return SFA_OK;
+    const int st = paged_ring(Who(base, in.fp8, true), *window_k, *window_v, in.table, in.table_stride, S, ring, in.fp8);
+    if (st) return st;
+    *window_k = &ring->k, *window_v = &ring->v, pool->pt = ring->pt;
     return SFA_OK;
 }
 
@@ -513,8 +522,8 @@ int check_multi(const RingCall& c) {
     const sfa_tensor *k_new = c.k_new, *v_new = c.v_new, *o = c.o;
     const int64_t sink_len = c.sink_len, window_len = c.window_len, write_pos = c.write_pos;
     int st;
-    const bool kv8 = c.cache_es == 1;       // sfa_decode_ring_ragged_fp8_slots, sfa_decode_ring_ragged_paged_fp8_slots
-    const char* who8 = c.pt.table ? "decode_ragged_paged_fp8" : "decode_ragged_fp8";
+    const bool kv8 = c.pool.fp8;            // sfa_decode_ring_ragged_fp8_slots, sfa_decode_ring_ragged_paged_fp8_slots
+    const Who who8("decode_ragged", c.pool);
     if ((st = check_device_state(c))) return st;
     if ((st = check_tensor(q, "q")) || (st = check_tensor(o, "o")) || (st = check_tensor(sink_k, "sink_k", kv8)) ||
         (st = check_tensor(sink_v, "sink_v", kv8)) || (st = check_tensor(window_k, "window_k", kv8)) ||
@@ -558,8 +567,7 @@ int check_multi(const RingCall& c) {
     SFA_CHECK_ARG(sink_len + window_len + n < (1ll << 30) && B * Hq * n < (1ll << 30) && Wc < (1ll << 30),
                   "problem too large");
     if (kv8) {      // the activations at 2 bytes per element, the cache rows at 1
-        if ((st = c.pt.table ? check_paged_fp8_served(who8, q->dtype, D, c.flags) : check_fp8_served(who8, q->dtype, D, c.flags)))
-            return st;
+        if ((st = check_pool_served(who8, c.pool, q->dtype, D, c.flags))) return st;
         if ((st = check_rows16({q, o, k_new, v_new}, 2, 7, "decode_multi: rows of every tensor must be 16-byte aligned")))
             return st;
         return check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
@@ -615,7 +623,8 @@ int ring_ragged(const RingCall& c) {
     SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
                   (long long)q->shape[0]);
     SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
-    if (c.pt.table && c.cache_es != 1 && (st = check_paged_served("decode_ragged_paged", q->dtype, q->shape[3], c.flags)))
+    if (c.pool.pt.table && !c.pool.fp8 &&
+        (st = check_pool_served(Who("decode_ragged", c.pool), c.pool, q->dtype, q->shape[3], c.flags)))
         return st;
     const size_t need = decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                 c.sink_len + c.window_len, q->shape[3], q->dtype);
@@ -623,12 +632,31 @@ int ring_ragged(const RingCall& c) {
     return decode_ragged_launch(c);
 }
 
+// the packed attention entry points, sfa_decode_ring_ragged{,_tree,_fp8,_paged,_paged_fp8}_slots: c as SFA_ATTEND_CALL
+// fills it, `in` the pool.  The order of the checks: the pages and table of a paged call, the null device arrays, n_seq,
+// then ring_ragged
+int ragged_slots(RingCall c, const int32_t* parent, const int32_t* commit_seq, int commit, int32_t* state,
+                 const int32_t* slots, const int32_t* cu_q, int n_seq, const PoolIn& in = PoolIn{}) {
+    g_err[0] = 0;
+    PagedRing ring;
+    int st;
+    if ((st = pool_of("decode_ragged", in, c.sink_k ? c.sink_k->shape[0] : 1, &c.window_k, &c.window_v, &ring, &c.pool)))
+        return st;
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
+    c.parent = parent, c.commit_seq = commit_seq;
+    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+}
+
 // every host-checkable argument of sfa_ring_commit*; nothing launches
 int check_commit(const RingCall& c) {
     const sfa_tensor *window_k = c.window_k, *window_v = c.window_v, *k_new = c.k_new, *v_new = c.v_new;
     int st;
-    const bool kv8 = c.cache_es == 1;       // sfa_ring_commit_path_ragged_fp8_slots and its _paged_fp8 form
-    const char* who8 = c.pt.table ? "ring_commit_ragged_paged_fp8" : "ring_commit_ragged_fp8";
+    const bool kv8 = c.pool.fp8;            // sfa_ring_commit_path_ragged_fp8_slots and its _paged_fp8 form
+    const Who who8("ring_commit_ragged", c.pool);
     if ((st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
         (st = check_tensor(k_new, "k_new")) || (st = check_tensor(v_new, "v_new")))
         return st;
@@ -653,9 +681,7 @@ int check_commit(const RingCall& c) {
     SFA_CHECK_ARG(n < (1ll << 30) && Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k_new->dtype);
     if (kv8) {
-        if ((st = c.pt.table ? check_paged_fp8_served(who8, k_new->dtype, k_new->shape[3], 0)
-                             : check_fp8_served(who8, k_new->dtype, k_new->shape[3], 0)))
-            return st;
+        if ((st = check_pool_served(who8, c.pool, k_new->dtype, k_new->shape[3], 0))) return st;
         if ((st = check_rows16({k_new, v_new}, es, 3, "ring_commit: rows of every tensor must be 16-byte aligned"))) return st;
         return check_rows16({window_k, window_v}, 1, 3, "ring_commit: rows of every tensor must be 16-byte aligned");
     }
@@ -701,19 +727,41 @@ int ring_commit_ragged(const RingCall& c) {
     if ((st = check_commit(c))) return st;
     SFA_CHECK_ARG(c.k_new->shape[0] == 1, "ring_commit_ragged: k_new / v_new must be packed [1, H_kv, T, D] (got shape[0] = %lld)",
                   (long long)c.k_new->shape[0]);
-    if (c.pt.table && c.cache_es != 1 &&
-        (st = check_paged_served("ring_commit_ragged_paged", c.k_new->dtype, c.k_new->shape[3], 0)))
+    if (c.pool.pt.table && !c.pool.fp8 &&
+        (st = check_pool_served(Who("ring_commit_ragged", c.pool), c.pool, c.k_new->dtype, c.k_new->shape[3], 0)))
         return st;
     return ring_commit_dyn_launch(c);
 }
 
-// sfa_ring_fill_varlen (slots null: sequence i -> cache row i of n_seq) and sfa_ring_fill_varlen_slots (pool)
+// the packed commit entry points, sfa_ring_commit_path_ragged{,_fp8,_paged,_paged_fp8}_slots; n_slots: the S of a paged
+// pool, whose page buffers do not tell it
+int commit_ragged_slots(const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
+                        const sfa_tensor* v_new, const int32_t* count, const int32_t* path, const int32_t* cu_q, int n_seq,
+                        int32_t* state, const int32_t* slots, void* stream, const PoolIn& in = PoolIn{}, int n_slots = 0) {
+    g_err[0] = 0;
+    PagedRing ring;
+    SlotPool pool;
+    int st;
+    if ((st = pool_of("ring_commit_ragged", in, n_slots, &window_k, &window_v, &ring, &pool))) return st;
+    SFA_NEED(slots, "slots");
+    SFA_NEED(cu_q, "cu_q");
+    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
+    RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
+    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq, c.pool = pool;
+    return ring_commit_ragged(c);
+}
+
+// sfa_ring_fill_varlen (slots null: sequence i -> cache row i of n_seq) and the slot prefills
+// sfa_ring_fill_varlen{,_fp8,_paged,_paged_fp8}_slots (pool; `in` names its kind)
 int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                 const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu_seqlens,
-                int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool, bool kv8 = false,
-                const float* kv_scale = nullptr, const PageTable* pt = nullptr) {
+                int n_seq, int32_t* state, void* stream, const int32_t* slots, bool pool, const PoolIn& in = PoolIn{}) {
     g_err[0] = 0;
+    PagedRing ring;
+    SlotPool kind;
     int st;
+    if ((st = pool_of("ring_fill_varlen", in, sink_k ? sink_k->shape[0] : 1, &window_k, &window_v, &ring, &kind))) return st;
+    const bool kv8 = kind.fp8;
     if ((st = check_tensor(sink_k, "sink_k", kv8)) || (st = check_tensor(sink_v, "sink_v", kv8)) ||
         (st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
         (st = check_tensor(k, "k")) || (st = check_tensor(v, "v")))
@@ -726,9 +774,9 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(!pool || slots != nullptr, "slots: null device pointer");
     SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
     SFA_CHECK_ARG(k->shape[0] == 1, "packed layout: k / v must be [1, H_kv, T, D] (batch dim %lld)", (long long)k->shape[0]);
-    const char* who8 = pt ? "ring_fill_varlen_paged_fp8" : "ring_fill_varlen_fp8";
+    const Who who("ring_fill_varlen", kind);
     if (kv8) {      // sfa_ring_fill_varlen_fp8_slots, sfa_ring_fill_varlen_paged_fp8_slots
-        if ((st = check_fp8_dtypes(who8, sink_k, window_k, k, v, "k and v"))) return st;
+        if ((st = check_fp8_dtypes(who, sink_k, window_k, k, v, "k and v"))) return st;
     } else
         SFA_CHECK_ARG(k->dtype == sink_k->dtype && k->dtype == window_k->dtype,
                       "k / v and the cache buffers must share one dtype");
@@ -747,29 +795,29 @@ int fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_te
     SFA_CHECK_ARG(k->shape[2] < (1ll << 30) && sink_k->shape[2] + Wc < (1ll << 30), "problem too large");
     const int es = dtype_size(k->dtype);
     if (kv8) {
-        if ((st = pt ? check_paged_fp8_served(who8, k->dtype, D, 0) : check_fp8_served(who8, k->dtype, D, 0))) return st;
+        if ((st = check_pool_served(who, kind, k->dtype, D, 0))) return st;
         if ((st = check_rows16({k, v}, es, 7, "ring_fill_varlen: rows of every tensor must be 16-byte aligned")) ||
             (st = check_rows16({sink_k, sink_v, window_k, window_v}, 1, 7,
                                "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
             return st;
         return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
-                                       (hipStream_t)stream, slots, kv_scale, pt);
+                                       (hipStream_t)stream, slots, kind);
     }
     SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_fill_varlen: K/V rows must be a multiple of 16 bytes (head dim %lld)",
                   (long long)D);
     if ((st = check_rows16({sink_k, sink_v, window_k, window_v, k, v}, es, 7,
                            "ring_fill_varlen: rows of every tensor must be 16-byte aligned")))
         return st;
-    if (pt && (st = check_paged_served("ring_fill_varlen_paged", k->dtype, D, 0))) return st;
+    if (kind.pt.table && (st = check_pool_served(who, kind, k->dtype, D, 0))) return st;
     return ring_fill_varlen_launch(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state,
-                                   (hipStream_t)stream, slots, nullptr, pt);
+                                   (hipStream_t)stream, slots, kind);
 }
 
 // sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools.  The device arrays (slots,
 // state) are not looked at: skipped pairs are decided by the kernel
 int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream,
-               const PageTable* src_pt = nullptr, const PageTable* dst_pt = nullptr) {
+               const SlotPool& src_pool = SlotPool{}, const SlotPool& dst_pool = SlotPool{}) {
     g_err[0] = 0;
     static const char* const names[8] = {"src_sink_k", "src_sink_v", "src_window_k", "src_window_v",
                                          "dst_sink_k", "dst_sink_v", "dst_window_k", "dst_window_v"};
@@ -811,9 +859,10 @@ int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const s
     if ((st = check_rows16({src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3]}, es, 7,
                            "ring_copy_slots: rows of every tensor must be 16-byte aligned")))
         return st;
-    if (src_pt && (st = check_paged_served("ring_copy_paged", src[0]->dtype, D, 0, true))) return st;      // FP8 pages: bytes
+    if (src_pool.pt.table && (st = check_pool_served(Who("ring_copy", src_pool), src_pool, src[0]->dtype, D, 0, true)))
+        return st;      // FP8 pages: bytes
     return ring_copy_slots_launch(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, (hipStream_t)stream,
-                                  src_pt, dst_pt);
+                                  src_pool, dst_pool);
 }
 
 }  // namespace
@@ -921,43 +970,19 @@ size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv,
 
 int sfa_decode_ring_ragged_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, const int32_t* slots,
                                  const int32_t* cu_q, int n_seq, SFA_TAIL_PARAMS) {
-    g_err[0] = 0;
-    SFA_NEED(state, "state");
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = SFA_ATTEND_CALL;
-    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
-    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+    return ragged_slots(SFA_ATTEND_CALL, nullptr, nullptr, commit, state, slots, cu_q, n_seq);
 }
 
 int sfa_decode_ring_ragged_tree_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
                                       int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
                                       SFA_TAIL_PARAMS) {
-    g_err[0] = 0;
-    SFA_NEED(state, "state");
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = SFA_ATTEND_CALL;
-    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.parent = parent, c.commit_seq = commit_seq;
-    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+    return ragged_slots(SFA_ATTEND_CALL, parent, commit_seq, commit, state, slots, cu_q, n_seq);
 }
 
 int sfa_decode_ring_ragged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
                                      int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
                                      const float* kv_scale, SFA_TAIL_PARAMS) {
-    g_err[0] = 0;
-    SFA_NEED(state, "state");
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = SFA_ATTEND_CALL;
-    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.parent = parent, c.commit_seq = commit_seq;
-    c.kv_scale = kv_scale, c.cache_es = 1;
-    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+    return ragged_slots(SFA_ATTEND_CALL, parent, commit_seq, commit, state, slots, cu_q, n_seq, PoolIn{true, kv_scale});
 }
 
 int sfa_decode_ring_tree(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v, int64_t sink_len,
@@ -1031,82 +1056,43 @@ int sfa_ring_commit_path_slots(SFA_COMMIT_PARAMS, const int32_t* path, int64_t p
 
 int sfa_ring_commit_path_ragged_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
                                       int32_t* state, const int32_t* slots, void* stream) {
-    g_err[0] = 0;
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
-    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
-    return ring_commit_ragged(c);
+    return commit_ragged_slots(window_k, window_v, k_new, v_new, count, path, cu_q, n_seq, state, slots, stream);
 }
 
 int sfa_ring_commit_path_ragged_fp8_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
                                           int32_t* state, const int32_t* slots, const float* kv_scale, void* stream) {
-    g_err[0] = 0;
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = commit_call(window_k, window_v, k_new, v_new, count, RingState::Rows, state, slots, stream);
-    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.kv_scale = kv_scale, c.cache_es = 1;
-    return ring_commit_ragged(c);
+    return commit_ragged_slots(window_k, window_v, k_new, v_new, count, path, cu_q, n_seq, state, slots, stream,
+                               PoolIn{true, kv_scale});
 }
 
 int sfa_ring_fill_varlen_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                                    const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
                                    const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
                                    const float* kv_scale, void* stream) {
-    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true, true,
-                       kv_scale);
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true,
+                       PoolIn{true, kv_scale});
 }
 
 int sfa_decode_ring_ragged_paged_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
                                        int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
                                        const int32_t* page_table, int table_stride, SFA_TAIL_PARAMS) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("decode_ragged_paged", window_k, window_v, page_table, table_stride, sink_k ? sink_k->shape[0] : 1, &ring)))
-        return st;
-    SFA_NEED(state, "state");
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = attend_call(q, sink_k, sink_v, &ring.k, &ring.v, k_new, v_new, o, s_aux, workspace, workspace_bytes, scale,
-                             flags, stream);
-    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.parent = parent, c.commit_seq = commit_seq;
-    c.pt = ring.pt;
-    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+    return ragged_slots(SFA_ATTEND_CALL, parent, commit_seq, commit, state, slots, cu_q, n_seq,
+                        PoolIn{false, nullptr, true, page_table, table_stride});
 }
 
 int sfa_ring_commit_path_ragged_paged_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
                                             int32_t* state, const int32_t* slots, const int32_t* page_table,
                                             int table_stride, int n_slots, void* stream) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("ring_commit_ragged_paged", window_k, window_v, page_table, table_stride, n_slots, &ring))) return st;
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = commit_call(&ring.k, &ring.v, k_new, v_new, count, RingState::Rows, state, slots, stream);
-    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.pt = ring.pt;
-    return ring_commit_ragged(c);
+    return commit_ragged_slots(window_k, window_v, k_new, v_new, count, path, cu_q, n_seq, state, slots, stream,
+                               PoolIn{false, nullptr, true, page_table, table_stride}, n_slots);
 }
 
 int sfa_ring_fill_varlen_paged_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                                      const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v,
                                      const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
                                      const int32_t* page_table, int table_stride, void* stream) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("ring_fill_varlen_paged", window_k, window_v, page_table, table_stride, sink_k ? sink_k->shape[0] : 1, &ring)))
-        return st;
-    return fill_varlen(sink_k, sink_v, &ring.k, &ring.v, k, v, cu_seqlens, n_seq, state, stream, slots, true, false, nullptr,
-                       &ring.pt);
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true,
+                       PoolIn{false, nullptr, true, page_table, table_stride});
 }
 
 int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const sfa_tensor* src_window_k,
@@ -1127,47 +1113,23 @@ int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* sr
                   (long long)sr.pt.page_size, (long long)dr.pt.page_size);
     const sfa_tensor* const src[4] = {src_sink_k, src_sink_v, &sr.k, &sr.v};
     const sfa_tensor* const dst[4] = {dst_sink_k, dst_sink_v, &dr.k, &dr.v};
-    return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream, &sr.pt, &dr.pt);
+    return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream, SlotPool{false, nullptr, sr.pt},
+                      SlotPool{false, nullptr, dr.pt});
 }
 
-// the *_paged_fp8_slots calls: the descriptor of the paged call with kv_scale and cache_es = 1 set beside pt
 int sfa_decode_ring_ragged_paged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* parent, const int32_t* commit_seq, int commit,
                                            int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
                                            const int32_t* page_table, int table_stride, const float* kv_scale,
                                            SFA_TAIL_PARAMS) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("decode_ragged_paged_fp8", window_k, window_v, page_table, table_stride,
-                         sink_k ? sink_k->shape[0] : 1, &ring, true)))
-        return st;
-    SFA_NEED(state, "state");
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = attend_call(q, sink_k, sink_v, &ring.k, &ring.v, k_new, v_new, o, s_aux, workspace, workspace_bytes, scale,
-                             flags, stream);
-    c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.parent = parent, c.commit_seq = commit_seq;
-    c.pt = ring.pt, c.kv_scale = kv_scale, c.cache_es = 1;
-    return ring_ragged(device_state(c, RingState::Rows, state, slots));
+    return ragged_slots(SFA_ATTEND_CALL, parent, commit_seq, commit, state, slots, cu_q, n_seq,
+                        PoolIn{true, kv_scale, true, page_table, table_stride});
 }
 
 int sfa_ring_commit_path_ragged_paged_fp8_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,
                                                 int32_t* state, const int32_t* slots, const int32_t* page_table,
                                                 int table_stride, int n_slots, const float* kv_scale, void* stream) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("ring_commit_ragged_paged_fp8", window_k, window_v, page_table, table_stride, n_slots, &ring, true)))
-        return st;
-    SFA_NEED(slots, "slots");
-    SFA_NEED(cu_q, "cu_q");
-    SFA_CHECK_ARG(n_seq >= 1, "ring_commit_ragged: n_seq (%d) must be at least 1", n_seq);
-    RingCall c = commit_call(&ring.k, &ring.v, k_new, v_new, count, RingState::Rows, state, slots, stream);
-    c.path = path, c.cu_q = cu_q, c.n_seq = n_seq;
-    c.pt = ring.pt, c.kv_scale = kv_scale, c.cache_es = 1;
-    return ring_commit_ragged(c);
+    return commit_ragged_slots(window_k, window_v, k_new, v_new, count, path, cu_q, n_seq, state, slots, stream,
+                               PoolIn{true, kv_scale, true, page_table, table_stride}, n_slots);
 }
 
 int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
@@ -1175,14 +1137,8 @@ int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_ten
                                          const int32_t* cu_seqlens, int n_seq, int32_t* state, const int32_t* slots,
                                          const int32_t* page_table, int table_stride, const float* kv_scale,
                                          void* stream) {
-    g_err[0] = 0;
-    PagedRing ring;
-    int st;
-    if ((st = paged_ring("ring_fill_varlen_paged_fp8", window_k, window_v, page_table, table_stride,
-                         sink_k ? sink_k->shape[0] : 1, &ring, true)))
-        return st;
-    return fill_varlen(sink_k, sink_v, &ring.k, &ring.v, k, v, cu_seqlens, n_seq, state, stream, slots, true, true, kv_scale,
-                       &ring.pt);
+    return fill_varlen(sink_k, sink_v, window_k, window_v, k, v, cu_seqlens, n_seq, state, stream, slots, true,
+                       PoolIn{true, kv_scale, true, page_table, table_stride});
 }
 
 int sfa_ring_fill_varlen(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,

@@ -62,8 +62,6 @@ template <> struct Mma<f16_t> {
 struct Kv8Args {
     const float* scale;
 };
-__device__ __forceinline__ Kv8Args kv8_of() { return Kv8Args{nullptr}; }
-__device__ __forceinline__ const Kv8Args& kv8_of(const Kv8Args& kv) { return kv; }
 
 // the scale of KV head hk: row 0 for K, 1 for V
 __device__ __forceinline__ float kv8_scale(const Kv8Args& kv, int row, int Hkv, int hk) {
@@ -173,14 +171,6 @@ struct RaggedArgs {
     const int* commit_seq;       // [n_seq], device, or null
 };
 
-// the second argument of a ragged kernel instance (`RA...` is empty for every other instance: its signature, argument
-// block and code stay those of a kernel without the flag)
-__device__ __forceinline__ RaggedArgs ragged_of() { return RaggedArgs{}; }
-__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg) { return rg; }
-__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const Kv8Args&) { return rg; }
-__device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&) { return Kv8Args{nullptr}; }
-__device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Args& kv) { return kv; }
-
 // ---- paged pool (the *_paged_slots calls).  The ring buffers are PAGES [n_pages, Hkv, P, D] (the
 // page index where the slot index was, same strides); table[c * stride + j] is the page that holds ring slots
 // [j P, (j + 1) P) of cache row c.  P = 1 << shift >= kTile, Wc = stride * P, so a 32-slot ring tile lies inside one page.
@@ -192,21 +182,23 @@ struct PageArgs {
     int shift;
     int npages;
 };
-__device__ __forceinline__ PageArgs page_of() { return PageArgs{}; }
-__device__ __forceinline__ PageArgs page_of(const Kv8Args&) { return PageArgs{}; }
-__device__ __forceinline__ const PageArgs& page_of(const PageArgs& pg) { return pg; }
-__device__ __forceinline__ PageArgs page_of(const RaggedArgs&) { return PageArgs{}; }
-__device__ __forceinline__ PageArgs page_of(const RaggedArgs&, const Kv8Args&) { return PageArgs{}; }
-__device__ __forceinline__ const PageArgs& page_of(const RaggedArgs&, const PageArgs& pg) { return pg; }
-__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const PageArgs&) { return rg; }
-__device__ __forceinline__ Kv8Args kv8_of(const PageArgs&) { return Kv8Args{nullptr}; }
-__device__ __forceinline__ Kv8Args kv8_of(const RaggedArgs&, const PageArgs&) { return Kv8Args{nullptr}; }
-// the paged FP8 pool: (RaggedArgs, Kv8Args, PageArgs) behind MultiArgs, (Kv8Args, PageArgs) behind a storing kernel's own
-__device__ __forceinline__ const RaggedArgs& ragged_of(const RaggedArgs& rg, const Kv8Args&, const PageArgs&) { return rg; }
-__device__ __forceinline__ const Kv8Args& kv8_of(const RaggedArgs&, const Kv8Args& kv, const PageArgs&) { return kv; }
-__device__ __forceinline__ const PageArgs& page_of(const RaggedArgs&, const Kv8Args&, const PageArgs& pg) { return pg; }
-__device__ __forceinline__ const Kv8Args& kv8_of(const Kv8Args& kv, const PageArgs&) { return kv; }
-__device__ __forceinline__ const PageArgs& page_of(const Kv8Args&, const PageArgs& pg) { return pg; }
+
+// The optional trailing arguments of a kernel (`RA...` behind MultiArgs, `KA...` behind a storing kernel's own): of
+// RaggedArgs, Kv8Args and PageArgs, in that order, an instance takes the ones its flags name and no other - its
+// signature, argument block and code stay those of a kernel without the others.  arg_of<W>(pack...) is the member of
+// type W by reference, or a W of zeros where the instance takes none (Kv8Args: scale null = all ones).
+template <typename W>
+__device__ __forceinline__ W arg_of() { return W{}; }
+template <typename W, typename A0, typename... A>
+__device__ __forceinline__ decltype(auto) arg_of(const A0& a0, const A&... rest) {
+    if constexpr (std::is_same_v<W, A0>) return (a0);
+    else return arg_of<W>(rest...);
+}
+// the guard of every kernel with such a pack: exactly the arguments that the flags name (their order is dispatch_pool's)
+template <bool Ragged, bool KV8, bool Paged, typename... A>
+constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) &&
+                         (std::is_same_v<A, RaggedArgs> || ...) == Ragged && (std::is_same_v<A, Kv8Args> || ...) == KV8 &&
+                         (std::is_same_v<A, PageArgs> || ...) == Paged;
 
 // the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
 // of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
@@ -580,13 +572,13 @@ template <typename T, int D, bool Dyn, bool Tree, bool Slots = false, bool Ragge
           bool Paged = false, typename... RA>
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && Ragged && D == 80) ? 2 : 1)))
 void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
-                      !(KV8 && !Ragged) && !(Paged && !Ragged),
+    static_assert(tail_is<Ragged, KV8, Paged, RA...> && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged) &&
+                      !(Paged && !Ragged),
                   "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args); paged pool: (MultiArgs, "
                   "RaggedArgs, PageArgs); paged FP8 pool: (MultiArgs, RaggedArgs, Kv8Args, PageArgs)");
-    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
-    [[maybe_unused]] const Kv8Args kv = kv8_of(ra...);
-    [[maybe_unused]] const PageArgs pg = page_of(ra...);
+    [[maybe_unused]] const RaggedArgs& rg = arg_of<RaggedArgs>(ra...);
+    [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ra...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
@@ -933,8 +925,8 @@ __device__ __forceinline__ bool ragged_row(const MultiArgs& a, const RaggedArgs&
 // f32-accumulate path: one wave per (partial row, split); lane owns columns lane + 64 j.  Keys one at a time.
 template <typename T, bool Dyn, bool Tree, bool Slots = false, bool Ragged = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_split_f32_kernel(MultiArgs a, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
-    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
+    static_assert(tail_is<Ragged, false, false, RA...> && !(Ragged && (!Dyn || !Slots)), "ragged: (MultiArgs, RaggedArgs)");
+    [[maybe_unused]] const RaggedArgs& rg = arg_of<RaggedArgs>(ra...);
     constexpr int MAXJ = 8;   // D <= 512 (1 KiB rows of 16-bit types; fp32 stops at 256)
     const int lane = threadIdx.x & 63;
     const int64_t rowid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1077,10 +1069,9 @@ __device__ __forceinline__ void commit_piece(const MultiArgs& a, int64_t item, i
 // Q (store_piece): void, or the chunk's 16-bit type when the pool is FP8 - es stays the chunk's element size, a piece 8
 // elements.
 // Paged: a ring slot is stored into row slot mod P of its page (page_at); a slot on an unmapped page is dropped.
-template <typename Q = void, bool Paged = false>
+template <typename Q, bool Paged>
 __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const RaggedArgs& rg, int64_t item, int es,
-                                                    const Kv8Args& kv = Kv8Args{nullptr},
-                                                    [[maybe_unused]] const PageArgs& pg = PageArgs{}) {
+                                                    const Kv8Args& kv, [[maybe_unused]] const PageArgs& pg) {
     const int cpr = a.D * es / 16;
     if (item >= (int64_t)a.Hkv * rg.T * cpr) return;
     const int ch = (int)(item % cpr);
@@ -1134,20 +1125,17 @@ __device__ __forceinline__ void commit_piece_ragged(const MultiArgs& a, const Ra
 // KV8 and Paged: the commit blocks quantise as they store through the table.
 template <typename T, bool Dyn, bool Slots = false, bool Ragged = false, bool KV8 = false, bool Paged = false, typename... RA>
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred, RA... ra) {
-    static_assert(sizeof...(RA) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) && !(Ragged && (!Dyn || !Slots)) &&
-                      !(KV8 && !Ragged) && !(Paged && !Ragged),
+    static_assert(tail_is<Ragged, KV8, Paged, RA...> && !(Ragged && (!Dyn || !Slots)) && !(KV8 && !Ragged) &&
+                      !(Paged && !Ragged),
                   "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 "
                   "pool: (..., Kv8Args, PageArgs)");
-    [[maybe_unused]] const RaggedArgs& rg = ragged_of(ra...);
+    [[maybe_unused]] const RaggedArgs& rg = arg_of<RaggedArgs>(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
-        if constexpr (Paged && KV8)
-            commit_piece_ragged<T, true>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...), page_of(ra...));
-        else if constexpr (Paged)
-            commit_piece_ragged<void, true>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, Kv8Args{nullptr}, page_of(ra...));
-        else if constexpr (KV8) commit_piece_ragged<T>(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, kv8_of(ra...));
-        else if constexpr (Ragged) commit_piece_ragged(a, rg, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es);
-        else commit_piece<false, Slots>(a, (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x, es, nullptr);
+        const int64_t item = (int64_t)(blockIdx.x - nred) * 256 + threadIdx.x;
+        if constexpr (Ragged)
+            commit_piece_ragged<std::conditional_t<KV8, T, void>, Paged>(a, rg, item, es, arg_of<Kv8Args>(ra...), arg_of<PageArgs>(ra...));
+        else commit_piece<false, Slots>(a, item, es, nullptr);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -1235,7 +1223,7 @@ __global__ __launch_bounds__(256) void ring_commit_slots_kernel(MultiArgs a, con
 template <typename Q = void, bool Paged = false, typename... KA>
 __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, RaggedArgs rg, const int* count, int es,
                                                                  KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0),
+    static_assert(tail_is<false, !std::is_void_v<Q>, Paged, KA...>,
                   "FP8 ring: (..., Kv8Args); paged ring: (..., PageArgs); paged FP8 ring: (..., Kv8Args, PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int cpr = a.D * es / 16;
@@ -1260,7 +1248,7 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
     int slot = (int)(((int64_t)state_wp(a, c) + j) % a.wc);
     int drow = c;                // the ring's row of its buffer: the cache row, or the slot's page
     if constexpr (Paged) {
-        const PageArgs& pg = page_of(ka...);
+        const PageArgs& pg = arg_of<PageArgs>(ka...);
         if ((drow = page_at(pg, c, slot)) < 0) return;
         slot = page_row(pg, slot);
     }
@@ -1275,7 +1263,7 @@ __global__ __launch_bounds__(256) void ring_commit_ragged_kernel(MultiArgs a, Ra
     const char* vs = a.vn.ptr + ((int64_t)hk * a.vn.sh + row * a.vn.sn) * es + so;
     char* kd = a.wk.ptr + ((int64_t)drow * a.wk.sb + (int64_t)hk * a.wk.sh + (int64_t)slot * a.wk.sn) * ed + dso;
     char* vd = a.wv.ptr + ((int64_t)drow * a.wv.sb + (int64_t)hk * a.wv.sh + (int64_t)slot * a.wv.sn) * ed + dso;
-    store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), a.Hkv, hk);
+    store_piece<Q>(kd, vd, ks, vs, arg_of<Kv8Args>(ka...), a.Hkv, hk);
 }
 
 // sfa_ring_fill_varlen: the prefill placement of SinkCacheLayer._prefill for every sequence of a packed [1, Hkv, T, D]
@@ -1295,7 +1283,7 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
                                                                const int* cu, int* state, int n_seq, int Hkv, int ns,
                                                                int wc, int T, int cpr, int es, const int* slots,
                                                                int npool, KA... ka) {
-    static_assert(sizeof...(KA) == (std::is_void_v<Q> ? 0 : 1) + (Paged ? 1 : 0) && !(Paged && !Slots),
+    static_assert(tail_is<false, !std::is_void_v<Q>, Paged, KA...> && !(Paged && !Slots),
                   "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 pool: (..., Kv8Args, PageArgs)");
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nj = ns + wc;
@@ -1322,7 +1310,7 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     int drow = c;                // the destination's row of its buffer: the cache row, or the page of a ring slot
     if constexpr (Paged) {
         if (j >= ns) {
-            const PageArgs& pg = page_of(ka...);
+            const PageArgs& pg = arg_of<PageArgs>(ka...);
             if ((drow = page_at(pg, c, row)) < 0) return;
             row = page_row(pg, row);
         }
@@ -1333,7 +1321,7 @@ __global__ __launch_bounds__(256) void ring_fill_varlen_kernel(View sk, View sv,
     const char* vs = v.ptr + ((int64_t)hk * v.sh + tok * v.sn) * es + so;
     char* kd = dk->ptr + ((int64_t)drow * dk->sb + (int64_t)hk * dk->sh + (int64_t)row * dk->sn) * ed + dso;
     char* vd = dv->ptr + ((int64_t)drow * dv->sb + (int64_t)hk * dv->sh + (int64_t)row * dv->sn) * ed + dso;
-    store_piece<Q>(kd, vd, ks, vs, kv8_of(ka...), Hkv, hk);
+    store_piece<Q>(kd, vd, ks, vs, arg_of<Kv8Args>(ka...), Hkv, hk);
 }
 
 // sfa_ring_copy_slots: pair i copies slot s = src_slots[i] of the source pool into slot d = dst_slots[i] of the
@@ -1553,6 +1541,39 @@ void dispatch_mode(const MultiArgs& a, const RaggedArgs* rg, F&& f) {
     else f(Mode<false, false, false, false>{});
 }
 
+// the table argument of a paged pool (pt.table set): the API has checked that P is a power of two
+PageArgs page_args(const PageTable& pt) {
+    int shift = 0;
+    while ((1ll << shift) < pt.page_size) ++shift;
+    return PageArgs{pt.table, (int)pt.stride, shift, (int)pt.n_pages};
+}
+
+// The pool forms of the instances, one line per kind of pool: f gets the (KV8, Paged) of the kernels that read a pool and
+// the Q of the ones that store into it (void: the rows are copied; FP8: the 16-bit type `act_dtype` of the activations,
+// which are quantised - a launcher of kernels that only read the pool leaves it out), then the trailing arguments of
+// that form: none, (Kv8Args), (PageArgs) or (Kv8Args, PageArgs).  A further kind of pool is a field of SlotPool, its
+// kernel argument and its lines here.
+template <typename Q_, bool Paged_>
+struct PoolForm {
+    using Q = Q_;
+    static constexpr bool KV8 = !std::is_void_v<Q_>, Paged = Paged_;
+};
+
+template <typename F>
+void dispatch_pool(const SlotPool& pool, F&& f, int act_dtype = SFA_DTYPE_BF16) {
+    const Kv8Args kv{pool.kv_scale};
+    const bool f16 = act_dtype == SFA_DTYPE_F16;
+    if (!pool.fp8 && !pool.pt.table) f(PoolForm<void, false>{});
+    else if (!pool.fp8) f(PoolForm<void, true>{}, page_args(pool.pt));
+    else if (!pool.pt.table) f16 ? f(PoolForm<f16_t, false>{}, kv) : f(PoolForm<bf16_t, false>{}, kv);
+    else f16 ? f(PoolForm<f16_t, true>{}, kv, page_args(pool.pt)) : f(PoolForm<bf16_t, true>{}, kv, page_args(pool.pt));
+}
+
+// the tail of sfa_last_path that names the pool
+const char* pool_tag(const SlotPool& pool) {
+    return pool.fp8 ? (pool.pt.table ? "_paged_kvfp8" : "_kvfp8") : pool.pt.table ? "_paged" : "";
+}
+
 // launch_status of a split launch: decode_{multi,tree}_{mfma,f32}[_slots | _ragged]
 int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
     char tag[40];
@@ -1560,44 +1581,41 @@ int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
     return launch_status(tag);
 }
 
-// kv (packed calls only): the FP8 pool - the (Dyn, Slots, Ragged) instances with the cache format, Tree on or off
-// pg (packed calls only): the paged pool - the same instances with the table lookup
-// kv and pg: the paged FP8 pool - the same instances with both
+// pool (packed calls only): the (Dyn, Slots, Ragged) instances in the form of the pool, Tree on or off
 template <typename T, int D>
-int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, hipStream_t stream) {
+int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, hipStream_t stream) {
     const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
-        if constexpr (M::Ragged) {
-            if (kv && pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv, *pg);
-            else if (pg) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, false, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *pg);
-            else if (kv) multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, *kv);
-            else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg);
-        }
+        if constexpr (M::Ragged)
+            dispatch_pool(pool, [&](auto p, auto... tail) {
+                using P = decltype(p);
+                multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(a, *rg, tail...);
+            });
         else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots><<<grid, kWaves * 64, 0, stream>>>(a);
     });
     return split_status(a, rg, "mfma");
 }
 
 template <typename T>
-int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, hipStream_t stream) {
+int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, hipStream_t stream) {
     switch (a.D) {
-        case 64: return launch_mfma<T, 64>(a, rg, kv, pg, stream);
-        case 80: return launch_mfma<T, 80>(a, rg, kv, pg, stream);
-        case 96: return launch_mfma<T, 96>(a, rg, kv, pg, stream);
-        case 128: return launch_mfma<T, 128>(a, rg, kv, pg, stream);
+        case 64: return launch_mfma<T, 64>(a, rg, pool, stream);
+        case 80: return launch_mfma<T, 80>(a, rg, pool, stream);
+        case 96: return launch_mfma<T, 96>(a, rg, pool, stream);
+        case 128: return launch_mfma<T, 128>(a, rg, pool, stream);
     }
     set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
     return SFA_ERR_UNSUPPORTED;
 }
 
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
-// kv / pg: the FP8 / paged pool of a packed call, both for a paged FP8 one (the API admits them for the MFMA instances only)
+// pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
-int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, const PageArgs* pg, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, kv, pg, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, pool, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
         dispatch_mode(a, rg, [&](auto m) {
@@ -1617,23 +1635,12 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const Kv8Args* kv, con
     const dim3 rgrid((unsigned)(nred + ncommit));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
-        if constexpr (M::Ragged) {
-            if constexpr (sizeof(T) == 2) {
-                if (kv && pg) {
-                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, true, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *kv, *pg);
-                    return;
-                }
-                if (pg) {
-                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, false, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *pg);
-                    return;
-                }
-                if (kv) {
-                    multi_reduce_kernel<T, M::Dyn, M::Slots, true, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, *kv);
-                    return;
-                }
-            }
-            multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
-        }
+        if constexpr (M::Ragged && sizeof(T) == 2)
+            dispatch_pool(pool, [&](auto p, auto... tail) {
+                using P = decltype(p);
+                multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail...);
+            });
+        else if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
         else multi_reduce_kernel<T, M::Dyn, M::Slots><<<rgrid, 256, 0, stream>>>(a, nred);
     });
     if ((st = launch_status(rg ? "decode_multi_reduce_ragged" : "decode_multi_reduce"))) return st;
@@ -1669,30 +1676,18 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
     return a;
 }
 
-// the table argument of a paged call (pt.table set): the API has checked that P is a power of two
-PageArgs page_args(const PageTable& pt) {
-    int shift = 0;
-    while ((1ll << shift) < pt.page_size) ++shift;
-    return PageArgs{pt.table, (int)pt.stride, shift, (int)pt.n_pages};
-}
-
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
-int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
-                 const Kv8Args* kv = nullptr, const PageArgs* pg = nullptr) {
+int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
-    if (kv && !*mfma) {         // refused by the API before: no f32-accumulate instance reads an FP8 pool
-        set_error("%s: no kernel instance for this call", pg ? "decode_ragged_paged_fp8" : "decode_ragged_fp8");
+    if ((c.pool.fp8 || c.pool.pt.table) && !*mfma) {    // refused by the API before: no f32-accumulate instance reads an FP8 or a paged pool
+        set_error("decode_ragged%s%s: no kernel instance for this call", c.pool.pt.table ? "_paged" : "", c.pool.fp8 ? "_fp8" : "");
         return SFA_ERR_UNSUPPORTED;
     }
-    if (pg && !*mfma) {         // refused by the API before: no f32-accumulate instance reads a paged pool
-        set_error("decode_ragged_paged: no kernel instance for this call");
-        return SFA_ERR_UNSUPPORTED;
-    }
-    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, nullptr, nullptr, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, kv, pg, *mfma, c.stream);
-    return launch_rest<bf16_t>(a, rg, kv, pg, *mfma, c.stream);
+    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, false, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, *mfma, c.stream);
+    return launch_rest<bf16_t>(a, rg, c.pool, *mfma, c.stream);
 }
 
 }  // namespace
@@ -1810,12 +1805,10 @@ int decode_ragged_launch(const RingCall& c) {
     if ((st = launch_status("ragged_prep"))) return st;
     bool mfma;
     const char* dname;
-    const Kv8Args kv{c.kv_scale};
-    const PageArgs pg = page_args(c.pt);
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cache_es == 1 ? &kv : nullptr, c.pt.table ? &pg : nullptr))) return st;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cache_es == 1 ? (c.pt.table ? "_paged_kvfp8" : "_kvfp8") : c.pt.table ? "_paged" : "");
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }
@@ -1833,23 +1826,15 @@ int ring_commit_dyn_launch(const RingCall& c) {
         }
         int st;
         if (nb > 0) {
-            const Kv8Args kv{c.kv_scale};
             const dim3 grid((unsigned)nb);
-            if (c.pt.table && c.cache_es == 1 && c.k_new->dtype == SFA_DTYPE_F16)
-                ring_commit_ragged_kernel<f16_t, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv, page_args(c.pt));
-            else if (c.pt.table && c.cache_es == 1)
-                ring_commit_ragged_kernel<bf16_t, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv, page_args(c.pt));
-            else if (c.pt.table) ring_commit_ragged_kernel<void, true><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, page_args(c.pt));
-            else if (c.cache_es != 1) ring_commit_ragged_kernel<<<grid, 256, 0, c.stream>>>(a, rg, c.count, es);
-            else if (c.k_new->dtype == SFA_DTYPE_F16) ring_commit_ragged_kernel<f16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
-            else ring_commit_ragged_kernel<bf16_t><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, kv);
+            dispatch_pool(c.pool, [&](auto p, auto... tail) {
+                using P = decltype(p);
+                ring_commit_ragged_kernel<typename P::Q, P::Paged><<<grid, 256, 0, c.stream>>>(a, rg, c.count, es, tail...);
+            }, c.k_new->dtype);
             if ((st = launch_status("ring_commit_path_ragged"))) return st;
         }
         if ((st = launch_advance(a, c.count, &rg, c.stream))) return st;   // after every reader of the state
-        set_path(c.cache_es == 1 && c.pt.table ? "ring_commit_path_ragged_slots_paged_kvfp8"
-                 : c.cache_es == 1 ? "ring_commit_path_ragged_slots_kvfp8"
-                 : c.pt.table  ? "ring_commit_path_ragged_slots_paged"
-                                 : "ring_commit_path_ragged_slots");
+        set_path("ring_commit_path_ragged_slots%s", pool_tag(c.pool));
         return SFA_OK;
     }
     const int64_t ncm = a.n < a.wc ? a.n : a.wc;
@@ -1876,10 +1861,8 @@ int ring_commit_dyn_launch(const RingCall& c) {
 
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const float* kv_scale,
-                            const PageTable* pt) {
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const SlotPool& pool) {
     const int es = dtype_size(k->dtype);
-    const bool kv8 = sink_k->dtype == SFA_DTYPE_FP8_E4M3;       // the API: with slots and 16-bit k / v only
     const int Hkv = (int)k->shape[1], ns = (int)sink_k->shape[2], wc = (int)window_k->shape[2];
     const int cpr = (int)(k->shape[3] * es / 16);
     const int64_t nblk = cdiv64((int64_t)n_seq * Hkv * (ns + wc) * cpr, 256);
@@ -1888,46 +1871,27 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
         return SFA_ERR_UNSUPPORTED;
     }
     if (nblk > 0) {
-        if (kv8 && pt && k->dtype == SFA_DTYPE_F16)
-            ring_fill_varlen_kernel<true, f16_t, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
+        auto launch = [&](auto kernel, auto... tail) {
+            kernel<<<dim3((unsigned)nblk), 256, 0, stream>>>(
                 make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale},
-                page_args(*pt));
-        else if (kv8 && pt)
-            ring_fill_varlen_kernel<true, bf16_t, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale},
-                page_args(*pt));
-        else if (kv8 && k->dtype == SFA_DTYPE_F16)
-            ring_fill_varlen_kernel<true, f16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
-        else if (kv8)
-            ring_fill_varlen_kernel<true, bf16_t><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], Kv8Args{kv_scale});
-        else if (pt)
-            ring_fill_varlen_kernel<true, void, true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0], page_args(*pt));
-        else if (slots)
-            ring_fill_varlen_kernel<true><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, (int)sink_k->shape[0]);
+                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, slots, slots ? (int)sink_k->shape[0] : 0, tail...);
+        };
+        if (!slots) launch(ring_fill_varlen_kernel<false>);     // the API: a pool is all zero without slots
         else
-            ring_fill_varlen_kernel<false><<<dim3((unsigned)nblk), 256, 0, stream>>>(
-                make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k), make_view(v),
-                cu, state, n_seq, Hkv, ns, wc, (int)k->shape[2], cpr, es, nullptr, 0);
+            dispatch_pool(pool, [&](auto p, auto... tail) {
+                using P = decltype(p);
+                launch(ring_fill_varlen_kernel<true, typename P::Q, P::Paged, decltype(tail)...>, tail...);
+            }, k->dtype);
         int st;
         if ((st = launch_status("ring_fill_varlen"))) return st;
     }
-    set_path(kv8 && pt ? "ring_fill_varlen_slots_paged_kvfp8" : kv8 ? "ring_fill_varlen_slots_kvfp8" : pt ? "ring_fill_varlen_slots_paged" : slots ? "ring_fill_varlen_slots" : "ring_fill_varlen");
+    set_path("ring_fill_varlen%s%s", slots ? "_slots" : "", pool_tag(pool));
     return SFA_OK;
 }
 
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
-                           hipStream_t stream, const PageTable* src_pt, const PageTable* dst_pt) {
+                           hipStream_t stream, const SlotPool& src_pool, const SlotPool& dst_pool) {
     const sfa_tensor *sk = src[0], *wk = src[2];
     const int es = dtype_size(wk->dtype);
     const int Hkv = (int)wk->shape[1], ns = (int)sk->shape[2], wc = (int)wk->shape[2];
@@ -1943,16 +1907,16 @@ int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_st
                           const_cast<int*>(src_state), src_slots, (int)wk->shape[0]};
         const CopyPools d{make_view(dst[0]), make_view(dst[1]), make_view(dst[2]), make_view(dst[3]),
                           dst_state, dst_slots, (int)dst[2]->shape[0]};
-        if (src_pt)
+        if (src_pool.pt.table)
             ring_copy_slots_kernel<true><<<dim3((unsigned)grid), 256, 0, stream>>>(
-                s, d, Hkv, ns, wc, cpr, es, (int)nblk, src_state == dst_state ? 1 : 0, page_args(*src_pt), page_args(*dst_pt));
+                s, d, Hkv, ns, wc, cpr, es, (int)nblk, src_state == dst_state ? 1 : 0, page_args(src_pool.pt), page_args(dst_pool.pt));
         else
             ring_copy_slots_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(s, d, Hkv, ns, wc, cpr, es, (int)nblk,
                                                                              src_state == dst_state ? 1 : 0);
         int st;
         if ((st = launch_status("ring_copy_slots"))) return st;
     }
-    set_path(src_pt ? "ring_copy_slots_paged" : "ring_copy_slots");
+    set_path("ring_copy_slots%s", pool_tag(src_pool));
     return SFA_OK;
 }
 

@@ -48,6 +48,18 @@ struct PageTable {
     int64_t stride, page_size, n_pages;
 };
 
+// The slot pool of a packed call (and of the slot prefill and copy), beyond its buffers: the launchers below take it as
+// one value, all zero for a 16-bit contiguous pool and for every call that is not on a pool.
+// fp8 (the *_fp8_slots calls): the cache buffers hold e4m3fn codes, one byte per element against the 2 of the
+// activations; kv_scale = device float [2][H_kv], row 0 K and row 1 V, null = all ones.  Read by the kernels only.
+// pt.table set (the *_paged_slots calls): window_k / window_v are the descriptors described at PageTable.
+// Both (the *_paged_fp8_slots calls): the pages hold codes
+struct SlotPool {
+    bool fp8;
+    const float* kv_scale;
+    PageTable pt;
+};
+
 enum class RingState {
     Host,     // {sink_len, window_len, write_pos} below are the state
     Shared,   // `state` = device {sink_len, window_len, write_pos}, one row for the whole batch (the *_dyn calls)
@@ -86,14 +98,7 @@ struct RingCall {
     // (null: every sequence).  In a packed call `parent` is [T], packed like q, with sequence-local entries, and a
     // packed commit (cu_q set) takes `path` [T] and `count` [n_seq] the same way
     const int32_t* commit_seq;
-    // FP8 pool (the *_fp8_slots calls): the cache buffers hold e4m3fn codes, cache_es = 1 byte per element against the 2
-    // of the activations (every other call: 0, the cache has q's / k_new's dtype); kv_scale = device float [2][H_kv],
-    // row 0 K and row 1 V, null = all ones.  Read by the kernels only
-    const float* kv_scale;
-    int cache_es;
-    // paged pool (the *_paged_slots calls): window_k / window_v are the descriptors described at PageTable
-    // paged FP8 pool (the *_paged_fp8_slots calls): pt, kv_scale and cache_es = 1 are set together, the pages hold codes
-    PageTable pt;
+    SlotPool pool;               // packed calls: the kind of pool the slots belong to (every other call: zero)
 };
 
 // sfa_decode.hip
@@ -124,16 +129,16 @@ int decode_ragged_launch(const RingCall& c);
 int ring_commit_dyn_launch(const RingCall& c);
 // sfa_ring_fill_varlen: per-sequence prefill placement of a packed K/V into [n_seq, Hkv, *, D] buffers + state rows;
 // slots (null: sequence i -> cache row i): sequence i -> row slots[i] of a pool
-// kv_scale: with FP8 pool buffers (k / v stay 16-bit) the rows are quantised as they are stored; null = all ones
+// pool (with slots only): FP8 buffers take k / v in 16 bits and quantise the rows as they are stored, pages are stored
+// through the table
 int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
                             const sfa_tensor* window_v, const sfa_tensor* k, const sfa_tensor* v, const int32_t* cu,
-                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots,
-                            const float* kv_scale = nullptr, const PageTable* pt = nullptr);
+                            int n_seq, int32_t* state, hipStream_t stream, const int32_t* slots, const SlotPool& pool);
 // sfa_ring_copy_slots: src / dst = {sink_k, sink_v, window_k, window_v} of the two pools (the same pool: a fork); pair i
-// copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i].  src_pt / dst_pt (both or none):
-// paged pools, window_k / window_v as described at PageTable
+// copies the live rows and the state row of slot src_slots[i] into slot dst_slots[i].  The pools are both paged or both
+// contiguous; the copy moves bytes, so of a pool it reads pt alone
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
-                           hipStream_t stream, const PageTable* src_pt = nullptr, const PageTable* dst_pt = nullptr);
+                           hipStream_t stream, const SlotPool& src_pool, const SlotPool& dst_pool);
 
 }  // namespace sfa

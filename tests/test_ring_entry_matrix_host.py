@@ -1,4 +1,5 @@
-"""CPU-only characterisation of the argument checks of all 23 sink + ring cache entry points of libsfa.so: a table of
+"""CPU-only characterisation of the argument checks of 33 sink + ring cache entry points of libsfa.so (the 23 calls on
+16-bit contiguous caches and the ten calls on an FP8, a paged or a paged FP8 slot pool): a table of
 entry point x defect, each cell the status code and the exact sfa_last_error() text; a second table of combined defects
 that pins which message wins (the order of the checks); and the empty-shape calls that return SFA_OK without a launch.
 Host tensors stand in for device memory as in tests/test_slots_host.py: every call here returns before any launch, so
@@ -9,7 +10,8 @@ import torch
 from sink_attention import _native as N
 
 B, S, HQ, HKV, NN, D, NS, W, T = 2, 5, 8, 2, 3, 64, 4, 16, 6
-BF, FP = torch.bfloat16, torch.float16
+PG, PER, NPG = 32, 2, 7                          # paged pools: page size, pages per slot (Wc = 64), pages of the pool
+BF, FP, F32, FP8 = torch.bfloat16, torch.float16, torch.float32, torch.float8_e4m3fn
 
 
 def _z(*shape, dtype=BF):
@@ -21,10 +23,14 @@ def _odd(*shape, dtype=BF):
     return torch.zeros(*shape[:3], shape[3] + 1, dtype=dtype)[..., :shape[3]]
 
 
-def _tensors(mk=_z, dtype=BF, b=B, s=S, hq=HQ, n=NN, t=T):
+def _tensors(mk=_z, dtype=BF, b=B, s=S, hq=HQ, n=NN, t=T, pg=PG):
     """q / kn / vn / o: a chunk of n tokens for b batch rows; q1 / k1 / v1 / o1: one token; qp / kp / vp / op: a pack of
-    t rows; sk .. wv: the cache of b rows; psk .. pwv: a pool of s slots"""
-    return dict(q=mk(b, hq, n, D, dtype=dtype), kn=mk(b, HKV, n, D, dtype=dtype), vn=mk(b, HKV, n, D, dtype=dtype),
+    t rows; sk .. wv: the cache of b rows; psk .. pwv: a pool of s slots; fsk .. fwv: that pool in FP8; gk / gv: the
+    pages of a paged pool (its sinks are psk / psv), hk / hv: FP8 pages (sinks fsk / fsv)"""
+    return dict(fsk=mk(s, HKV, NS, D, dtype=FP8), fsv=mk(s, HKV, NS, D, dtype=FP8), fwk=mk(s, HKV, W, D, dtype=FP8),
+                fwv=mk(s, HKV, W, D, dtype=FP8), gk=mk(NPG, HKV, pg, D, dtype=dtype), gv=mk(NPG, HKV, pg, D, dtype=dtype),
+                hk=mk(NPG, HKV, pg, D, dtype=FP8), hv=mk(NPG, HKV, pg, D, dtype=FP8),
+                q=mk(b, hq, n, D, dtype=dtype), kn=mk(b, HKV, n, D, dtype=dtype), vn=mk(b, HKV, n, D, dtype=dtype),
                 o=mk(b, hq, n, D, dtype=dtype), q1=mk(b, hq, 1, D, dtype=dtype), k1=mk(b, HKV, 1, D, dtype=dtype),
                 v1=mk(b, HKV, 1, D, dtype=dtype), o1=mk(b, hq, 1, D, dtype=dtype), qp=mk(1, hq, t, D, dtype=dtype),
                 kp=mk(1, HKV, t, D, dtype=dtype), vp=mk(1, HKV, t, D, dtype=dtype), op=mk(1, hq, t, D, dtype=dtype),
@@ -43,16 +49,19 @@ def _descs(**kw):
 
 
 BASE = _descs()
+BASE.update(dsk=BASE["psk"], dsv=BASE["psv"], dgk=BASE["gk"], dgv=BASE["gv"])    # the destination pool of the paged copy
 _HOST = torch.zeros(64, dtype=torch.int32)      # stands in for state / slots / parent / path / count / cu: never read
 P = _HOST.data_ptr()
 WS = 1 << 20                                     # a 256-byte aligned address, never dereferenced
 SCALARS = dict(aux=None, ws=None, wsb=0, scale=0.125, flags=0, stream=None, state=P, slots=P, parent=P, pstride=0,
-               count=P, path=P, pathstride=0, cu=P, nseq=2, commit=1, sl=NS, wl=W, wp=0)
+               count=P, path=P, pathstride=0, cu=P, nseq=2, commit=1, sl=NS, wl=W, wp=0, cseq=P, kvs=P, table=P,
+               tstride=PER, nslots=S, dstate=P, dslots=P, npairs=1, dtable=P, dtstride=PER)
 
 # the argument list of every entry point in the names of BASE / SCALARS.  act: the activations an entry point takes
 # (chunk, one token, pack or none); cache: the buffers of B rows, the pool, or a single key segment
 CHUNK, ONE, PACK = ("q", "kn", "vn", "o"), ("q1", "k1", "v1", "o1"), ("qp", "kp", "vp", "op")
 ROWS, POOL = ("sk", "sv", "wk", "wv"), ("psk", "psv", "pwk", "pwv")
+POOL8, PAGED, PAGED8 = ("fsk", "fsv", "fwk", "fwv"), ("psk", "psv", "gk", "gv"), ("fsk", "fsv", "hk", "hv")
 
 
 def _sig(act, cache, mid, tail="ws wsb scale flags stream"):
@@ -92,6 +101,25 @@ ENTRY = {
 }
 assert len(ENTRY) == 23
 
+# the ten calls on an FP8, a paged and a paged FP8 pool: the packed step, the packed commit, the slot prefill (and the
+# paged copy, which takes two pools and no activations).  ENTRY stays the 23 calls on 16-bit contiguous caches
+POOL_ENTRY = {}
+_STEP = _DYN + " parent cseq commit state slots cu nseq"
+_CMP = _CM + " path cu nseq state slots"
+_FILL = "{sk} {sv} {wk} {wv} {kn} {vn} cu nseq state slots"
+COPY = "sfa_ring_copy_paged_slots"
+for _kind, _cache, _tail in (("fp8", POOL8, " kvs"), ("paged", PAGED, " table tstride{n}"),
+                             ("paged_fp8", PAGED8, " table tstride{n} kvs")):
+    POOL_ENTRY[f"sfa_decode_ring_ragged_{_kind}_slots"] = (PACK, _cache, _sig(PACK, _cache, _STEP + _tail.format(n="")))
+    POOL_ENTRY[f"sfa_ring_commit_path_ragged_{_kind}_slots"] = (PACK, _cache, _sig(PACK, _cache,
+                                                                                    _CMP + _tail.format(n=" nslots"), "stream"))
+    POOL_ENTRY[f"sfa_ring_fill_varlen_{_kind}_slots"] = (PACK, _cache, _sig(PACK, _cache, _FILL + _tail.format(n=""), "stream"))
+POOL_ENTRY[COPY] = ((), PAGED, "psk psv gk gv state dsk dsv dgk dgv dstate slots dslots npairs table tstride dtable dtstride "
+                    "stream".split())
+NEW = list(POOL_ENTRY)
+ALL = {**ENTRY, **POOL_ENTRY}
+assert len(NEW) == 10 and len(ALL) == 33
+
 
 def call(name, descs=None, **scalars):
     """Run entry point `name` on BASE with `descs` (name -> descriptor or None) and `scalars` replaced; returns
@@ -99,13 +127,13 @@ def call(name, descs=None, **scalars):
     d = dict(BASE, **(descs or {}))
     s = dict(SCALARS, **scalars)
     lib = N.lib()
-    st = getattr(lib, name)(*[d[a] if a in d else s[a] for a in ENTRY[name][2]])
+    st = getattr(lib, name)(*[d[a] if a in d else s[a] for a in ALL[name][2]])
     return st, lib.sfa_last_error().decode()
 
 
 def _swap(name, other, *roles):
     """the entry point's tensors of the given roles (q, kn, vn, o, sk, sv, wk, wv) taken from the descriptor set `other`"""
-    act, cache, _ = ENTRY[name]
+    act, cache, _ = ALL[name]
     names = dict(zip(("q", "kn", "vn", "o", "sk", "sv", "wk", "wv"), act + cache))
     return {names[r]: (other[names[r]] if other is not None else None) for r in roles}
 
@@ -113,28 +141,84 @@ def _swap(name, other, *roles):
 HALF, HQ7, N0, N65, ODD, S7 = (_descs(dtype=FP), _descs(hq=7), _descs(n=0, t=0), _descs(n=65), _descs(mk=_odd),
                                _descs(s=7))
 B2PACK = {"qp": BASE["q"], "kp": BASE["kn"], "vp": BASE["vn"], "op": BASE["o"]}    # [2, H, 3, D] where a pack belongs
+# the pools' own: fp32 everywhere, pages of 48 / 16 / 64 rows, head dim 48 (the first 48 columns of every tensor)
+FLOAT, PG48, PG16, PG64 = _descs(dtype=F32), _descs(pg=48), _descs(pg=16), _descs(pg=64)
+D48 = {k: N.desc(t[..., :48]) for k, t in _tensors().items()}
+_KEEP.append(D48)
+ALL8 = ("q", "kn", "vn", "o", "sk", "sv", "wk", "wv")
 
 
 def _has(name, arg):
-    return arg in ENTRY[name][2]
+    return arg in ALL[name][2]
+
+
+def _kind(name):
+    """(FP8?, paged?) of one of the ten pool entry points; (False, False) for the 23 others"""
+    return name in NEW and "fp8_slots" in name, name in NEW and "_paged_" in name
 
 
 def _need(name):
     """the workspace size the entry point asks for at BASE"""
     lib = N.lib()
-    act = ENTRY[name][0]
+    act = ALL[name][0]
     if act is ONE:
         nkv = NS if name == "sfa_decode" else NS + W
         return lib.sfa_decode_workspace_bytes(B, HQ, HKV, nkv, D, 2)
     if act is PACK:
-        return lib.sfa_decode_ragged_workspace_bytes(2, HQ, HKV, T, NS + W, D, 2)
+        return lib.sfa_decode_ragged_workspace_bytes(2, HQ, HKV, T, NS + (PER * PG if _kind(name)[1] else W), D, 2)
     return lib.sfa_decode_multi_workspace_bytes(B, HQ, HKV, NN, NS + W + NN, D, 2)
+
+
+def _copy_defect(which):
+    """defect() of sfa_ring_copy_paged_slots: two pools (psk psv gk gv -> dsk dsv dgk dgv), no activations"""
+    pool = ("psk", "psv", "gk", "gv", "dsk", "dsv", "dgk", "dgv")
+    both = lambda other: {k: other[k[1:] if k[0] == "d" else k] for k in pool}
+    return {"null_state": dict(state=None), "null_slots": dict(slots=None), "null_cache": dict(descs={"psk": None}),
+            "null_table": dict(table=None), "table_stride0": dict(tstride=0),
+            "page_npo2": dict(descs={"gk": PG48["gk"], "gv": PG48["gv"]}),
+            "page_small": dict(descs={"gk": PG16["gk"], "gv": PG16["gv"]}),
+            "cache_dtype": dict(descs={"gk": BASE["hk"], "gv": BASE["hv"]}),      # FP8 pages beside 16-bit sinks
+            "head_dim": dict(descs=both(D48)), "fp32": dict(descs=both(FLOAT)),
+            "copy_page_sizes": dict(descs={"dgk": PG64["gk"], "dgv": PG64["gv"]})}.get(which)
+
+
+def _pool_defect(name, which):
+    """the defects that only the ten pool entry points can have"""
+    fp8, paged = _kind(name)
+    if which in ("page_npo2", "page_small"):
+        return dict(descs=_swap(name, PG48 if which == "page_npo2" else PG16, "wk", "wv")) if paged else None
+    if which == "table_stride0":
+        return dict(tstride=0) if paged else None
+    if which == "null_table":
+        return dict(table=None) if paged else None
+    if which == "cache_dtype":      # 16-bit buffers where FP8 ones belong, and the other way round
+        other = {POOL8: POOL, PAGED8: PAGED, PAGED: PAGED8}[ALL[name][1]]
+        return dict(descs={c: BASE[o] for c, o in zip(ALL[name][1], other)})
+    if which == "act_dtype":        # k_new in f16 beside bf16 q / v_new
+        return dict(descs=_swap(name, HALF, "kn")) if fp8 else None
+    if which == "head_dim":
+        return dict(descs=_swap(name, D48, *ALL8))
+    if which == "fp32":             # fp32 activations; a 16-bit paged pool shares their dtype
+        return dict(descs=_swap(name, FLOAT, "q", "kn", "vn", "o") if fp8 else _swap(name, FLOAT, *ALL8))
+    if which == "force_generic":
+        return dict(flags=N.FLAG_FORCE_GENERIC) if _has(name, "flags") else None
+    return None                     # copy_page_sizes: the copy alone
+
+
+POOL_DEFECTS = ("page_npo2", "page_small", "table_stride0", "null_table", "cache_dtype", "act_dtype", "head_dim", "fp32",
+                "force_generic", "copy_page_sizes")
 
 
 def defect(name, which):
     """keyword arguments of call() that plant defect `which` in entry point `name`, or None where it does not apply"""
     commit, fill = name.startswith("sfa_ring_commit"), name.startswith("sfa_ring_fill")
     chunkless = name in ("sfa_decode", "sfa_decode_ring")
+    if name == COPY:
+        return _copy_defect(which)
+    if which in POOL_DEFECTS:
+        return _pool_defect(name, which) if name in NEW else None
+    if which == "dtype" and _kind(name)[0] and (commit or fill):
+        return None                 # k / v of one 16-bit dtype are what an FP8 commit or prefill takes: see act_dtype
     if which == "null_state":
         return dict(state=None) if _has(name, "state") else None
     if which == "null_slots":
@@ -148,7 +232,7 @@ def defect(name, which):
     if which == "heads":
         return None if commit or fill else dict(descs=_swap(name, HQ7, "q", "o"))
     if which == "n0":
-        if fill or ENTRY[name][0] is ONE:
+        if fill or ALL[name][0] is ONE:
             return None
         return dict(descs=_swap(name, N0, "kn", "vn") if commit else _swap(name, N0, "q", "o", "kn", "vn"))
     if which == "n65":
@@ -160,7 +244,7 @@ def defect(name, which):
     if which == "misaligned":
         return dict(descs=_swap(name, ODD, "q") if chunkless else _swap(name, ODD, "kn"))
     if which == "pool_s":
-        return dict(descs=_swap(name, S7, "wk", "wv")) if ENTRY[name][1] is POOL and not commit else None
+        return dict(descs=_swap(name, S7, "wk", "wv")) if ALL[name][1] in (POOL, POOL8) and not commit else None
     if which == "null_ws":
         return dict(ws=None, wsb=0) if _has(name, "ws") else None
     if which == "short_ws":
@@ -168,7 +252,7 @@ def defect(name, which):
     if which == "unaligned_ws":
         return dict(ws=WS + 16, wsb=1 << 30) if _has(name, "ws") else None
     if which == "not_packed":
-        return dict(descs=B2PACK) if name == "sfa_decode_ring_ragged_slots" else None
+        return dict(descs=B2PACK) if name == "sfa_decode_ring_ragged_slots" or name in NEW else None
     if which == "n_seq0":
         return dict(nseq=0) if _has(name, "nseq") else None
     if which in ("null_parent", "null_count", "null_path", "null_cu"):      # only used in COMBINED
@@ -178,7 +262,7 @@ def defect(name, which):
 
 
 DEFECTS = ("null_state", "null_slots", "null_cache", "null_k_new", "dtype", "heads", "n0", "n65", "bstride",
-           "misaligned", "pool_s", "null_ws", "short_ws", "unaligned_ws", "not_packed", "n_seq0")
+           "misaligned", "pool_s", "null_ws", "short_ws", "unaligned_ws", "not_packed", "n_seq0") + POOL_DEFECTS
 
 # entry point -> defect -> (status, sfa_last_error()); a defect that an entry point cannot have is absent
 EXPECT = {
@@ -440,7 +524,99 @@ EXPECT = {
     },
 }
 
-CELLS = [(name, which) for name in ENTRY for which in DEFECTS if defect(name, which) is not None]
+# the ten pool entry points.  Three texts recur under the call's own name `who`
+_FP8_ONLY = '{who}: the cache buffers must be FP8 (e4m3)'
+_PAGE = '{who}: the page size (window_k shape[2] = {p}) must be a power of two and at least 32'
+_STRIDE = '{who}: table_stride (0) must be at least 1 (Wc = table_stride * P)'
+_SERVES = {(True, False): '{who}: an FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 ',
+           (False, True): '{who}: a paged pool serves bf16 / f16 at head dims 64 / 80 / 96 / 128 ',
+           (True, True): '{who}: a paged FP8 pool serves bf16 / f16 activations at head dims 64 / 80 / 96 / 128 '}
+
+
+def _pool_rows(who, fp8, paged, rows):
+    """the cells every call of one pool kind shares, under its name in the messages, joined to its own `rows`"""
+    serves = _SERVES[fp8, paged].format(who=who)
+    out = dict(rows, head_dim=(-2, serves + '(got dtype 2, head dim 48)'), fp32=(-2, serves + '(got dtype 0, head dim 64)'))
+    out["cache_dtype"] = (-1, _FP8_ONLY.format(who=who) if fp8 else 'window_k: unknown dtype 3')
+    if paged:
+        out.update(page_npo2=(-1, _PAGE.format(who=who, p=48)), page_small=(-1, _PAGE.format(who=who, p=16)),
+                   table_stride0=(-1, _STRIDE.format(who=who)), null_table=(-1, 'page_table: null device pointer'))
+    if "null_ws" in rows:
+        out["force_generic"] = (-2, serves + '(got dtype 2, head dim 64, SFA_FLAG_FORCE_GENERIC)')
+    return out
+
+
+def _step_rows(need, fp8, who):
+    ws = f'decode_ragged workspace: need {need} bytes, 256-byte aligned '
+    rows = {
+        "null_state": (-1, 'state: null device pointer'),
+        "null_slots": (-1, 'slots: null device pointer'),
+        "null_cache": (-1, 'cache buffers: null tensor descriptor'),
+        "null_k_new": (-1, 'k_new: null tensor descriptor'),
+        "dtype": (-1, f'{who}: q and k_new / v_new must share one dtype' if fp8 else
+                  'q, the cache buffers and k_new / v_new must share one dtype'),
+        "heads": (-1, 'H_q (7) must be divisible by H_kv (2)'),
+        "n0": (-1, 'decode_multi: the chunk needs at least one token'),
+        "misaligned": (-1, 'decode_multi: rows of every tensor must be 16-byte aligned'),
+        "null_ws": (-3, ws + '(got 0 at (nil))'),
+        "short_ws": (-3, ws + f'(got {need - 1} at 0x100000)'),
+        "unaligned_ws": (-3, ws + '(got 1073741824 at 0x100010)'),
+        "not_packed": (-1, 'decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = 2)'),
+        "n_seq0": (-1, 'decode_ragged: n_seq (0) must be at least 1'),
+    }
+    if fp8:
+        rows["act_dtype"] = (-1, 'k_new and v_new differ in dtype')
+    return rows
+
+
+def _commit_rows(fp8):
+    rows = {
+        "null_state": (-1, 'state: null device pointer'),
+        "null_slots": (-1, 'slots: null device pointer'),
+        "null_cache": (-1, 'window_k: null tensor descriptor'),
+        "null_k_new": (-1, 'k_new: null tensor descriptor'),
+        "n0": (-1, 'ring_commit: the chunk needs at least one token'),
+        "misaligned": (-1, 'ring_commit: rows of every tensor must be 16-byte aligned'),
+        "not_packed": (-1, 'ring_commit_ragged: k_new / v_new must be packed [1, H_kv, T, D] (got shape[0] = 2)'),
+        "n_seq0": (-1, 'ring_commit_ragged: n_seq (0) must be at least 1'),
+    }
+    rows.update({"act_dtype": (-1, 'k_new and v_new differ in dtype')} if fp8 else
+                {"dtype": (-1, 'k_new / v_new and the ring must share one dtype')})
+    return rows
+
+
+def _fill_rows(fp8):
+    rows = {
+        "null_state": (-1, 'state: null device pointer'),
+        "null_slots": (-1, 'slots: null device pointer'),
+        "null_cache": (-1, 'sink_k: null tensor descriptor'),
+        "null_k_new": (-1, 'k: null tensor descriptor'),
+        "misaligned": (-1, 'ring_fill_varlen: rows of every tensor must be 16-byte aligned'),
+        "not_packed": (-1, 'packed layout: k / v must be [1, H_kv, T, D] (batch dim 2)'),
+        "n_seq0": (-1, 'n_seq must be >= 1 (got 0)'),
+    }
+    rows.update({"act_dtype": (-1, 'k and v differ in dtype')} if fp8 else
+                {"dtype": (-1, 'k / v and the cache buffers must share one dtype')})
+    return rows
+
+
+_POOL_S = (-1, 'pool: sink and window buffers must share shape[0] = S >= 1 (sink 5, window 7)')
+for _sfx, _fp8, _paged in (("fp8", True, False), ("paged", False, True), ("paged_fp8", True, True)):
+    _own = {} if _paged else {"pool_s": _POOL_S}          # a paged ring takes S from the sinks
+    EXPECT[f"sfa_decode_ring_ragged_{_sfx}_slots"] = _pool_rows(
+        f"decode_ragged_{_sfx}", _fp8, _paged, dict(_step_rows(26112 if _paged else 13312, _fp8, f"decode_ragged_{_sfx}"), **_own))
+    EXPECT[f"sfa_ring_commit_path_ragged_{_sfx}_slots"] = _pool_rows(f"ring_commit_ragged_{_sfx}", _fp8, _paged,
+                                                                     _commit_rows(_fp8))
+    EXPECT[f"sfa_ring_fill_varlen_{_sfx}_slots"] = _pool_rows(f"ring_fill_varlen_{_sfx}", _fp8, _paged,
+                                                              dict(_fill_rows(_fp8), **_own))
+EXPECT[COPY] = dict(_pool_rows("ring_copy_paged", False, True, {
+    "null_state": (-1, 'src_state: null device pointer'),
+    "null_slots": (-1, 'src_slots: null device pointer'),
+    "null_cache": (-1, 'src_sink_k: null tensor descriptor'),
+    "copy_page_sizes": (-1, 'ring_copy_paged: the pools differ in page size (src 32, dst 64)'),
+}), cache_dtype=(-1, 'ring_copy_slots: src_window_k and src_sink_k differ in dtype (the eight buffers must share one)'))
+
+CELLS = [(name, which) for name in ALL for which in DEFECTS if defect(name, which) is not None]
 
 
 def test_the_table_covers_every_applicable_cell():
@@ -449,7 +625,7 @@ def test_the_table_covers_every_applicable_cell():
         assert any(w == which for _, w in CELLS), which
 
 
-@pytest.mark.parametrize("name", list(ENTRY))
+@pytest.mark.parametrize("name", list(ALL))
 def test_every_defect_fails_with_its_status_and_text_before_any_launch(name):
     for which, want in EXPECT[name].items():
         assert call(name, **defect(name, which)) == want, which
@@ -526,6 +702,66 @@ COMBINED = [
 @pytest.mark.parametrize("name,whiches,text", COMBINED, ids=[f"{n[4:]}-{'+'.join(w)}" for n, w, _ in COMBINED])
 def test_of_two_defects_the_earlier_check_reports(name, whiches, text):
     assert call(name, **_both(name, *whiches)) == (-1, text)
+
+
+# the same for the ten pool entry points, with the status: a paged call checks its pages and table first (paged_ring),
+# then the null device arrays, then n_seq, then what its contiguous sibling checks; an FP8 call says what it serves where
+# its sibling checks the head dim, a 16-bit paged call after every check of its sibling
+_RAG, _CMT, _FIL = "sfa_decode_ring_ragged_%s_slots", "sfa_ring_commit_path_ragged_%s_slots", "sfa_ring_fill_varlen_%s_slots"
+COMBINED_POOL = [
+    (_RAG % "paged", ("cache_dtype", "null_table"), -1, "window_k: unknown dtype 3"),
+    (_RAG % "paged", ("null_table", "page_npo2"), -1, "page_table: null device pointer"),
+    (_RAG % "paged", ("page_small", "table_stride0"), -1, _PAGE.format(who="decode_ragged_paged", p=16)),
+    (_RAG % "paged", ("table_stride0", "null_state"), -1, _STRIDE.format(who="decode_ragged_paged")),
+    (_RAG % "paged", ("null_state", "null_slots"), -1, "state: null device pointer"),
+    (_RAG % "paged", ("null_slots", "null_cu"), -1, "slots: null device pointer"),
+    (_RAG % "paged", ("null_cu", "n_seq0"), -1, "cu_q: null device pointer"),
+    (_RAG % "paged", ("n_seq0", "null_cache"), -1, "decode_ragged: n_seq (0) must be at least 1"),
+    (_RAG % "paged", ("not_packed", "force_generic"), -1,
+     "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = 2)"),
+    (_RAG % "paged", ("force_generic", "null_ws"), -2,
+     _SERVES[False, True].format(who="decode_ragged_paged") + "(got dtype 2, head dim 64, SFA_FLAG_FORCE_GENERIC)"),
+    (_RAG % "paged_fp8", ("null_table", "null_state"), -1, "page_table: null device pointer"),
+    (_RAG % "paged_fp8", ("page_npo2", "act_dtype"), -1, _PAGE.format(who="decode_ragged_paged_fp8", p=48)),
+    (_RAG % "paged_fp8", ("cache_dtype", "dtype"), -1, _FP8_ONLY.format(who="decode_ragged_paged_fp8")),
+    (_RAG % "paged_fp8", ("dtype", "heads"), -1, "decode_ragged_paged_fp8: q and k_new / v_new must share one dtype"),
+    (_RAG % "paged_fp8", ("not_packed", "force_generic"), -2,
+     _SERVES[True, True].format(who="decode_ragged_paged_fp8") + "(got dtype 2, head dim 64, SFA_FLAG_FORCE_GENERIC)"),
+    (_RAG % "fp8", ("null_state", "null_slots"), -1, "state: null device pointer"),
+    (_RAG % "fp8", ("n_seq0", "cache_dtype"), -1, "decode_ragged: n_seq (0) must be at least 1"),
+    (_RAG % "fp8", ("cache_dtype", "n0"), -1, _FP8_ONLY.format(who="decode_ragged_fp8")),
+    (_RAG % "fp8", ("pool_s", "not_packed"), -1, _POOL_S[1]),
+    (_RAG % "fp8", ("pool_s", "force_generic"), -1, _POOL_S[1]),
+    (_RAG % "fp8", ("not_packed", "force_generic"), -2,
+     _SERVES[True, False].format(who="decode_ragged_fp8") + "(got dtype 2, head dim 64, SFA_FLAG_FORCE_GENERIC)"),
+    (_RAG % "fp8", ("head_dim", "null_ws"), -2,
+     _SERVES[True, False].format(who="decode_ragged_fp8") + "(got dtype 2, head dim 48)"),
+    (_CMT % "paged", ("page_npo2", "null_slots"), -1, _PAGE.format(who="ring_commit_ragged_paged", p=48)),
+    (_CMT % "paged", ("null_slots", "null_cu"), -1, "slots: null device pointer"),
+    (_CMT % "paged", ("n_seq0", "null_count"), -1, "ring_commit_ragged: n_seq (0) must be at least 1"),
+    (_CMT % "paged", ("null_count", "null_state"), -1, "count: null device pointer"),
+    (_CMT % "paged_fp8", ("table_stride0", "cache_dtype"), -1, _STRIDE.format(who="ring_commit_ragged_paged_fp8")),
+    (_CMT % "paged_fp8", ("cache_dtype", "n0"), -1, _FP8_ONLY.format(who="ring_commit_ragged_paged_fp8")),
+    (_CMT % "fp8", ("null_slots", "null_cu"), -1, "slots: null device pointer"),
+    (_CMT % "fp8", ("null_state", "cache_dtype"), -1, "state: null device pointer"),
+    (_CMT % "fp8", ("fp32", "null_state"), -1, "state: null device pointer"),
+    (_FIL % "paged", ("table_stride0", "null_cu"), -1, _STRIDE.format(who="ring_fill_varlen_paged")),
+    (_FIL % "paged", ("null_cu", "n_seq0"), -1, "cu_seqlens: null device pointer"),
+    (_FIL % "paged_fp8", ("page_npo2", "act_dtype"), -1, _PAGE.format(who="ring_fill_varlen_paged_fp8", p=48)),
+    (_FIL % "paged_fp8", ("n_seq0", "cache_dtype"), -1, "n_seq must be >= 1 (got 0)"),
+    (_FIL % "fp8", ("cache_dtype", "pool_s"), -1, _FP8_ONLY.format(who="ring_fill_varlen_fp8")),
+    (_FIL % "fp8", ("pool_s", "fp32"), -1, _POOL_S[1]),
+    (COPY, ("null_table", "page_npo2"), -1, "page_table: null device pointer"),
+    (COPY, ("page_npo2", "copy_page_sizes"), -1, _PAGE.format(who="ring_copy_paged", p=48)),
+    (COPY, ("copy_page_sizes", "null_state"), -1, "ring_copy_paged: the pools differ in page size (src 32, dst 64)"),
+    (COPY, ("fp32", "null_state"), -1, "src_state: null device pointer"),
+]
+
+
+@pytest.mark.parametrize("name,whiches,status,text", COMBINED_POOL,
+                         ids=[f"{n[4:]}-{'+'.join(w)}" for n, w, _, _ in COMBINED_POOL])
+def test_of_two_pool_defects_the_earlier_check_reports(name, whiches, status, text):
+    assert call(name, **_both(name, *whiches)) == (status, text)
 
 
 def test_other_refusals_keep_their_status_and_text():
