@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Randomised cross-check on the GPU: MFMA kernels against the exact-f32 kernels of the same library (and the
 N_q < N_kv / packed paths against their padded / per-sequence formulations) on random shapes.
-usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe|range]
+usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe|range|dsaux]
 (skew: only shapes of the short-window dK/dV kernel - no sink keys, head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or
 packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn,
 and dK / dV of the MFMA kernels also judged element by element against the fp64 oracle with the sum bound of tests/util.py
 (4 u A + u |ref|), which a mask error confined to the dK/dV kernel cannot pass;
---inputs=range: a random family of tests/range_inputs.py - logit staircases, a common offset - that moves the softmax reference)"""
+--inputs=range: a random family of tests/range_inputs.py - logit staircases, a common offset - that moves the softmax reference;
+--inputs=dsaux: the problem of tests/dsaux_inputs.py - s_aux calibrated to p_aux about 1/2 with per-head offsets, dO = sign(o_ref) on
+one random row class and 0 elsewhere, at most 500 rows - and ds_aux of the MFMA path also judged against the fp64 oracle under the
+class's own bound 4 u A + u |ref|)"""
 import os
 import random
 import sys
@@ -15,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "sink-flash-attention-kernel_amd"), ROOT, os.path.join(ROOT, "tests")]
 import torch
 
+import dsaux_inputs
 import probe_inputs
 import range_inputs
 import util
@@ -23,13 +27,14 @@ from sink_attention.sink_flash_attention import _sink_flash_attention_ex
 from sink_attention.varlen import sink_flash_attention_varlen
 
 inputs = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--inputs=")] or ["randn"])[-1]
-assert inputs in ("randn", "probe", "range"), inputs
+assert inputs in ("randn", "probe", "range", "dsaux"), inputs
 sys.argv = [a for a in sys.argv if not a.startswith("--inputs=")]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 torch.manual_seed(rng.randrange(1 << 30))
 focus_skew = len(sys.argv) > 3 and sys.argv[3] == "skew"
 bad = 0
+DSAUX = {}          # --inputs=dsaux: the problem and the class of the last draw
 
 
 def draw(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, cu=None):
@@ -37,12 +42,21 @@ def draw(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, cu=None):
     if inputs == "probe":
         pr = probe_inputs.dense_probe(B, Hq, Hkv, Nq, Nk, D, ns, W, dt, rng.randrange(1 << 30), cu=cu)
         return tuple(pr[x].cuda() for x in ("q", "k", "v", "do"))
+    if inputs == "dsaux":
+        pr = dsaux_inputs.build(B, Hq, Hkv, Nq, D, dt, ns, W, Nk=Nk, cu=cu, seed=rng.randrange(1 << 30))
+        DSAUX.update(pr=pr, cls=rng.choice(sorted(pr["classes"])))
+        return tuple(x.cuda() for x in (pr["q"], pr["k"], pr["v"], dsaux_inputs.make_do(pr, pr["classes"][DSAUX["cls"]])))
     if inputs == "range":
         fam = rng.choice(("staircase_up", "staircase_down", "offset"))
         pr = range_inputs.dense_range(fam, B, Hq, Hkv, Nq, Nk, D, ns, W, dt, rng.randrange(1 << 30), cu=cu)
         return tuple(pr[x].cuda() for x in ("q", "k", "v", "do"))
     return (torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt), torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt),
             torch.randn(B, Hkv, Nk, D, device="cuda", dtype=dt), torch.randn(B, Hq, Nq, D, device="cuda", dtype=dt))
+
+
+def calibrated(sa):
+    """--inputs=dsaux: the s_aux that belongs to the tensors just drawn"""
+    return DSAUX["pr"]["s_aux"].cuda() if inputs == "dsaux" else sa
 
 
 def run(q, k, v, do, ns, W, sa, generic):
@@ -87,6 +101,8 @@ for case in range(n_cases):
     if focus_skew:
         D, ns, W = rng.choice([64, 80, 96]), 0, rng.choice([1, 5, 31, 64, 100, 128, 300, 512])
         mode = rng.choice(["plain", "plain", "varlen"])
+    if inputs == "dsaux":
+        aux, N, W = True, min(N, 500), max(W, 1)        # (W >= 1: every row sees a key, the calibration needs a finite LSE)
     sa = (torch.randn(Hq, device="cuda") * 0.5) if aux else None
     cu = None
     tol_o, tol_g = (2e-2, 2e-1) if dt == torch.bfloat16 else (5e-3, 6e-2)
@@ -94,10 +110,12 @@ for case in range(n_cases):
     try:
         if mode == "plain":
             q, k, v, do = draw(B, Hq, Hkv, N, N, D, ns, W, dt)
+            sa = calibrated(sa)
             a, b = run(q, k, v, do, ns, W, sa, False), run(q, k, v, do, ns, W, sa, True)
         elif mode == "offset":
             Nk = N + rng.choice([1, 17, 64, 100, 300])
             q, k, v, do = draw(B, Hq, Hkv, N, Nk, D, ns, W, dt)
+            sa = calibrated(sa)
             a = run(q, k, v, do, ns, W, sa, False)
             qp = torch.cat([torch.zeros(B, Hq, Nk - N, D, device="cuda", dtype=dt), q], 2)
             dop = torch.cat([torch.zeros(B, Hq, Nk - N, D, device="cuda", dtype=dt), do], 2)
@@ -114,6 +132,7 @@ for case in range(n_cases):
                 cu.append(cu[-1] + L)
             T = cu[-1]
             q, k, v, do = draw(1, Hq, Hkv, T, T, D, ns, W, dt, cu=cu)
+            sa = calibrated(sa)
             qq, kk, vv = (t.clone().requires_grad_(True) for t in (q, k, v))
             ss = sa.clone().requires_grad_(True) if aux else None
             o = sink_flash_attention_varlen(qq, kk, vv, cu, ns, W, ss)
@@ -136,6 +155,11 @@ for case in range(n_cases):
         if inputs == "probe" and not nan:
             errs += sum_bound_ratios(q, k, v, do, ns, W, sa, cu if mode == "varlen" else None, a[2], a[3])
             ok = ok and max(errs[-2:]) <= 1.0
+        if inputs == "dsaux" and not nan:
+            ref = dsaux_inputs.reference(DSAUX["pr"], DSAUX["pr"]["classes"][DSAUX["cls"]])
+            errs.append(dsaux_inputs.ratio(a[4], ref["ds"], ref["tol_ds"]))
+            ok = ok and errs[-1] <= 1.0
+            desc += " class " + DSAUX["cls"]
     except Exception as e:      # noqa: BLE001 - report and continue
         ok, errs = False, [repr(e)[:200]]
     if not ok:
