@@ -724,7 +724,9 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
  * Pages needed are a prefix.  A ring fills from slot 0 upwards until it is full (the prefill placement and the commit
  * both do), so a slot whose ring has held at most r tokens touches table entries 0 .. ceil(min(r, Wc) / P) - 1 only,
  * in reads and in stores.  An allocator maps that prefix before the call that makes the ring reach it and nothing else.
- * Two pages mapped into two live slots at once are undefined for storing calls, as the same slot twice is.
+ * One page mapped into two live slots at once is undefined only where a storing call REACHES it (a ring slot the call
+ * writes lies in that page), as the same slot twice is.  Reads through two table rows that name one page are defined:
+ * that is how a fork shares its prompt (sfa_ring_share_paged_slots, sfa_pages_copy below).
  * Contract.  Let the TWIN be the contiguous pool with window[s, :, j P : (j + 1) P] = pages[table[s][j]], the same
  * sinks and the same state.  Two bitwise equalities, which are what the tests hold the calls to:
  *   - Read.  o of a paged step is bit for bit o of the same call on the twin: a ring tile's address is one wave-uniform
@@ -793,6 +795,53 @@ int sfa_ring_copy_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* sr
                               int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
                               const int32_t* src_page_table, int src_table_stride, const int32_t* dst_page_table,
                               int dst_table_stride, void* stream);
+
+/*
+ * Sharing pages on a fork (copy on first write).  Within ONE paged pool a fork need not copy the ring: the caller writes
+ * the source's table row into the destination's row (host bookkeeping with reference counts, outside this library) and
+ * calls sfa_ring_share_paged_slots for what is not paged.  Every later read of the destination goes through its own row
+ * to the shared pages.  Before a storing call reaches a page that more than one row names, the caller gives the storing
+ * slot a page of its own: a fresh entry in its row, then sfa_pages_copy(old page -> new page) on the same stream in front
+ * of the storing call, once for every layer that reads the table.  A page that two rows name is therefore never stored
+ * into.
+ *
+ * sfa_ring_share_paged_slots: the unpaged half of sfa_ring_copy_paged_slots.  For every live pair the live sink rows
+ * (j < clamp(sink_len, 0, num_sink), all KV heads) and the state row (4 ints, verbatim) of slot src_slots[i] are copied
+ * into slot dst_slots[i]; no ring memory is read or written and the call takes no ring buffers and no table.  Sinks and
+ * state rows end bitwise as sfa_ring_copy_paged_slots leaves them for the same pairs.  Skipped pairs (-1 / out of range
+ * on either side, s == d where src_state == dst_state) and the aliasing rules are those of sfa_ring_copy_slots.  One
+ * launch on `stream`, capturable, nothing read on the host.  The sink buffers are bf16, f16, f32 or SFA_DTYPE_FP8_E4M3
+ * (a byte copy, no scales).
+ * Host checks, in this order: null descriptors ("src_sink_k: null tensor descriptor", ...); null src_state / dst_state /
+ * src_slots / dst_slots; n_pairs < 0 (n_pairs == 0 returns SFA_OK without a launch); "ring_share_slots: <name> and
+ * src_sink_k differ in dtype (the four buffers must share one)"; equal Hkv, num_sink, D ("ring_share_slots: <name> must
+ * be [S, H_kv, num_sink, D] = ..."); one shape[0] >= 1 within each pool; rows a multiple of 16 bytes and 16-byte aligned.
+ * sfa_last_path(): "ring_share_slots_paged".
+ */
+int sfa_ring_share_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const int32_t* src_state,
+                               const sfa_tensor* dst_sink_k, const sfa_tensor* dst_sink_v, int32_t* dst_state,
+                               const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream);
+
+/*
+ * sfa_pages_copy: copy whole ring pages within the page buffers of one layer.  window_k / window_v [n_pages, Hkv, P, D]
+ * are bf16, f16 or SFA_DTYPE_FP8_E4M3, both of one dtype and shape; src_pages / dst_pages are device int32 [n_pairs].
+ * Pair i copies page src_pages[i] onto page dst_pages[i], K and V, every head and row, as bytes (no scales).
+ *   - Skipped pairs, decided on the device: either entry outside [0, n_pages) (compared as unsigned, so -1 is outside),
+ *     or both entries equal.
+ *   - Undefined, and not validated: one destination named twice; a destination that is also a source of the same call.
+ * One launch on `stream`, capturable, no workspace, nothing read on the host.  A workgroup reads its pair's two page ids
+ * once; each thread moves 16-byte pieces and holds several of K and of V in flight before its first store; the grid is
+ * n_pairs x the pieces of a page.  Page, head and row offsets are 64-bit products of the descriptor's strides: the
+ * buffers may be strided views and a page buffer may exceed 4 GiB.
+ * Host checks, in this order, SFA_ERR_INVALID_ARGUMENT: null descriptors ("window_k: null tensor descriptor"); n_pairs
+ * < 0; unequal shapes or dtypes ("window_k and window_v differ in shape[i]: ...", "... differ in dtype"); "pages_copy:
+ * the page buffers hold bf16, f16 or FP8 (e4m3) (got dtype d)"; "pages_copy: the page buffers need shape[0] = n_pages in
+ * [1, 2^30) (got n)"; n_pairs == 0 returns SFA_OK here, without a launch; "src_pages: null device pointer" /
+ * "dst_pages: ..."; "pages_copy: K/V rows must be a multiple of 16 bytes (head dim n)"; "pages_copy: rows of every tensor
+ * must be 16-byte aligned".  sfa_last_path(): "pages_copy".
+ */
+int sfa_pages_copy(const sfa_tensor* window_k, const sfa_tensor* window_v, const int32_t* src_pages,
+                   const int32_t* dst_pages, int n_pairs, void* stream);
 
 /*
  * Paged FP8 slot pool: the two pools above composed - the ring memory follows the sequence length AND holds one byte per

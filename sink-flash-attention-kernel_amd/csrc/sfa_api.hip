@@ -1164,4 +1164,69 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
     return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream);
 }
 
+// The device arrays (slots, state) are not looked at: skipped pairs are decided by the kernel, as in copy_slots
+int sfa_ring_share_paged_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const int32_t* src_state,
+                               const sfa_tensor* dst_sink_k, const sfa_tensor* dst_sink_v, int32_t* dst_state,
+                               const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, void* stream) {
+    g_err[0] = 0;
+    static const char* const names[4] = {"src_sink_k", "src_sink_v", "dst_sink_k", "dst_sink_v"};
+    const sfa_tensor* const t[4] = {src_sink_k, src_sink_v, dst_sink_k, dst_sink_v};
+    int st;
+    for (int i = 0; i < 4; ++i)
+        if ((st = check_tensor(t[i], names[i], true))) return st;      // FP8 sinks: a byte copy
+    SFA_NEED(src_state, "src_state");
+    SFA_NEED(dst_state, "dst_state");
+    SFA_NEED(src_slots, "src_slots");
+    SFA_NEED(dst_slots, "dst_slots");
+    SFA_CHECK_ARG(n_pairs >= 0, "n_pairs must be >= 0 (got %d)", n_pairs);
+    if (n_pairs == 0) return SFA_OK;
+    for (int i = 1; i < 4; ++i)
+        SFA_CHECK_ARG(t[i]->dtype == t[0]->dtype,
+                      "ring_share_slots: %s and src_sink_k differ in dtype (the four buffers must share one)", names[i]);
+    const int64_t Hkv = t[0]->shape[1], ns = t[0]->shape[2], D = t[0]->shape[3];
+    for (int i = 0; i < 4; ++i)
+        SFA_CHECK_ARG(t[i]->shape[1] == Hkv && t[i]->shape[2] == ns && t[i]->shape[3] == D,
+                      "ring_share_slots: %s must be [S, H_kv, num_sink, D] = [S, %lld, %lld, %lld] in both pools (got [%lld, "
+                      "%lld, %lld, %lld])", names[i], (long long)Hkv, (long long)ns, (long long)D, (long long)t[i]->shape[0],
+                      (long long)t[i]->shape[1], (long long)t[i]->shape[2], (long long)t[i]->shape[3]);
+    for (int p = 0; p < 2; ++p) {
+        const int64_t S = t[2 * p]->shape[0];
+        SFA_CHECK_ARG(S >= 1 && S < (1ll << 30) && t[2 * p + 1]->shape[0] == S,
+                      "pool: the %s sink buffers must share shape[0] = S >= 1 (sink %lld / %lld)", p ? "dst" : "src",
+                      (long long)S, (long long)t[2 * p + 1]->shape[0]);
+    }
+    const int es = dtype_size(t[0]->dtype);
+    SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_share_slots: K/V rows must be a multiple of 16 bytes (head dim %lld)",
+                  (long long)D);
+    SFA_CHECK_ARG(Hkv >= 1 && Hkv < (1ll << 30) && ns * (D * es / 16) < (1ll << 30), "problem too large");
+    if ((st = check_rows16({t[0], t[1], t[2], t[3]}, es, 7, "ring_share_slots: rows of every tensor must be 16-byte aligned")))
+        return st;
+    return ring_share_slots_launch(src_sink_k, src_sink_v, src_state, dst_sink_k, dst_sink_v, dst_state, src_slots,
+                                   dst_slots, n_pairs, (hipStream_t)stream);
+}
+
+int sfa_pages_copy(const sfa_tensor* window_k, const sfa_tensor* window_v, const int32_t* src_pages,
+                   const int32_t* dst_pages, int n_pairs, void* stream) {
+    g_err[0] = 0;
+    int st;
+    if ((st = check_tensor(window_k, "window_k", true)) || (st = check_tensor(window_v, "window_v", true))) return st;
+    SFA_CHECK_ARG(n_pairs >= 0, "n_pairs must be >= 0 (got %d)", n_pairs);
+    if ((st = same_shape(window_k, window_v, "window_k", "window_v"))) return st;
+    SFA_CHECK_ARG(window_k->dtype != SFA_DTYPE_F32, "pages_copy: the page buffers hold bf16, f16 or FP8 (e4m3) (got dtype %d)",
+                  window_k->dtype);
+    SFA_CHECK_ARG(window_k->shape[0] >= 1 && window_k->shape[0] < (1ll << 30),
+                  "pages_copy: the page buffers need shape[0] = n_pages in [1, 2^30) (got %lld)", (long long)window_k->shape[0]);
+    if (n_pairs == 0) return SFA_OK;
+    SFA_NEED(src_pages, "src_pages");
+    SFA_NEED(dst_pages, "dst_pages");
+    const int64_t Hkv = window_k->shape[1], P = window_k->shape[2], D = window_k->shape[3];
+    const int es = dtype_size(window_k->dtype);
+    SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "pages_copy: K/V rows must be a multiple of 16 bytes (head dim %lld)",
+                  (long long)D);
+    SFA_CHECK_ARG(Hkv < (1ll << 30) && P < (1ll << 30) && Hkv * P < (1ll << 30) && Hkv * P * (D * es / 16) < (1ll << 30),
+                  "problem too large");
+    if ((st = check_rows16({window_k, window_v}, es, 6, "pages_copy: rows of every tensor must be 16-byte aligned"))) return st;
+    return pages_copy_launch(window_k, window_v, src_pages, dst_pages, n_pairs, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -1437,6 +1437,75 @@ __global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, Cop
     else copy(std::false_type{});
 }
 
+// sfa_ring_share_paged_slots: the unpaged half of a fork whose ring pages are shared through the table.  Pair i copies the
+// live sink rows (j < clamp(sink_len, 0, num_sink)) and the state row of slot s into slot d with the skip rules of
+// ring_copy_slots_kernel; src / dst carry no ring views, no ring byte is read or written.  A workgroup is (pair, KV head,
+// block of 256 16-byte pieces of that head's sink rows); the first thread of a pair's first block writes the state row.
+__global__ __launch_bounds__(256) void ring_share_slots_kernel(CopyPools src, CopyPools dst, int Hkv, int ns, int cpr,
+                                                               int es, int nblk, int same) {
+    const int blk = (int)(blockIdx.x % (unsigned)nblk);
+    const int rest = (int)(blockIdx.x / (unsigned)nblk);
+    const int hk = rest % Hkv, pair = rest / Hkv;
+    const int s = src.slots[pair], d = dst.slots[pair];
+    if ((unsigned)s >= (unsigned)src.S || (unsigned)d >= (unsigned)dst.S || (same && s == d)) return;
+    const int* st = src.state + (int64_t)s * 4;
+    const int st0 = st[0], st1 = st[1], st2 = st[2], st3 = st[3];
+    const int sl = st0 < 0 ? 0 : (st0 > ns ? ns : st0);
+    if (blk == 0 && hk == 0 && threadIdx.x == 0) {
+        int* dt = dst.state + (int64_t)d * 4;
+        dt[0] = st0, dt[1] = st1, dt[2] = st2, dt[3] = st3;
+    }
+    const int p = blk * 256 + (int)threadIdx.x;
+    if (p >= sl * cpr) return;
+    const int r = p / cpr, c = p - r * cpr;
+    auto at = [&](const View& b, int slot) {
+        return reinterpret_cast<u32x4*>(b.ptr + ((int64_t)slot * b.sb + (int64_t)hk * b.sh + (int64_t)r * b.sn) * es + (int64_t)c * 16);
+    };
+    const u32x4 kr = *at(src.sk, s), vr = *at(src.sv, s);
+    *at(dst.sk, d) = kr, *at(dst.sv, d) = vr;
+}
+
+// sfa_pages_copy: pair i copies the whole page s = src_pages[i] onto page d = dst_pages[i] of the page buffers
+// wk / wv [n_pages, Hkv, P, D], K and V, as bytes (the copy-on-write of a shared page).  A pair with s or d outside
+// [0, n_pages) or with s == d moves nothing.  A workgroup is (pair, block of 256 * kPagePieces consecutive 16-byte pieces
+// of the page: piece p = (hk * P + row) * cpr + ch); it reads the pair's two page ids once (blockIdx only: scalar loads).
+// As in ring_copy_slots_kernel a thread issues its kPagePieces loads of K and of V, 256 pieces apart (a wave-instruction
+// reads 1 KiB contiguous within a row run), before its first store; a piece past the page in the last block is loaded
+// from the page's last piece (a valid address) and not stored.  Page, head and row offsets are 64-bit products of the
+// view's strides, so the buffers may be strided views and lie behind 4 GiB.
+constexpr int kPagePieces = 4;
+
+__global__ __launch_bounds__(256) void pages_copy_kernel(View wk, View wv, const int* src_pages, const int* dst_pages,
+                                                         int n_pages, int P, int cpr, int es, int nblk, int per_page) {
+    const int blk = (int)(blockIdx.x % (unsigned)nblk), pair = (int)(blockIdx.x / (unsigned)nblk);
+    const int s = src_pages[pair], d = dst_pages[pair];
+    if ((unsigned)s >= (unsigned)n_pages || (unsigned)d >= (unsigned)n_pages || s == d) return;
+    const int p = blk * (256 * kPagePieces) + (int)threadIdx.x;     // < per_page + 1024 < 2^31 (host check)
+    const int rstep = 256 / cpr, cstep = 256 - rstep * cpr;
+    int r = p / cpr, c = p - r * cpr;            // r = hk * P + row
+    int64_t off_k[kPagePieces], off_v[kPagePieces];
+    bool ok[kPagePieces];
+#pragma unroll
+    for (int u = 0; u < kPagePieces; ++u) {
+        ok[u] = p + u * 256 < per_page;
+        const int rr = ok[u] ? r : per_page / cpr - 1, cc = ok[u] ? c : cpr - 1;
+        const int hk = rr / P, row = rr - hk * P;
+        off_k[u] = ((int64_t)hk * wk.sh + (int64_t)row * wk.sn) * es + (int64_t)cc * 16;
+        off_v[u] = ((int64_t)hk * wv.sh + (int64_t)row * wv.sn) * es + (int64_t)cc * 16;
+        r += rstep, c += cstep;
+        if (c >= cpr) c -= cpr, ++r;
+    }
+    const char *ks = wk.ptr + (int64_t)s * wk.sb * es, *vs = wv.ptr + (int64_t)s * wv.sb * es;
+    char *kd = wk.ptr + (int64_t)d * wk.sb * es, *vd = wv.ptr + (int64_t)d * wv.sb * es;
+    u32x4 kr[kPagePieces], vr[kPagePieces];
+#pragma unroll
+    for (int u = 0; u < kPagePieces; ++u)
+        kr[u] = *reinterpret_cast<const u32x4*>(ks + off_k[u]), vr[u] = *reinterpret_cast<const u32x4*>(vs + off_v[u]);
+#pragma unroll
+    for (int u = 0; u < kPagePieces; ++u)
+        if (ok[u]) *reinterpret_cast<u32x4*>(kd + off_k[u]) = kr[u], *reinterpret_cast<u32x4*>(vd + off_v[u]) = vr[u];
+}
+
 // one state row after every reader of it: write_pos += acc (mod Wc), window_len = min(window_len + acc, Wc), and - for a
 // per-sequence row - seen += acc.  Plain stores from vector lanes.
 __device__ __forceinline__ void advance_row(int* st, int acc, int wc, bool seen) {
@@ -1917,6 +1986,55 @@ int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_st
         if ((st = launch_status("ring_copy_slots"))) return st;
     }
     set_path("ring_copy_slots%s", pool_tag(src_pool));
+    return SFA_OK;
+}
+
+int ring_share_slots_launch(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const int32_t* src_state,
+                            const sfa_tensor* dst_sink_k, const sfa_tensor* dst_sink_v, int32_t* dst_state,
+                            const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, hipStream_t stream) {
+    const int es = dtype_size(src_sink_k->dtype);
+    const int Hkv = (int)src_sink_k->shape[1], ns = (int)src_sink_k->shape[2];
+    const int cpr = (int)(src_sink_k->shape[3] * es / 16);
+    const int64_t nblk = ns > 0 ? cdiv64((int64_t)ns * cpr, 256) : 1;      // num_sink == 0: the state row alone
+    const int64_t grid = (int64_t)n_pairs * Hkv * nblk;
+    if (grid >= (1ll << 31)) {
+        set_error("ring_share_slots: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (grid > 0) {
+        const CopyPools s{make_view(src_sink_k), make_view(src_sink_v), View{}, View{}, const_cast<int*>(src_state),
+                          src_slots, (int)src_sink_k->shape[0]};
+        const CopyPools d{make_view(dst_sink_k), make_view(dst_sink_v), View{}, View{}, dst_state, dst_slots,
+                          (int)dst_sink_k->shape[0]};
+        ring_share_slots_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(s, d, Hkv, ns, cpr, es, (int)nblk,
+                                                                          src_state == dst_state ? 1 : 0);
+        int st;
+        if ((st = launch_status("ring_share_slots"))) return st;
+    }
+    set_path("ring_share_slots_paged");
+    return SFA_OK;
+}
+
+int pages_copy_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const int32_t* src_pages,
+                      const int32_t* dst_pages, int n_pairs, hipStream_t stream) {
+    const int es = dtype_size(window_k->dtype);
+    const int Hkv = (int)window_k->shape[1], P = (int)window_k->shape[2];
+    const int cpr = (int)(window_k->shape[3] * es / 16);
+    const int64_t per_page = (int64_t)Hkv * P * cpr;        // < 2^30: checked on the host
+    const int64_t nblk = cdiv64(per_page, 256 * kPagePieces);
+    const int64_t grid = (int64_t)n_pairs * nblk;
+    if (grid >= (1ll << 31)) {
+        set_error("pages_copy: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (grid > 0) {
+        pages_copy_kernel<<<dim3((unsigned)grid), 256, 0, stream>>>(make_view(window_k), make_view(window_v), src_pages,
+                                                                    dst_pages, (int)window_k->shape[0], P, cpr, es,
+                                                                    (int)nblk, (int)per_page);
+        int st;
+        if ((st = launch_status("pages_copy"))) return st;
+    }
+    set_path("pages_copy");
     return SFA_OK;
 }
 

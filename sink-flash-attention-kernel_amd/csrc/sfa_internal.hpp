@@ -140,5 +140,12 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
                            hipStream_t stream, const SlotPool& src_pool, const SlotPool& dst_pool);
+// sfa_ring_share_paged_slots: the live sink rows and the state row of slot src_slots[i] into slot dst_slots[i]; no ring
+int ring_share_slots_launch(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const int32_t* src_state,
+                            const sfa_tensor* dst_sink_k, const sfa_tensor* dst_sink_v, int32_t* dst_state,
+                            const int32_t* src_slots, const int32_t* dst_slots, int n_pairs, hipStream_t stream);
+// sfa_pages_copy: page src_pages[i] onto page dst_pages[i] of the page buffers [n_pages, Hkv, P, D], K and V, as bytes
+int pages_copy_launch(const sfa_tensor* window_k, const sfa_tensor* window_v, const int32_t* src_pages,
+                      const int32_t* dst_pages, int n_pairs, hipStream_t stream);
 
 }  // namespace sfa

@@ -183,6 +183,12 @@ def _bind(lib):
     lib.sfa_ring_fill_varlen_paged_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp]
     lib.sfa_ring_copy_paged_slots.restype = i32
     lib.sfa_ring_copy_paged_slots.argtypes = [P, P, P, P, vp, P, P, P, P, vp, vp, vp, i32, vp, i32, vp, i32, vp]
+    # shared fork of a paged pool: the unpaged half of the slot copy (sinks + state of each side, no ring, no table), and
+    # the copy of whole pages (page buffers, src_pages, dst_pages, n_pairs, stream) in front of a store into a shared page
+    lib.sfa_ring_share_paged_slots.restype = i32
+    lib.sfa_ring_share_paged_slots.argtypes = [P, P, vp, P, P, vp, vp, vp, i32, vp]
+    lib.sfa_pages_copy.restype = i32
+    lib.sfa_pages_copy.argtypes = [P, P, vp, vp, i32, vp]
     # paged FP8 pool: the paged step, commit and fill plus `kv_scale` behind the table arguments (the copy is the paged one)
     lib.sfa_decode_ring_ragged_paged_fp8_slots.restype = i32
     lib.sfa_decode_ring_ragged_paged_fp8_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32,

@@ -40,12 +40,33 @@ class PageAllocator:
     """Host-side bookkeeping of a paged pool's table: a free list of pages and, per slot, the pages mapped so far.  Pure
     Python: it launches no kernel and never reads the device; the changed entries are written into ``table`` (device
     int32 ``[S, Wc / P]``) with torch ops.  It assumes that it alone writes the table it was given (a fresh table is
-    all -1)."""
+    all -1).
+
+    Shared pages (``share``, behind ``fork_slots(share=True)``): ``refcount[p]`` is the number of table entries that name
+    page p, and a page is on the free list iff its count is 0.  A page with a count above 1 is never stored into:
+    ``reserve`` gives a slot that is about to write into such a page one of its own and returns the ``(src_page,
+    dst_page)`` copies that every layer on this table must run (``sfa_pages_copy``) before the step.  What a step may
+    write is decided on the host from token counts alone: while ``tokens_after <= Wc`` the ring has not wrapped, ring
+    position equals token index, and the pages that intersect ``[lo, tokens_after)`` are the candidates (``lo[s]``: a
+    lower bound of the tokens slot s's ring held when it last took part in a share); beyond ``Wc`` the host cannot know
+    ``write_pos`` (a prompt longer than the ring is placed with ``write_pos = 0`` whatever its length modulo ``Wc``), so
+    every shared entry of the slot is made private.  ``shared[s]`` says whether slot s ever took part in a share: a pool
+    that never shares pays one flag test per slot in ``reserve``.  ``layers`` are the cache layers whose pools read this
+    table."""
 
     def __init__(self, table: torch.Tensor, num_pages: int, page_size: int, window_size: int):
         self.table, self.num_pages, self.page_size, self.window_size = table, int(num_pages), int(page_size), int(window_size)
         self.free_list = list(range(self.num_pages - 1, -1, -1))        # pop() hands out page 0 first
         self.rows = [[] for _ in range(table.shape[0])]                 # slot -> its pages, entry j = table[slot][j]
+        self.refcount = [0] * self.num_pages                            # page -> table entries that name it
+        self.lo = [0] * table.shape[0]                                  # slot -> ring tokens at its last share
+        self.shared = [False] * table.shape[0]                          # slot -> it may hold a page with a count above 1
+        self.layers = []                                                # the layers attached to this table
+
+    def attach(self, layer) -> None:
+        """Register a layer whose pool reads this table: ``reserve_pages`` runs the page copies on every one."""
+        if not any(l is layer for l in self.layers):
+            self.layers.append(layer)
 
     def _slots(self, slots):
         lst = slots.tolist() if isinstance(slots, torch.Tensor) else [int(x) for x in slots]
@@ -60,35 +81,118 @@ class PageAllocator:
             self.table[torch.tensor(rows, device=dev), torch.tensor(cols, device=dev)] = \
                 torch.tensor(vals, dtype=torch.int32, device=dev)
 
-    def reserve(self, slots, tokens_after) -> None:
+    @staticmethod
+    def _per_slot(x, n, what):
+        lst = [x] * n if isinstance(x, int) else (x.tolist() if isinstance(x, torch.Tensor) else [int(v) for v in x])
+        if len(lst) != n:
+            raise ValueError(f"{what} must be one number or one per slot ({n}), got {len(lst)}")
+        return lst
+
+    def reserve(self, slots, tokens_after, tokens_before=None):
+        """Map the prefix of pages ``tokens_after`` needs and make private every shared page the step may store into
+        (the class docstring has the rule).  Returns the ``(src_page, dst_page)`` copies decided, in table order; empty
+        for slots that share nothing.  ``tokens_before`` (ring tokens, one number or one per slot) lowers ``lo`` of a slot
+        first, for a caller that re-admitted it below the count of its last share.  Raises ``RuntimeError("out of pages:
+        need X, free Y")``, copies and growth counted together, before anything changes."""
         lst = self._slots(slots)
-        tok = [tokens_after] * len(lst) if isinstance(tokens_after, int) else \
-            (tokens_after.tolist() if isinstance(tokens_after, torch.Tensor) else [int(x) for x in tokens_after])
-        if len(tok) != len(lst):
-            raise ValueError(f"tokens_after must be one number or one per slot ({len(lst)}), got {len(tok)}")
-        more = [max(pages_needed(t, self.window_size, self.page_size) - len(self.rows[s]), 0) for s, t in zip(lst, tok)]
-        if sum(more) > len(self.free_list):
-            raise RuntimeError(f"out of pages: need {sum(more)}, free {len(self.free_list)}")
-        rows, cols, vals = [], [], []
+        tok = self._per_slot(tokens_after, len(lst), "tokens_after")
+        lo = [self.lo[s] for s in lst] if tokens_before is None else \
+            [min(self.lo[s], max(b, 0)) for s, b in zip(lst, self._per_slot(tokens_before, len(lst), "tokens_before"))]
+        P = self.page_size
+        more = [max(pages_needed(t, self.window_size, P) - len(self.rows[s]), 0) for s, t in zip(lst, tok)]
+        # an entry is copied if, after the copies decided before it in this call, its page still has another owner: of a
+        # source and its last fork reserving together only the first one copies
+        cow, taken, private = [], {}, []
+        for s, t, l in zip(lst, tok, lo):
+            if not self.shared[s]:          # never took part in a share: nothing to look at, whatever its length
+                continue
+            row = self.rows[s]
+            if t > self.window_size:        # every entry; afterwards the slot holds no shared page
+                js = range(len(row))
+                private.append(s)
+            else:                           # the entries j with j P < t and (j + 1) P > lo
+                js = range(min(l // P, len(row)), min(-(-t // P), len(row)))
+            for j in js:
+                if self.refcount[row[j]] - taken.get(row[j], 0) > 1:
+                    cow.append((s, j))
+                    taken[row[j]] = taken.get(row[j], 0) + 1
+        if len(cow) + sum(more) > len(self.free_list):
+            raise RuntimeError(f"out of pages: need {len(cow) + sum(more)}, free {len(self.free_list)}")
+        for s, l in zip(lst, lo):
+            self.lo[s] = l
+        for s in private:
+            self.shared[s] = False
+        rows, cols, vals, copies = [], [], [], []
+        for s, j in cow:
+            old, page = self.rows[s][j], self.free_list.pop()
+            self.refcount[old] -= 1
+            self.refcount[page] = 1
+            self.rows[s][j] = page
+            rows.append(s), cols.append(j), vals.append(page)
+            copies.append((old, page))
         for s, m in zip(lst, more):
             for _ in range(m):
                 page = self.free_list.pop()
+                self.refcount[page] = 1
                 rows.append(s), cols.append(len(self.rows[s])), vals.append(page)
                 self.rows[s].append(page)
         self._write(rows, cols, vals)
+        return copies
+
+    def share(self, src, dst, ring_tokens) -> None:
+        """Alias table rows (host lists only, nothing is popped from the free list): the row of ``dst[i]`` becomes the row
+        of ``src[i]`` and every aliased page gains a reference.  ``ring_tokens[i]`` (one number or one per pair) is the
+        exact number of tokens the ring of ``src[i]`` holds; it becomes ``lo`` of both slots.  One source may feed many
+        destinations.  A destination must map no page (``free`` comes first) and differ from its source."""
+        src, dst = [int(x) for x in src], self._slots(dst)
+        if len(src) != len(dst):
+            raise ValueError(f"share: src and dst must pair up, got {len(src)} and {len(dst)} entries")
+        lo = self._per_slot(ring_tokens, len(dst), "ring_tokens")
+        bad = [s for s in src if not 0 <= s < len(self.rows)]
+        if bad or any(s == d for s, d in zip(src, dst)) or set(src) & set(dst):
+            raise ValueError(f"share: src {src} / dst {dst}: each source must be a slot of the pool of {len(self.rows)} "
+                             f"that is no destination of the call")
+        for d in dst:
+            if self.rows[d]:
+                raise ValueError(f"share: slot {d} still maps {len(self.rows[d])} pages: free_pages({d}) comes first")
+        for s, d, l in zip(src, dst, lo):
+            self.rows[d] = list(self.rows[s])
+            self.lo[s] = self.lo[d] = max(int(l), 0)
+            self.shared[s] = self.shared[d] = True
+        for s in set(src):                  # one pass over a source's pages, however many destinations it feeds
+            n = src.count(s)
+            for page in self.rows[s]:
+                self.refcount[page] += n
+        if dst:                             # whole rows, copied where the table lives (a destination's row was all -1)
+            dev = self.table.device
+            self.table[torch.tensor(dst, device=dev)] = self.table[torch.tensor(src, device=dev)]
 
     def free(self, slots) -> None:
         rows, cols = [], []
         for s in self._slots(slots):
             for j, page in enumerate(self.rows[s]):
                 rows.append(s), cols.append(j)
-                self.free_list.append(page)
+                self.refcount[page] -= 1
+                if self.refcount[page] == 0:
+                    self.free_list.append(page)
             self.rows[s] = []
+            self.lo[s], self.shared[s] = 0, False
         self._write(rows, cols, [-1] * len(rows))
 
     def pool_bytes(self, H_kv: int, D: int, elem_bytes: int) -> int:
-        """Bytes of ring memory (K and V) the mapped pages hold."""
-        return 2 * sum(len(r) for r in self.rows) * H_kv * self.page_size * D * elem_bytes
+        """Bytes of ring memory (K and V) the mapped pages hold, a page that several slots share counted once."""
+        return 2 * len({p for r in self.rows for p in r}) * H_kv * self.page_size * D * elem_bytes
+
+
+def _copy_pages(pages: PageAllocator, copies) -> None:
+    """Run the page copies ``reserve`` decided: one upload of the pairs, then ``sfa_pages_copy`` on every layer attached to
+    the table, on the current stream.  A layer left out would go on reading the page of another sequence."""
+    if not copies:
+        return
+    pairs = torch.tensor([[s for s, _ in copies], [d for _, d in copies]], dtype=torch.int32, device=pages.table.device)
+    for layer in pages.layers:
+        if layer._pages is pages:       # a layer whose pool was set up anew has left this table
+            layer._pages_copy(pairs[0], pairs[1])
 
 
 class SinkCacheLayer(_HFLayer if _HAS_HF else object):
@@ -694,8 +798,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         of the slot's ``seen`` after the step; ``seen`` counts the sink tokens too, so at most one page more than the ring
         reaches is reserved (``num_sink <= page_size``).  The changed
         entries are written into ``page_table`` with torch ops on the current stream.  Raises ``RuntimeError("out of
-        pages: need X, free Y")`` before anything changes."""
-        self._require_paged("reserve_pages").reserve(slots, tokens_after)
+        pages: need X, free Y")`` before anything changes.
+
+        A slot that shares pages (``fork_slots(share=True)``) first gets a page of its own for every shared page the step
+        may store into (``PageAllocator``): the pairs are uploaded once and ``sfa_pages_copy`` runs on EVERY layer
+        attached to the table, on the current stream, behind the table write and in front of the caller's step."""
+        pages = self._require_paged("reserve_pages")
+        _copy_pages(pages, pages.reserve(slots, tokens_after))
 
     def free_pages(self, slots) -> None:
         """Return the pages of the host ``slots`` to the free list and write -1 into their table rows (a retired
@@ -818,6 +927,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             self.page_table = page_table if page_table is not None else \
                 torch.full((int(num_slots), per_slot), -1, dtype=torch.int32, device=device)
             self._pages = PageAllocator(self.page_table, num_pages, P, self.window_size)
+            self._pages.attach(self)
         # FP8 (OCP e4m3fn, one byte per element): the pool holds codes, the activations of the packed calls stay 16-bit;
         # the caller-owned static scales start at one (set_kv_scale)
         self.kv_scale = torch.ones(2, H_kv, dtype=torch.float32, device=device) if dtype == torch.float8_e4m3fn else None
@@ -901,8 +1011,21 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         hit = (torch.arange(st.shape[0], device=st.device, dtype=torch.int32)[:, None] == idx[None, :]).any(dim=1)
         st.mul_((~hit).to(torch.int32)[:, None])
 
-    def fork_slots(self, src, dst, source: Optional["SinkCacheLayer"] = None) -> None:
-        """Copy slots on the device (``sfa_ring_copy_slots``, one launch, no allocation, capturable): pair i copies slot
+    def fork_slots(self, src, dst, source: Optional["SinkCacheLayer"] = None, share: bool = False, tokens=None) -> None:
+        """``share=True`` (paged pool, within one pool): the fork SHARES the source's ring pages instead of copying them.
+        ``PageAllocator.share`` writes the source's table row into the destination's row (every page gains a reference),
+        ``sfa_ring_share_paged_slots`` copies the live sink rows and the state row, and no ring byte moves: time and
+        memory of the fork do not grow with the prompt.  Every later call on ``dst[i]`` still gives bitwise what it gives
+        after a copying fork, because ``reserve_pages`` hands a slot a private copy of a shared page before a step stores
+        into it (copy on first write).  ``tokens`` is required: the exact ``seen`` of each source (one int or one per
+        pair), from which the ring's fill ``max(tokens - num_sink, 0)`` is passed on.  ``src`` / ``dst`` must be host
+        lists or CPU tensors, every pair two distinct slots of the pool (no -1), and ``dst[i]`` must map no page
+        (``free_pages`` first): the table is host bookkeeping, so the call is not capturable.  ``source`` must be None or
+        this layer.  A slot that is re-admitted after ``release_slots`` needs ``free_pages`` in between, or the allocator
+        keeps the count of its last share.  On a layer whose table serves several layers use
+        ``SinkAttentionCache.fork_slots(share=True)``: the table is aliased once, not once per layer.
+
+        ``share=False`` (the default), every pool: copy slots on the device (``sfa_ring_copy_slots``, one launch, no allocation, capturable): pair i copies slot
         ``src[i]`` of ``source``'s pool (another pooled layer of equal geometry, dtype and device; default: this layer,
         a fork) into slot ``dst[i]`` of this layer's pool.  The live sink rows, the live ring slots (each at its
         position) and the state row are copied, so any later call on ``dst[i]`` gives bitwise what the same call on
@@ -914,6 +1037,17 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         of permuting in place.  ``src`` / ``dst``: device int32 ``[n]`` tensors, passed through unread, or host lists /
         CPU tensors, which are checked (equal lengths, range, the two undefined cases) and uploaded."""
         from . import _native as N
+        if share:
+            pages = self._require_paged("fork_slots(share=True)")
+            if len(pages.layers) > 1:
+                raise ValueError(f"fork_slots(share=True): this layer's page table serves {len(pages.layers)} layers and is "
+                                 f"aliased once, not once per layer: call SinkAttentionCache.fork_slots(share=True)")
+            src_l, dst_l, ring, src_t, dst_t = self._share_args(src, dst, source, tokens)
+            N.require_gpu(self.sink_k)
+            pages.share(src_l, dst_l, ring)
+            return self._share_call(src_t, dst_t)
+        if tokens is not None:
+            raise ValueError("fork_slots: tokens belongs to share=True")
         source = self if source is None else source
         if not isinstance(source, SinkCacheLayer):
             raise TypeError("fork_slots: source must be a SinkCacheLayer")
@@ -966,6 +1100,60 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                     raise ValueError(f"fork_slots: slots {both} are a destination and the source of another pair in one "
                                      f"call; fork into free slots (beam_fork_plan)")
         return src_t.to(self.window_k.device), dst_t.to(self.window_k.device)
+
+    def _share_args(self, src, dst, source, tokens):
+        """The arguments of ``fork_slots(share=True)`` checked on the host: (src list, dst list, the ring fill of each
+        source, src / dst as device int32 tensors)."""
+        self._require_pool("fork_slots")
+        self._require_paged("fork_slots(share=True)")
+        if source is not None and source is not self:
+            raise ValueError("fork_slots(share=True): pages are shared within one page buffer: source must be None or the "
+                             "object itself (between two pools use share=False)")
+        if any(isinstance(x, torch.Tensor) and x.is_cuda for x in (src, dst)):
+            raise TypeError("fork_slots(share=True): src / dst must be host lists or CPU tensors: the page table is host "
+                            "bookkeeping, so the call is not capturable")
+        src_l, dst_l = ([int(v) for v in (x.tolist() if isinstance(x, torch.Tensor) else x)] for x in (src, dst))
+        if len(src_l) != len(dst_l):
+            raise ValueError(f"fork_slots: src and dst must pair up, got {len(src_l)} and {len(dst_l)} entries")
+        S = self.num_slots
+        bad = [(s, d) for s, d in zip(src_l, dst_l) if not (0 <= s < S and 0 <= d < S) or s == d]
+        if bad:
+            raise ValueError(f"fork_slots(share=True): pairs {bad}: each must name two distinct slots of the pool of {S} "
+                             f"(no -1: a shared fork is not replayed)")
+        if tokens is None:
+            raise ValueError("fork_slots(share=True) needs tokens=: the exact seen of each source (one int or one per "
+                             "pair), which bounds the pages a later step may store into")
+        tok = [tokens] * len(src_l) if isinstance(tokens, int) else \
+            [int(t) for t in (tokens.tolist() if isinstance(tokens, torch.Tensor) else tokens)]
+        if len(tok) != len(src_l):
+            raise ValueError(f"fork_slots(share=True): tokens must be one number or one per pair ({len(src_l)}), got "
+                             f"{len(tok)}")
+        src_t, dst_t = self._fork_args(src_l, dst_l, self)      # a destination twice, a destination that is a source
+        return src_l, dst_l, [max(t - self.num_sink, 0) for t in tok], src_t, dst_t
+
+    def _share_call(self, src_t, dst_t) -> None:
+        """``sfa_ring_share_paged_slots`` on this layer: sinks and state rows of the pairs, no ring memory."""
+        from . import _native as N
+        N.require_gpu(self.sink_k, src_t, dst_t)
+        if src_t.numel() == 0:
+            return
+        st = self._dev_state
+        with torch.cuda.device(self.sink_k.device):
+            rc = N.lib().sfa_ring_share_paged_slots(N.desc(self.sink_k), N.desc(self.sink_v), st.data_ptr(),
+                                                    N.desc(self.sink_k), N.desc(self.sink_v), st.data_ptr(),
+                                                    src_t.data_ptr(), dst_t.data_ptr(), src_t.numel(),
+                                                    N.stream_ptr(self.sink_k.device))
+        N.check(rc, "sfa_ring_share_paged_slots")
+
+    def _pages_copy(self, src_pages, dst_pages) -> None:
+        """``sfa_pages_copy`` on this layer's page buffers (device int32 page ids, pair i: src -> dst)."""
+        from . import _native as N
+        N.require_gpu(self.window_k, src_pages, dst_pages)
+        wk, wv = self._ring_descs()
+        with torch.cuda.device(self.window_k.device):
+            rc = N.lib().sfa_pages_copy(wk, wv, src_pages.data_ptr(), dst_pages.data_ptr(), src_pages.numel(),
+                                        N.stream_ptr(self.window_k.device))
+        N.check(rc, "sfa_pages_copy")
 
     def _require_dyn(self, what):
         if not (self.is_initialized and self.prefilled):
@@ -1329,6 +1517,7 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
                 raise ValueError("init_pool: the paged layers of a cache share one table and must agree in page_size "
                                  "and num_pages")
             layer._pages = self._pages
+            self._pages.attach(layer)      # reserve_pages copies pages on every layer of the table
         else:
             self.page_table, self._pages = layer.page_table, layer._pages
         return state
@@ -1337,7 +1526,7 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         """``SinkCacheLayer.reserve_pages`` on the table the layers share: one mapping serves every layer."""
         if self._pages is None:
             raise TypeError("reserve_pages needs a paged pool: init_pool(..., page_size=P)")
-        self._pages.reserve(slots, tokens_after)
+        _copy_pages(self._pages, self._pages.reserve(slots, tokens_after))
 
     def free_pages(self, slots) -> None:
         """``SinkCacheLayer.free_pages`` on the table the layers share."""
@@ -1375,10 +1564,34 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
             if layer._pool:
                 layer.release_slots(slots)
 
-    def fork_slots(self, src, dst, source: Optional["SinkAttentionCache"] = None) -> None:
+    def fork_slots(self, src, dst, source: Optional["SinkAttentionCache"] = None, share: bool = False,
+                   tokens=None) -> None:
         """``SinkCacheLayer.fork_slots`` of every layer that holds a pool: slot ``src[i]`` of ``source`` (another
         ``SinkAttentionCache`` whose layer l holds the pool that layer l here is paired with; default: this cache) into
-        slot ``dst[i]`` of this cache."""
+        slot ``dst[i]`` of this cache.  ``share=True`` (paged pools on the cache's one table; ``tokens``: the exact
+        ``seen`` of each source): the table rows are aliased ONCE (``PageAllocator.share``), then every pooled layer
+        copies its sinks and state rows (``sfa_ring_share_paged_slots``); rules and refusals as in
+        ``SinkCacheLayer.fork_slots``.  Host bookkeeping: not capturable."""
+        if share:
+            if self._pages is None:
+                raise TypeError("fork_slots(share=True) needs a paged pool: init_pool(..., page_size=P)")
+            if source is not None and source is not self:
+                raise ValueError("fork_slots(share=True): pages are shared within one page buffer: source must be None or "
+                                 "the object itself (between two pools use share=False)")
+            pooled = [layer for layer in self.layers if layer._pool]
+            if any(layer._pages is not self._pages for layer in pooled):
+                raise ValueError("fork_slots(share=True): every pooled layer of the cache must be paged on the cache's table")
+            args = [layer._share_args(src, dst, None, tokens) for layer in pooled]
+            if not args:
+                return
+            from . import _native as N
+            N.require_gpu(*(layer.sink_k for layer in pooled))
+            self._pages.share(*args[0][:3])
+            for layer, a in zip(pooled, args):
+                layer._share_call(a[3], a[4])
+            return
+        if tokens is not None:
+            raise ValueError("fork_slots: tokens belongs to share=True")
         if source is not None and not isinstance(source, SinkAttentionCache):
             raise TypeError("fork_slots: source must be a SinkAttentionCache")
         for l, layer in enumerate(self.layers):

@@ -21,7 +21,10 @@ Bytes: `live` = pairs x H_kv x (sink_len + window_len) x D x 2 bytes x 2 (K and 
 write.  TB/s = bytes each variant actually moves over its time: fork reads and writes `live` (2 x live; the 7
 destinations of 1to7 read the same source rows, counted 7 times), index reads and writes the capacity of the named slots
 twice (4 x capacity, with capacity = pairs x H_kv x (num_sink + W) x D x 2 x 2).
-usage: python tools/kbench_fork.py [--W 128,4096] [--rounds 7] [--calls 16] [--sets 4] [--eager]"""
+--share: another measurement - on a PAGED pool, fork_slots(share=True) against the copying fork: fork time, bytes of
+pages mapped, and the first reserve_pages + decode step after the fork (share_bench below).
+usage: python tools/kbench_fork.py [--W 128,4096] [--rounds 7] [--calls 16] [--sets 4] [--eager]
+       python tools/kbench_fork.py --share [--W 131072] [--page 64] [--prompt 100000] [--rounds 7]"""
 import argparse
 import os
 import sys
@@ -119,6 +122,73 @@ def _timed(torch, fn, calls, eager):
     return once
 
 
+def share_bench(torch, args, dev, dt):
+    """--share: a paged pool (P = --page, Wc = the first --W), one prompt of --prompt tokens forked into 7 slots, once by
+    the copying fork (reserve_pages of the destinations + fork_slots) and once by fork_slots(share=True), alternating;
+    then the first reserve_pages of the 8 slots (the copy-on-write pages of the shared fork) plus one committing decode
+    step of the 8.  Host clock around work that ends in a device synchronise (a shared fork is host bookkeeping plus one
+    launch and cannot be captured); median of --rounds rounds after two warm-up rounds, (+-x) half the spread."""
+    import time
+    from sink_attention import SinkCacheLayer
+    W, P, prompt, G = int(args.W.split(",")[0]), args.page, args.prompt, 8
+    per = W // P
+    need = -(-min(prompt + 8, W) // P)
+    layer = SinkCacheLayer(NS, W)
+    layer.init_pool(8, HKV, D, dt, dev, page_size=P, num_pages=8 * need + 8)
+    torch.manual_seed(0)
+    k = torch.randn(1, HKV, prompt, D, device=dev, dtype=dt)
+    layer.reserve_pages([0], prompt)
+    layer.prefill_slots(k, torch.randn_like(k), [0, prompt], [0])
+    al, dst, seen = layer._pages, list(range(1, 8)), prompt
+    q = torch.randn(1, HKV * G, 8, D, device=dev, dtype=dt)
+    kn, vn = torch.randn(1, HKV, 8, D, device=dev, dtype=dt), torch.randn(1, HKV, 8, D, device=dev, dtype=dt)
+    cu, slots = list(range(9)), list(range(8))
+    page_bytes = 2 * HKV * P * D * ES
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    def copy_fork():
+        layer.reserve_pages(dst, seen)
+        layer.fork_slots([0] * 7, dst)
+
+    def share_fork():
+        layer.fork_slots([0] * 7, dst, share=True, tokens=seen)
+
+    def first_step():
+        layer.reserve_pages(slots, seen + 1)
+        layer.ragged_step_dyn(q, kn, vn, cu, slots)
+
+    res = {v: {"fork": [], "step": [], "bytes": [], "cow": []} for v in ("copy", "share")}
+    for r in range(args.rounds + 2):
+        for v, fork in (("copy", copy_fork), ("share", share_fork)):
+            t_fork = clock(fork)
+            mapped = al.pool_bytes(HKV, D, ES)
+            free = len(al.free_list)
+            t_step = clock(first_step)
+            seen += 1
+            if r >= 2:
+                res[v]["fork"].append(t_fork), res[v]["step"].append(t_step), res[v]["bytes"].append(mapped)
+                res[v]["cow"].append(free - len(al.free_list))
+            layer.release_slots(dst)
+            layer.free_pages(dst)
+    med = lambda x: sorted(x)[len(x) // 2]
+    half = lambda x: (max(x) - min(x)) / 2
+    print(f"shared fork vs copying fork: H_kv={HKV} D={D} P={P} Wc={W} bf16, a prompt of {prompt} tokens ({need} pages of "
+          f"{page_bytes // 1024} KiB K+V, table rows of {per}) forked into 7 slots; host clock to a device synchronise, us, "
+          f"median of {args.rounds} rounds (+- half the spread), variants alternating", flush=True)
+    print("  variant   fork us (+-)      pages mapped MiB   first reserve + decode step us (+-)   pages taken by that step",
+          flush=True)
+    for v in ("copy", "share"):
+        x = res[v]
+        print(f"  {v:7s} {med(x['fork']):10.1f} ({half(x['fork']):7.1f})   {med(x['bytes']) / 2**20:12.1f}       "
+              f"{med(x['step']):10.1f} ({half(x['step']):7.1f})                  {med(x['cow']):6d}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--W", default="128,4096")
@@ -126,12 +196,18 @@ def main():
     ap.add_argument("--calls", type=int, default=16)
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--eager", action="store_true")
+    ap.add_argument("--share", action="store_true", help="paged pool: the shared fork against the copying fork")
+    ap.add_argument("--page", type=int, default=64, help="--share: page size")
+    ap.add_argument("--prompt", type=int, default=100000, help="--share: tokens of the forked prompt")
     args = ap.parse_args()
     import torch
     from sink_attention import _native
     if not torch.cuda.is_available():
         sys.exit("kbench_fork needs the GPU: there is nothing to time without one")
     dev, dt = "cuda", torch.bfloat16
+    if args.share:
+        print(f"library {_native.LIB_PATH}", flush=True)
+        return share_bench(torch, args, dev, dt)
     print(f"gpt-oss K/V geometry H_kv={HKV} D={D} num_sink={NS} bf16, pool of {S} slots; device us per call, median of "
           f"{args.rounds} rounds of {args.calls} calls ({'eager' if args.eager else 'one graph per variant'}), variants "
           f"alternating, {args.sets} slot sets in rotation; library {_native.LIB_PATH}", flush=True)
