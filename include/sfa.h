@@ -899,6 +899,58 @@ int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_ten
                                          const int32_t* page_table, int table_stride, const float* kv_scale,
                                          void* stream);
 
+/* ---- Fork groups: a shared prompt prefix is read once per group.
+ *
+ * sfa_decode_ring_ragged_group_paged_slots / sfa_decode_ring_ragged_group_paged_fp8_slots: the arguments of their paged
+ * siblings without `parent`, plus (cu_g, n_grp) behind (cu_q, n_seq).  cu_g: device int32 [n_grp + 1], offsets over the
+ * SEQUENCES of the pack, clamped into [0, n_seq] and made non-decreasing pairwise as cu_q is; group g is the consecutive
+ * sequences [cu_g[g], cu_g[g + 1]); a sequence that no group covers is ungrouped.  Never read on the host.
+ *
+ * The caller promises nothing about the groups: a preparation launch reads the state rows and the table and decides per
+ * group a shared length Lg, the largest multiple of P such that every MEMBER (an active sequence with n_i > 0; inactive
+ * and empty ones are skipped)
+ *   - is not admitting (SFA_FLAG_RAGGED_ADMIT and a fresh slot),
+ *   - has window_len + n_i <= Wc and write_pos == window_len (the ring is unwrapped and stays so within the step),
+ *   - has Lg <= window_len,
+ *   - has table entries j < Lg / P that are mapped and equal those of the group's first member.
+ * A group with fewer than two members has Lg = 0.  Groups must not overlap: if cu_g, clamped, decreases anywhere, every
+ * group of the call has Lg = 0 (the pairwise clamp alone would let [0, 4, 2, 6] name sequences 2 and 3 twice), so o is
+ * defined - the ungrouped call's - for any cu_g.  Ring slots [0, Lg) are then read once per 32-row block of the group's
+ * packed rows (from the first member's pages); every member reads its sinks, its ring slots [Lg, window_len) and its
+ * chunk itself.
+ *   - o is the softmax over exactly the keys the ungrouped call sees, within the tolerance of that call; where every
+ *     group has Lg = 0 it is bitwise the ungrouped call's.  The partition of a row's keys into splits depends on Lg, on the
+ *     call's shape and on the sequence's own (state row, n_i) only, and the fold order is fixed (the row's own partials,
+ *     its group's, s_aux): the same inputs give the same bits, under any grouping that yields the same Lg.
+ *   - Commit, advance, commit_seq, zeros for inactive and empty rows and the state-ordering rule are those of
+ *     sfa_decode_ring_ragged_paged_slots: the pool and the state rows end bitwise as the ungrouped call leaves them.  The
+ *     preparation launch only reads state rows and table; the advance stays the call's last launch.
+ * Workspace: sfa_decode_ragged_group_workspace_bytes(n_seq, n_grp, Hq, Hkv, T, Nkv_cache = num_sink + table_stride * P, D,
+ * dtype): the ungrouped workspace plus the group partials and tables; 0 for shapes no grouped instance serves (fp32, head
+ * dims other than 64 / 80 / 96 / 128).  Host checks: those of the sibling in its order, with "cu_g: null device pointer"
+ * and "decode_ragged: n_grp (n) must be at least 1" behind the n_seq check.  sfa_last_path(): the sibling's with "_group"
+ * in front of the pool tag ("..._ragged_commit_group_paged").  Out of scope: draft trees inside a group (no parent
+ * argument), groups on contiguous pools, a wrapped shared prefix, shared sink rows. */
+size_t sfa_decode_ragged_group_workspace_bytes(int64_t n_seq, int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T,
+                                               int64_t Nkv_cache, int64_t D, int dtype);
+
+int sfa_decode_ring_ragged_group_paged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                             const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                             const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                                             const float* s_aux, const int32_t* commit_seq, int commit, int32_t* state,
+                                             const int32_t* slots, const int32_t* cu_q, int n_seq, const int32_t* cu_g,
+                                             int n_grp, const int32_t* page_table, int table_stride, void* workspace,
+                                             size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
+int sfa_decode_ring_ragged_group_paged_fp8_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
+                                                 const sfa_tensor* window_k, const sfa_tensor* window_v,
+                                                 const sfa_tensor* k_new, const sfa_tensor* v_new, const sfa_tensor* o,
+                                                 const float* s_aux, const int32_t* commit_seq, int commit,
+                                                 int32_t* state, const int32_t* slots, const int32_t* cu_q, int n_seq,
+                                                 const int32_t* cu_g, int n_grp, const int32_t* page_table,
+                                                 int table_stride, const float* kv_scale, void* workspace,
+                                                 size_t workspace_bytes, float scale, unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -626,17 +626,20 @@ int ring_ragged(const RingCall& c) {
     if (c.pool.pt.table && !c.pool.fp8 &&
         (st = check_pool_served(Who("decode_ragged", c.pool), c.pool, q->dtype, q->shape[3], c.flags)))
         return st;
-    const size_t need = decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
-                                                c.sink_len + c.window_len, q->shape[3], q->dtype);
+    const size_t need = c.cu_g ? decode_ragged_group_workspace(c.n_seq, c.n_grp, q->shape[1], c.k_new->shape[1], q->shape[2],
+                                                               c.sink_len + c.window_len, q->shape[3], q->dtype)
+                               : decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
+                                                         c.sink_len + c.window_len, q->shape[3], q->dtype);
     if ((st = check_workspace("decode_ragged", need, need != 0, c.workspace, c.workspace_bytes))) return st;
     return decode_ragged_launch(c);
 }
 
 // the packed attention entry points, sfa_decode_ring_ragged{,_tree,_fp8,_paged,_paged_fp8}_slots: c as SFA_ATTEND_CALL
 // fills it, `in` the pool.  The order of the checks: the pages and table of a paged call, the null device arrays, n_seq,
-// then ring_ragged
+// then ring_ragged.  grouped (the *_group_paged_slots calls): cu_g / n_grp are checked behind cu_q / n_seq
 int ragged_slots(RingCall c, const int32_t* parent, const int32_t* commit_seq, int commit, int32_t* state,
-                 const int32_t* slots, const int32_t* cu_q, int n_seq, const PoolIn& in = PoolIn{}) {
+                 const int32_t* slots, const int32_t* cu_q, int n_seq, const PoolIn& in = PoolIn{}, bool grouped = false,
+                 const int32_t* cu_g = nullptr, int n_grp = 0) {
     g_err[0] = 0;
     PagedRing ring;
     int st;
@@ -646,6 +649,11 @@ int ragged_slots(RingCall c, const int32_t* parent, const int32_t* commit_seq, i
     SFA_NEED(slots, "slots");
     SFA_NEED(cu_q, "cu_q");
     SFA_CHECK_ARG(n_seq >= 1, "decode_ragged: n_seq (%d) must be at least 1", n_seq);
+    if (grouped) {
+        SFA_NEED(cu_g, "cu_g");
+        SFA_CHECK_ARG(n_grp >= 1, "decode_ragged: n_grp (%d) must be at least 1", n_grp);
+        c.cu_g = cu_g, c.n_grp = n_grp;
+    }
     c.commit = commit, c.cu_q = cu_q, c.n_seq = n_seq;
     c.parent = parent, c.commit_seq = commit_seq;
     return ring_ragged(device_state(c, RingState::Rows, state, slots));
@@ -1123,6 +1131,26 @@ int sfa_decode_ring_ragged_paged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* par
                                            SFA_TAIL_PARAMS) {
     return ragged_slots(SFA_ATTEND_CALL, parent, commit_seq, commit, state, slots, cu_q, n_seq,
                         PoolIn{true, kv_scale, true, page_table, table_stride});
+}
+
+size_t sfa_decode_ragged_group_workspace_bytes(int64_t n_seq, int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T,
+                                               int64_t Nkv_cache, int64_t D, int dtype) {
+    return decode_ragged_group_workspace(n_seq, n_grp, Hq, Hkv, T, Nkv_cache, D, dtype);
+}
+
+int sfa_decode_ring_ragged_group_paged_slots(SFA_ATTEND_PARAMS, const int32_t* commit_seq, int commit, int32_t* state,
+                                             const int32_t* slots, const int32_t* cu_q, int n_seq, const int32_t* cu_g,
+                                             int n_grp, const int32_t* page_table, int table_stride, SFA_TAIL_PARAMS) {
+    return ragged_slots(SFA_ATTEND_CALL, nullptr, commit_seq, commit, state, slots, cu_q, n_seq,
+                        PoolIn{false, nullptr, true, page_table, table_stride}, true, cu_g, n_grp);
+}
+
+int sfa_decode_ring_ragged_group_paged_fp8_slots(SFA_ATTEND_PARAMS, const int32_t* commit_seq, int commit, int32_t* state,
+                                                 const int32_t* slots, const int32_t* cu_q, int n_seq, const int32_t* cu_g,
+                                                 int n_grp, const int32_t* page_table, int table_stride,
+                                                 const float* kv_scale, SFA_TAIL_PARAMS) {
+    return ragged_slots(SFA_ATTEND_CALL, nullptr, commit_seq, commit, state, slots, cu_q, n_seq,
+                        PoolIn{true, kv_scale, true, page_table, table_stride}, true, cu_g, n_grp);
 }
 
 int sfa_ring_commit_path_ragged_paged_fp8_slots(SFA_COMMIT_PARAMS, const int32_t* path, const int32_t* cu_q, int n_seq,

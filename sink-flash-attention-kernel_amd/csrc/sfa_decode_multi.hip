@@ -183,8 +183,29 @@ struct PageArgs {
     int npages;
 };
 
+// ---- fork groups (the *_group_paged_slots calls).  Group g = the consecutive sequences
+// [cu_g[g], cu_g[g + 1]) of the pack.  group_prep_kernel decides a shared length Lg per group (ring slots [0, Lg) are the
+// same pages for every member, unwrapped and visible to every row); those slots are read once per 32-row block of the
+// GROUP's rows by the shared-phase workgroups (the first `nsh` block ids of the split launch), which write one partial per
+// row and group split into the second partial area (Mg, Lg, Og; stride Sgw).  A member's own workgroups skip [0, Lg).
+// The last trailing argument, and the `Grouped` flag of an instance: an instance is grouped iff its pack ends in GroupArgs
+// (has_arg below) - the flag is read off the pack and is no template parameter, so that every instance without groups
+// keeps its name.
+struct GroupArgs {
+    const int* cu_g;             // [n_grp + 1], device, not validated: offsets over the sequences of the pack
+    int n_grp;
+    const int2* gblk;            // [ngrb] group row-block id -> (group, local 32-row block); group -1: surplus
+    const int2* glg;             // [n_grp] (Lg, cache row of the group's first active non-empty member)
+    const int* gseq;             // [n_seq] sequence -> its group, -1: ungrouped
+    float *Mg, *Lg, *Og;         // the group partials [rows][Sgw], [rows][Sgw], [rows][Sgw][D], rows as in MultiArgs
+    int ngrb;                    // the group row-block bound ceil(G * T / 32) + n_grp
+    int Sgw;                     // launched group splits = stride of the group partials: the bound over Lg <= Wc
+    int want_g;                  // want_splits(1, Hkv, ngrb): the cap of a group's split count
+    int nsh;                     // shared-phase block ids of the split launch: Hkv * Sgw * ngrb rounded up to 8
+};
+
 // The optional trailing arguments of a kernel (`RA...` behind MultiArgs, `KA...` behind a storing kernel's own): of
-// RaggedArgs, Kv8Args and PageArgs, in that order, an instance takes the ones its flags name and no other - its
+// RaggedArgs, Kv8Args, PageArgs and GroupArgs, in that order, an instance takes the ones its flags name and no other - its
 // signature, argument block and code stay those of a kernel without the others.  arg_of<W>(pack...) is the member of
 // type W by reference, or a W of zeros where the instance takes none (Kv8Args: scale null = all ones).
 template <typename W>
@@ -194,11 +215,14 @@ __device__ __forceinline__ decltype(auto) arg_of(const A0& a0, const A&... rest)
     if constexpr (std::is_same_v<W, A0>) return (a0);
     else return arg_of<W>(rest...);
 }
-// the guard of every kernel with such a pack: exactly the arguments that the flags name (their order is dispatch_pool's)
+template <typename W, typename... A>
+constexpr bool has_arg = (std::is_same_v<A, W> || ...);
+// the guard of every kernel with such a pack: exactly the arguments that the flags name (their order is dispatch_pool's);
+// GroupArgs may follow on a (Ragged, Paged) instance
 template <bool Ragged, bool KV8, bool Paged, typename... A>
-constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) &&
-                         (std::is_same_v<A, RaggedArgs> || ...) == Ragged && (std::is_same_v<A, Kv8Args> || ...) == KV8 &&
-                         (std::is_same_v<A, PageArgs> || ...) == Paged;
+constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) + (has_arg<GroupArgs, A...> ? 1 : 0) &&
+                         has_arg<RaggedArgs, A...> == Ragged && has_arg<Kv8Args, A...> == KV8 &&
+                         has_arg<PageArgs, A...> == Paged && !(has_arg<GroupArgs, A...> && !(Ragged && Paged));
 
 // the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
 // of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
@@ -247,6 +271,23 @@ __global__ __launch_bounds__(1024) void ragged_prep_kernel(RaggedArgs rg, int2* 
             blk[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
         }
     }
+}
+
+// group g of the pack: its sequences [i0, i1) (cu_g clamped into [0, n_seq] and made non-decreasing pairwise, as
+// ragged_seq does for cu_q) and its packed rows [c0, c0 + n): from the first row of sequence i0 to the end of sequence
+// i1 - 1.  An empty group has n = 0.
+struct GroupSpan {
+    int i0, i1, c0, n;
+};
+
+__device__ __forceinline__ GroupSpan group_span(const RaggedArgs& rg, const GroupArgs& gr, int g) {
+    int i0 = gr.cu_g[g], i1 = gr.cu_g[g + 1];
+    i0 = i0 < 0 ? 0 : (i0 > rg.n_seq ? rg.n_seq : i0);
+    i1 = i1 < i0 ? i0 : (i1 > rg.n_seq ? rg.n_seq : i1);
+    if (i1 == i0) return GroupSpan{i0, i1, 0, 0};
+    const RaggedSeq a = ragged_seq(rg, i0), z = ragged_seq(rg, i1 - 1);
+    const int n = z.c0 + z.n - a.c0;
+    return GroupSpan{i0, i1, a.c0, n < 0 ? 0 : n};
 }
 
 inline __host__ __device__ int cdiv_i(int x, int y) { return (x + y - 1) / y; }
@@ -341,8 +382,16 @@ __device__ __forceinline__ int state_wp(const MultiArgs& a, int c) {
 // Ragged: the chunk length is n (the sequence's own n_i) in place of a.n; admit (the call's flag): a fresh slot
 // (seen == 0) reads as an empty cache whatever the other three fields hold, and the first min(n, ns) chunk tokens are
 // the sequence's sinks
-template <bool Dyn, bool Ragged = false>
-__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0, [[maybe_unused]] int admit = 0) {
+// Grouped: lg = the shared length of the sequence's group (0: none).  The plan covers the PRIVATE ring slots
+// [lg, window_len) alone - ring tile i starts at slot lg + 32 (i - T0), tile_info's roff - while wl and wp stay the
+// ring's, for the mask.
+// shared (a shared-phase workgroup of the group, c = its first member's row): ring slots [0, lg) as a ring of lg slots
+// without sinks and without a chunk, split by a plan of (lg, want_g = the call's shape) alone - every member, whatever
+// its own state, folds the same S partials.  One construction of the Fill for both phases.
+template <bool Dyn, bool Ragged = false, bool Grouped = false>
+__device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0, [[maybe_unused]] int admit = 0,
+                                         [[maybe_unused]] int lg = 0, [[maybe_unused]] bool shared = false,
+                                         [[maybe_unused]] int want_g = 0) {
     if constexpr (!Dyn) {
         return Fill{a.sink_len, a.wl, a.wp, a.T0, a.T1, a.T, a.tps, a.S, 0};
     } else {
@@ -360,9 +409,117 @@ __device__ __forceinline__ Fill get_fill(const MultiArgs& a, int c, int n = 0, [
         if constexpr (Ragged) {
             if (__builtin_amdgcn_readfirstlane((int)admits(admit, st))) sl = wl = wp = 0, nsk = n < a.ns ? n : a.ns;
         }
-        const MultiPlan p = multi_plan(sl, wl, Ragged ? n : a.n, a.want);
+        int pwl = wl;                // the ring slots the plan covers
+        [[maybe_unused]] int want = a.want;
+        if constexpr (Grouped) {
+            pwl = lg < wl ? wl - lg : 0;
+            if (shared) sl = 0, wl = lg, wp = 0, nsk = 0, n = 0, pwl = lg, want = want_g;
+        }
+        const MultiPlan p = multi_plan(sl, pwl, Ragged ? n : a.n, Grouped ? want : a.want);
         auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };   // keep the plan in SGPRs
         return Fill{sl, wl, wp, u(p.T0), u(p.T1), u(p.T), u(p.tps), u(p.S), nsk};
+    }
+}
+
+// the second preparation launch of a grouped call, one workgroup of 1024 threads per group (block g decides group g;
+// the two maps are strided over the whole grid).  Unlike ragged_prep_kernel it READS the state rows and the page table:
+// the advance of the state is still the trailing launch of the call and the commit blocks run behind the split launch,
+// so every reader of a state row or a ring slot still comes before its writer (the state-ordering rule of
+// include/sfa.h holds unchanged).
+//   gblk: as ragged_prep_kernel's blk with groups in the place of sequences: group g owns the block ids
+//         [start_g, start_g + ceil(G n_g / 32)), start_g = floor(G c0_g / 32) + g, below ngrb = ceil(G T / 32) + n_grp;
+//   gseq: the last group that starts at or before the sequence, if it covers it;
+//   glg:  (Lg, the cache row of the first member).  A MEMBER is an active sequence (slot in the pool) with n_i > 0.
+//         Lg = the largest multiple of P such that for every member: it is not admitting; window_len + n_i <= Wc and
+//         write_pos == window_len (the ring is unwrapped and stays so within the step: slot = token, every slot visible
+//         to every new row); Lg <= window_len; table entries j < Lg / P are mapped and equal the first member's.
+//         Fewer than two members: Lg = 0.  A member whose rows leave the group's span (offsets that are not monotonic)
+//         makes Lg = 0 too, so that a row that folds group partials is always one a shared-phase workgroup wrote.
+//         Groups must not overlap for the same reason (two groups would write the same rows of the group partials
+//         under different plans): if the clamped cu_g decreases ANYWHERE, every group of the call gets Lg = 0 and the
+//         call computes what the ungrouped one does.
+//         The state fields are clamped as get_fill clamps them.  Pass 1: members strided over the threads (limit per
+//         member, minimum and first member through LDS; mrow[i] = the member's cache row, -1 for a sequence that is
+//         none).  Pass 2: the (member, entry) pairs strided over the threads - 8 members x 1563 entries are 13 rounds,
+//         not a serial walk - without a division and without a branch in front of the loads (a round is mrow, then two
+//         independent table entries); the first differing entry by an LDS minimum.
+__global__ __launch_bounds__(1024) void group_prep_kernel(RaggedArgs rg, GroupArgs gr, PageArgs pg, int2* gblk, int2* glg,
+                                                          int* gseq, int* mrow, const int* state, const int* slots,
+                                                          int npool, int wc, int G) {
+    __shared__ int s_lim, s_first, s_cnt, s_diff, s_bad;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    for (int x = g * 1024 + tid; x < gr.ngrb + rg.n_seq; x += gridDim.x * 1024) {
+        const bool sq = x >= gr.ngrb;
+        const int id = sq ? x - gr.ngrb : x;
+        int lo = 0, hi = gr.n_grp - 1;       // the last group whose start is at or before the id
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const GroupSpan s = group_span(rg, gr, mid);
+            // an empty group has no rows: it starts where it would lie in the pack, at the first row of sequence i0
+            const int c0 = s.n > 0 ? s.c0 : (s.i0 < rg.n_seq ? ragged_seq(rg, s.i0).c0 : rg.T);
+            const int64_t start = sq ? s.i0 : (int64_t)G * c0 / 32 + mid;
+            if (start <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        const GroupSpan s = group_span(rg, gr, lo);
+        if (sq) {
+            gseq[id] = (id >= s.i0 && id < s.i1) ? lo : -1;
+        } else {
+            const int64_t local = id - ((int64_t)G * s.c0 / 32 + lo);
+            const bool hit = s.n > 0 && local >= 0 && local * 32 < (int64_t)G * s.n;
+            gblk[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
+        }
+    }
+    if (tid == 0) s_lim = INT_MAX, s_first = INT_MAX, s_cnt = 0, s_diff = INT_MAX, s_bad = 0;
+    __syncthreads();
+    const GroupSpan sp = group_span(rg, gr, g);
+    const int P = 1 << pg.shift;
+    for (int x = tid; x < gr.n_grp; x += 1024) {       // offsets that decrease somewhere: groups may overlap
+        const int a0 = gr.cu_g[x], a1 = gr.cu_g[x + 1];
+        const int b0 = a0 < 0 ? 0 : (a0 > rg.n_seq ? rg.n_seq : a0), b1 = a1 < 0 ? 0 : (a1 > rg.n_seq ? rg.n_seq : a1);
+        if (b1 < b0) s_bad = 1;
+    }
+    for (int i = sp.i0 + tid; i < sp.i1; i += 1024) {
+        const int c = slots[i];
+        const RaggedSeq s = ragged_seq(rg, i);
+        const bool member = (unsigned)c < (unsigned)npool && s.n > 0;
+        mrow[i] = member ? c : -1;
+        if (!member) continue;                                         // inactive or empty
+        const int* st = state + (int64_t)c * 4;
+        int wl = st[1], wp = st[2];
+        wl = wl < 0 ? 0 : (wl > wc ? wc : wl);
+        wp = wp < 0 ? 0 : (wp >= wc ? wc - 1 : wp);
+        int lim = wl & ~(P - 1);
+        if (admits(rg.admit, st) || wl + s.n > wc || wp != wl) lim = 0;
+        if (s.c0 < sp.c0 || s.c0 + s.n > sp.c0 + sp.n) lim = 0;
+        atomicMin(&s_lim, lim);
+        atomicMin(&s_first, i);
+        atomicAdd(&s_cnt, 1);
+    }
+    __syncthreads();
+    const int first = s_first, cnt = s_cnt;
+    int lg = cnt >= 2 && !s_bad ? s_lim : 0;
+    const int c_first = cnt >= 1 ? slots[first] : 0;
+    const int ne = lg >> pg.shift, nm = sp.i1 - sp.i0;
+    if (ne > 0) {
+        // pair x = (member x / ne, entry x mod ne), x = tid + 1024 round: one division, then steps of 1024 pairs
+        const int istep = 1024 / ne, jstep = 1024 - istep * ne;
+        int i = sp.i0 + tid / ne, j = tid % ne;
+        int diff = INT_MAX;
+        for (int64_t x = tid; x < (int64_t)nm * ne; x += 1024) {
+            const int c = mrow[i];         // this workgroup wrote it in front of the barrier above
+            const int e0 = pg.table[(int64_t)c_first * pg.stride + j];
+            const int e = pg.table[(int64_t)(c < 0 ? c_first : c) * pg.stride + j];
+            if (c >= 0 && ((unsigned)e0 >= (unsigned)pg.npages || e != e0)) diff = min(diff, j);
+            i += istep, j += jstep;
+            if (j >= ne) j -= ne, ++i;
+        }
+        if (diff != INT_MAX) atomicMin(&s_diff, diff);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (s_diff < ne) lg = s_diff << pg.shift;
+        glg[g] = make_int2(lg, c_first);
     }
 }
 
@@ -387,16 +544,17 @@ __device__ __forceinline__ int ring_chron(const MultiArgs& a, const Fill& f, int
 // KV8: sink and ring tiles are FP8 rows (1 byte per element); the chunk keeps es
 // Paged: a ring tile gets its place inside its page (rows [start mod P, ...) of page 0); tile_page adds the page once
 // the tile is known to be live
+// roff (a grouped sequence's own workgroups): the first ring slot of the plan, a multiple of P; 0 everywhere else
 template <bool Ragged = false, bool KV8 = false, bool Paged = false>
 __device__ __forceinline__ TileInfo tile_info(const MultiArgs& a, const Fill& f, int i, int b, int c, int hk, int es,
-                                              int n = 0, int crow = 0, [[maybe_unused]] int pshift = 0) {
+                                              int n = 0, int crow = 0, [[maybe_unused]] int pshift = 0, int roff = 0) {
     TileInfo ti;
     const View *kv, *vv;
     int len, row = c;            // sink and ring: the cache row; the chunk: the batch row
     if (i < f.T0) {
         ti.seg = 0, ti.start = kTile * i, len = f.sink_len, kv = &a.sk, vv = &a.sv;
     } else if (i < f.T1) {
-        ti.seg = 1, ti.start = kTile * (i - f.T0), len = f.wl, kv = &a.wk, vv = &a.wv;
+        ti.seg = 1, ti.start = roff + kTile * (i - f.T0), len = f.wl, kv = &a.wk, vv = &a.wv;
     } else {
         ti.seg = 2, ti.start = kTile * (i - f.T1), len = Ragged ? n : a.n, kv = &a.kn, vv = &a.vn, row = b;
     }
@@ -576,9 +734,12 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
                       !(Paged && !Ragged),
                   "ragged: (MultiArgs, RaggedArgs); FP8 pool: (MultiArgs, RaggedArgs, Kv8Args); paged pool: (MultiArgs, "
                   "RaggedArgs, PageArgs); paged FP8 pool: (MultiArgs, RaggedArgs, Kv8Args, PageArgs)");
+    constexpr bool Grouped = has_arg<GroupArgs, RA...>;      // fork groups: the paged forms plus a trailing GroupArgs
+    static_assert(!(Grouped && Tree), "no draft trees inside a group");
     [[maybe_unused]] const RaggedArgs& rg = arg_of<RaggedArgs>(ra...);
     [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ra...);
     [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ra...);
+    [[maybe_unused]] const GroupArgs& gr = arg_of<GroupArgs>(ra...);
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int DK = D / 16;           // k-steps of the K Q^T contraction
@@ -592,33 +753,67 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     static_assert(2 * kWaves * 32 * 4 + 32 * DP * 4 <= kWaves * 2 * TILE_BYTES, "merge area must fit the tile area");
     __shared__ __attribute__((aligned(16))) char smem[kWaves * 2 * TILE_BYTES];
 
-    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
-    int rb = wid % a.nrb;
-    int rest = wid / a.nrb;
-    const int split = rest % a.Sw;   // decomposition over the LAUNCHED splits
-    rest /= a.Sw;
+    // Grouped: block ids [0, nsh) are the shared-phase workgroups (the long ones, so they start first), the rest the
+    // members' own; each range gets its own XCD-aware ids (nsh is a multiple of 8: a block's XCD stays bid mod 8)
+    int bid = blockIdx.x, nbid = gridDim.x;
+    [[maybe_unused]] bool shared = false;
+    if constexpr (Grouped) {
+        shared = bid < gr.nsh;
+        if (shared) nbid = gr.nsh;
+        else bid -= gr.nsh, nbid -= gr.nsh;
+    }
+    const int wid = xcd_work_id(bid, nbid);
+    const int nrb_w = Grouped && shared ? gr.ngrb : a.nrb, Sw_w = Grouped && shared ? gr.Sgw : a.Sw;
+    int rb = wid % nrb_w;
+    int rest = wid / nrb_w;
+    const int split = rest % Sw_w;   // decomposition over the LAUNCHED splits
+    rest /= Sw_w;
     const int hk = rest % a.Hkv;
     const int b = rest / a.Hkv;
+    if (Grouped && b > 0) return;      // the padding of nsh (a pack has B = 1)
     int c = b;                         // the cache row: per workgroup, in an SGPR
     // ragged: the sequence's length, rows and first packed row (in place of a.n, a.R and batch row b)
     [[maybe_unused]] int rn = 0, rR = 0, prow = 0;
+    // grouped: the shared length of the workgroup's group (0: the sequence is in none, or its group shares nothing)
+    [[maybe_unused]] int lg = 0;
     const auto nrow = [&]() { if constexpr (Ragged) return rR; else return a.R; };
     if constexpr (Ragged) {
-        const int2 e = rg.blk[rb];
-        const int seq = __builtin_amdgcn_readfirstlane(e.x);
-        if (seq < 0) return;           // surplus of the row-block bound (whole workgroup)
-        rb = __builtin_amdgcn_readfirstlane(e.y);
-        c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
-        if (c < 0) return;             // inactive sequence: the reduce writes its zeros
-        const RaggedSeq s = ragged_seq(rg, seq);
-        prow = __builtin_amdgcn_readfirstlane(s.c0);
-        rn = __builtin_amdgcn_readfirstlane(s.n);
-        rR = a.G * rn;
+        if (Grouped && shared) {
+            // a shared-phase workgroup: (group, 32-row block of the group's rows, KV head, group split).  Its rows are
+            // the group's packed rows as ONE virtual sequence, its keys ring slots [0, lg) of the first member's pages
+            const int2 e = gr.gblk[rb];
+            const int g = __builtin_amdgcn_readfirstlane(e.x);
+            if (g < 0) return;         // surplus of the group row-block bound
+            rb = __builtin_amdgcn_readfirstlane(e.y);
+            const int2 gl = gr.glg[g];
+            lg = __builtin_amdgcn_readfirstlane(gl.x);
+            if (lg <= 0) return;       // nothing shared: the members read everything themselves
+            c = __builtin_amdgcn_readfirstlane(gl.y);
+            const GroupSpan sp = group_span(rg, gr, g);
+            prow = __builtin_amdgcn_readfirstlane(sp.c0);
+            rn = __builtin_amdgcn_readfirstlane(sp.n);
+            rR = a.G * rn;
+        } else {
+            const int2 e = rg.blk[rb];
+            const int seq = __builtin_amdgcn_readfirstlane(e.x);
+            if (seq < 0) return;           // surplus of the row-block bound (whole workgroup)
+            rb = __builtin_amdgcn_readfirstlane(e.y);
+            c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+            if (c < 0) return;             // inactive sequence: the reduce writes its zeros
+            const RaggedSeq s = ragged_seq(rg, seq);
+            prow = __builtin_amdgcn_readfirstlane(s.c0);
+            rn = __builtin_amdgcn_readfirstlane(s.n);
+            rR = a.G * rn;
+            if constexpr (Grouped) {
+                const int g = __builtin_amdgcn_readfirstlane(gr.gseq[seq]);
+                if (g >= 0) lg = __builtin_amdgcn_readfirstlane(gr.glg[g].x);
+            }
+        }
     } else if constexpr (Slots) {
         c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, b));
         if (c < 0) return;             // inactive row (whole workgroup): the reduce writes its zeros
     }
-    const Fill f = get_fill<Dyn, Ragged>(a, c, rn, rg.admit);
+    const Fill f = get_fill<Dyn, Ragged, Grouped>(a, c, rn, rg.admit, lg, shared, gr.want_g);
     if (Dyn && split >= f.S) return;   // surplus of the full-cache grid at this fill level (whole workgroup)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -744,9 +939,14 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
     auto next_live = [&](int i, TileInfo& ti, int& cls) {
         for (; i < tend; i += kWaves) {
-            ti = tile_info<Ragged, KV8, Paged>(a, f, i, b, c, hk, es, rn, prow, pg.shift);
+            // Grouped: a member's private ring slots start at lg; the shared phase walks ring tiles of [0, lg) only
+            if constexpr (Grouped) ti = tile_info<Ragged, KV8, Paged>(a, f, i, b, c, hk, es, rn, prow, pg.shift, shared ? 0 : lg);
+            else ti = tile_info<Ragged, KV8, Paged>(a, f, i, b, c, hk, es, rn, prow, pg.shift);
             if (Tree && Ragged && !is_tree) cls = tile_class(a, ti, tmin, tmax, f.nsk);
             else cls = tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
+            if constexpr (Grouped) {
+                if (shared) cls = 1;   // every shared tile is of class full: no sink tile, no chunk tile, no mask
+            }
             if (cls != 0) break;
         }
         if constexpr (Paged) {
@@ -877,6 +1077,32 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     // partial row of the block's first row
     const int64_t row0 = Ragged ? ((int64_t)hk * rg.T + prow) * a.G + 32 * rb : ((int64_t)b * a.Hkv + hk) * a.R + 32 * rb;
     const int nrows = nrow() - 32 * rb < 32 ? nrow() - 32 * rb : 32;
+    // one partial per row and split: [rows][Sw] of m and l, [rows][Sw][D] of O.  The same statements as the ungrouped
+    // stores below, which stay as they are for the resource records of the existing instances: change both together
+    [[maybe_unused]] auto store_partials = [&](float* Mp, float* Lp, float* Op, int Sw) {
+        if (tid < nrows) {
+            float ms = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) ms = fmaxf(ms, sm[w * 32 + tid]);
+            float lt = 0.f;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) {
+                const float mw = sm[w * 32 + tid];
+                lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
+            }
+            Mp[(row0 + tid) * Sw + split] = ms;
+            Lp[(row0 + tid) * Sw + split] = lt;
+        }
+        for (int e = tid; e < nrows * D; e += kWaves * 64) {
+            const int rr = e / D, d = e - rr * D;
+            Op[((row0 + rr) * Sw + split) * D + d] = so[rr * DP + d];
+        }
+    };
+    if constexpr (Grouped) {           // the same rows; a shared-phase workgroup writes the group's area with its stride
+        if (shared) store_partials(gr.Mg, gr.Lg, gr.Og, gr.Sgw);
+        else store_partials(a.Mp, a.Lp, a.Op, a.Sw);
+        return;
+    }
     if (tid < nrows) {
         float ms = -INFINITY;
 #pragma unroll
@@ -1129,6 +1355,7 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
                       !(Paged && !Ragged),
                   "ragged: (MultiArgs, nred, RaggedArgs); FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 "
                   "pool: (..., Kv8Args, PageArgs)");
+    constexpr bool Grouped = has_arg<GroupArgs, RA...>;      // fork groups: the paged forms plus a trailing GroupArgs
     [[maybe_unused]] const RaggedArgs& rg = arg_of<RaggedArgs>(ra...);
     const int es = (int)sizeof(T);
     if ((int)blockIdx.x >= nred) {
@@ -1164,23 +1391,47 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
             return;
         }
     }
-    const Fill f = get_fill<Dyn, Ragged>(a, c, rn, rg.admit);
+    // Grouped: a row of a sequence whose group shares lg > 0 ring slots folds its own S partials (the plan of its private
+    // part), then its group's Sg (the plan of (lg, the call's shape)), then s_aux - a fixed order, the same butterflies
+    [[maybe_unused]] int lg = 0, Sg = 0;
+    [[maybe_unused]] const GroupArgs& gr = arg_of<GroupArgs>(ra...);
+    if constexpr (Grouped) {
+        const int g = __builtin_amdgcn_readfirstlane(gr.gseq[rg.rowseq[prow + t]]);
+        if (g >= 0) lg = __builtin_amdgcn_readfirstlane(gr.glg[g].x);
+        if (lg > 0) Sg = multi_plan(0, lg, 0, gr.want_g).S;
+    }
+    const Fill f = get_fill<Dyn, Ragged, Grouped>(a, c, rn, rg.admit, lg);
     const int S = f.S, D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
     const float* Lr = a.Lp + rowid * a.Sw;
     const float* Or = a.Op + rowid * a.Sw * D;
+    [[maybe_unused]] const float *Mgr = nullptr, *Lgr = nullptr, *Ogr = nullptr;
+    if constexpr (Grouped) Mgr = gr.Mg + rowid * gr.Sgw, Lgr = gr.Lg + rowid * gr.Sgw, Ogr = gr.Og + rowid * gr.Sgw * D;
     const float sa = a.s_aux ? a.s_aux[head] * kLog2e : -INFINITY;
     // split statistics spread over the lanes (latency-bound: one round of loads, not S dependent ones), folded by the
     // fixed butterflies of wave_max / wave_sum
     float mloc = -INFINITY;
     for (int s = lane; s < S; s += 64) mloc = fmaxf(mloc, Mr[s]);
+    if constexpr (Grouped)
+        for (int s = lane; s < Sg; s += 64) mloc = fmaxf(mloc, Mgr[s]);
     const float mstar = fmaxf(wave_max(mloc), sa);   // finite: every row sees at least its own token
     float lloc = 0.f;
     for (int s = lane; s < S; s += 64) {
         const float ms = Mr[s];
         if (ms != -INFINITY) lloc += Lr[s] * __builtin_amdgcn_exp2f(ms - mstar);
     }
-    const float L = wave_sum(lloc) + (sa == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sa - mstar));
+    float Lsum = wave_sum(lloc);
+    if constexpr (Grouped) {
+        if (Sg > 0) {                 // lg = 0: the sum above alone, bit for bit the instance without groups
+            float gloc = 0.f;
+            for (int s = lane; s < Sg; s += 64) {
+                const float ms = Mgr[s];
+                if (ms != -INFINITY) gloc += Lgr[s] * __builtin_amdgcn_exp2f(ms - mstar);
+            }
+            Lsum += wave_sum(gloc);
+        }
+    }
+    const float L = Lsum + (sa == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sa - mstar));
     const float inv = 1.f / L;
     T* orow = reinterpret_cast<T*>(a.o.ptr + ((int64_t)b * a.o.sb + (int64_t)head * a.o.sh + (int64_t)(Ragged ? prow + t : t) * a.o.sn) * es);
     for (int d = lane; d < D; d += 64) {
@@ -1189,6 +1440,13 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
         for (int s = 0; s < S; ++s) {
             const float ms = Mr[s];
             if (ms != -INFINITY) acc = fmaf(Or[(int64_t)s * D + d], __builtin_amdgcn_exp2f(ms - mstar), acc);
+        }
+        if constexpr (Grouped) {
+#pragma unroll 8
+            for (int s = 0; s < Sg; ++s) {     // no branch in front of the loads: a round of them is in flight at once
+                const float ms = Mgr[s];
+                acc = fmaf(Ogr[(int64_t)s * D + d], ms == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ms - mstar), acc);
+            }
         }
         orow[d] = from_f32<T>(acc * inv);
     }
@@ -1651,14 +1909,21 @@ int split_status(const MultiArgs& a, const RaggedArgs* rg, const char* kind) {
 }
 
 // pool (packed calls only): the (Dyn, Slots, Ragged) instances in the form of the pool, Tree on or off
+// grp (a grouped call: paged pool, no tree): the grouped instance of that form, its shared-phase block ids in front
 template <typename T, int D>
-int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, hipStream_t stream) {
-    const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb));
+int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, hipStream_t stream) {
+    const dim3 grid((unsigned)((int64_t)a.B * a.Hkv * a.Sw * a.nrb + (grp ? grp->nsh : 0)));
     dispatch_mode(a, rg, [&](auto m) {
         using M = decltype(m);
         if constexpr (M::Ragged)
             dispatch_pool(pool, [&](auto p, auto... tail) {
                 using P = decltype(p);
+                if constexpr (P::Paged && !M::Tree) {
+                    if (grp) {
+                        multi_split_mfma_kernel<T, D, M::Dyn, false, M::Slots, true, P::KV8, true><<<grid, kWaves * 64, 0, stream>>>(a, *rg, tail..., *grp);
+                        return;
+                    }
+                }
                 multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots, true, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(a, *rg, tail...);
             });
         else multi_split_mfma_kernel<T, D, M::Dyn, M::Tree, M::Slots><<<grid, kWaves * 64, 0, stream>>>(a);
@@ -1667,12 +1932,12 @@ int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
 }
 
 template <typename T>
-int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, hipStream_t stream) {
+int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, hipStream_t stream) {
     switch (a.D) {
-        case 64: return launch_mfma<T, 64>(a, rg, pool, stream);
-        case 80: return launch_mfma<T, 80>(a, rg, pool, stream);
-        case 96: return launch_mfma<T, 96>(a, rg, pool, stream);
-        case 128: return launch_mfma<T, 128>(a, rg, pool, stream);
+        case 64: return launch_mfma<T, 64>(a, rg, pool, grp, stream);
+        case 80: return launch_mfma<T, 80>(a, rg, pool, grp, stream);
+        case 96: return launch_mfma<T, 96>(a, rg, pool, grp, stream);
+        case 128: return launch_mfma<T, 128>(a, rg, pool, grp, stream);
     }
     set_error("decode_multi: no MFMA kernel for head dim %d", a.D);
     return SFA_ERR_UNSUPPORTED;
@@ -1681,10 +1946,10 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
 // pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
-int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, pool, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, pool, grp, stream) : SFA_OK;
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
         dispatch_mode(a, rg, [&](auto m) {
@@ -1707,6 +1972,12 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
         if constexpr (M::Ragged && sizeof(T) == 2)
             dispatch_pool(pool, [&](auto p, auto... tail) {
                 using P = decltype(p);
+                if constexpr (P::Paged) {
+                    if (grp) {
+                        multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail..., *grp);
+                        return;
+                    }
+                }
                 multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail...);
             });
         else if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
@@ -1746,7 +2017,8 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 }
 
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
-int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname) {
+int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
+                 const GroupArgs* grp = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
@@ -1754,9 +2026,9 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
         set_error("decode_ragged%s%s: no kernel instance for this call", c.pool.pt.table ? "_paged" : "", c.pool.fp8 ? "_fp8" : "");
         return SFA_ERR_UNSUPPORTED;
     }
-    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, *mfma, c.stream);
-    return launch_rest<bf16_t>(a, rg, c.pool, *mfma, c.stream);
+    if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, nullptr, false, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream);
+    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream);
 }
 
 }  // namespace
@@ -1846,6 +2118,37 @@ size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T
            al256((size_t)g.nrb * sizeof(int2)) + al256((size_t)T * sizeof(int));
 }
 
+namespace {
+
+// host-known geometry of the groups of a packed call: nothing here depends on cu_g, cu_q, the slots or the state
+struct GroupGeom {
+    int64_t ngrb, want, Sgw, nsh, P;     // P = rows * Sgw sizes the group partials
+};
+
+GroupGeom group_geom(int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache) {
+    GroupGeom g;
+    const int64_t G = Hq / Hkv;
+    g.ngrb = cdiv64(G * T, 32) + n_grp;              // sum of ceil(G n_g / 32) over n_grp groups of T rows in all
+    g.want = want_splits(1, Hkv, g.ngrb);
+    g.Sgw = max_splits(1, Hkv, g.ngrb, Nkv_cache);   // bound of multi_plan(0, Lg, 0, want).S over Lg <= Wc <= Nkv_cache
+    g.nsh = (Hkv * g.Sgw * g.ngrb + 7) / 8 * 8;
+    g.P = Hkv * T * G * g.Sgw;
+    return g;
+}
+
+}  // namespace
+
+// the workspace of a grouped call: that of the ungrouped call, then the group partials and the four tables of
+// group_prep_kernel (gblk, glg, gseq and its own mrow)
+size_t decode_ragged_group_workspace(int64_t n_seq, int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                     int64_t D, int dtype) {
+    const size_t base = decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+    if (base == 0 || n_grp <= 0 || n_grp >= (1ll << 30) || dtype == SFA_DTYPE_F32 || !mfma_head_dim((int)D)) return 0;
+    const GroupGeom g = group_geom(n_grp, Hq, Hkv, T, Nkv_cache);
+    return base + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)D * sizeof(float)) +
+           al256((size_t)g.ngrb * sizeof(int2)) + al256((size_t)n_grp * sizeof(int2)) + 2 * al256((size_t)n_seq * sizeof(int));
+}
+
 int decode_ragged_launch(const RingCall& c) {
     const int64_t T = c.q->shape[2];
     const RaggedGeom g = ragged_geom(c.n_seq, c.q->shape[1], c.k_new->shape[1], T, c.sink_len + c.window_len);
@@ -1872,12 +2175,36 @@ int decode_ragged_launch(const RingCall& c) {
     ragged_prep_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, a.G, a.nrb);
     int st;
     if ((st = launch_status("ragged_prep"))) return st;
+    GroupArgs gr{};
+    if (c.cu_g) {       // fork groups: the second partial area and the tables lie behind the ungrouped call's workspace
+        const GroupGeom gg = group_geom(c.n_grp, c.q->shape[1], a.Hkv, T, c.sink_len + c.window_len);
+        char* gw = ws + decode_ragged_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, c.sink_len + c.window_len, a.D, c.q->dtype);
+        gr.cu_g = c.cu_g, gr.n_grp = c.n_grp;
+        gr.Mg = reinterpret_cast<float*>(gw);
+        gr.Lg = reinterpret_cast<float*>(gw + al256((size_t)gg.P * sizeof(float)));
+        gr.Og = reinterpret_cast<float*>(gw + 2 * al256((size_t)gg.P * sizeof(float)));
+        char* gt = gw + 2 * al256((size_t)gg.P * sizeof(float)) + al256((size_t)gg.P * (size_t)a.D * sizeof(float));
+        int2* gblk = reinterpret_cast<int2*>(gt);
+        int2* glg = reinterpret_cast<int2*>(gt + al256((size_t)gg.ngrb * sizeof(int2)));
+        int* gseq = reinterpret_cast<int*>(gt + al256((size_t)gg.ngrb * sizeof(int2)) + al256((size_t)c.n_grp * sizeof(int2)));
+        int* mrow = gseq + al256((size_t)c.n_seq * sizeof(int)) / sizeof(int);     // group_prep_kernel's own
+        gr.gblk = gblk, gr.glg = glg, gr.gseq = gseq;
+        gr.ngrb = (int)gg.ngrb, gr.Sgw = (int)gg.Sgw, gr.want_g = (int)gg.want, gr.nsh = (int)gg.nsh;
+        if ((int64_t)a.Hkv * a.Sw * g.nrb + gg.nsh >= (1ll << 31)) {
+            set_error("decode_ragged: grid too large");
+            return SFA_ERR_UNSUPPORTED;
+        }
+        // reads the state rows and the table; the advance stays the trailing launch (the state-ordering rule)
+        group_prep_kernel<<<c.n_grp, 1024, 0, c.stream>>>(rg, gr, page_args(c.pool.pt), gblk, glg, gseq, mrow, c.state,
+                                                          c.slots, a.npool, a.wc, a.G);
+        if ((st = launch_status("group_prep"))) return st;
+    }
     bool mfma;
     const char* dname;
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname))) return st;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s", fam, dname, a.D, a.nrb, ad, cm, pool_tag(c.pool));
+    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }

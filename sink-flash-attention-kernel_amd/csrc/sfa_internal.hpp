@@ -98,7 +98,11 @@ struct RingCall {
     // (null: every sequence).  In a packed call `parent` is [T], packed like q, with sequence-local entries, and a
     // packed commit (cu_q set) takes `path` [T] and `count` [n_seq] the same way
     const int32_t* commit_seq;
-    SlotPool pool;               // packed calls: the kind of pool the slots belong to (every other call: zero)
+    // packed call on a paged pool with fork groups (the *_group_paged_slots calls): group g = the consecutive sequences
+    // [cu_g[g], cu_g[g + 1]) of the pack; device offsets, read by the kernels only.  Null: no groups
+    const int32_t* cu_g;
+    int n_grp;
+    SlotPool pool;              // packed calls: the kind of pool the slots belong to (every other call: zero)
 };
 
 // sfa_decode.hip
@@ -124,6 +128,10 @@ int decode_multi_launch(const RingCall& c);      // sfa_decode_ring_multi* / sfa
 // sfa_decode_ring_ragged_slots / sfa_decode_ring_ragged_tree_slots.  Workspace: partials for T packed rows plus the tables of the preparation launch
 size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
 int decode_ragged_launch(const RingCall& c);
+// the same with fork groups (c.cu_g): the ungrouped workspace plus the group partials and the group tables; 0 where no
+// grouped instance exists (fp32, head dims other than 64 / 80 / 96 / 128)
+size_t decode_ragged_group_workspace(int64_t n_seq, int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                     int64_t D, int dtype);
 
 // sfa_ring_commit*: store clamp(count, 0, n) chunk tokens into the ring at the device state, then advance it
 int ring_commit_dyn_launch(const RingCall& c);

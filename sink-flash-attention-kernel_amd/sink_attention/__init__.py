@@ -7,7 +7,7 @@ behind libsfa.so (no Triton)."""
 from .sink_flash_attention import sink_flash_attention, SinkFlashAttentionFunc
 from .decode_kernel import (sink_decode_attention, sink_decode_attention_ring, sink_decode_attention_ring_multi,
                             sink_decode_attention_ring_tree)
-from .cache import SinkCacheLayer, SinkAttentionCache, PageAllocator, beam_fork_plan, pages_needed
+from .cache import SinkCacheLayer, SinkAttentionCache, PageAllocator, beam_fork_plan, group_offsets, pages_needed
 from .spec_tree import tree_depth, tree_ancestor_mask, greedy_accept
 from .verl_patch import patch_verl_with_sink_attention, unpatch_verl
 from .generate_patch import patch_for_generation, unpatch_generation
@@ -32,6 +32,7 @@ __all__ = [
     "SinkCacheLayer",
     "SinkAttentionCache",
     "beam_fork_plan",
+    "group_offsets",
     "PageAllocator",
     "pages_needed",
     "patch_for_generation",

@@ -197,6 +197,16 @@ def _bind(lib):
     lib.sfa_ring_commit_path_ragged_paged_fp8_slots.argtypes = [P, P, P, P, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
     lib.sfa_ring_fill_varlen_paged_fp8_slots.restype = i32
     lib.sfa_ring_fill_varlen_paged_fp8_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, i32, vp, vp]
+    # fork groups on a paged pool: the paged step without `parent`, plus (`cu_g` device int32 [n_grp + 1], `n_grp`) behind
+    # (`cu_q`, `n_seq`); the workspace query takes n_grp behind n_seq
+    lib.sfa_decode_ragged_group_workspace_bytes.restype = sz
+    lib.sfa_decode_ragged_group_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i64, i32]
+    lib.sfa_decode_ring_ragged_group_paged_slots.restype = i32
+    lib.sfa_decode_ring_ragged_group_paged_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i32, vp, vp, vp, i32, vp, i32,
+                                                             vp, i32, vp, sz, f32, u32, vp]
+    lib.sfa_decode_ring_ragged_group_paged_fp8_slots.restype = i32
+    lib.sfa_decode_ring_ragged_group_paged_fp8_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i32, vp, vp, vp, i32, vp,
+                                                                 i32, vp, i32, vp, vp, sz, f32, u32, vp]
 
 
 def lib():

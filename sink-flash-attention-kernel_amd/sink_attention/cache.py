@@ -1220,7 +1220,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
 
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                        commit: bool = True, admit: bool = False, parent=None, commit_seq=None) -> torch.Tensor:
+                        commit: bool = True, admit: bool = False, parent=None, commit_seq=None,
+                        groups=None) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -1250,9 +1251,24 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         entries.  Write ``u - 1`` for chains (decode rows, short chunks, chain drafts).  ``commit_seq`` ``[n_seq]``:
         with ``commit``, sequence i is stored and advanced iff ``commit_seq[i] != 0`` - 1 for decode rows and prompt
         chunks, 0 for draft rows, whose accepted prefix ``commit_packed_dyn`` stores afterwards.  Device int32 tensors are
-        taken as they are and never read on the host; host lists are checked for their length (T, n_seq)."""
+        taken as they are and never read on the host; host lists are checked for their length (T, n_seq).
+
+        ``groups`` (``sfa_decode_ring_ragged_group_paged_slots``; None: the call above, unchanged; paged pools only):
+        offsets ``cu_g`` ``[n_grp + 1]`` over the SEQUENCES of the pack (``group_offsets`` builds them from group ids) -
+        group g is the consecutive sequences ``cu_g[g] : cu_g[g + 1]``, forks of one prompt made with
+        ``fork_slots(share=True)``.  The ring slots that the members of a group share (the same pages in their table rows,
+        unwrapped, decided on the device) are read once per group instead of once per member; the output is that of the
+        ungrouped call within its tolerance, pool and state rows end bitwise as it leaves them, and a group that shares
+        nothing is computed exactly as without ``groups``.  The caller promises nothing: any grouping is safe.  A device
+        int32 tensor is never read on the host (a captured step replays at any grouping by rewriting it in place), a host
+        list is checked and uploaded once.  ``parent`` together with ``groups`` is refused."""
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
+        if groups is not None:
+            if not self.page_size:
+                raise TypeError("ragged_step_dyn(groups=) needs a paged pool: init_pool(..., page_size=P)")
+            if parent is not None:
+                raise ValueError("ragged_step_dyn(groups=) takes no parent=: draft trees inside a group are not served")
         N.require_gpu(q, k_new, v_new, s_aux, out, self.window_k)
         if q.dim() != 4 or q.shape[0] != 1:
             raise ValueError(f"q must be a packed [1, H_q, T, D] tensor, got {tuple(q.shape)}")
@@ -1265,15 +1281,25 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         N.require_gpu(slots)
         parent = self._packed_i32(parent, T, "parent", "T", q.device)
         commit_seq = self._packed_i32(commit_seq, n_seq, "commit_seq", "n_seq", q.device)
-        st = getattr(self, "_ragged_state", None)
-        key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype)
+        cu_g = None if groups is None else self._group_arg(groups, n_seq, q.device)
+        n_grp = 0 if cu_g is None else cu_g.numel() - 1
+        # the grouped call keeps constants and workspace of its own, so that grouped and ungrouped steps (and graphs
+        # captured of either) can alternate on one layer without replacing each other's workspace
+        attr = "_ragged_group_state" if n_grp else "_ragged_state"
+        st = getattr(self, attr, None)
+        key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype) + ((n_grp,) if n_grp else ())
         if st is None or st["key"] != key:
-            ws_bytes = N.lib().sfa_decode_ragged_workspace_bytes(n_seq, H_q, H_kv, T, self.num_sink + self.window_size,
-                                                                 D, N.SFA_DTYPE[q.dtype])
+            ws_bytes = 0
+            if n_grp:
+                ws_bytes = N.lib().sfa_decode_ragged_group_workspace_bytes(
+                    n_seq, n_grp, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
+            if ws_bytes == 0:        # no groups; or a shape no grouped instance serves, which the library refuses itself
+                ws_bytes = N.lib().sfa_decode_ragged_workspace_bytes(
+                    n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
             if ws_bytes == 0:
                 raise ValueError(f"D={D}: a K/V row must be a multiple of 16 bytes, <= 1 KiB (H_q = {H_q} a multiple "
                                  f"of H_kv = {H_kv}, T >= 1)")
-            st = self._call_consts("_ragged_state", key, ws_bytes, False, q)
+            st = self._call_consts(attr, key, ws_bytes, False, q)
         q, k_new, v_new = self._rows16(q), self._rows16(k_new), self._rows16(v_new)
         s_aux_f, aux = self._aux(s_aux)
         if out is None:
@@ -1285,14 +1311,35 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                     "sfa_decode_ring_ragged_paged")
             mid = (None if parent is None else parent.data_ptr(), None if commit_seq is None else commit_seq.data_ptr())
             kvs = self._pool_tail()
+        grp = ()
+        if cu_g is not None:     # the grouped forms of the two paged entry points: no parent, (cu_g, n_grp) behind n_seq
+            name = "sfa_decode_ring_ragged_group_paged_fp8_slots" if self._kv8 else "sfa_decode_ring_ragged_group_paged_slots"
+            mid, grp = mid[1:], (cu_g.data_ptr(), n_grp)
         with torch.cuda.device(q.device):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
-                                          cu.data_ptr(), n_seq, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
+                                          cu.data_ptr(), n_seq, *grp, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
                                           st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
                                           N.stream_ptr(q.device))
         N.check(rc, name)
         return out
+
+    @staticmethod
+    def _group_arg(groups, n_seq, device):
+        """``groups`` of ``ragged_step_dyn`` as a device int32 tensor ``[n_grp + 1]``: a device tensor is taken as it is
+        (no sync), a host list / CPU tensor is checked against n_seq and uploaded."""
+        if isinstance(groups, torch.Tensor) and groups.is_cuda:
+            if groups.dtype.is_floating_point or groups.dtype == torch.bool or groups.dim() != 1:
+                raise TypeError("groups must be a 1-D integer tensor")
+            cu_g = groups.to(device=device, dtype=torch.int32).contiguous()
+        else:
+            lst = groups.tolist() if isinstance(groups, torch.Tensor) else [int(x) for x in groups]
+            if len(lst) < 2 or lst[0] < 0 or lst[-1] > n_seq or any(b < a for a, b in zip(lst[:-1], lst[1:])):
+                raise ValueError(f"bad groups {lst} for n_seq={n_seq}: need 0 <= g_0 <= g_1 <= ... <= n_seq")
+            cu_g = torch.tensor(lst, dtype=torch.int32, device=device)
+        if cu_g.numel() < 2:
+            raise ValueError("groups needs at least two offsets")
+        return cu_g
 
     @staticmethod
     def _packed_i32(x, n, what, nname, device):
@@ -1543,12 +1590,14 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
-                        commit=True, admit: bool = False, parent=None, commit_seq=None):
+                        commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
-        draft trees in the pack and per-sequence commit."""
+        draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
+        (paged pools)."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
-                                                      commit=commit, admit=admit, parent=parent, commit_seq=commit_seq)
+                                                      commit=commit, admit=admit, parent=parent, commit_seq=commit_seq,
+                                                      groups=groups)
 
     def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
         """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""
@@ -1614,6 +1663,25 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     @property
     def seen_tokens(self) -> int:
         return self._seen_tokens
+
+
+def group_offsets(group_ids) -> list:
+    """``groups`` of ``ragged_step_dyn`` from one group id per sequence of the pack: sequences with the same id must be
+    consecutive (a run is one group), ``None`` or a negative id leaves a sequence ungrouped.  Returns the host list of
+    offsets ``[n_grp + 1]``.  Offsets are consecutive, so every sequence lies in some run: an ungrouped sequence becomes
+    a group of one, which the step computes exactly as an ungrouped one."""
+    ids = [None if (g is None or (isinstance(g, int) and g < 0)) else g for g in group_ids]
+    cu, seen, prev = [0], set(), object()
+    for i, g in enumerate(ids):
+        if i and (g is None or g != prev):
+            cu.append(i)
+        if g is not None and g != prev:
+            if g in seen:
+                raise ValueError(f"group id {g} is not consecutive in {list(group_ids)}")
+            seen.add(g)
+        prev = g if g is not None else object()
+    cu.append(len(ids))
+    return cu
 
 
 def beam_fork_plan(beam_idx, slots, free_slots):
