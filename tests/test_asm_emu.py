@@ -224,6 +224,14 @@ def test_other_head_dims_in_emulator(D):
     (4, 1, 330, 64, 192, 4, 6, "bf16", True, False),      # four tiles per item (5-slot ring), one strip over the whole sequence
     (4, 1, 400, 80, 128, 3, 3, "bf16", True, "staircase"),  # tests/range_inputs.py staircase_up: mid-range alpha between blocks
     (4, 1, 330, 96, 128, 3, 2, "f16", True, "staircase"),
+    # the window-class edges of strip_asm_nt (tests/sliding_regime.py), at the smallest N with two items on a full ring and a
+    # ragged last tile: NT = 2 at W = 65 (steady blocks), NT = 3 at W = 66 (general blocks) and 129, NT = 4 at W = 130 and 193
+    (4, 1, 141, 64, 65, 2, 3, "bf16", True, False),
+    (4, 1, 141, 80, 65, 2, 2, "f16", False, False),
+    (4, 1, 205, 96, 66, 3, 2, "bf16", True, False),
+    (4, 1, 205, 64, 129, 3, 4, "f16", True, False),
+    (4, 1, 269, 80, 130, 4, 2, "bf16", False, False),
+    (4, 1, 269, 96, 193, 4, 5, "f16", True, False),
 ])
 def test_short_window_strip_forward_in_emulator(Hq, Hkv, N, D, W, NT, strip, dtype, aux, spike):
     """tools/asmgen/fwd_strip.py: strips of consecutive query tiles over a sliding K / V ring, double-buffered Q fragments,
@@ -254,6 +262,9 @@ def test_short_window_strip_forward_in_emulator(Hq, Hkv, N, D, W, NT, strip, dty
     (4, 1, 400, 80, 128, 3, 3, "bf16"),      # gpt-oss sliding layer shape (C4): 3 tiles per item, steady blocks after the first two items
     (8, 2, 300, 64, 100, 3, 5, "f16"),       # window not a tile multiple (general blocks throughout), two KV heads
     (4, 1, 330, 64, 192, 4, 6, "bf16"),      # four tiles per item (5-slot ring), one strip over the whole sequence
+    (4, 1, 141, 64, 65, 2, 3, "bf16"),       # two tiles per item at the largest window of the class, one strip
+    (4, 1, 269, 80, 193, 4, 2, "f16"),       # four tiles per item at the largest window the bodies serve, strips of 2 + a last of 1
+    (4, 1, 141, 80, 65, 2, 2, "f16"),        # two tiles per item, f16
 ])
 def test_short_window_strip_dq_in_emulator(Hq, Hkv, N, D, W, NT, strip, dtype):
     """tools/asmgen/dq_strip.py: the backward twin of the strip forward (sliding K / V ring, double-buffered Q / dO fragments
@@ -282,7 +293,10 @@ def test_short_window_strip_dq_in_emulator(Hq, Hkv, N, D, W, NT, strip, dtype):
     (1, 2, 1, 300, 80, 128, "bf16"),      # the gpt-oss window: T = 6, two key blocks, ragged last slice
     (1, 3, 1, 520, 64, 100, "bf16"),      # three blocks, group of 3
     (1, 2, 2, 333, 64, 200, "f16"),       # T = 9: trips without a B slice; MHA
-    (2, 1, 1, 257, 96, 33, "bf16")])      # T rounded up to 6; a last block of one key
+    (2, 1, 1, 257, 96, 33, "bf16"),       # T rounded up to 6; a last block of one key
+    (1, 2, 1, 300, 64, 130, "bf16"),      # T = 7: the first window past the minimum of 6 trips
+    (1, 2, 1, 300, 80, 162, "f16"),       # T = 8, the first window of its step
+    (1, 1, 1, 525, 96, 512, "bf16")])     # T = 18, the largest window the sweep serves, three key blocks
 def test_dkdv_skew_body_in_emulator_matches_oracle(B, Hq, Hkv, N, D, W, dtype):
     """the short-window dK/dV body (tools/asmgen/dkdv_skew.py: wave w on slice r of head h or slice T + r of head h - 1)"""
     from asmgen.dkdv_skew import DkdvSkewGen

@@ -101,6 +101,16 @@ def assert_close(actual, expected, atol, rtol, what=""):
                            f"(atol={atol}, rtol={rtol}); max abs err {err.max().item():.3e}")
 
 
+# tolerances of the dense mask-edge probe tests (tests/test_gpu_mask_edges.py::test_dense_mask_edges and, imported from
+# here, tests/test_gpu_sliding.py): O and dQ atol = rtol; dK / dV and ds_aux scale with max(1, max |ref|); LSE as
+# tests/test_gpu_softmax_range.py
+PROBE_TOL_O = {torch.bfloat16: 2e-2, torch.float16: 1e-2}
+PROBE_TOL_DQ = 5e-2
+PROBE_TOL_DKDV = 5e-2
+PROBE_TOL_DS_AUX = 5e-2
+PROBE_TOL_LSE = 5e-3
+
+
 # unit roundoff of the storage dtype: round-to-nearest moves a value by at most u |value|
 UNIT_ROUNDOFF = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 SUM_BOUND_FACTOR = 4.0

@@ -3,7 +3,8 @@
 N_q < N_kv / packed paths against their padded / per-sequence formulations) on random shapes.
 usage: python tools/fuzz.py [n_cases] [seed] [skew] [--inputs=randn|probe|range|dsaux]
 (skew: only shapes of the short-window dK/dV kernel - no sink keys, head dims 64 / 80 / 96, windows up to 512, N_q = N_kv or
-packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn,
+packed; --inputs=probe: q / k / v / dO from tests/probe_inputs.py, rows peaked on one key of a mask edge, instead of randn
+(without sink keys the window is then drawn from tests/sliding_regime.py::EDGE_WINDOWS, the class edges of the short-window kernels),
 and dK / dV of the MFMA kernels also judged element by element against the fp64 oracle with the sum bound of tests/util.py
 (4 u A + u |ref|), which a mask error confined to the dK/dV kernel cannot pass;
 --inputs=range: a random family of tests/range_inputs.py - logit staircases, a common offset - that moves the softmax reference;
@@ -21,6 +22,7 @@ import torch
 import dsaux_inputs
 import probe_inputs
 import range_inputs
+import sliding_regime
 import util
 
 from sink_attention.sink_flash_attention import _sink_flash_attention_ex
@@ -101,6 +103,9 @@ for case in range(n_cases):
     if focus_skew:
         D, ns, W = rng.choice([64, 80, 96]), 0, rng.choice([1, 5, 31, 64, 100, 128, 300, 512])
         mode = rng.choice(["plain", "plain", "varlen"])
+    if inputs == "probe" and ns == 0:
+        # the class edges of the short-window kernels (tiles per item, trips of the skewed sweep, the dispatch windows)
+        W = rng.choice(sliding_regime.EDGE_WINDOWS)
     if inputs == "dsaux":
         aux, N, W = True, min(N, 500), max(W, 1)        # (W >= 1: every row sees a key, the calibration needs a finite LSE)
     sa = (torch.randn(Hq, device="cuda") * 0.5) if aux else None
