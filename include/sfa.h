@@ -899,6 +899,76 @@ int sfa_ring_fill_varlen_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_ten
                                          const int32_t* page_table, int table_stride, const float* kv_scale,
                                          void* stream);
 
+/* ---- Export: the inverse of sfa_ring_fill_varlen_slots.
+ *
+ * sfa_ring_export_slots writes the live tokens of n_seq named slots of a pool, in TOKEN order, into a pack of the layout
+ * the fills take - what hands a request to another process or device, moves it into a pool of another shape (a longer
+ * ring, another page size, 16-bit <-> FP8: export here, sfa_ring_fill_varlen_*_slots there), or spills it to the host.
+ *   sink_k/v [S, Hkv, num_sink, D]   window_k/v [S, Hkv, Wc, D]   state int32 [S][4] (const: read only)
+ *   k_out, v_out [1, Hkv, T, D]      cu_seqlens device int32 [n_seq + 1]   slots device int32 [n_seq]
+ *   pos_out      device int32 [T] or NULL
+ * Sequence i owns the packed rows [cu[i], cu[i + 1]) (m_i of them; offsets read on the device, clamped into [0, T] and
+ * made non-decreasing as sfa_ring_fill_varlen does) and names slot c = slots[i].  Its state row {sl = sink_len, wl =
+ * window_len, wp = write_pos, seen} is clamped as the attention kernels clamp it (sl into [0, num_sink], wl into [0, Wc],
+ * wp into [0, Wc - 1]); live = sl + wl tokens are held, and token-order index j is
+ *   - j < sl: sink row j, at position j;
+ *   - j = sl + r, r < wl: ring slot (wp - wl + r) mod Wc, at position seen - wl + r - the oldest ring token first.  That is
+ *     slot r while the ring fills (every placement above keeps wp == wl until the ring is full) and after a prefill
+ *     (sfa_ring_fill_varlen leaves a full ring at wp == 0 with the oldest token in slot 0), and slot (wp + r) mod Wc once
+ *     commits have wrapped a full ring (a commit stores token t at (wp + t) mod Wc and advances wp, so the oldest live
+ *     token sits at the new wp).
+ * Row j < min(m_i, live) of the sequence receives token j, all KV heads.  EVERY other row of the pack is written as
+ * zeros, so a pack exported at a fixed T is fully defined: rows j >= live of a sequence (m_i > live), the rows of a
+ * sequence whose slot is outside [0, S) (the slots = -1 rule), and rows that no sequence covers (in front of cu[0], behind
+ * cu[n_seq]).  m_i < live truncates: the first m_i tokens are written.  pos_out[row] = the token's position, -1 on a
+ * zeroed row.  A sequence of a fresh slot (all-zero state row) has live = 0.
+ *   - The pack has the pool's dtype (bf16, f16 or f32) and the rows are copied verbatim, 16 bytes per thread and buffer.
+ *   - Nothing of the pool, the state or the table is written; nothing is read on the host.  One launch on `stream`, no
+ *     workspace, no allocation, no atomics: capturable, and a repeated call is bitwise identical.  The same slot may be
+ *     named twice.  The grid follows T (Hkv * T rows), not the pool's capacity; every offset is formed in 64 bits from the
+ *     descriptors' strides, as in the packed calls (a pack behind a 4 GiB head stride, a slot past 4 GiB).
+ *   - Undefined: a pool buffer that overlaps k_out / v_out / pos_out (not checked).
+ * Host checks before anything launches, SFA_ERR_INVALID_ARGUMENT: null descriptors; unequal shapes within (sink_k,
+ * sink_v), (window_k, window_v), (k_out, v_out); null cu_seqlens / state / slots; n_seq >= 1; "packed layout: k_out /
+ * v_out must be [1, H_kv, T, D] (batch dim n)"; "k_out / v_out and the cache buffers must share one dtype"; one S >= 1;
+ * the pool's Hkv and D; rows a multiple of 16 bytes and 16-byte aligned ("ring_export: rows of every tensor must be
+ * 16-byte aligned").  T == 0 returns SFA_OK without a launch.  sfa_last_path(): "ring_export_slots".
+ *
+ * sfa_ring_export_fp8_slots: an FP8 pool; the same arguments plus kv_scale (device float [2][Hkv] or NULL = ones) in
+ * front of stream.  k_out / v_out are bf16 or f16 (T) and every element is T(float(code) * scale[h]), the reading rule
+ * above through the same device function as the packed step: bit for bit what that step feeds its LDS.  A thread reads
+ * 8 codes and writes 16 bytes.  "ring_export_fp8: the cache buffers must be FP8 (e4m3)"; fp32 packs and head dims outside
+ * 64 / 80 / 96 / 128 are SFA_ERR_UNSUPPORTED.  sfa_last_path(): "ring_export_slots_kvfp8".
+ *
+ * sfa_ring_export_paged_slots: a paged pool (window_k/v = the pages); the same arguments plus (page_table, table_stride)
+ * in front of stream, checked as the paged pool documents under the name ring_export_paged.  A ring slot is read from row
+ * slot mod P of its page; a slot whose table entry is unmapped reads nothing: its row is zeros and pos_out still gives
+ * its position.  sfa_last_path(): "ring_export_slots_paged".
+ *
+ * sfa_ring_export_paged_fp8_slots: both, (page_table, table_stride, kv_scale) in front of stream, byte offsets at one
+ * byte per element.  sfa_last_path(): "ring_export_slots_paged_kvfp8".
+ */
+int sfa_ring_export_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                          const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                          const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                          int32_t* pos_out, void* stream);
+
+int sfa_ring_export_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                              const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                              const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                              int32_t* pos_out, const float* kv_scale, void* stream);
+
+int sfa_ring_export_paged_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                                const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                                int32_t* pos_out, const int32_t* page_table, int table_stride, void* stream);
+
+int sfa_ring_export_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                    const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                                    const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                                    int32_t* pos_out, const int32_t* page_table, int table_stride,
+                                    const float* kv_scale, void* stream);
+
 /* ---- Fork groups: a shared prompt prefix is read once per group.
  *
  * sfa_decode_ring_ragged_group_paged_slots / sfa_decode_ring_ragged_group_paged_fp8_slots: the arguments of their paged

@@ -873,6 +873,58 @@ int copy_slots(const sfa_tensor* const src[4], const int32_t* src_state, const s
                                   src_pool, dst_pool);
 }
 
+// sfa_ring_export{,_fp8,_paged,_paged_fp8}_slots: the live tokens of the named slots into a pack (`in` names the kind of
+// pool).  The device arrays (cu, state, slots, the table) are not looked at
+int export_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k, const sfa_tensor* window_v,
+                 const sfa_tensor* k_out, const sfa_tensor* v_out, const int32_t* cu_seqlens, int n_seq, const int32_t* state,
+                 const int32_t* slots, int32_t* pos_out, void* stream, const PoolIn& in = PoolIn{}) {
+    g_err[0] = 0;
+    PagedRing ring;
+    SlotPool kind;
+    int st;
+    if ((st = pool_of("ring_export", in, sink_k ? sink_k->shape[0] : 1, &window_k, &window_v, &ring, &kind))) return st;
+    const bool kv8 = kind.fp8;
+    if ((st = check_tensor(sink_k, "sink_k", kv8)) || (st = check_tensor(sink_v, "sink_v", kv8)) ||
+        (st = check_tensor(window_k, "window_k", kv8)) || (st = check_tensor(window_v, "window_v", kv8)) ||
+        (st = check_tensor(k_out, "k_out")) || (st = check_tensor(v_out, "v_out")))
+        return st;
+    if ((st = same_shape(sink_k, sink_v, "sink_k", "sink_v")) ||
+        (st = same_shape(window_k, window_v, "window_k", "window_v")) || (st = same_shape(k_out, v_out, "k_out", "v_out")))
+        return st;
+    SFA_NEED(cu_seqlens, "cu_seqlens");
+    SFA_NEED(state, "state");
+    SFA_NEED(slots, "slots");
+    SFA_CHECK_ARG(n_seq >= 1, "n_seq must be >= 1 (got %d)", n_seq);
+    SFA_CHECK_ARG(k_out->shape[0] == 1, "packed layout: k_out / v_out must be [1, H_kv, T, D] (batch dim %lld)",
+                  (long long)k_out->shape[0]);
+    const Who who("ring_export", kind);
+    if (kv8) {      // sfa_ring_export_fp8_slots, sfa_ring_export_paged_fp8_slots
+        if ((st = check_fp8_dtypes(who, sink_k, window_k, k_out, v_out, "k_out and v_out"))) return st;
+    } else
+        SFA_CHECK_ARG(k_out->dtype == sink_k->dtype && k_out->dtype == window_k->dtype,
+                      "k_out / v_out and the cache buffers must share one dtype");
+    const int64_t Hkv = k_out->shape[1], D = k_out->shape[3], Wc = window_k->shape[2];
+    SFA_CHECK_ARG(sink_k->shape[0] >= 1 && sink_k->shape[0] == window_k->shape[0] && sink_k->shape[0] < (1ll << 30),
+                  "pool: sink and window buffers must share shape[0] = S >= 1 (sink %lld, window %lld)",
+                  (long long)sink_k->shape[0], (long long)window_k->shape[0]);
+    SFA_CHECK_ARG(sink_k->shape[1] == Hkv && sink_k->shape[3] == D && window_k->shape[1] == Hkv && window_k->shape[3] == D,
+                  "sink / window buffers must be [S, H_kv, *, D] like k_out");
+    SFA_CHECK_ARG(Wc >= 1, "the ring needs a capacity of at least one slot");
+    const int es = dtype_size(k_out->dtype);
+    SFA_CHECK_ARG(D > 0 && (D * es) % 16 == 0, "ring_export: K/V rows must be a multiple of 16 bytes (head dim %lld)",
+                  (long long)D);
+    SFA_CHECK_ARG(k_out->shape[2] < (1ll << 30) && k_out->shape[2] * (D * es / 16) < (1ll << 30) &&
+                      sink_k->shape[2] + Wc < (1ll << 30) && Hkv < (1ll << 30),
+                  "problem too large");
+    if ((kv8 || kind.pt.table) && (st = check_pool_served(who, kind, k_out->dtype, D, 0))) return st;
+    if ((st = check_rows16({k_out, v_out}, es, 7, "ring_export: rows of every tensor must be 16-byte aligned")) ||
+        (st = check_rows16({sink_k, sink_v, window_k, window_v}, kv8 ? 1 : es, 7,
+                           "ring_export: rows of every tensor must be 16-byte aligned")))
+        return st;
+    return ring_export_slots_launch(sink_k, sink_v, window_k, window_v, k_out, v_out, cu_seqlens, n_seq, state, slots,
+                                    pos_out, (hipStream_t)stream, kind);
+}
+
 }  // namespace
 
 // the parameter lists of include/sfa.h and their pass to attend_call / commit_call
@@ -1190,6 +1242,38 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
     const sfa_tensor* const src[4] = {src_sink_k, src_sink_v, src_window_k, src_window_v};
     const sfa_tensor* const dst[4] = {dst_sink_k, dst_sink_v, dst_window_k, dst_window_v};
     return copy_slots(src, src_state, dst, dst_state, src_slots, dst_slots, n_pairs, stream);
+}
+
+int sfa_ring_export_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                          const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                          const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                          int32_t* pos_out, void* stream) {
+    return export_slots(sink_k, sink_v, window_k, window_v, k_out, v_out, cu_seqlens, n_seq, state, slots, pos_out, stream);
+}
+
+int sfa_ring_export_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                              const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                              const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                              int32_t* pos_out, const float* kv_scale, void* stream) {
+    return export_slots(sink_k, sink_v, window_k, window_v, k_out, v_out, cu_seqlens, n_seq, state, slots, pos_out, stream,
+                        PoolIn{true, kv_scale});
+}
+
+int sfa_ring_export_paged_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                                const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                                int32_t* pos_out, const int32_t* page_table, int table_stride, void* stream) {
+    return export_slots(sink_k, sink_v, window_k, window_v, k_out, v_out, cu_seqlens, n_seq, state, slots, pos_out, stream,
+                        PoolIn{false, nullptr, true, page_table, table_stride});
+}
+
+int sfa_ring_export_paged_fp8_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                                    const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out,
+                                    const int32_t* cu_seqlens, int n_seq, const int32_t* state, const int32_t* slots,
+                                    int32_t* pos_out, const int32_t* page_table, int table_stride, const float* kv_scale,
+                                    void* stream) {
+    return export_slots(sink_k, sink_v, window_k, window_v, k_out, v_out, cu_seqlens, n_seq, state, slots, pos_out, stream,
+                        PoolIn{true, kv_scale, true, page_table, table_stride});
 }
 
 // The device arrays (slots, state) are not looked at: skipped pairs are decided by the kernel, as in copy_slots

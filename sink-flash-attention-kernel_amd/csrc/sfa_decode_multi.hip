@@ -70,7 +70,10 @@ __device__ __forceinline__ float kv8_scale(const Kv8Args& kv, int row, int Hkv, 
 
 // reading: the 8 codes of one 8-byte piece -> 8 elements of T, each T(float(code) * s): one f32 multiply, then the
 // round-to-nearest-even conversion.  Byte i of the piece is element i.
-template <typename T>
+// Pairs (the export, whose output is compared bit by bit): the products are converted two at a time by the packed
+// conversion.  Converted one by one, the compiler fuses some lanes' multiply and f16 conversion into one instruction that
+// adds +0, which turns the code of -0 into +0 there - invisible to an attention product, visible in exported bytes.
+template <typename T, bool Pairs = false>
 __device__ __forceinline__ u32x4 kv8_read(unsigned lo, unsigned hi, float s) {
     using E = typename Mma<T>::elem;
     typename Mma<T>::frag out;
@@ -79,6 +82,12 @@ __device__ __forceinline__ u32x4 kv8_read(unsigned lo, unsigned hi, float s) {
     for (int i = 0; i < 2; ++i) {
         const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
         const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        if constexpr (Pairs) {
+            typedef E e2 __attribute__((ext_vector_type(2)));
+            const e2 ca = __builtin_convertvector(a * s, e2), cb = __builtin_convertvector(b * s, e2);
+            out[4 * i + 0] = ca[0], out[4 * i + 1] = ca[1], out[4 * i + 2] = cb[0], out[4 * i + 3] = cb[1];
+            continue;
+        }
         out[4 * i + 0] = (E)(a[0] * s);
         out[4 * i + 1] = (E)(a[1] * s);
         out[4 * i + 2] = (E)(b[0] * s);
@@ -1695,6 +1704,145 @@ __global__ __launch_bounds__(256) void ring_copy_slots_kernel(CopyPools src, Cop
     else copy(std::false_type{});
 }
 
+// sfa_ring_export_slots: the inverse of ring_fill_varlen_kernel<true>.  Sequence i of the pack k_out / v_out
+// [1, Hkv, T, D] owns the packed rows [c0, c0 + m) (cu clamped by ragged_seq) and names slot c = slots[i] with the state
+// row {sl, wl, wp, seen}, clamped as get_fill clamps it.  Its live tokens in token order: index j < sl is sink row j at
+// position j; index j = sl + r, r < wl, is ring slot (wp - wl + r) mod Wc at position seen - wl + r, the oldest ring
+// token first (r while the ring fills, where wp == wl, and after a prefill, which leaves a full ring at wp == 0;
+// (wp + r) mod Wc once commits have wrapped it).  Row j < min(m, sl + wl) gets token j; every other row of the pack - the
+// tail of a sequence, a sequence whose slot is outside [0, S), a row that no sequence covers - is written as zeros, and
+// pos gets the position of a token row and -1 of a zeroed one.  Nothing of the pool or the state is written.
+// A workgroup is (KV head, block of 256 * kExportPieces consecutive 16-byte pieces of the head's T rows of the pack:
+// piece p = row * cpr + ch), so the grid follows T and not the pool's capacity.  It finds the last sequence that starts at
+// or before its first row by the binary search of ring_commit_ragged_kernel, on block-uniform values (scalar loads); when
+// no later sequence starts inside the block, the sequence, its slot and the state row are read once for the workgroup.
+// Otherwise each piece walks on from that sequence and reads its own.  As in ring_copy_slots_kernel a thread issues its
+// kExportPieces loads of K and of V, 256 pieces apart, without a branch among them, before its first store; a piece with
+// nothing to read loads the first bytes of the ring buffers (a valid address) and stores zeros.
+// Q = void: the pack has the pool's dtype and 16 bytes are copied.  Q = the pack's 16-bit type, KA starts with Kv8Args: an
+// FP8 pool, 8 codes are read and kv8_read makes the 16 bytes, as the packed step does on the way into LDS.
+// Paged: KA ends in PageArgs; a ring slot is read from row slot mod P of its page (page_at), a slot on an unmapped page
+// gives zeros and keeps its position in pos.
+#ifndef SFA_EXPORT_PIECES
+#define SFA_EXPORT_PIECES 4
+#endif
+constexpr int kExportPieces = SFA_EXPORT_PIECES;
+
+struct ExportArgs {
+    View sk, sv, wk, wv, ko, vo;
+    const int* cu;
+    const int* state;
+    const int* slots;
+    int* pos;                    // [T] or null
+    int n_seq, S, Hkv, ns, wc, T, cpr, es, nblk;
+};
+
+// sequence i of an export: its packed rows [c0, c0 + m), its slot (-1: outside the pool) and that slot's clamped state
+struct ExportSeq {
+    int c0, m, c, sl, wl, wp, seen;
+};
+
+__device__ __forceinline__ int export_start(const ExportArgs& a, int i) {
+    const int c = a.cu[i];
+    return c < 0 ? 0 : (c > a.T ? a.T : c);
+}
+
+__device__ __forceinline__ ExportSeq export_seq(const ExportArgs& a, int i) {
+    const RaggedSeq s = ragged_seq(RaggedArgs{a.cu, nullptr, nullptr, a.n_seq, a.T, 0, nullptr}, i);
+    const int c = a.slots[i];
+    const bool in = (unsigned)c < (unsigned)a.S;
+    const int* st = a.state + (int64_t)(in ? c : 0) * 4;      // S >= 1: row 0 is a valid address
+    const int sl = st[0], wl = st[1], wp = st[2], seen = st[3];
+    return ExportSeq{s.c0, s.n, in ? c : -1, sl < 0 ? 0 : (sl > a.ns ? a.ns : sl), wl < 0 ? 0 : (wl > a.wc ? a.wc : wl),
+                     wp < 0 ? 0 : (wp >= a.wc ? a.wc - 1 : wp), seen};
+}
+
+template <typename Q = void, bool Paged = false, typename... KA>
+__global__ __launch_bounds__(256) void ring_export_slots_kernel(ExportArgs a, KA... ka) {
+    constexpr bool KV8 = !std::is_void_v<Q>;
+    static_assert(tail_is<false, KV8, Paged, KA...>,
+                  "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); paged FP8 pool: (..., Kv8Args, PageArgs)");
+    using Raw = std::conditional_t<KV8, uint2, u32x4>;        // what a thread reads of one piece
+    const int blk = (int)(blockIdx.x % (unsigned)a.nblk), hk = (int)(blockIdx.x / (unsigned)a.nblk);
+    const int total = a.T * a.cpr;                   // < 2^30: checked on the host
+    const int p0 = blk * (256 * kExportPieces);
+    const int plast = p0 + 256 * kExportPieces <= total ? p0 + 256 * kExportPieces - 1 : total - 1;
+    const int r0 = p0 / a.cpr, r1 = plast / a.cpr;
+    int lo = 0, hi = a.n_seq - 1;                    // the last sequence that starts at or before row r0
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (export_start(a, mid) <= r0) lo = mid;
+        else hi = mid - 1;
+    }
+    const bool one = lo + 1 >= a.n_seq || export_start(a, lo + 1) > r1;      // no later sequence starts in the block
+    const ExportSeq e0 = export_seq(a, lo);
+    [[maybe_unused]] float ksc = 1.f, vsc = 1.f;
+    if constexpr (KV8) ksc = kv8_scale(arg_of<Kv8Args>(ka...), 0, a.Hkv, hk), vsc = kv8_scale(arg_of<Kv8Args>(ka...), 1, a.Hkv, hk);
+    const int esrc = KV8 ? 1 : a.es, sbytes = KV8 ? 8 : 16;
+    auto run = [&](auto one_seq) {
+        constexpr bool uni = decltype(one_seq)::value;
+        const int p = p0 + (int)threadIdx.x, rstep = 256 / a.cpr, cstep = 256 - rstep * a.cpr;
+        int r = p / a.cpr, c = p - r * a.cpr;
+        [[maybe_unused]] int seq = lo;
+        const char *ks[kExportPieces], *vs[kExportPieces];
+        int64_t doff_k[kExportPieces], doff_v[kExportPieces];
+        int pos[kExportPieces], row[kExportPieces];
+        bool in[kExportPieces], data[kExportPieces], first[kExportPieces];
+#pragma unroll
+        for (int u = 0; u < kExportPieces; ++u) {
+            in[u] = p + u * 256 < total;
+            const int rr = in[u] ? r : a.T - 1, cc = in[u] ? c : a.cpr - 1;
+            ExportSeq e = e0;
+            if constexpr (!uni) {
+                while (seq + 1 < a.n_seq && export_start(a, seq + 1) <= rr) ++seq;
+                e = export_seq(a, seq);
+            }
+            const int j = rr - e.c0, live = e.sl + e.wl;
+            const bool tok = e.c >= 0 && j >= 0 && j < (e.m < live ? e.m : live);
+            const bool sink = tok && j < e.sl;
+            const int rg = j - e.sl;
+            int slot = !tok ? 0 : sink ? j : (int)(((int64_t)e.wp - e.wl + rg + a.wc) % a.wc);
+            int brow = tok ? e.c : 0;            // the source's row of its buffer: the cache row, or the page of a ring slot
+            bool mapped = true;
+            if constexpr (Paged) {
+                if (!sink) {
+                    const PageArgs& pg = arg_of<PageArgs>(ka...);
+                    const int e_pg = page_at(pg, brow, slot);
+                    mapped = e_pg >= 0;
+                    brow = mapped ? e_pg : 0, slot = page_row(pg, slot);
+                }
+            }
+            const View &bk = sink ? a.sk : a.wk, &bv = sink ? a.sv : a.wv;
+            ks[u] = bk.ptr + ((int64_t)brow * bk.sb + (int64_t)hk * bk.sh + (int64_t)slot * bk.sn) * esrc + (int64_t)cc * sbytes;
+            vs[u] = bv.ptr + ((int64_t)brow * bv.sb + (int64_t)hk * bv.sh + (int64_t)slot * bv.sn) * esrc + (int64_t)cc * sbytes;
+            doff_k[u] = ((int64_t)hk * a.ko.sh + (int64_t)rr * a.ko.sn) * a.es + (int64_t)cc * 16;
+            doff_v[u] = ((int64_t)hk * a.vo.sh + (int64_t)rr * a.vo.sn) * a.es + (int64_t)cc * 16;
+            pos[u] = !tok ? -1 : sink ? j : e.seen - e.wl + rg;
+            row[u] = rr, data[u] = tok && mapped, first[u] = in[u] && cc == 0;
+            r += rstep, c += cstep;
+            if (c >= a.cpr) c -= a.cpr, ++r;
+        }
+        Raw kr[kExportPieces], vr[kExportPieces];
+#pragma unroll
+        for (int u = 0; u < kExportPieces; ++u)
+            kr[u] = *reinterpret_cast<const Raw*>(ks[u]), vr[u] = *reinterpret_cast<const Raw*>(vs[u]);
+#pragma unroll
+        for (int u = 0; u < kExportPieces; ++u) {
+            u32x4 ko, vo;
+            if constexpr (KV8) ko = kv8_read<Q, true>(kr[u].x, kr[u].y, ksc), vo = kv8_read<Q, true>(vr[u].x, vr[u].y, vsc);
+            else ko = kr[u], vo = vr[u];
+            const u32x4 zero = {0u, 0u, 0u, 0u};
+            if (in[u]) {
+                *reinterpret_cast<u32x4*>(a.ko.ptr + doff_k[u]) = data[u] ? ko : zero;
+                *reinterpret_cast<u32x4*>(a.vo.ptr + doff_v[u]) = data[u] ? vo : zero;
+            }
+            if (a.pos && hk == 0 && first[u]) a.pos[row[u]] = pos[u];
+        }
+    };
+    if (one) run(std::true_type{});
+    else run(std::false_type{});
+}
+
 // sfa_ring_share_paged_slots: the unpaged half of a fork whose ring pages are shared through the table.  Pair i copies the
 // live sink rows (j < clamp(sink_len, 0, num_sink)) and the state row of slot s into slot d with the skip rules of
 // ring_copy_slots_kernel; src / dst carry no ring views, no ring byte is read or written.  A workgroup is (pair, KV head,
@@ -2313,6 +2461,34 @@ int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_st
         if ((st = launch_status("ring_copy_slots"))) return st;
     }
     set_path("ring_copy_slots%s", pool_tag(src_pool));
+    return SFA_OK;
+}
+
+int ring_export_slots_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                             const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out, const int32_t* cu,
+                             int n_seq, const int32_t* state, const int32_t* slots, int32_t* pos_out, hipStream_t stream,
+                             const SlotPool& pool) {
+    const int es = dtype_size(k_out->dtype);
+    const int Hkv = (int)k_out->shape[1], T = (int)k_out->shape[2];
+    const int cpr = (int)(k_out->shape[3] * es / 16);
+    const int64_t nblk = cdiv64((int64_t)T * cpr, 256 * kExportPieces);      // the pack's pieces per head: < 2^30 (host check)
+    const int64_t grid = (int64_t)Hkv * nblk;
+    if (grid >= (1ll << 31)) {
+        set_error("ring_export_slots: grid too large");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    if (grid > 0) {
+        const ExportArgs a{make_view(sink_k), make_view(sink_v), make_view(window_k), make_view(window_v), make_view(k_out),
+                           make_view(v_out), cu, state, slots, pos_out, n_seq, (int)sink_k->shape[0], Hkv,
+                           (int)sink_k->shape[2], (int)window_k->shape[2], T, cpr, es, (int)nblk};
+        dispatch_pool(pool, [&](auto p, auto... tail) {
+            using P = decltype(p);
+            ring_export_slots_kernel<typename P::Q, P::Paged><<<dim3((unsigned)grid), 256, 0, stream>>>(a, tail...);
+        }, k_out->dtype);
+        int st;
+        if ((st = launch_status("ring_export_slots"))) return st;
+    }
+    set_path("ring_export_slots%s", pool_tag(pool));
     return SFA_OK;
 }
 

@@ -148,6 +148,14 @@ int ring_fill_varlen_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, 
 int ring_copy_slots_launch(const sfa_tensor* const src[4], const int32_t* src_state, const sfa_tensor* const dst[4],
                            int32_t* dst_state, const int32_t* src_slots, const int32_t* dst_slots, int n_pairs,
                            hipStream_t stream, const SlotPool& src_pool, const SlotPool& dst_pool);
+// sfa_ring_export_slots: the live tokens of slot slots[i], in token order, into rows [cu[i], cu[i + 1]) of the pack
+// k_out / v_out [1, Hkv, T, D], zeros in every other row; pos_out (optional, [T]): the position of each row, -1 on zeroed
+// rows.  Reads the pool, writes the pack alone.  pool: FP8 buffers are read into the pack's 16-bit dtype by the reading
+// rule, pages are read through the table
+int ring_export_slots_launch(const sfa_tensor* sink_k, const sfa_tensor* sink_v, const sfa_tensor* window_k,
+                             const sfa_tensor* window_v, const sfa_tensor* k_out, const sfa_tensor* v_out, const int32_t* cu,
+                             int n_seq, const int32_t* state, const int32_t* slots, int32_t* pos_out, hipStream_t stream,
+                             const SlotPool& pool);
 // sfa_ring_share_paged_slots: the live sink rows and the state row of slot src_slots[i] into slot dst_slots[i]; no ring
 int ring_share_slots_launch(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink_v, const int32_t* src_state,
                             const sfa_tensor* dst_sink_k, const sfa_tensor* dst_sink_v, int32_t* dst_state,

@@ -207,6 +207,16 @@ def _bind(lib):
     lib.sfa_decode_ring_ragged_group_paged_fp8_slots.restype = i32
     lib.sfa_decode_ring_ragged_group_paged_fp8_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i32, vp, vp, vp, i32, vp,
                                                                  i32, vp, i32, vp, vp, sz, f32, u32, vp]
+    # export (the inverse of the slot fills): the pool buffers, k_out / v_out, cu, n_seq, state, slots, pos_out, then the
+    # table arguments and / or kv_scale of the pool's kind as the fills take them, then stream
+    lib.sfa_ring_export_slots.restype = i32
+    lib.sfa_ring_export_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, vp]
+    lib.sfa_ring_export_fp8_slots.restype = i32
+    lib.sfa_ring_export_fp8_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, vp, vp]
+    lib.sfa_ring_export_paged_slots.restype = i32
+    lib.sfa_ring_export_paged_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.sfa_ring_export_paged_fp8_slots.restype = i32
+    lib.sfa_ring_export_paged_fp8_slots.argtypes = [P, P, P, P, P, P, vp, i32, vp, vp, vp, vp, i32, vp, vp]
 
 
 def lib():

@@ -905,6 +905,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                            tuple(page_table.shape) != (int(num_slots), per_slot) or
                                            not page_table.is_contiguous()):
                 raise ValueError(f"page_table must be a contiguous int32 [S, Wc / P] = [{int(num_slots)}, {per_slot}] tensor")
+        # what export_slots gives back: the activations' dtype (an FP8 pool spelled dtype=float8_e4m3fn names none: bfloat16)
+        self._act_dtype = torch.bfloat16 if dtype == torch.float8_e4m3fn else dtype
         if kv_dtype is not None:     # from here on `dtype` is what the buffers hold
             dtype = kv_dtype
         if self.window_size < 1:
@@ -1154,6 +1156,150 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             rc = N.lib().sfa_pages_copy(wk, wv, src_pages.data_ptr(), dst_pages.data_ptr(), src_pages.numel(),
                                         N.stream_ptr(self.window_k.device))
         N.check(rc, "sfa_pages_copy")
+
+    # ------------------------------------------------ export / import (the way out of a pool, and back in)
+    _act_dtype = None    # set by init_pool: the dtype of the packs an FP8 pool exports
+
+    def live_lengths(self, slots) -> torch.Tensor:
+        """Tokens each named slot of a pool holds: ``clamp(sink_len) + clamp(window_len)`` of its state row, ``[n]`` int32;
+        0 for a -1 entry and for a fresh (released) slot.  Torch ops on the device state (no sync, capturable), in the
+        manner of ``positions``: what ``export_slots`` writes per sequence, and the lengths its offsets are built from."""
+        st = self._require_pool("live_lengths")
+        if slots is None:
+            raise TypeError("live_lengths: slots must name the slots (list or integer tensor)")
+        idx = self._slots_arg(slots, None, writes=False).to(st.device).long()
+        S = st.shape[0]
+        ok = (idx >= 0) & (idx < S)
+        row = st[idx.clamp(0, S - 1)]
+        live = row[:, 0].clamp(0, self.num_sink) + row[:, 1].clamp(0, self.window_size)
+        return torch.where(ok, live, torch.zeros_like(live))
+
+    def export_slots(self, slots, cu=None, T=None, out=None, return_positions: bool = False):
+        """Read slots of a pool out as packed K/V in TOKEN order - the inverse of ``prefill_slots``
+        (``sfa_ring_export_slots``, one launch, nothing of the pool is written).  Sequence i is slot ``slots[i]`` and owns
+        rows ``cu[i] : cu[i + 1]`` of ``k`` / ``v`` ``[1, H_kv, T, D]``: its sink rows, then its ring from the oldest
+        token to the newest, whatever ``write_pos`` is, through the page table of a paged pool and dequantised
+        (``code * kv_scale``, the packed step's own read) into the ``dtype`` given to ``init_pool`` on an FP8 pool.  A
+        sequence with fewer rows than live tokens is truncated (its FIRST rows are written); every other row of the pack
+        - behind a sequence's live tokens, of a -1 slot, behind ``cu[-1]`` - is zero.  A ring slot whose page is unmapped
+        exports zeros.  Returns ``(k, v, cu)`` with ``cu`` the device int32 offsets, or ``(k, v, cu, pos)`` with
+        ``return_positions=True``: ``pos`` ``[T]`` int32, the position of each token (what RoPE took; -1 on zeroed rows).
+
+        ``cu=None`` is the convenient form: the offsets are the cumulative sum of ``live_lengths(slots)`` (on the
+        device), and unless ``T`` or ``out`` gives it the total is read back ONCE to size the pack - not capturable.
+        With ``cu`` (a device int32 tensor, unread; or a host list, checked) and ``T`` or ``out``, nothing is read on the
+        host and the call is capturable.  ``out = (k, v)`` or ``(k, v, pos)``: the pack to write into (``T`` is its row
+        count; any strides with 16-byte aligned rows, e.g. a ``[1, T, H_kv, D]``-stored view).  ``slots`` as for the dyn
+        calls (a device tensor is passed through unread, a host list is checked); a slot may be named twice."""
+        from . import _native as N
+        st = self._require_pool("export_slots")
+        if slots is None:
+            raise TypeError("export_slots: slots must name the slots (list or integer tensor)")
+        slots = self._slots_arg(slots, None, writes=False)
+        n_seq = slots.numel()
+        if n_seq < 1:
+            raise ValueError("export_slots needs at least one slot")
+        dev = self.sink_k.device
+        _S, H_kv, _ns, D = self.sink_k.shape
+        dt = self._act_dtype if self._kv8 else self.window_k.dtype
+        pos = None
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) not in (2, 3) or not all(isinstance(t, torch.Tensor) for t in out):
+                raise TypeError("export_slots: out must be (k, v) or (k, v, pos) tensors")
+            k, v = out[0], out[1]
+            pos = out[2] if len(out) == 3 else None
+            if self._kv8:
+                self._act16("out of export_slots", k, v)
+            elif k.dtype != dt or v.dtype != dt:
+                raise TypeError(f"export_slots: out must have the pool's dtype {dt}, got {k.dtype} / {v.dtype}")
+            if k.dim() != 4 or k.shape[0] != 1 or k.shape[1] != H_kv or k.shape[3] != D or v.shape != k.shape:
+                raise ValueError(f"export_slots: out must be packed [1, H_kv, T, D] = [1, {H_kv}, T, {D}] tensors of one "
+                                 f"shape, got {tuple(k.shape)} / {tuple(v.shape)}")
+            if T is not None and int(T) != k.shape[2]:
+                raise ValueError(f"export_slots: T = {T} but out holds {k.shape[2]} rows")
+            T = k.shape[2]
+            for t in (k, v):     # an output cannot be copied into shape as _rows16 does for an input
+                if t.numel() and (t.stride(3) != 1 or t.data_ptr() % 16 or
+                                  any((t.stride(i) * t.element_size()) % 16 for i in range(3))):
+                    raise ValueError("export_slots: the rows of out must be 16-byte aligned with a unit last stride")
+            if pos is not None and (pos.dtype != torch.int32 or pos.dim() != 1 or pos.numel() != T or not pos.is_contiguous()):
+                raise ValueError(f"export_slots: pos of out must be a contiguous int32 [T] = [{T}] tensor")
+        if cu is None:
+            live = self.live_lengths(slots)
+            cu_t = torch.zeros(n_seq + 1, dtype=torch.int32, device=live.device)
+            cu_t[1:] = torch.cumsum(live, 0)
+            if T is None:
+                T = int(cu_t[-1].item())         # the one read-back of the convenient form
+        else:
+            if isinstance(cu, torch.Tensor) and cu.is_cuda:
+                if T is None:
+                    raise ValueError("export_slots: a device cu needs T or out: the size of the pack is not read back from "
+                                     "the device")
+            elif T is None:
+                T = int(cu[-1])
+            cu_t = self._cu_arg(cu, int(T), dev)
+            if cu_t.numel() != n_seq + 1:
+                raise ValueError(f"export_slots: cu must hold n + 1 = {n_seq + 1} offsets for {n_seq} slots, got "
+                                 f"{cu_t.numel()}")
+        T = int(T)
+        if T < 0:
+            raise ValueError(f"export_slots: T must be >= 0, got {T}")
+        N.require_gpu(self.window_k, slots, cu_t)
+        if out is None:
+            k = torch.empty(1, H_kv, T, D, dtype=dt, device=dev)      # every row is written by the kernel
+            v = torch.empty_like(k)
+        N.require_gpu(k, v, pos)
+        if pos is None and return_positions:
+            pos = torch.empty(T, dtype=torch.int32, device=dev)
+        if T > 0:
+            name = self._pool_entry("sfa_ring_export_slots", "sfa_ring_export_fp8", "sfa_ring_export_paged")
+            with torch.cuda.device(dev):
+                rc = getattr(N.lib(), name)(*(N.desc(t) for t in (self.sink_k, self.sink_v, self.window_k, self.window_v,
+                                                                  k, v)),
+                                            cu_t.data_ptr(), n_seq, st.data_ptr(), slots.data_ptr(),
+                                            None if pos is None else pos.data_ptr(), *self._pool_tail(),
+                                            N.stream_ptr(dev))
+            N.check(rc, name)
+        return (k, v, cu_t, pos) if return_positions else (k, v, cu_t)
+
+    def import_slots(self, k: torch.Tensor, v: torch.Tensor, cu, slots, seen=None) -> torch.Tensor:
+        """Admit exported sequences: ``prefill_slots(k, v, cu, slots)``, then - with ``seen`` (device int32 ``[n]`` or a
+        host list: the source's ``positions(slots)``) - column 3 of the named state rows is overwritten by a torch
+        scatter on the current stream (-1 slots are skipped; no sync).  That is what lets a sequence that has already
+        evicted tokens (``seen > num_sink + Wc``) resume at the right RoPE position: the mask depends on ``sink_len``,
+        ``window_len`` and ``write_pos`` only, ``seen`` is the position counter.  Returns the pool's state.
+
+        - The imported ring is rotated to ``write_pos = 0`` when it is full (the prefill placement), so later steps read
+          the same tokens in another physical order: their outputs are within tolerance of the source's, not bitwise
+          equal to them.  A second export is bitwise the first.
+        - Importing into a smaller ``Wc`` keeps the sinks and the newest ``Wc`` tokens - the cache policy itself.
+        - Importing an evicted sequence into a larger ``Wc`` cannot bring back what was evicted: the ring holds what the
+          pack held and grows from there.
+        A pack exported with zero tails (``m_i > live``) must be imported with the offsets of the live tokens
+        (``export_slots`` with ``cu=None`` gives exactly those), or the zero rows are admitted as tokens.  A slot that was
+        admitted by a first chunk shorter than ``num_sink`` (``sink_len < num_sink`` under a non-empty ring) arrives with
+        its first ``num_sink`` tokens as sinks.  On a paged pool ``reserve_pages(slots, seen)`` comes first, as before
+        ``prefill_slots``."""
+        st = self._require_pool("import_slots")
+        if not isinstance(k, torch.Tensor) or not isinstance(v, torch.Tensor):
+            raise TypeError("import_slots: k / v must be tensors")
+        if self._kv8:
+            self._act16("k / v", k, v)
+        elif k.dtype != self.window_k.dtype or v.dtype != k.dtype:
+            raise TypeError("k / v must have the pool's dtype")
+        n_seq = (cu.numel() if isinstance(cu, torch.Tensor) else len(cu)) - 1
+        seen_t = self._packed_i32(seen, n_seq, "seen", "n", st.device)
+        idx = self._slots_arg(slots, n_seq, writes=True)
+        self.prefill_slots(k, v, cu, idx)
+        if seen_t is not None:
+            S = st.shape[0]
+            idx = idx.to(st.device).long()
+            ok = (idx >= 0) & (idx < S)
+            # rows of skipped entries go to a scratch row S behind the state, so that the scatter stays branch-free
+            col = torch.cat([st[:, 3], st.new_zeros(1)])
+            col.scatter_(0, torch.where(ok, idx, torch.full_like(idx, S)), seen_t)
+            st[:, 3] = col[:S]
+        return st
 
     def _require_dyn(self, what):
         if not (self.is_initialized and self.prefilled):
@@ -1606,6 +1752,18 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
     def packed_positions(self, cu_q, slots, T: int, layer_idx: int = 0) -> torch.Tensor:
         """``SinkCacheLayer.packed_positions`` of one layer: the RoPE position of every packed row (-1: no row)."""
         return self._layer(layer_idx).packed_positions(cu_q, slots, T)
+
+    def live_lengths(self, slots, layer_idx: int = 0) -> torch.Tensor:
+        """``SinkCacheLayer.live_lengths`` of one layer: the tokens each named slot holds (sinks + ring)."""
+        return self._layer(layer_idx).live_lengths(slots)
+
+    def export_slots(self, slots, layer_idx: int, cu=None, T=None, out=None, return_positions: bool = False):
+        """``SinkCacheLayer.export_slots`` of one layer: the named slots as packed K/V in token order."""
+        return self._layer(layer_idx).export_slots(slots, cu=cu, T=T, out=out, return_positions=return_positions)
+
+    def import_slots(self, key_states, value_states, cu, slots, layer_idx: int, seen=None) -> torch.Tensor:
+        """``SinkCacheLayer.import_slots`` of one layer: admit an exported pack; ``seen`` restores the positions."""
+        return self._layer(layer_idx).import_slots(key_states, value_states, cu, slots, seen=seen)
 
     def release_slots(self, slots) -> None:
         """``SinkCacheLayer.release_slots`` of every layer that holds a pool (layers without one are skipped)."""
