@@ -92,6 +92,24 @@ extern "C" {
  * sfa_ring_fill_varlen_slots does.  Every other sequence of the pack, and every call without the flag, is unchanged.
  * Other entry points ignore the bit.  See the packed ragged step below. */
 #define SFA_FLAG_RAGGED_ADMIT 0x40u
+/* The packed ragged step: serve prompt chunks by the 128-row chunk kernel.  Sequence i of the pack is a CHUNK sequence
+ * iff G * n_i >= 128 and (parent == NULL or n_i > 64) - decided on the device from cu_q alone, so a possible draft tree
+ * never is one and an admitting sequence usually is.  A chunk sequence is computed by workgroups of 128 rows whose four
+ * waves share every K/V tile of a split (one load per tile where the 32-row blocks of the default kernel make four);
+ * every other sequence runs the code, plan and grid of the call without the flag.  Three contracts:
+ *   1. the o rows of a chunk sequence meet the tolerance of the call without the flag against an fp64 reference;
+ *   2. the rows of every other sequence are bitwise those of the call without the flag, and with commit the pool and
+ *      the state rows are bitwise what that call leaves (every pool kind); rows of inactive or empty sequences and rows
+ *      behind cu_q[n_seq] are zeros;
+ *   3. the rows of a chunk sequence are bitwise the same wherever it lies in a pack of the same T and n_seq, when the
+ *      call is repeated and when it is replayed from a captured graph (both launches always happen: a captured call
+ *      replays at any mix).
+ * Honoured by sfa_decode_ring_ragged{,_tree,_fp8,_paged,_paged_fp8}_slots, which then need
+ * sfa_decode_ragged_chunk_workspace_bytes of workspace.  SFA_ERR_UNSUPPORTED, with a message that names the flag, from
+ * the two _group_ entry points and where no MFMA instance serves the call (fp32 activations, head dims other than
+ * 64 / 80 / 96 / 128, SFA_FLAG_FORCE_GENERIC).  sfa_last_path(): "_chunk128" directly behind "_ragged".  Other entry
+ * points ignore the bit. */
+#define SFA_FLAG_RAGGED_CHUNK128 0x80u
 
 /* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
  * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.
@@ -548,6 +566,11 @@ int sfa_ring_fill_varlen_slots(const sfa_tensor* sink_k, const sfa_tensor* sink_
  */
 size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                          int64_t D, int dtype);
+/* the workspace of a packed call with SFA_FLAG_RAGGED_CHUNK128: the size above plus the table of 128-row blocks
+ * (ceil(G T / 128) + n_seq entries of 8 bytes, rounded up to 256).  0 where the flag is refused for the shape: fp32,
+ * head dims other than 64 / 80 / 96 / 128 (and wherever the size above is 0).  No GPU needed. */
+size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                               int64_t D, int dtype);
 
 int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                  const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,

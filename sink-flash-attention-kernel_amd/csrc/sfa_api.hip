@@ -626,7 +626,17 @@ int ring_ragged(const RingCall& c) {
     if (c.pool.pt.table && !c.pool.fp8 &&
         (st = check_pool_served(Who("decode_ragged", c.pool), c.pool, q->dtype, q->shape[3], c.flags)))
         return st;
-    const size_t need = c.cu_g ? decode_ragged_group_workspace(c.n_seq, c.n_grp, q->shape[1], c.k_new->shape[1], q->shape[2],
+    const bool chunk = (c.flags & SFA_FLAG_RAGGED_CHUNK128) != 0;
+    if (chunk && (c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) ||
+                  decode_ragged_chunk_workspace(1, 1, 1, 1, 1, q->shape[3], q->dtype) == 0)) {
+        set_error("decode_ragged: SFA_FLAG_RAGGED_CHUNK128 serves bf16 / f16 at head dims 64 / 80 / 96 / 128 without fork groups "
+                  "(got dtype %d, head dim %lld%s%s)", q->dtype, (long long)q->shape[3], c.cu_g ? ", groups" : "",
+                  (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    const size_t need = chunk ? decode_ragged_chunk_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
+                                                              c.sink_len + c.window_len, q->shape[3], q->dtype)
+                        : c.cu_g ? decode_ragged_group_workspace(c.n_seq, c.n_grp, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                                c.sink_len + c.window_len, q->shape[3], q->dtype)
                                : decode_ragged_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                          c.sink_len + c.window_len, q->shape[3], q->dtype);
@@ -1026,6 +1036,11 @@ int sfa_decode_ring_multi_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, c
 size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                          int64_t D, int dtype) {
     return decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+}
+
+size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                               int64_t D, int dtype) {
+    return decode_ragged_chunk_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
 }
 
 int sfa_decode_ring_ragged_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, const int32_t* slots,

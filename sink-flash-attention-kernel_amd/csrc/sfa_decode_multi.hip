@@ -1131,6 +1131,335 @@ void multi_split_mfma_kernel(MultiArgs a, RA... ra) {
     }
 }
 
+// ---- chunk kernel (SFA_FLAG_RAGGED_CHUNK128).  The kernel above gives a 32-row block its own
+// workgroup, whose waves deal the tiles among themselves: right for a few rows over a long cache, wrong for a prompt
+// chunk, whose G n_i / 32 blocks each stream the whole sink + ring + chunk through their own loads and LDS writes.
+// Here a workgroup is 128 rows of one sequence x KV head x split and wave w owns rows [128 rb + 32 w, +32) for the whole
+// split.  The split's tiles are walked in rounds of four: wave w loads tile 4 j + w of round j (if some row of the
+// workgroup sees it), every wave consumes the round's tiles in index order, so a tile is loaded once and used four times
+// and a row's result does not depend on the other waves or on where the sequence lies in the pack.  Two sets of the
+// four-region LDS image: round j + 1 is loaded into registers before round j is computed from set j & 1 and written to
+// the other set behind the compute, one barrier per round (the set being written was last read one round earlier, and
+// every wave has passed that round's barrier).  A round that no row of the workgroup sees is skipped without a barrier:
+// the decision is a function of (round, workgroup), the same in all four waves.  No merge: each wave holds the complete
+// (m, l, O) of its rows and stores them at the addresses of the kernel above.  Plan, tile classes, mask, softmax and
+// the two products per tile are that kernel's for a 32-row block; the pieces are restated here so that its instances
+// keep their code.  Always (Dyn, Slots, Ragged), no trees, no groups.
+constexpr int kChunkRows = kWaves * 32;
+
+// sequence i of a packed call with the flag is a CHUNK sequence - served by the kernel below and by no workgroup of the
+// one above - iff it has at least one full 128-row block and cannot be a draft tree.  From cu_q and the call alone.
+__device__ __forceinline__ bool chunk_seq(int G, int n, int tree) {
+    return (int64_t)G * n >= kChunkRows && (!tree || n > 64);
+}
+
+// ragged_prep_kernel for a call with the flag: the same two tables, except that the 32-row blocks of chunk sequences
+// become surplus, plus wblk: sequence i owns the 128-row block ids [floor(G c0_i / 128) + i, + ceil(G n_i / 128)) below
+// nwb = ceil(G T / 128) + n_seq - disjoint by the argument made there - and the ids of every other sequence are surplus.
+__global__ __launch_bounds__(1024) void ragged_prep_chunk_kernel(RaggedArgs rg, int2* blk, int* rowseq, int2* wblk, int G,
+                                                                 int nrb, int nwb, int tree) {
+    for (int64_t x = threadIdx.x; x < (int64_t)nrb + rg.T + nwb; x += 1024) {
+        const int kind = x < nrb ? 0 : (x < (int64_t)nrb + rg.T ? 1 : 2);     // blk, rowseq, wblk
+        const int id = (int)(kind == 0 ? x : kind == 1 ? x - nrb : x - nrb - rg.T);
+        const int unit = kind == 2 ? kChunkRows : 32;
+        int lo = 0, hi = rg.n_seq - 1;       // the last i with start(i) <= id; sequence 0 starts at 0
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const int c = ragged_seq(rg, mid).c0;
+            const int64_t start = kind == 1 ? c : (int64_t)G * c / unit + mid;
+            if (start <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        const RaggedSeq s = ragged_seq(rg, lo);
+        if (kind == 1) {
+            rowseq[id] = (id >= s.c0 && id < s.c0 + s.n) ? lo : -1;
+        } else {
+            const int64_t local = id - ((int64_t)G * s.c0 / unit + lo);
+            const bool hit = local >= 0 && local * unit < (int64_t)G * s.n && chunk_seq(G, s.n, tree) == (kind == 2);
+            (kind == 2 ? wblk : blk)[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
+        }
+    }
+}
+
+template <typename T, int D, bool KV8, bool Paged, typename... KA>
+__global__ __launch_bounds__(kWaves * 64) void multi_chunk_mfma_kernel(MultiArgs a, RaggedArgs rg, const int2* wblk, int nwb,
+                                                                       KA... ka) {
+    static_assert(tail_is<false, KV8, Paged, KA...>, "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); both: (..., Kv8Args, PageArgs)");
+    [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ka...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ka...);
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int DK = D / 16;
+    constexpr int DVB = (D + 31) / 32;
+    constexpr int CPR = D / 8;
+    constexpr int ROWB = D <= 64 ? 128 : 256;
+    constexpr int TILE_BYTES = kTile * ROWB;
+    constexpr int NLD = kTile * CPR / 64;
+    constexpr int SET_BYTES = kWaves * 2 * TILE_BYTES;       // one round: four (K, V) regions
+    static_assert(kTile * CPR % 64 == 0, "tile chunks must split evenly over a wave");
+    static_assert(2 * SET_BYTES <= 160 * 1024, "two rounds must fit the LDS of a workgroup");
+    __shared__ __attribute__((aligned(16))) char smem[2 * SET_BYTES];
+
+    // (128-row block, split, KV head): the row blocks of one (KV head, split) read the same tiles and share an L2
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int split = (wid / nwb) % a.Sw;
+    const int hk = wid / nwb / a.Sw;
+    const int2 e = wblk[wid % nwb];
+    const int seq = __builtin_amdgcn_readfirstlane(e.x);
+    if (seq < 0) return;               // surplus of the block bound, or a sequence of the other kernel
+    const int rb = __builtin_amdgcn_readfirstlane(e.y);
+    const int c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (c < 0) return;                 // inactive sequence: the reduce writes its zeros
+    const RaggedSeq sq = ragged_seq(rg, seq);
+    const int prow = __builtin_amdgcn_readfirstlane(sq.c0);
+    const int rn = __builtin_amdgcn_readfirstlane(sq.n);
+    const int rR = a.G * rn;
+    const Fill f = get_fill<true, true>(a, c, rn, rg.admit);
+    if (split >= f.S) return;          // surplus of the full-cache grid at this fill level
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    // the wave's 32 rows: everything below is what the kernel above computes for the 32-row block 4 rb + wave
+    const int w0 = kChunkRows * rb + 32 * wave;
+    const int rho = w0 + r;
+    const bool row_live = rho < rR;
+    const bool wave_live = w0 < rR;    // a wave without a live row computes and stores nothing, but loads its share
+    const int tq = row_live ? rho / a.G : 0;
+    const int tmin = w0 / a.G;
+    const int tmax = ((w0 + 31 < rR - 1) ? w0 + 31 : rR - 1) / a.G;
+    // the union of the workgroup's live rows (kChunkRows rb < rR: the table holds no other block): what is loaded
+    const int gmin = (kChunkRows * rb) / a.G;
+    const int gmax = ((kChunkRows * rb + kChunkRows - 1 < rR - 1) ? kChunkRows * rb + kChunkRows - 1 : rR - 1) / a.G;
+
+    frag qf[DK];
+    {
+        const int head = hk * a.G + (row_live ? rho % a.G : 0);
+        const char* qp = a.q.ptr + ((int64_t)head * a.q.sh + (int64_t)(prow + tq) * a.q.sn) * 2;
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            u32x4 raw = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
+            if (!row_live) raw = u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(frag, raw);
+        }
+    }
+
+    u32x4 kst[NLD], vst[NLD];
+    [[maybe_unused]] float ksc = 1.f, vsc = 1.f;
+    [[maybe_unused]] bool st8 = false;
+    if constexpr (KV8) ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
+    auto issue_loads = [&](const TileInfo& ti) {
+        if constexpr (KV8) {
+            st8 = ti.seg != 2;
+            if (st8) {
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    const int ci = lane + 64 * j;
+                    const int key = ci / CPR, ch = ci % CPR;
+                    const int row = key < ti.count ? key : ti.count - 1;
+                    const uint2 k8 = *reinterpret_cast<const uint2*>(ti.k + row * ti.ksn + ch * 8);
+                    const uint2 v8 = *reinterpret_cast<const uint2*>(ti.v + row * ti.vsn + ch * 8);
+                    kst[j][0] = k8.x, kst[j][1] = k8.y, vst[j][0] = v8.x, vst[j][1] = v8.y;
+                }
+                return;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int ci = lane + 64 * j;
+            const int key = ci / CPR, ch = ci % CPR;
+            const int row = key < ti.count ? key : ti.count - 1;   // rows past the segment: a valid row, masked later
+            kst[j] = *reinterpret_cast<const u32x4*>(ti.k + row * ti.ksn + ch * 16);
+            vst[j] = *reinterpret_cast<const u32x4*>(ti.v + row * ti.vsn + ch * 16);
+        }
+    };
+    // the wave's region of a set: K, then V
+    auto write_lds = [&](char* kl) {
+        char* vl = kl + TILE_BYTES;
+        if constexpr (KV8) {
+            if (st8) {                 // the conversion: between the global load and the LDS store
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    kst[j] = kv8_read<T>(kst[j][0], kst[j][1], ksc);
+                    vst[j] = kv8_read<T>(vst[j][0], vst[j][1], vsc);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int ci = lane + 64 * j;
+            const int key = ci / CPR, ch = ci % CPR;
+            const int ksw = ROWB == 256 ? (key & 15) : ((key >> 1) & 7);
+            const int vsw = ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2);
+            *reinterpret_cast<u32x4*>(kl + key * ROWB + ((ch ^ ksw) << 4)) = kst[j];
+            *reinterpret_cast<u32x4*>(vl + key * ROWB + ((ch ^ vsw) << 4)) = vst[j];
+        }
+    };
+
+    const int ksw_l = ROWB == 256 ? (r & 15) : ((r >> 1) & 7);
+    const int k_rowoff = r * ROWB;
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    const int vsw_l = ROWB == 256 ? (q4 << 2) : (((q4 >> 1) & 1) << 2);
+    const int v_rowoff = (4 * h + q4) * ROWB + (p4 & 1) * 8;
+    const int v_chunk_lo = 2 * g1 + (p4 >> 1);
+
+    float m = -INFINITY, l = 0.f;   // log2 domain; l: this half-wave's partial sum
+    f32x16 o[DVB];
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+    const int es = 2;
+
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
+    const int nround = (tend - tbeg + kWaves - 1) / kWaves;
+    auto tile_at = [&](int i) { return tile_info<true, KV8, Paged>(a, f, i, 0, c, hk, es, rn, prow, pg.shift); };
+    // the classes of a round, one bit per tile: live for some row of the workgroup (what is loaded), live for this wave's
+    // rows (what it consumes; their range lies in the union's, so such a tile was loaded) and of class edge for them.
+    // A tile's descriptor and classes are evaluated here, once per round and wave; the loads and the edge mask build
+    // the descriptor of their own tile again, a full tile needs none
+    struct Round {
+        int live, mine, edge;
+    };
+    // the first round from j on that holds a tile some row of the workgroup sees, and its classes; nround: none
+    auto next_round = [&](int j, Round& rd) {
+        for (; j < nround; ++j) {
+            rd = Round{0, 0, 0};
+            for (int t = 0; t < kWaves; ++t) {
+                const int i = tbeg + kWaves * j + t;
+                if (i >= tend) break;
+                const TileInfo ti = tile_at(i);
+                if (tile_class(a, ti, gmin, gmax, f.nsk) == 0) continue;
+                const int cls = wave_live ? tile_class(a, ti, tmin, tmax, f.nsk) : 0;
+                rd.live |= 1 << t, rd.mine |= (cls != 0) << t, rd.edge |= (cls == 2) << t;
+            }
+            if (rd.live) return j;
+        }
+        return j;
+    };
+    // the wave's share of round j into registers; false: its tile is past the split or dead for the workgroup
+    auto load_round = [&](int j, const Round& rd) {
+        if (!((rd.live >> wave) & 1)) return false;
+        TileInfo ti = tile_at(tbeg + kWaves * j + wave);
+        if constexpr (Paged) {
+            if (ti.seg == 1) tile_page(ti, a, pg, c, KV8 ? 1 : es);
+        }
+        issue_loads(ti);
+        return true;
+    };
+
+    int set = 0;
+    Round cr{}, nr{};
+    int j = next_round(0, cr);
+    if (j < nround && load_round(j, cr)) write_lds(smem + wave * 2 * TILE_BYTES);
+    __syncthreads();
+    while (j < nround) {
+        const int jn = next_round(j + 1, nr);
+        const bool ld = jn < nround && load_round(jn, nr);
+#pragma unroll 1
+        for (int t = 0; t < kWaves; ++t) {
+            if (!((cr.mine >> t) & 1)) continue;     // past the split, or dead for this wave's rows
+            const bool edge = (cr.edge >> t) & 1;
+            const char* kl = smem + set * SET_BYTES + t * 2 * TILE_BYTES;
+            const char* vl = kl + TILE_BYTES;
+
+            f32x16 s;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) s[x] = 0.f;
+            {
+                frag kf[DK];
+#pragma unroll
+                for (int ks = 0; ks < DK; ++ks) kf[ks] = *reinterpret_cast<const frag*>(kl + k_rowoff + (((2 * ks + h) ^ ksw_l) << 4));
+#pragma unroll
+                for (int ks = 0; ks < DK; ++ks) s = M::run(kf[ks], qf[ks], s);
+            }
+            if (edge) {
+                const TileInfo cur = tile_at(tbeg + kWaves * j + t);
+                if (admitting(f, cur)) {
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) {
+                        const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                        s[x] = key_visible_admit(a, f, cur, kk, tq) ? s[x] : -INFINITY;
+                    }
+                } else {
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) {
+                        const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                        s[x] = key_visible(a, f, cur, kk, tq) ? s[x] : -INFINITY;
+                    }
+                }
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) mx = fmaxf(mx, s[x]);
+            mx = half_swap_max(mx);
+            const float m_new = fmaxf(m, mx * c2);
+            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+            float rs = 0.f;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                s[x] = __builtin_amdgcn_exp2f(fmaf(s[x], c2, -m_safe));
+                rs += s[x];
+            }
+            l = fmaf(l, alpha, rs);
+            m = m_new;
+#pragma unroll
+            for (int db = 0; db < DVB; ++db)
+#pragma unroll
+                for (int x = 0; x < 16; ++x) o[db][x] *= alpha;
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                frag pf;
+#pragma unroll
+                for (int x = 0; x < 8; ++x) pf[x] = (typename M::elem)s[8 * st + x];
+                const char* vrow = vl + 16 * st * ROWB + v_rowoff;
+#pragma unroll
+                for (int db = 0; db < DVB; ++db) {
+                    const int ch = (4 * db + v_chunk_lo) ^ vsw_l;
+                    const char* p1 = vrow + (ch << 4);
+                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1));
+                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1 + 8 * ROWB));
+                    s16x8 vv;
+                    vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
+                    vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
+                    o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+                }
+            }
+        }
+        set ^= 1;
+        if (ld) write_lds(smem + set * SET_BYTES + wave * 2 * TILE_BYTES);
+        __syncthreads();
+        j = jn, cr = nr;
+    }
+
+    // ---- each wave stores the partials of its own rows: one per row and split, at the addresses of the kernel above
+    if (!wave_live) return;
+    const float lw = half_swap_sum(l);
+    if (!row_live) return;
+    const bool none = m == -INFINITY;      // no visible key in this split: (-inf, 0, zeros)
+    const int64_t pr = ((((int64_t)hk * rg.T + prow) * a.G + rho) * a.Sw + split);
+    if (h == 0) {
+        a.Mp[pr] = m;
+        a.Lp[pr] = none ? 0.f : lw;
+    }
+    // lane (r, h) holds columns 32 db + 8 q + 4 h + [0, 4) of row r: four consecutive floats per (db, q)
+    float* op = a.Op + pr * D;
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int col = 32 * db + 8 * q + 4 * h;
+            if (col < D) {
+                float4 v4 = make_float4(o[db][4 * q], o[db][4 * q + 1], o[db][4 * q + 2], o[db][4 * q + 3]);
+                if (none) v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(op + col) = v4;
+            }
+        }
+}
+
 // a packed (ragged) partial row: rowid = (hk * T + packed row) * G + g.  Finds the row's sequence in the table: the
 // callers go on as for B = 1 with rho = the row within the sequence, n = its length and c0 = its first packed row.
 // False: the row has no work (padding, an empty or inactive sequence); rho = the query head within the group and tp =
@@ -2079,6 +2408,33 @@ int launch_mfma(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
     return split_status(a, rg, "mfma");
 }
 
+// the chunk kernel of a packed call with SFA_FLAG_RAGGED_CHUNK128: the table of ragged_prep_chunk_kernel and its bound
+struct ChunkTable {
+    const int2* wblk;
+    int nwb;
+};
+
+// behind the split launch, on Hkv * Sw * nwb blocks whatever the pack holds (a captured call replays at any mix)
+template <typename T>
+int launch_chunk(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, const ChunkTable& ck, hipStream_t stream) {
+    const dim3 grid((unsigned)((int64_t)a.Hkv * a.Sw * ck.nwb));
+    auto go = [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        dispatch_pool(pool, [&](auto p, auto... tail) {
+            using P = decltype(p);
+            multi_chunk_mfma_kernel<T, D, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(a, rg, ck.wblk, ck.nwb, tail...);
+        });
+    };
+    switch (a.D) {
+        case 64: go(std::integral_constant<int, 64>{}); break;
+        case 80: go(std::integral_constant<int, 80>{}); break;
+        case 96: go(std::integral_constant<int, 96>{}); break;
+        case 128: go(std::integral_constant<int, 128>{}); break;
+        default: set_error("decode_ragged: SFA_FLAG_RAGGED_CHUNK128 has no kernel for head dim %d", a.D); return SFA_ERR_UNSUPPORTED;
+    }
+    return launch_status("decode_multi_chunk128");
+}
+
 template <typename T>
 int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, hipStream_t stream) {
     switch (a.D) {
@@ -2094,10 +2450,15 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool
 // split launch, reduce (+ commit) launch, state advance; rg: the packed call (a.B = 1, a.n = T, a.R = G * T)
 // pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
-int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream) {
+int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream,
+                const ChunkTable* ck = nullptr) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
-    if constexpr (sizeof(T) == 2) st = mfma ? launch_mfma_d<T>(a, rg, pool, grp, stream) : SFA_OK;
+    if constexpr (sizeof(T) == 2) {
+        st = mfma ? launch_mfma_d<T>(a, rg, pool, grp, stream) : SFA_OK;
+        // chunk sequences: their 32-row blocks left the split launch as surplus; the reduce folds either kernel's partials
+        if (!st && mfma && ck) st = launch_chunk<T>(a, *rg, pool, *ck, stream);
+    }
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
         dispatch_mode(a, rg, [&](auto m) {
@@ -2166,7 +2527,7 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
 int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
-                 const GroupArgs* grp = nullptr) {
+                 const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
@@ -2175,8 +2536,8 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
         return SFA_ERR_UNSUPPORTED;
     }
     if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, nullptr, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream);
-    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck);
+    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck);
 }
 
 }  // namespace
@@ -2297,6 +2658,15 @@ size_t decode_ragged_group_workspace(int64_t n_seq, int64_t n_grp, int64_t Hq, i
            al256((size_t)g.ngrb * sizeof(int2)) + al256((size_t)n_grp * sizeof(int2)) + 2 * al256((size_t)n_seq * sizeof(int));
 }
 
+// the workspace of a call with SFA_FLAG_RAGGED_CHUNK128: that of the ungrouped call, then wblk.  0 where the flag is
+// refused: no chunk instance (fp32, head dims other than 64 / 80 / 96 / 128)
+size_t decode_ragged_chunk_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype) {
+    const size_t base = decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+    if (base == 0 || dtype == SFA_DTYPE_F32 || !mfma_head_dim((int)D)) return 0;
+    const int64_t nwb = cdiv64(Hq / Hkv * T, kChunkRows) + n_seq;
+    return base + al256((size_t)nwb * sizeof(int2));
+}
+
 int decode_ragged_launch(const RingCall& c) {
     const int64_t T = c.q->shape[2];
     const RaggedGeom g = ragged_geom(c.n_seq, c.q->shape[1], c.k_new->shape[1], T, c.sink_len + c.window_len);
@@ -2320,7 +2690,17 @@ int decode_ragged_launch(const RingCall& c) {
         set_error("decode_ragged: grid too large");
         return SFA_ERR_UNSUPPORTED;
     }
-    ragged_prep_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, a.G, a.nrb);
+    // SFA_FLAG_RAGGED_CHUNK128 (the API has refused it where no chunk instance exists): the third table lies behind the
+    // ungrouped call's workspace, the preparation marks the chunk sequences in both block tables
+    const bool chunk = (c.flags & SFA_FLAG_RAGGED_CHUNK128) != 0;
+    ChunkTable ck{};
+    if (chunk) {
+        int2* wblk = reinterpret_cast<int2*>(ws + decode_ragged_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, c.sink_len + c.window_len, a.D, c.q->dtype));
+        ck = ChunkTable{wblk, (int)(cdiv64(g.G * T, kChunkRows) + c.n_seq)};
+        ragged_prep_chunk_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, wblk, a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+    } else {
+        ragged_prep_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, a.G, a.nrb);
+    }
     int st;
     if ((st = launch_status("ragged_prep"))) return st;
     GroupArgs gr{};
@@ -2349,10 +2729,12 @@ int decode_ragged_launch(const RingCall& c) {
     }
     bool mfma;
     const char* dname;
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr))) return st;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr, chunk ? &ck : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
-    if (mfma) set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s", fam, dname, a.D, a.nrb, ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
+    if (mfma)
+        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "", ad, cm,
+                 c.cu_g ? "_group" : "", pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }

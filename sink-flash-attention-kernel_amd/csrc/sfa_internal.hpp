@@ -128,6 +128,9 @@ int decode_multi_launch(const RingCall& c);      // sfa_decode_ring_multi* / sfa
 // sfa_decode_ring_ragged_slots / sfa_decode_ring_ragged_tree_slots.  Workspace: partials for T packed rows plus the tables of the preparation launch
 size_t decode_ragged_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
 int decode_ragged_launch(const RingCall& c);
+// the same with SFA_FLAG_RAGGED_CHUNK128: the ungrouped workspace plus the 128-row block table; 0 where no chunk instance
+// exists (fp32, head dims other than 64 / 80 / 96 / 128)
+size_t decode_ragged_chunk_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
 // the same with fork groups (c.cu_g): the ungrouped workspace plus the group partials and the group tables; 0 where no
 // grouped instance exists (fp32, head dims other than 64 / 80 / 96 / 128)
 size_t decode_ragged_group_workspace(int64_t n_seq, int64_t n_grp, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,

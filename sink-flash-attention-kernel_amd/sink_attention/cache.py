@@ -1367,7 +1367,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                         commit: bool = True, admit: bool = False, parent=None, commit_seq=None,
-                        groups=None) -> torch.Tensor:
+                        groups=None, chunk_kernel: bool = False) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -1407,9 +1407,18 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ungrouped call within its tolerance, pool and state rows end bitwise as it leaves them, and a group that shares
         nothing is computed exactly as without ``groups``.  The caller promises nothing: any grouping is safe.  A device
         int32 tensor is never read on the host (a captured step replays at any grouping by rewriting it in place), a host
-        list is checked and uploaded once.  ``parent`` together with ``groups`` is refused."""
+        list is checked and uploaded once.  ``parent`` together with ``groups`` is refused.
+
+        ``chunk_kernel=True`` (``SFA_FLAG_RAGGED_CHUNK128``; False: the call above, unchanged): a sequence with
+        ``G * n_i >= 128`` rows (and more than 64 tokens when ``parent`` is given) - a prompt chunk, an admitting prompt -
+        is computed by workgroups of 128 rows whose waves share every K/V tile they load; its output is that of the
+        default call within its tolerance and does not depend on its place in the pack.  Every other sequence, the pool
+        and the state rows are bitwise those of the default call.  bf16 / fp16 at head dims 64 / 80 / 96 / 128, every pool
+        kind; ``groups`` together with ``chunk_kernel`` is refused."""
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
+        if chunk_kernel and groups is not None:
+            raise ValueError("ragged_step_dyn(chunk_kernel=True) takes no groups=: the grouped call has no chunk kernel")
         if groups is not None:
             if not self.page_size:
                 raise TypeError("ragged_step_dyn(groups=) needs a paged pool: init_pool(..., page_size=P)")
@@ -1431,15 +1440,18 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         n_grp = 0 if cu_g is None else cu_g.numel() - 1
         # the grouped call keeps constants and workspace of its own, so that grouped and ungrouped steps (and graphs
         # captured of either) can alternate on one layer without replacing each other's workspace
-        attr = "_ragged_group_state" if n_grp else "_ragged_state"
+        attr = "_ragged_chunk_state" if chunk_kernel else "_ragged_group_state" if n_grp else "_ragged_state"
         st = getattr(self, attr, None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype) + ((n_grp,) if n_grp else ())
         if st is None or st["key"] != key:
             ws_bytes = 0
+            if chunk_kernel:
+                ws_bytes = N.lib().sfa_decode_ragged_chunk_workspace_bytes(
+                    n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
             if n_grp:
                 ws_bytes = N.lib().sfa_decode_ragged_group_workspace_bytes(
                     n_seq, n_grp, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
-            if ws_bytes == 0:        # no groups; or a shape no grouped instance serves, which the library refuses itself
+            if ws_bytes == 0:        # the plain call; or a shape no grouped / chunk instance serves, which the library refuses itself
                 ws_bytes = N.lib().sfa_decode_ragged_workspace_bytes(
                     n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
             if ws_bytes == 0:
@@ -1465,8 +1477,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
                                           cu.data_ptr(), n_seq, *grp, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
-                                          st["scale"], N.FLAG_RAGGED_ADMIT if admit else 0,
-                                          N.stream_ptr(q.device))
+                                          st["scale"], (N.FLAG_RAGGED_ADMIT if admit else 0) |
+                                          (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0), N.stream_ptr(q.device))
         N.check(rc, name)
         return out
 
@@ -1736,14 +1748,15 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         return self._layer(layer_idx).prefill_slots(key_states, value_states, cu_seqlens, slots)
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
-                        commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None):
+                        commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None,
+                        chunk_kernel: bool = False):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
         draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
-        (paged pools)."""
+        (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
                                                       commit=commit, admit=admit, parent=parent, commit_seq=commit_seq,
-                                                      groups=groups)
+                                                      groups=groups, chunk_kernel=chunk_kernel)
 
     def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
         """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""

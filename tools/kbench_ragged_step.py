@@ -34,6 +34,11 @@ Variants per (W, step), alternating in one process:
     each named format and, per page size, on a paged pool of each (shuffled table) - with fp8 the last one is the paged
     FP8 pool (init_pool(page_size=P, kv_dtype=float8_e4m3fn)) - all alternating in one process.  Prints ms per step, the
     spread and each time over the contiguous 16-bit one.  A pool the library lacks is skipped (a parent build).
+--chunk: the 128-row chunk kernel instead (wall mode): H_q=64, H_kv=8 (G = 8), D = 64 and 128, bf16,
+    Wc = 4096 with every ring full, packs dec8_pre512 (8 decode rows + one chunk of 512 tokens, committing) and admit2048
+    (one chunk of 2048 tokens admitted on a fresh slot; commit off, so that the slot stays fresh).  Variants ragged (the
+    call without the keyword) and ragged_chunk (chunk_kernel=True) on one pool and one pack, alternating in one process.
+    Prints ms per step, the spread, the ratio and the largest difference between the two outputs.
 --pkg DIR: import sink_attention from DIR/sink-flash-attention-kernel_amd (a checkout of another commit with its own
     built library), to time two commits' libraries with one tool.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
@@ -42,7 +47,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
+       [--admit | --tree | --chunk | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -379,6 +384,48 @@ def paged_dtypes(args):
                       flush=True)
 
 
+CHUNK_PACKS = {"dec8_pre512": ([1] * 8 + [512], False), "admit2048": ([2048], True)}
+
+
+def chunk_kernel(args):
+    """--chunk: the packed step with and without chunk_kernel=True, alternating"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt = "cuda", torch.bfloat16
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nH_q={HQ} H_kv={HKV} num_sink={NS} s_aux bf16, rings full; device ms per step, "
+          f"median of {args.rounds} rounds of {args.calls} calls (events) after {WARM} warm-up calls, variants alternating", flush=True)
+    for W in Ws:
+        for d in (64, 128):
+            for step, (lengths, admit) in CHUNK_PACKS.items():
+                torch.manual_seed(0)
+                n_seq, T = len(lengths), sum(lengths)
+                pool = SinkCacheLayer(NS, W)
+                pool.init_pool(n_seq, HKV, d, dt, dev)
+                if not admit:
+                    pre = NS + W + 37                          # full ring, wrapped
+                    k = torch.randn(1, HKV, n_seq * pre, d, device=dev, dtype=dt)
+                    pool.prefill_slots(k, torch.randn_like(k), [pre * i for i in range(n_seq + 1)], list(range(n_seq)))
+                    del k
+                q = torch.randn(1, HQ, T, d, device=dev, dtype=dt)
+                kn, vn = (torch.randn(1, HKV, T, d, device=dev, dtype=dt) for _ in range(2))
+                sa = torch.randn(HQ, device=dev) * 0.5
+                cu = torch.tensor([sum(lengths[:i]) for i in range(n_seq + 1)], dtype=torch.int32, device=dev)
+                slots = torch.arange(n_seq, dtype=torch.int32, device=dev)
+                outs = {n: torch.empty_like(q) for n in ("ragged", "ragged_chunk")}
+                fns = {n: (lambda n=n: pool.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=outs[n], commit=not admit,
+                                                            admit=admit, chunk_kernel=n == "ragged_chunk")) for n in outs}
+                res = _alternate(torch, args, fns, list(fns))
+                med = {n: sorted(x)[len(x) // 2] for n, x in res.items()}
+                for n in outs:          # the comparison: both on the pool as the timing left it, commit off
+                    pool.ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=outs[n], commit=False, admit=admit,
+                                         chunk_kernel=n == "ragged_chunk")
+                diff = (outs["ragged"].float() - outs["ragged_chunk"].float()).abs().max().item()
+                print(f"  W={W:5d} D={d:3d} {step:12s} T={T:4d}  " +
+                      "  ".join(f"{n} {med[n]:7.4f} ms (min {min(res[n]):.4f} max {max(res[n]):.4f})" for n in fns) +
+                      f"  ragged_chunk / ragged {med['ragged_chunk'] / med['ragged']:.3f}  max |o diff| {diff:.2e}", flush=True)
+
+
 def kernels(args):
     torch, names, have = _setup(args)
     dev, dt = "cuda", torch.bfloat16
@@ -403,7 +450,7 @@ def summarize(args):
     ev = []
     for r in rows:
         name = r["Kernel_Name"]
-        kind = "prep" if "ragged_prep_kernel" in name else "split" if "multi_split_" in name else \
+        kind = "prep" if "ragged_prep_kernel" in name else "split" if "multi_split_" in name or "multi_chunk_" in name else \
             "reduce" if "multi_reduce_kernel" in name else "advance" if "ring_advance_" in name else None
         if kind:
             ev.append((kind, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
@@ -451,10 +498,13 @@ def main():
     ap.add_argument("--summarize", default=None, help="kernel_trace.csv of a --mode kernels run")
     ap.add_argument("--pool-dtypes", default=None, help="bf16,fp8: the packed step on pools of these formats (wall mode)")
     ap.add_argument("--page-size", default=None, help="64,256: the packed step on a contiguous and on paged pools (wall mode)")
+    ap.add_argument("--chunk", action="store_true", help="the 128-row chunk kernel (wall mode): variants ragged and ragged_chunk")
     ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
     if args.summarize:
         summarize(args)
+    elif args.chunk:
+        chunk_kernel(args)
     elif args.page_size and args.pool_dtypes:
         paged_dtypes(args)
     elif args.page_size:
