@@ -572,6 +572,14 @@ size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv,
 size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                                int64_t D, int dtype);
 
+/* Head dim 256 (bf16 / f16): the packed calls - this one and its _tree, _fp8, _paged and _paged_fp8 forms - run an MFMA
+ * split kernel of their own there (wave pairs: a pair shares one K/V tile in LDS, each wave owns half of the output
+ * columns), with SFA_FLAG_RAGGED_ADMIT, parent and commit_seq as at the other head dims.  On the
+ * contiguous 16-bit pool SFA_FLAG_FORCE_GENERIC keeps the exact-f32 kernel, whose output the MFMA kernel meets within
+ * the tolerance of the call, not bitwise; the pool and the state rows after a commit are bitwise the same.  Workspace:
+ * sfa_decode_ragged_workspace_bytes, unchanged.  sfa_last_path(): "decode_multi_mfma_{bf16,f16}_d256_rb<n>_ragged...".
+ * SFA_FLAG_RAGGED_CHUNK128 and the _group_ entry points have no instance at 256 and refuse it as before; the multi-token
+ * calls that are not packed keep the exact-f32 kernel there. */
 int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                  const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
                                  const sfa_tensor* v_new, const sfa_tensor* o, const float* s_aux, int commit,
@@ -601,7 +609,7 @@ int sfa_decode_ring_ragged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, 
  *     sequence stores the WHOLE chunk in packed order: defined, and meaningful only for a chain-shaped parent.
  * Plan, grid, workspace (sfa_decode_ragged_workspace_bytes), launches and host checks are those of
  * sfa_decode_ring_ragged_slots.  sfa_last_path(): "decode_tree_{mfma,f32}_..._ragged..." with parent, else
- * "decode_multi_...".
+ * "decode_multi_...".  Head dim 256: the (Tree) instances of the pair kernel, "decode_tree_mfma_{bf16,f16}_d256_...".
  */
 int sfa_decode_ring_ragged_tree_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                       const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
@@ -657,7 +665,8 @@ int sfa_ring_commit_path_ragged_slots(const sfa_tensor* window_k, const sfa_tens
  * its order, with "decode_ragged_fp8: the cache buffers must be FP8 (e4m3)" (SFA_ERR_INVALID_ARGUMENT) where it
  * compares the dtypes; fp32 activations and head dims outside 64 / 80 / 96 / 128 are SFA_ERR_UNSUPPORTED (there is no
  * exact-f32 instance for an FP8 pool, and SFA_FLAG_FORCE_GENERIC is refused the same way).  sfa_last_path(): the name of
- * the 16-bit call plus "_kvfp8".
+ * the 16-bit call plus "_kvfp8".  Head dim 256 is served too (rows of 256 bytes; the pair kernel, and the storing,
+ * copying and exporting calls of an FP8 pool); the message above keeps its text.
  */
 int sfa_decode_ring_ragged_fp8_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                      const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
@@ -770,7 +779,8 @@ int sfa_ring_copy_slots(const sfa_tensor* src_sink_k, const sfa_tensor* src_sink
  * sfa_decode_ring_ragged_paged_slots: the arguments of sfa_decode_ring_ragged_tree_slots plus (page_table,
  * table_stride) in front of workspace; parent, commit_seq, commit and SFA_FLAG_RAGGED_ADMIT as there.  Workspace:
  * sfa_decode_ragged_workspace_bytes with Nkv_cache = num_sink + Wc.  sfa_last_path(): the name of the contiguous call
- * plus "_paged".
+ * plus "_paged".  Head dim 256 is served too - by this call (the pair kernel) and by the storing, copying and exporting
+ * calls of a paged pool - but not by the _group_ forms, which answer with the message above.
  */
 int sfa_decode_ring_ragged_paged_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                        const sfa_tensor* window_k, const sfa_tensor* window_v, const sfa_tensor* k_new,
@@ -895,7 +905,7 @@ int sfa_pages_copy(const sfa_tensor* window_k, const sfa_tensor* window_v, const
  *
  * sfa_decode_ring_ragged_paged_fp8_slots: the arguments of sfa_decode_ring_ragged_paged_slots plus kv_scale in front of
  * workspace.  Workspace: sfa_decode_ragged_workspace_bytes with q's dtype and Nkv_cache = num_sink + table_stride * P.
- * sfa_last_path(): the name of the 16-bit contiguous call plus "_paged_kvfp8".
+ * sfa_last_path(): the name of the 16-bit contiguous call plus "_paged_kvfp8".  Head dim 256 as for the paged pool.
  */
 int sfa_decode_ring_ragged_paged_fp8_slots(const sfa_tensor* q, const sfa_tensor* sink_k, const sfa_tensor* sink_v,
                                            const sfa_tensor* window_k, const sfa_tensor* window_v,

@@ -453,9 +453,12 @@ struct Who {
 // What an FP8 or a paged pool serves: bf16 / f16 at 64 / 80 / 96 / 128, the MFMA instances (no exact-f32 one reads such a
 // pool).  An FP8 call asks where its 16-bit sibling checks the head dim, a 16-bit paged call after the sibling's checks.
 // fp8_pages_ok (sfa_ring_copy_paged_slots): FP8 pages pass too - the copy moves bytes
-int check_pool_served(const char* who, const SlotPool& pool, int dtype, int64_t D, unsigned flags, bool fp8_pages_ok = false) {
-    if (dtype == SFA_DTYPE_F32 || (dtype == SFA_DTYPE_FP8_E4M3 && !fp8_pages_ok) || !(D == 64 || D == 80 || D == 96 || D == 128) ||
-        (flags & SFA_FLAG_FORCE_GENERIC)) {
+// Head dim 256 is served as well (the pair kernel of the packed step; the storing and copying kernels take any row
+// of 16-byte pieces), except by a grouped step (`grouped`), which has no instance there; the message keeps its text.
+int check_pool_served(const char* who, const SlotPool& pool, int dtype, int64_t D, unsigned flags, bool fp8_pages_ok = false,
+                      bool grouped = false) {
+    if (dtype == SFA_DTYPE_F32 || (dtype == SFA_DTYPE_FP8_E4M3 && !fp8_pages_ok) ||
+        !(D == 64 || D == 80 || D == 96 || D == 128 || (D == 256 && !grouped)) || (flags & SFA_FLAG_FORCE_GENERIC)) {
         set_error("%s: %s at head dims 64 / 80 / 96 / 128 (got dtype %d, head dim %lld%s)", who,
                   !pool.fp8 ? "a paged pool serves bf16 / f16" : pool.pt.table ? "a paged FP8 pool serves bf16 / f16 activations"
                                                                                : "an FP8 pool serves bf16 / f16 activations",
@@ -623,8 +626,8 @@ int ring_ragged(const RingCall& c) {
     SFA_CHECK_ARG(q->shape[0] == 1, "decode_ragged: q / k_new / v_new / o must be packed [1, H, T, D] (got shape[0] = %lld)",
                   (long long)q->shape[0]);
     SFA_CHECK_ARG(q->shape[1] >= 1, "decode_ragged: H_q must be at least 1");
-    if (c.pool.pt.table && !c.pool.fp8 &&
-        (st = check_pool_served(Who("decode_ragged", c.pool), c.pool, q->dtype, q->shape[3], c.flags)))
+    if (c.pool.pt.table && (!c.pool.fp8 || c.cu_g) &&     // an FP8 pool was asked in check_multi; its groups are asked here
+        (st = check_pool_served(Who("decode_ragged", c.pool), c.pool, q->dtype, q->shape[3], c.flags, false, c.cu_g != nullptr)))
         return st;
     const bool chunk = (c.flags & SFA_FLAG_RAGGED_CHUNK128) != 0;
     if (chunk && (c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) ||

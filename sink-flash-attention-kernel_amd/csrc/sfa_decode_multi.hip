@@ -6,7 +6,7 @@
 // (-window_len = oldest, -1 = newest); chunk token u has c = u.  Query t sees c in [t - Wc + 1, t].  Softmax is order-free,
 // so the ring is walked in PHYSICAL slot order (contiguous rows); c is only needed for the mask.
 //
-// MFMA path (bf16 / f16, head dims 64 / 80 / 96 / 128): the G = H_q / H_kv query heads and the n chunk queries of one
+// MFMA path (bf16 / f16, head dims 64 / 80 / 96 / 128; packed calls also 256, see multi_split_mfma_d256_kernel): the G = H_q / H_kv query heads and the n chunk queries of one
 // KV head are R = G * n rows, ordered rho = t * G + g, cut into 32-row blocks (a block covers ceil(32 / G) consecutive
 // queries, so its mask band is narrow).  A workgroup = (batch, KV head, key split, row block), 4 waves; the split's
 // 32-key tiles are dealt round-robin to the waves, each wave streams its tiles through its own LDS slot (no barriers in
@@ -1460,6 +1460,340 @@ __global__ __launch_bounds__(kWaves * 64) void multi_chunk_mfma_kernel(MultiArgs
         }
 }
 
+// ---- head dim 256 (packed calls).  multi_split_mfma_kernel gives every wave a K tile, a V tile and
+// all D output columns of its own; at D = 256 that is 128 KB of LDS and more than 256 registers per wave, one wave per
+// SIMD in a kernel that lives on loads in flight.  Here the four waves of a workgroup (still one 32-row block x KV head
+// x split) form two PAIRS and a pair owns a tile: pair p takes tiles tbeg + p, tbeg + p + 2, ... of the split.
+//   * loads: wave e of the pair loads keys [16 e, 16 e + 16) of the tile, K and V - 8 + 8 sixteen-byte pieces per lane -
+//     into ONE LDS image per pair (16 KB of K, 16 KB of V: 64 KB per workgroup);
+//   * K Q^T: both waves compute the whole S^T (16 k-steps), so they hold bit-identical m, l, alpha and P and exchange
+//     nothing but the tile.  The block's Q lies once in LDS (16 KB more: 80 KB per workgroup, still two per CU);
+//   * P V: wave e owns output columns [128 e, 128 e + 128), four column blocks = 64 accumulator registers, and reads that
+//     half of every V row;
+//   * a wave reads rows its partner wrote, so the walk goes in rounds of two tiles (one per pair) with two workgroup
+//     barriers per round: behind the last LDS read of the round and behind the writes of the next.  A round without a
+//     live tile is skipped; the decision is a function of (round, workgroup) - the four waves share their 32 rows - so
+//     every wave reaches the same barriers;
+//   * LDS rows are 512 bytes: K chunk ch of key k lies at chunk ch ^ (k & 31) (the 32 keys a b128 read touches at one
+//     logical chunk lie in 32 different chunks), V chunk ch at ch ^ ((k & 3) << 2), the transposed-read swizzle of
+//     the 256-byte rows, which depends on the address modulo 256 only;
+//   * merge: the two pairs fold (m, l, O) in pair order through the tile area, each wave its own 128 columns.
+// Plan, tile classes, masks, tree prologue, softmax, FP8 conversion, page lookup and the partials' format and addresses
+// are multi_split_mfma_kernel's, restated so that its instances keep their code.  Always (Dyn, Slots, Ragged), no groups.
+constexpr int kPairs = 2;
+
+template <typename T, bool Tree, bool KV8, bool Paged, typename... KA>
+// waves_per_eu: two waves per SIMD (256 registers) for every instance but the four (Tree, KV8) ones, which miss that
+// budget by two registers and would spill to scratch: they take one wave per SIMD instead
+__global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu((Tree && KV8) ? 1 : 2, (Tree && KV8) ? 1 : 2)))
+void multi_split_mfma_d256_kernel(MultiArgs a, RaggedArgs rg, KA... ka) {
+    static_assert(tail_is<false, KV8, Paged, KA...>, "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); both: (..., Kv8Args, PageArgs)");
+    [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ka...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ka...);
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int D = 256;
+    constexpr int DK = D / 16;              // k-steps of the K Q^T contraction
+    constexpr int DVW = D / 64;             // 32-wide output column blocks of ONE wave: half of the row
+    constexpr int CPR = D / 8;              // 16-byte chunks per row
+    constexpr int ROWB = 2 * D;             // LDS row: 512 bytes
+    constexpr int TILE_BYTES = kTile * ROWB;
+    constexpr int NLD = kTile / 2 * CPR / 64;   // chunks per lane and tile: half of the tile's rows
+    constexpr int DP = D + 1;               // merge rows: padded against bank conflicts
+    static_assert(2 * kPairs * 32 * 4 + 32 * DP * 4 <= kPairs * 2 * TILE_BYTES, "merge area must fit the tile area");
+    __shared__ __attribute__((aligned(16))) char smem[kPairs * 2 * TILE_BYTES + TILE_BYTES];     // the images, then Q
+
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int split = (wid / a.nrb) % a.Sw;      // decomposition over the LAUNCHED splits
+    const int hk = wid / a.nrb / a.Sw;
+    const int2 be = rg.blk[wid % a.nrb];
+    const int seq = __builtin_amdgcn_readfirstlane(be.x);
+    if (seq < 0) return;               // surplus of the row-block bound (whole workgroup)
+    const int rb = __builtin_amdgcn_readfirstlane(be.y);
+    const int c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (c < 0) return;                 // inactive sequence: the reduce writes its zeros
+    const RaggedSeq sq = ragged_seq(rg, seq);
+    const int prow = __builtin_amdgcn_readfirstlane(sq.c0);
+    const int rn = __builtin_amdgcn_readfirstlane(sq.n);
+    const int rR = a.G * rn;
+    const Fill f = get_fill<true, true>(a, c, rn, rg.admit);
+    if (split >= f.S) return;          // surplus of the full-cache grid at this fill level (whole workgroup)
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pair = wave >> 1, e = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int rho = 32 * rb + r;
+    const bool row_live = rho < rR;
+    const int tq = row_live ? rho / a.G : 0;            // the lane's query index (dead rows: any, never stored)
+    int tmin = (32 * rb) / a.G;
+    int tmax = ((32 * rb + 31 < rR - 1) ? 32 * rb + 31 : rR - 1) / a.G;
+    // tree: the lane's row is node tq at depth td; [tmin, tmax] becomes the block's depth range over its live rows
+    int td = tq;
+    uint64_t tvis = 0, vor = 0;
+    [[maybe_unused]] bool is_tree = false;
+    if constexpr (Tree) is_tree = __builtin_amdgcn_readfirstlane((int)ragged_is_tree(a, rg, c, rn)) != 0;
+    if (Tree && is_tree) {
+        const TreeNode me = tree_node(rn, a.parent + prow, a.wc, lane);
+        // every lane runs the cross-lane reads (a source lane masked off by a branch would read as 0), then selects
+        td = __shfl(me.depth, tq);
+        const uint64_t v = shfl64(me.vis, tq);
+        tvis = row_live ? v : 0;
+        int lo = row_live ? td : INT_MAX, hi = row_live ? td : -1;
+        vor = tvis;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            lo = min(lo, __shfl_xor(lo, s));
+            hi = max(hi, __shfl_xor(hi, s));
+            vor |= shfl64(vor, lane ^ s);
+        }
+        tmin = __builtin_amdgcn_readfirstlane(lo);   // wave-uniform: keep the tile classification scalar
+        tmax = __builtin_amdgcn_readfirstlane(hi);
+        vor = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(vor >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)vor);
+    }
+
+    // ---- Q: the B operand of X^T = K Q^T.  The four waves share their 32 rows, so the block's Q lies ONCE in LDS (16 KB
+    // behind the tile area, rows and swizzle as a K tile; dead rows are zeros) and a k-step reads its fragment next to
+    // the K fragment: 64 registers per wave that the two-waves-per-SIMD budget does not have
+    char* ql = smem + kPairs * 2 * TILE_BYTES;
+#pragma unroll
+    for (int j = 0; j < kTile * CPR / (kWaves * 64); ++j) {
+        const int x = tid + kWaves * 64 * j, row = x / CPR, ch = x % CPR;
+        const int qrho = 32 * rb + row;
+        const bool live = qrho < rR;
+        const int head = hk * a.G + (live ? qrho % a.G : 0);
+        const char* qp = a.q.ptr + ((int64_t)head * a.q.sh + (int64_t)(prow + (live ? qrho / a.G : 0)) * a.q.sn) * 2;
+        u32x4 raw = *reinterpret_cast<const u32x4*>(qp + ch * 16);
+        if (!live) raw = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(ql + row * ROWB + ((ch ^ row) << 4)) = raw;
+    }
+
+    // the pair's image; this wave loads and writes keys [16 e, 16 e + 16) of it: chunk x = lane + 64 j of the half is
+    // key 16 e + x / 32, chunk x mod 32 (a wave-instruction reads two whole rows)
+    char* kl = smem + pair * 2 * TILE_BYTES;
+    char* vl = kl + TILE_BYTES;
+    const int lkey = 16 * e + (lane >> 5), lch = lane & 31;   // piece j: key lkey + 2 j, chunk lch
+    u32x4 kst[NLD], vst[NLD];
+    [[maybe_unused]] float ksc = 1.f, vsc = 1.f;
+    [[maybe_unused]] bool st8 = false;
+    if constexpr (KV8) ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
+    auto issue_loads = [&](const TileInfo& ti) {
+        if constexpr (KV8) {
+            st8 = ti.seg != 2;
+            if (st8) {
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    const int key = lkey + 2 * j;
+                    const int row = key < ti.count ? key : ti.count - 1;
+                    const uint2 k8 = *reinterpret_cast<const uint2*>(ti.k + row * ti.ksn + lch * 8);
+                    const uint2 v8 = *reinterpret_cast<const uint2*>(ti.v + row * ti.vsn + lch * 8);
+                    kst[j][0] = k8.x, kst[j][1] = k8.y, vst[j][0] = v8.x, vst[j][1] = v8.y;
+                }
+                return;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int key = lkey + 2 * j;
+            const int row = key < ti.count ? key : ti.count - 1;   // rows past the segment: a valid row, masked later
+            kst[j] = *reinterpret_cast<const u32x4*>(ti.k + row * ti.ksn + lch * 16);
+            vst[j] = *reinterpret_cast<const u32x4*>(ti.v + row * ti.vsn + lch * 16);
+        }
+    };
+    auto write_lds = [&]() {
+        if constexpr (KV8) {
+            if (st8) {                 // the conversion: between the global load and the LDS store
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    kst[j] = kv8_read<T>(kst[j][0], kst[j][1], ksc);
+                    vst[j] = kv8_read<T>(vst[j][0], vst[j][1], vsc);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int key = lkey + 2 * j;
+            *reinterpret_cast<u32x4*>(kl + key * ROWB + ((lch ^ (key & 31)) << 4)) = kst[j];
+            *reinterpret_cast<u32x4*>(vl + key * ROWB + ((lch ^ ((key & 3) << 2)) << 4)) = vst[j];
+        }
+    };
+
+    // per-lane LDS read addressing: K row r, chunk (2 ks + h) ^ r; V as multi_split_mfma_kernel, the wave's columns
+    const int k_rowoff = r * ROWB;
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    const int vsw_l = q4 << 2;
+    const int v_rowoff = (4 * h + q4) * ROWB + (p4 & 1) * 8;
+    const int v_chunk_lo = 16 * e + 2 * g1 + (p4 >> 1);
+
+    float m = -INFINITY, l = 0.f;   // log2 domain; l: this half-wave's partial sum
+    f32x16 o[DVW];
+#pragma unroll
+    for (int db = 0; db < DVW; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+    const int es = 2;
+
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
+    const int nround = (tend - tbeg + kPairs - 1) / kPairs;
+    auto tile_cls = [&](int i, TileInfo& ti) {
+        if (i >= tend) return 0;
+        ti = tile_info<true, KV8, Paged>(a, f, i, 0, c, hk, es, rn, prow, pg.shift);
+        if (Tree && !is_tree) return tile_class(a, ti, tmin, tmax, f.nsk);
+        return tile_class_t<Tree>(a, ti, tmin, tmax, vor, f.nsk);
+    };
+    // the first round from j on with a live tile (nround: none), the pair's tile of it and its class (0: none or dead).
+    // The four waves have the same rows, so both classes - and with them the rounds walked - are the workgroup's
+    auto next_round = [&](int j, TileInfo& ti, int& cls) {
+        for (; j < nround; ++j) {
+            TileInfo other;
+            cls = tile_cls(tbeg + kPairs * j + pair, ti);
+            if (cls != 0 || tile_cls(tbeg + kPairs * j + (pair ^ 1), other) != 0) break;
+        }
+        if constexpr (Paged) {
+            if (j < nround && cls != 0 && ti.seg == 1) tile_page(ti, a, pg, c, KV8 ? 1 : es);
+        }
+        return j;
+    };
+    TileInfo cur, nxt;
+    int ccls = 0, ncls = 0;
+    int j = next_round(0, cur, ccls);
+    if (j < nround && ccls != 0) {
+        issue_loads(cur);
+        write_lds();
+    }
+    __syncthreads();
+    while (j < nround) {
+        const int jn = next_round(j + 1, nxt, ncls);
+        const bool ld = jn < nround && ncls != 0;
+        if (ld) issue_loads(nxt);
+        if (ccls != 0) {
+            f32x16 s;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[i] = 0.f;
+#pragma unroll
+            for (int k0 = 0; k0 < DK; k0 += 2) {       // two k-steps of K and Q fragments at a time: 16 registers
+                frag kf[2], qf[2];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const int off = k_rowoff + (((2 * (k0 + ks) + h) ^ r) << 4);
+                    kf[ks] = *reinterpret_cast<const frag*>(kl + off);
+                    qf[ks] = *reinterpret_cast<const frag*>(ql + off);
+                }
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) s = M::run(kf[ks], qf[ks], s);
+            }
+            if (ccls == 2 && admitting(f, cur)) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                    s[i] = key_visible_admit(a, f, cur, kk, td) ? s[i] : -INFINITY;
+                }
+            } else if (Tree && ccls == 2 && !(is_tree && cur.seg == 2)) {
+                // a tile outside a tree's chunk: the ragged mask (td = the depth for a tree sequence)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                    s[i] = key_visible(a, f, cur, kk, td) ? s[i] : -INFINITY;
+                }
+            } else if (ccls == 2) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int kk = (i & 3) + 8 * (i >> 2) + 4 * h;
+                    s[i] = key_visible_t<Tree>(a, f, cur, kk, td, tvis) ? s[i] : -INFINITY;
+                }
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[i]);
+            mx = half_swap_max(mx);
+            const float m_new = fmaxf(m, mx * c2);
+            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+            float rs = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], c2, -m_safe));
+                rs += s[i];
+            }
+            l = fmaf(l, alpha, rs);
+            m = m_new;
+#pragma unroll
+            for (int db = 0; db < DVW; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
+            // O^T += V^T X^T over the wave's 128 columns: the exponentiated accumulator is the B operand
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                frag pf;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) pf[i] = (typename M::elem)s[8 * st + i];
+                const char* vrow = vl + 16 * st * ROWB + v_rowoff;
+#pragma unroll
+                for (int db = 0; db < DVW; ++db) {
+                    const int ch = (4 * db + v_chunk_lo) ^ vsw_l;
+                    const char* p1 = vrow + (ch << 4);
+                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1));
+                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1 + 8 * ROWB));
+                    s16x8 vv;
+                    vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
+                    vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
+                    o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+                }
+            }
+        }
+        if (jn >= nround) break;       // the merge's barrier stands behind the last reads
+        __syncthreads();               // every read of this round's images returned: the partner may overwrite
+        if (ld) write_lds();
+        __syncthreads();               // the next round's images are whole
+        j = jn, cur = nxt, ccls = ncls;
+    }
+
+    // ---- merge the two pairs' (m, l, O) in pair order through LDS; the waves of a pair hold the same (m, l)
+    const float lw = half_swap_sum(l);
+    __syncthreads();
+    float* sm = reinterpret_cast<float*>(smem);      // [pair][32]
+    float* sl = sm + kPairs * 32;                    // [pair][32]
+    float* so = sl + kPairs * 32;                    // [32][DP]
+    if (h == 0 && e == 0) {
+        sm[pair * 32 + r] = m;
+        sl[pair * 32 + r] = lw;
+    }
+    __syncthreads();
+    const float mstar = fmaxf(sm[r], sm[32 + r]);
+    const float wgt = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mstar);
+#pragma unroll
+    for (int p = 0; p < kPairs; ++p) {
+        if (pair == p) {
+#pragma unroll
+            for (int db = 0; db < DVW; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    float* ptr = so + r * DP + 128 * e + 32 * db + 8 * (i >> 2) + 4 * h + (i & 3);
+                    *ptr = (p == 0 ? 0.f : *ptr) + o[db][i] * wgt;
+                }
+        }
+        __syncthreads();
+    }
+    // one partial per row and split: [rows][Sw] of m and l, [rows][Sw][D] of O, at multi_split_mfma_kernel's addresses
+    const int64_t row0 = ((int64_t)hk * rg.T + prow) * a.G + 32 * rb;
+    const int nrows = rR - 32 * rb < 32 ? rR - 32 * rb : 32;
+    if (tid < nrows) {
+        const float m0 = sm[tid], m1 = sm[32 + tid];
+        const float ms = fmaxf(m0, m1);
+        float lt = m0 == -INFINITY ? 0.f : sl[tid] * __builtin_amdgcn_exp2f(m0 - ms);
+        lt += m1 == -INFINITY ? 0.f : sl[32 + tid] * __builtin_amdgcn_exp2f(m1 - ms);
+        a.Mp[(row0 + tid) * a.Sw + split] = ms;
+        a.Lp[(row0 + tid) * a.Sw + split] = lt;
+    }
+    for (int x = tid; x < nrows * D; x += kWaves * 64) {
+        const int rr = x / D, d = x - rr * D;
+        a.Op[((row0 + rr) * a.Sw + split) * D + d] = so[rr * DP + d];
+    }
+}
+
 // a packed (ragged) partial row: rowid = (hk * T + packed row) * G + g.  Finds the row's sequence in the table: the
 // callers go on as for B = 1 with rho = the row within the sequence, n = its length and c0 = its first packed row.
 // False: the row has no work (padding, an empty or inactive sequence); rho = the query head within the group and tp =
@@ -2325,6 +2659,9 @@ int64_t max_splits(int64_t B, int64_t Hkv, int64_t nrb, int64_t Nkv) {
 }
 
 bool mfma_head_dim(int D) { return D == 64 || D == 80 || D == 96 || D == 128; }
+// the packed calls (RaggedArgs) have one more: the pair kernel of head dim 256.  No grouped and no chunk instance there,
+// so the two workspace sizes that mean "such an instance exists" keep asking mfma_head_dim
+bool mfma_packed_head_dim(int D) { return mfma_head_dim(D) || D == 256; }
 
 // The kernel instances that exist, one line per mode of a call: f gets the (Dyn, Tree, Slots, Ragged) of the split
 // kernels (the reduce kernel has no Tree).  A new mode is a new field of RingCall / MultiArgs plus one line here.
@@ -2435,8 +2772,21 @@ int launch_chunk(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool,
     return launch_status("decode_multi_chunk128");
 }
 
+// head dim 256 of a packed call: the pair kernel in the form of the pool, Tree on or off; the grid of launch_mfma
+template <typename T>
+int launch_mfma_d256(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, hipStream_t stream) {
+    const dim3 grid((unsigned)((int64_t)a.Hkv * a.Sw * a.nrb));
+    dispatch_pool(pool, [&](auto p, auto... tail) {
+        using P = decltype(p);
+        if (a.parent) multi_split_mfma_d256_kernel<T, true, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(a, rg, tail...);
+        else multi_split_mfma_d256_kernel<T, false, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(a, rg, tail...);
+    });
+    return split_status(a, &rg, "mfma");
+}
+
 template <typename T>
 int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, hipStream_t stream) {
+    if (a.D == 256 && rg && !grp) return launch_mfma_d256<T>(a, *rg, pool, stream);
     switch (a.D) {
         case 64: return launch_mfma<T, 64>(a, rg, pool, grp, stream);
         case 80: return launch_mfma<T, 80>(a, rg, pool, grp, stream);
@@ -2529,7 +2879,7 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
                  const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr) {
     const int dt = c.q->dtype;
-    *mfma = dt != SFA_DTYPE_F32 && mfma_head_dim(a.D) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
+    *mfma = dt != SFA_DTYPE_F32 && (rg ? mfma_packed_head_dim(a.D) : mfma_head_dim(a.D)) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
     if ((c.pool.fp8 || c.pool.pt.table) && !*mfma) {    // refused by the API before: no f32-accumulate instance reads an FP8 or a paged pool
         set_error("decode_ragged%s%s: no kernel instance for this call", c.pool.pt.table ? "_paged" : "", c.pool.fp8 ? "_fp8" : "");

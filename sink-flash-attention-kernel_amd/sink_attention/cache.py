@@ -869,8 +869,12 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         kernels read the table when they run, so an in-place update is seen by the next replay of a captured graph.
         ``reserve_pages`` before a step and ``free_pages`` at retirement keep the table; a store to an unmapped page is
         dropped and a read of one is in bounds but unspecified.  Served by the calls of an FP8 pool, at bfloat16 /
-        float16 and head dims 64 / 80 / 96 / 128; every other method raises ``TypeError``.  Sinks and state rows are not
-        paged.  The defaults (``page_size=None``) give the contiguous pool.
+        float16 and head dims 64 / 80 / 96 / 128 / 256; every other method raises ``TypeError``.  Sinks and state rows are
+        not paged.  The defaults (``page_size=None``) give the contiguous pool.
+
+        Head dim 256 (all four pool kinds; an FP8 pool likewise): ``ragged_step_dyn`` runs the pair kernel of DESIGN.md
+        3.3.16 there, with ``admit=``, ``parent=`` and ``commit_seq=``; ``groups=`` and ``chunk_kernel=True`` have no
+        instance at 256 and are refused by the library.
 
         ``kv_dtype=torch.float8_e4m3fn`` (default None: the buffers have ``dtype``): the cache buffers hold FP8 codes and
         ``dtype`` (bfloat16 / float16) only names the activations the pool is meant for.  With ``page_size`` this is the
@@ -891,7 +895,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             if dtype == torch.float8_e4m3fn:
                 raise TypeError("a paged FP8 pool is not served: init_pool takes dtype=float8_e4m3fn or page_size, not both "
                                 "(the paged FP8 pool is dtype=bfloat16 / float16, page_size=P, kv_dtype=float8_e4m3fn)")
-            if dtype not in (torch.float16, torch.bfloat16) or D not in (64, 80, 96, 128):
+            if dtype not in (torch.float16, torch.bfloat16) or D not in (64, 80, 96, 128, 256):
                 raise ValueError(f"a paged pool serves bfloat16 / float16 at head dims 64 / 80 / 96 / 128, got {dtype}, D = {D}")
             if P < 32 or P & (P - 1):
                 raise ValueError(f"page_size must be a power of two and at least 32, got {page_size}")
@@ -915,7 +919,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             raise ValueError(f"init_pool needs at least one slot, got num_slots = {num_slots}")
         if dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float8_e4m3fn):
             raise TypeError("the pool's dtype must be float32 / float16 / bfloat16 / float8_e4m3fn")
-        if dtype == torch.float8_e4m3fn and D not in (64, 80, 96, 128):
+        if dtype == torch.float8_e4m3fn and D not in (64, 80, 96, 128, 256):
             raise ValueError(f"an FP8 pool serves head dims 64 / 80 / 96 / 128, got D = {D}")
         mk = lambda n: torch.zeros(int(num_slots), H_kv, n, D, dtype=dtype, device=device)
         self.sink_k, self.sink_v = mk(self.num_sink), mk(self.num_sink)
@@ -1367,7 +1371,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                         commit: bool = True, admit: bool = False, parent=None, commit_seq=None,
-                        groups=None, chunk_kernel: bool = False) -> torch.Tensor:
+                        groups=None, chunk_kernel: bool = False, force_generic: bool = False) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -1414,7 +1418,13 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         is computed by workgroups of 128 rows whose waves share every K/V tile they load; its output is that of the
         default call within its tolerance and does not depend on its place in the pack.  Every other sequence, the pool
         and the state rows are bitwise those of the default call.  bf16 / fp16 at head dims 64 / 80 / 96 / 128, every pool
-        kind; ``groups`` together with ``chunk_kernel`` is refused."""
+        kind; ``groups`` together with ``chunk_kernel`` is refused.
+
+        Head dim 256 (bf16 / fp16, every pool kind): the step runs the pair kernel of DESIGN.md 3.3.16, with ``admit``,
+        ``parent`` and ``commit_seq``; ``groups`` and ``chunk_kernel`` have no instance there and are refused by the
+        library.  ``force_generic=True`` (``SFA_FLAG_FORCE_GENERIC``): the exact-f32 split kernel at any head dim, on a
+        contiguous 16-bit pool only (no such kernel reads an FP8 or a paged pool); pool and state rows end bitwise the
+        same either way."""
         from . import _native as N
         dev_state = self._require_pool("ragged_step_dyn")
         if chunk_kernel and groups is not None:
@@ -1478,7 +1488,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
                                           cu.data_ptr(), n_seq, *grp, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
                                           st["scale"], (N.FLAG_RAGGED_ADMIT if admit else 0) |
-                                          (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0), N.stream_ptr(q.device))
+                                          (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) |
+                                          (N.FLAG_FORCE_GENERIC if force_generic else 0), N.stream_ptr(q.device))
         N.check(rc, name)
         return out
 
@@ -1710,7 +1721,7 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         """``SinkCacheLayer.init_pool`` of one layer: a pool of ``num_slots`` cache rows and its ``[S, 4]`` state.  With
         ``page_size`` the layers' pools are paged and share ONE table tensor (``cache.page_table``: that of the first
         paged layer, or the given one) and one allocator, so one mapping serves every layer: the layers must agree in
-        ``num_slots``, ``page_size`` and ``num_pages``."""
+        ``num_slots``, ``page_size`` and ``num_pages``.  Paged and FP8 pools take head dims 64 / 80 / 96 / 128 / 256."""
         layer = self._layer(layer_idx)
         if page_size is None:
             return layer.init_pool(num_slots, H_kv, D, dtype, device, kv_dtype=kv_dtype)
@@ -1749,14 +1760,16 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
                         commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None,
-                        chunk_kernel: bool = False):
+                        chunk_kernel: bool = False, force_generic: bool = False):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
         draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
-        (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel."""
+        (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel; ``force_generic``: the exact-f32
+        kernel (contiguous 16-bit pools).  Head dim 256 is served on every pool kind, without ``groups`` / ``chunk_kernel``."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
                                                       commit=commit, admit=admit, parent=parent, commit_seq=commit_seq,
-                                                      groups=groups, chunk_kernel=chunk_kernel)
+                                                      groups=groups, chunk_kernel=chunk_kernel,
+                                                      force_generic=force_generic)
 
     def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
         """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""

@@ -39,6 +39,11 @@ Variants per (W, step), alternating in one process:
     (one chunk of 2048 tokens admitted on a fresh slot; commit off, so that the slot stays fresh).  Variants ragged (the
     call without the keyword) and ragged_chunk (chunk_kernel=True) on one pool and one pack, alternating in one process.
     Prints ms per step, the spread, the ratio and the largest difference between the two outputs.
+--d256: head dim 256 instead (wall mode): H_q=64, H_kv=8 (G = 8), D = 256, bf16, Wc = 4096 with every
+    ring full, packs dec8 (8 decode rows) and dec8_pre512 (8 decode rows + one chunk of 512 tokens), committing.  Variants
+    on pools of the same content, alternating in one process: mfma (the pair kernel, contiguous bf16 pool), f32 (the same
+    call with force_generic=True: the exact-f32 split kernel, the only path before), fp8, paged and paged_fp8 (P = 64,
+    shuffled table).  Prints ms per step, the spread and each time over f32.
 --pkg DIR: import sink_attention from DIR/sink-flash-attention-kernel_amd (a checkout of another commit with its own
     built library), to time two commits' libraries with one tool.
 --mode wall (default): device time of each variant between two events around --calls calls, median of --rounds rounds.
@@ -47,7 +52,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --chunk | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
+       [--admit | --tree | --chunk | --d256 | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -426,6 +431,53 @@ def chunk_kernel(args):
                       f"  ragged_chunk / ragged {med['ragged_chunk'] / med['ragged']:.3f}  max |o diff| {diff:.2e}", flush=True)
 
 
+D256_PACKS = {"dec8": [1] * 8, "dec8_pre512": [1] * 8 + [512]}
+
+
+def d256(args):
+    """--d256: the packed step at head dim 256 on the four pool kinds and under SFA_FLAG_FORCE_GENERIC, alternating"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt, d, P, fp8 = "cuda", torch.bfloat16, 256, 64, torch.float8_e4m3fn
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nH_q={HQ} H_kv={HKV} D={d} num_sink={NS} s_aux bf16, rings full; device ms per "
+          f"committing step, median of {args.rounds} rounds of {args.calls} calls (events) after {WARM} warm-up calls, variants "
+          f"alternating", flush=True)
+    for W in Ws:
+        for step, lengths in D256_PACKS.items():
+            torch.manual_seed(0)
+            n_seq, T, pre = len(lengths), sum(lengths), NS + W + 37        # full ring, wrapped
+            forms = {"mfma": {}, "fp8": dict(kv_dtype=fp8), "paged": dict(page_size=P), "paged_fp8": dict(page_size=P, kv_dtype=fp8)}
+            k = torch.randn(1, HKV, n_seq * pre, d, device=dev, dtype=dt)
+            v = torch.randn_like(k)
+            pools = {}
+            for name, kw in forms.items():
+                p = pools[name] = SinkCacheLayer(NS, W)
+                p.init_pool(n_seq, HKV, d, dt, dev, **kw)
+                if "page_size" in kw:
+                    order = torch.randperm(n_seq * (W // P), generator=torch.Generator().manual_seed(P))
+                    p.page_table.copy_(order.reshape(n_seq, W // P).to(torch.int32))
+                p.prefill_slots(k, v, [pre * i for i in range(n_seq + 1)], list(range(n_seq)))
+            del k, v
+            pools["f32"] = pools["mfma"]
+            q = torch.randn(1, HQ, T, d, device=dev, dtype=dt)
+            kn, vn = (torch.randn(1, HKV, T, d, device=dev, dtype=dt) for _ in range(2))
+            sa, o = torch.randn(HQ, device=dev) * 0.5, torch.empty_like(q)
+            cu = torch.tensor([sum(lengths[:i]) for i in range(n_seq + 1)], dtype=torch.int32, device=dev)
+            slots = torch.arange(n_seq, dtype=torch.int32, device=dev)
+            names = ["mfma", "f32", "fp8", "paged", "paged_fp8"]
+            paths = {}
+            def call(n):
+                pools[n].ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=o, commit=True, force_generic=n == "f32")
+                paths[n] = _native.lib().sfa_last_path().decode()
+            res = _alternate(torch, args, {n: (lambda n=n: call(n)) for n in names}, names)
+            med = {n: sorted(x)[len(x) // 2] for n, x in res.items()}
+            print(f"  W={W:5d} {step:12s} T={T:4d}", flush=True)
+            for n in names:
+                print(f"      {n:10s} {med[n]:8.4f} ms (min {min(res[n]):.4f} max {max(res[n]):.4f})  / f32 {med[n] / med['f32']:.3f}  "
+                      f"[{paths[n]}]", flush=True)
+
+
 def kernels(args):
     torch, names, have = _setup(args)
     dev, dt = "cuda", torch.bfloat16
@@ -499,12 +551,15 @@ def main():
     ap.add_argument("--pool-dtypes", default=None, help="bf16,fp8: the packed step on pools of these formats (wall mode)")
     ap.add_argument("--page-size", default=None, help="64,256: the packed step on a contiguous and on paged pools (wall mode)")
     ap.add_argument("--chunk", action="store_true", help="the 128-row chunk kernel (wall mode): variants ragged and ragged_chunk")
+    ap.add_argument("--d256", action="store_true", help="head dim 256 (wall mode): the pair kernel, the f32 kernel and the pool kinds")
     ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
     if args.summarize:
         summarize(args)
     elif args.chunk:
         chunk_kernel(args)
+    elif args.d256:
+        d256(args)
     elif args.page_size and args.pool_dtypes:
         paged_dtypes(args)
     elif args.page_size:
