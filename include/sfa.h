@@ -110,6 +110,27 @@ extern "C" {
  * 64 / 80 / 96 / 128, SFA_FLAG_FORCE_GENERIC).  sfa_last_path(): "_chunk128" directly behind "_ragged".  Other entry
  * points ignore the bit. */
 #define SFA_FLAG_RAGGED_CHUNK128 0x80u
+/* The packed ragged step: serve single-token rows by the decode-row kernel.  Sequence i of the pack is a DECODE sequence
+ * iff n_i == 1 - decided on the device from cu_q alone (a one-node draft tree is a chain; a fresh slot admitted with one
+ * token is one too).  A decode sequence is computed by workgroups of (sequence, KV head, split) whose K/V tiles go from
+ * global memory to LDS by direct-to-LDS loads (16-bit pools), under a split plan of its OWN:
+ * multi_plan(sink_len, window_len, 1, want_splits(1, H_kv, n_seq)), a function of its state row and of (n_seq, H_kv), not
+ * of T or of the rest of the pack.  Every other sequence runs the code, plan and grid of the call without the flag.
+ * May be combined with SFA_FLAG_RAGGED_CHUNK128 and SFA_FLAG_RAGGED_ADMIT.  Three contracts:
+ *   1. the o rows of a decode sequence meet the tolerance of the call without the flag against an fp64 reference (FP8
+ *      pools: against the reference over the dequantised codes);
+ *   2. the rows of every other sequence are bitwise those of the call without the flag (with SFA_FLAG_RAGGED_CHUNK128:
+ *      those of the call with that flag alone), and with commit the pool and the state rows are bitwise what the call
+ *      without the flag leaves (every pool kind); rows of inactive or empty sequences and rows behind cu_q[n_seq] are zeros;
+ *   3. the rows of a decode sequence are bitwise the same, at the same (n_seq, H_kv), alone in the pack (all other slots
+ *      -1), permuted or repeated, beside a chunk or beside nothing, and replayed from a captured graph (every launch always
+ *      happens: a captured call replays at any mix).
+ * Honoured by sfa_decode_ring_ragged{,_tree,_fp8,_paged,_paged_fp8}_slots, which then need
+ * sfa_decode_ragged_step_workspace_bytes(..., flags) of workspace.  SFA_ERR_UNSUPPORTED, with a message that names the
+ * flag, from the two _group_ entry points and where no instance serves the call (fp32 activations, head dims other than
+ * 64 / 80 / 96 / 128, SFA_FLAG_FORCE_GENERIC, H_q / H_kv > 32, K/V row strides of 2^25 elements or more).
+ * sfa_last_path(): "_dec1" behind "_ragged" (and behind "_chunk128").  Other entry points ignore the bit. */
+#define SFA_FLAG_RAGGED_DECODE1 0x100u
 
 /* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
  * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.
@@ -571,6 +592,13 @@ size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv,
  * head dims other than 64 / 80 / 96 / 128 (and wherever the size above is 0).  No GPU needed. */
 size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                                int64_t D, int dtype);
+/* the workspace of a packed call by its flags (SFA_FLAG_RAGGED_CHUNK128 and SFA_FLAG_RAGGED_DECODE1 are read, other bits
+ * ignored): the ungrouped size, then the table of 128-row blocks if the chunk flag is set, then with the decode flag the
+ * decode partials: H_q n_seq Sdw entries of m and of l and H_q n_seq Sdw D of O (floats, each area rounded up to 256
+ * bytes), Sdw = the largest split count a single-token row plans over Nkv_cache + 1 keys at (n_seq, H_kv).  0 where a
+ * flag is refused for the shape (as above; for the decode flag also H_q / H_kv > 32).  No GPU needed. */
+size_t sfa_decode_ragged_step_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                              int64_t D, int dtype, unsigned flags);
 
 /* Head dim 256 (bf16 / f16): the packed calls - this one and its _tree, _fp8, _paged and _paged_fp8 forms - run an MFMA
  * split kernel of their own there (wave pairs: a pair shares one K/V tile in LDS, each wave owns half of the output

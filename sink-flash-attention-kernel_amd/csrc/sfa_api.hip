@@ -637,7 +637,18 @@ int ring_ragged(const RingCall& c) {
                   (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
         return SFA_ERR_UNSUPPORTED;
     }
-    const size_t need = chunk ? decode_ragged_chunk_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
+    const bool dec = (c.flags & SFA_FLAG_RAGGED_DECODE1) != 0;
+    if (dec && (c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) || q->shape[1] > 32 * c.k_new->shape[1] ||
+                decode_ragged_flags_workspace(1, 1, 1, 1, 1, q->shape[3], q->dtype, SFA_FLAG_RAGGED_DECODE1) == 0)) {
+        set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 serves bf16 / f16 at head dims 64 / 80 / 96 / 128 and H_q / H_kv <= 32 "
+                  "without fork groups (got dtype %d, head dim %lld, H_q %lld, H_kv %lld%s%s)", q->dtype, (long long)q->shape[3],
+                  (long long)q->shape[1], (long long)c.k_new->shape[1], c.cu_g ? ", groups" : "",
+                  (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
+    const size_t need = dec ? decode_ragged_flags_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
+                                                            c.sink_len + c.window_len, q->shape[3], q->dtype, c.flags)
+                        : chunk ? decode_ragged_chunk_workspace(c.n_seq, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                               c.sink_len + c.window_len, q->shape[3], q->dtype)
                         : c.cu_g ? decode_ragged_group_workspace(c.n_seq, c.n_grp, q->shape[1], c.k_new->shape[1], q->shape[2],
                                                                c.sink_len + c.window_len, q->shape[3], q->dtype)
@@ -1044,6 +1055,11 @@ size_t sfa_decode_ragged_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv,
 size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                                int64_t D, int dtype) {
     return decode_ragged_chunk_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+}
+
+size_t sfa_decode_ragged_step_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
+                                              int64_t D, int dtype, unsigned flags) {
+    return decode_ragged_flags_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype, flags);
 }
 
 int sfa_decode_ring_ragged_slots(SFA_ATTEND_PARAMS, int commit, int32_t* state, const int32_t* slots,

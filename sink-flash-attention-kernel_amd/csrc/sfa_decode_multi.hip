@@ -213,6 +213,17 @@ struct GroupArgs {
     int nsh;                     // shared-phase block ids of the split launch: Hkv * Sgw * ngrb rounded up to 8
 };
 
+// ---- decode rows (SFA_FLAG_RAGGED_DECODE1).  A sequence of ONE new token is computed by
+// multi_decode1_mfma_kernel under a plan of its own - multi_plan(sink_len, window_len, 1, want_d) with
+// want_d = want_splits(1, Hkv, n_seq): a function of its state row and of (n_seq, Hkv), not of T or of its neighbours -
+// into a second partial area indexed by SEQUENCE: ((hk * n_seq + i) * G + g) * Sdw + split.  The last trailing argument of
+// the reduce instance of such a call (never together with GroupArgs); like GroupArgs it is read off the pack.
+struct Dec1Args {
+    float *Md, *Ld, *Od;         // [Hkv * n_seq * G][Sdw], the same, [...][Sdw][D]
+    int Sdw;                     // launched decode splits: max_splits(1, Hkv, n_seq, ns + Wc + 1)
+    int want_d;
+};
+
 // The optional trailing arguments of a kernel (`RA...` behind MultiArgs, `KA...` behind a storing kernel's own): of
 // RaggedArgs, Kv8Args, PageArgs and GroupArgs, in that order, an instance takes the ones its flags name and no other - its
 // signature, argument block and code stay those of a kernel without the others.  arg_of<W>(pack...) is the member of
@@ -227,11 +238,13 @@ __device__ __forceinline__ decltype(auto) arg_of(const A0& a0, const A&... rest)
 template <typename W, typename... A>
 constexpr bool has_arg = (std::is_same_v<A, W> || ...);
 // the guard of every kernel with such a pack: exactly the arguments that the flags name (their order is dispatch_pool's);
-// GroupArgs may follow on a (Ragged, Paged) instance
+// GroupArgs may follow on a (Ragged, Paged) instance, Dec1Args on a Ragged one without GroupArgs
 template <bool Ragged, bool KV8, bool Paged, typename... A>
-constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) + (has_arg<GroupArgs, A...> ? 1 : 0) &&
+constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) + (has_arg<GroupArgs, A...> ? 1 : 0) +
+                                             (has_arg<Dec1Args, A...> ? 1 : 0) &&
                          has_arg<RaggedArgs, A...> == Ragged && has_arg<Kv8Args, A...> == KV8 &&
-                         has_arg<PageArgs, A...> == Paged && !(has_arg<GroupArgs, A...> && !(Ragged && Paged));
+                         has_arg<PageArgs, A...> == Paged && !(has_arg<GroupArgs, A...> && !(Ragged && Paged)) &&
+                         !(has_arg<Dec1Args, A...> && (!Ragged || has_arg<GroupArgs, A...>));
 
 // the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
 // of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
@@ -1794,6 +1807,411 @@ void multi_split_mfma_d256_kernel(MultiArgs a, RaggedArgs rg, KA... ka) {
     }
 }
 
+// ---- decode-row kernel (SFA_FLAG_RAGGED_DECODE1).  multi_split_mfma_kernel holds the tile in flight
+// in staging registers (2 NLD u32x4) and so runs one wave per SIMD with one tile under way.  Here a workgroup is (decode
+// sequence, KV head, split of the sequence's OWN plan); the G <= 32 rows of the group are one 32-row MFMA block (padding
+// rows cost MFMA work, not bytes) and the tiles of the split are dealt round-robin to the four waves as there.  16-bit
+// pools: K and V tiles go global -> LDS by direct-to-LDS 16-byte buffer loads, no register in between.  The DMA fills LDS
+// linearly (lane L of instruction j writes bytes [1024 j + 16 L, +16) of the region), so the swizzle of the LDS image is
+// applied on the SOURCE side: the lane fetches the chunk that belongs at its position (positions of the 256-byte rows of
+// D = 80 / 96 that hold no chunk fetch out of range and read zeros, without traffic).  A tile has a buffer descriptor of
+// its own: 64-bit base = the tile's first row (far offsets and the page of tile_page included), range = its count rows,
+// so that rows past the count are clamped as everywhere and no lane can address past the tile.  Each wave owns a ring of
+// R slots (R = 4 at D = 64, 2 above: 128 KB) and keeps R - 1 tiles in flight; a tile is consumed behind a COUNTED vmcnt
+// wait (the loads of the younger live tiles stay outstanding).  Dead tiles issue nothing and count as nothing.
+// FP8 pools: codes cannot be converted by the DMA, so these instances keep the register path of the kernel above (8-byte
+// loads, kv8_read between load and LDS store, one tile in flight, one slot); they gain the plan and the grid, not the
+// data path.
+// Body (K Q^T, mask, online softmax, V^T X^T by ds_read_tr16_b64), merge in wave order and partial layout are those of
+// the kernel above for a block of G rows at query index 0, restated.  Deterministic, no atomics.
+template <typename T, int D, bool KV8, bool Paged, typename... KA>
+__global__ __launch_bounds__(kWaves * 64) void multi_decode1_mfma_kernel(MultiArgs a, RaggedArgs rg, KA... ka) {
+    static_assert(tail_is<false, KV8, Paged, KA...>, "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); both: (..., Kv8Args, PageArgs)");
+    [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ka...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ka...);
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int DK = D / 16;
+    constexpr int DVB = (D + 31) / 32;
+    constexpr int CPR = D / 8;
+    constexpr int ROWB = D <= 64 ? 128 : 256;
+    constexpr int PPR = ROWB / 16;                 // 16-byte positions per LDS row
+    constexpr int TILE_BYTES = kTile * ROWB;
+    constexpr int NLD = kTile * CPR / 64;
+    constexpr int NDMA = TILE_BYTES / 1024;        // DMA instructions per tile and tensor: 64 lanes x 16 bytes each
+    constexpr int LPT = 2 * NDMA;                  // loads of one tile (K and V)
+    constexpr int R = KV8 ? 1 : (D <= 64 ? 4 : 2);
+    constexpr int SLOT = 2 * TILE_BYTES;
+    constexpr int DP = D + 1;
+    static_assert((R - 1) * LPT <= 63, "the counted wait must fit vmcnt");
+    static_assert(kWaves * R * SLOT <= 128 * 1024, "the rings must fit 128 KB");
+    static_assert(2 * kWaves * 32 * 4 + 32 * DP * 4 <= kWaves * R * SLOT, "merge area must fit the tile area");
+    __shared__ __attribute__((aligned(1024))) char smem[kWaves * R * SLOT];
+
+    // (sequence, split, KV head); a workgroup without work leaves at once: the grid covers every sequence at every mix
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int seq = wid % rg.n_seq;
+    const int split = (wid / rg.n_seq) % a.Sw;
+    const int hk = wid / rg.n_seq / a.Sw;
+    const RaggedSeq sq = ragged_seq(rg, seq);
+    if (__builtin_amdgcn_readfirstlane(sq.n) != 1) return;     // not a decode sequence: the kernels above serve it
+    const int c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (c < 0) return;                 // inactive sequence: the reduce writes its zeros
+    const int prow = __builtin_amdgcn_readfirstlane(sq.c0);
+    const Fill f = get_fill<true, true>(a, c, 1, rg.admit);    // a.want = want_d here: the sequence's own plan
+    if (split >= f.S) return;          // surplus of the full-cache grid at this fill level
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const bool row_live = r < a.G;     // row r = query head r of the group, query index 0
+
+    // Q arrives before the first DMA is issued (the pin below): a register load that is first used behind DMAs would make
+    // the compiler drain them all there
+    frag qf[DK];
+    {
+        const int head = hk * a.G + (row_live ? r : 0);
+        const char* qp = a.q.ptr + ((int64_t)head * a.q.sh + (int64_t)prow * a.q.sn) * 2;
+        u32x4 raw[DK];
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) raw[ks] = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            asm volatile("" : "+v"(raw[ks]));
+            if (!row_live) raw[ks] = u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(frag, raw[ks]);
+        }
+    }
+
+    char* ring = smem + wave * R * SLOT;
+    const int es = 2;
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
+    const int nk = tend - tbeg > wave ? (tend - tbeg - wave + kWaves - 1) / kWaves : 0;    // this wave's tiles: tbeg + wave + 4 k
+    // tile k of the wave and its class against the one query index 0; a live ring tile of a paged pool gets its page
+    auto tile_k = [&](int k, TileInfo& ti) {
+        ti = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, 1, prow, pg.shift);
+        const int cls = tile_class(a, ti, 0, 0, f.nsk);
+        if constexpr (Paged) {
+            if (cls != 0 && ti.seg == 1) tile_page(ti, a, pg, c, KV8 ? 1 : es);
+        }
+        return cls;
+    };
+
+    const int ksw_l = ROWB == 256 ? (r & 15) : ((r >> 1) & 7);
+    const int k_rowoff = r * ROWB;
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    const int vsw_l = ROWB == 256 ? (q4 << 2) : (((q4 >> 1) & 1) << 2);
+    const int v_rowoff = (4 * h + q4) * ROWB + (p4 & 1) * 8;
+    const int v_chunk_lo = 2 * g1 + (p4 >> 1);
+
+    float m = -INFINITY, l = 0.f;   // log2 domain; l: this half-wave's partial sum
+    f32x16 o[DVB];
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+
+    // one live tile from the LDS image (kl, kl + TILE_BYTES); cur: its descriptor, read by the edge mask only
+    auto consume = [&](const TileInfo& cur, bool edge, const char* kl) {
+        const char* vl = kl + TILE_BYTES;
+        f32x16 s;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) s[x] = 0.f;
+        {
+            frag kf[DK];
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) kf[ks] = *reinterpret_cast<const frag*>(kl + k_rowoff + (((2 * ks + h) ^ ksw_l) << 4));
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) s = M::run(kf[ks], qf[ks], s);
+        }
+        if (edge) {
+            if (admitting(f, cur)) {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible_admit(a, f, cur, kk, 0) ? s[x] : -INFINITY;
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible(a, f, cur, kk, 0) ? s[x] : -INFINITY;
+                }
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) mx = fmaxf(mx, s[x]);
+        mx = half_swap_max(mx);
+        const float m_new = fmaxf(m, mx * c2);
+        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+        float rs = 0.f;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            s[x] = __builtin_amdgcn_exp2f(fmaf(s[x], c2, -m_safe));
+            rs += s[x];
+        }
+        l = fmaf(l, alpha, rs);
+        m = m_new;
+#pragma unroll
+        for (int db = 0; db < DVB; ++db)
+#pragma unroll
+            for (int x = 0; x < 16; ++x) o[db][x] *= alpha;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            frag pf;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) pf[x] = (typename M::elem)s[8 * st + x];
+            const char* vrow = vl + 16 * st * ROWB + v_rowoff;
+            // the transposing reads are written out: in front of the builtin the compiler drains vmcnt(0) while a DMA is in
+            // flight (it cannot tell the slots apart), which would wait for the prefetched tiles at every tile.  All reads
+            // of the step are issued, then each operand is pinned behind one lgkmcnt(0)
+            s16x4 lo[DVB], hi[DVB];
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                const int ch = (4 * db + v_chunk_lo) ^ vsw_l;
+                const unsigned p1 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(vrow + (ch << 4));
+                asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
+                             : "=&v"(lo[db]), "=&v"(hi[db]) : "v"(p1), "n"(8 * ROWB) : "memory");
+            }
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                s16x8 vv;
+                vv[0] = lo[db][0]; vv[1] = lo[db][1]; vv[2] = lo[db][2]; vv[3] = lo[db][3];
+                vv[4] = hi[db][0]; vv[5] = hi[db][1]; vv[6] = hi[db][2]; vv[7] = hi[db][3];
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vv)::"memory");
+                o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+            }
+        }
+    };
+
+    if constexpr (!KV8) {
+        // ---- the DMA ring.  cq: the classes of the tiles in the ring, two bits per slot k mod R
+        unsigned cq = 0;
+        // positions of a 256-byte LDS row that hold no chunk (D = 80 / 96): OR-ed onto the offset, which then lies out of
+        // range.  Per lane and instruction, loop-invariant; pinned in VGPRs (as lane masks they cost two SGPRs each and
+        // the allocator spilt them to scratch)
+        [[maybe_unused]] unsigned khole[NDMA], vhole[NDMA];
+        if constexpr (CPR < PPR) {
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int key = (64 * j + lane) / PPR, pos = (64 * j + lane) % PPR;
+                khole[j] = (pos ^ (key & 15)) < CPR ? 0u : 0xFFFFFFF0u;
+                vhole[j] = (pos ^ ((key & 3) << 2)) < CPR ? 0u : 0xFFFFFFF0u;
+                asm volatile("" : "+v"(khole[j]), "+v"(vhole[j]));
+            }
+        }
+        auto issue = [&](int k) {
+            TileInfo ti;
+            const int cls = tile_k(k, ti);
+            const int sl = k & (R - 1);
+            cq = (cq & ~(3u << (2 * sl))) | ((unsigned)cls << (2 * sl));
+            if (cls == 0) return;
+            // the tile's rows [0, count): every offset below lies inside (the launcher has bounded the row strides)
+            const unsigned ksn = (unsigned)ti.ksn, vsn = (unsigned)ti.vsn;
+            const unsigned last = (unsigned)(ti.count - 1);
+            char* kl = ring + sl * SLOT;
+            const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)ti.k, 0, (int)(last * ksn + D * 2), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int kch = pos ^ (ROWB == 256 ? (key & 15) : ((key >> 1) & 7));
+                unsigned ko = row * ksn + (unsigned)(kch * 16);
+                if constexpr (CPR < PPR) ko |= khole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(kl + 1024 * j), 16, ko, 0, 0, 0);
+            }
+            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)ti.v, 0, (int)(last * vsn + D * 2), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int vch = pos ^ (ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2));
+                unsigned vo = row * vsn + (unsigned)(vch * 16);
+                if constexpr (CPR < PPR) vo |= vhole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(kl + TILE_BYTES + 1024 * j), 16, vo, 0, 0, 0);
+            }
+        };
+#pragma unroll
+        for (int k = 0; k < R - 1; ++k)
+            if (k < nk) issue(k);
+#pragma unroll 1
+        for (int k = 0; k < nk; ++k) {
+            // slot (k - 1) mod R is free: every LDS read of tile k - 1 returned at the end of the last trip
+            if (k + R - 1 < nk) issue(k + R - 1);
+            int pend = 0;              // live tiles issued behind tile k: their loads may stay outstanding
+#pragma unroll
+            for (int d = 1; d < R; ++d)
+                if (k + d < nk && ((cq >> (2 * ((k + d) & (R - 1)))) & 3u) != 0) ++pend;
+            const int cls = (cq >> (2 * (k & (R - 1)))) & 3u;
+            if (cls == 0) continue;
+            if (pend >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 3 ? 3 : 0) * LPT) : "memory");
+            else if (pend == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 2 ? 2 : 0) * LPT) : "memory");
+            else if (pend == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 1 ? 1 : 0) * LPT) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            TileInfo cur{};
+            if (cls == 2) cur = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, 1, prow, pg.shift);
+            consume(cur, cls == 2, ring + (k & (R - 1)) * SLOT);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slot may be overwritten by the next trip's DMA
+        }
+    } else {
+        // ---- FP8 pool: the register path of multi_split_mfma_kernel, one slot, one tile in flight
+        char* kl = ring;
+        char* vl = kl + TILE_BYTES;
+        u32x4 kst[NLD], vst[NLD];
+        const float ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
+        bool st8 = false;
+        auto issue_loads = [&](const TileInfo& ti) {
+            st8 = ti.seg != 2;
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) {
+                const int ci = lane + 64 * j;
+                const int key = ci / CPR, ch = ci % CPR;
+                const int row = key < ti.count ? key : ti.count - 1;
+                if (st8) {
+                    const uint2 k8 = *reinterpret_cast<const uint2*>(ti.k + row * ti.ksn + ch * 8);
+                    const uint2 v8 = *reinterpret_cast<const uint2*>(ti.v + row * ti.vsn + ch * 8);
+                    kst[j][0] = k8.x, kst[j][1] = k8.y, vst[j][0] = v8.x, vst[j][1] = v8.y;
+                } else {
+                    kst[j] = *reinterpret_cast<const u32x4*>(ti.k + row * ti.ksn + ch * 16);
+                    vst[j] = *reinterpret_cast<const u32x4*>(ti.v + row * ti.vsn + ch * 16);
+                }
+            }
+        };
+        auto write_lds = [&]() {
+            if (st8) {                 // the conversion: between the global load and the LDS store
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    kst[j] = kv8_read<T>(kst[j][0], kst[j][1], ksc);
+                    vst[j] = kv8_read<T>(vst[j][0], vst[j][1], vsc);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) {
+                const int ci = lane + 64 * j;
+                const int key = ci / CPR, ch = ci % CPR;
+                const int ksw = ROWB == 256 ? (key & 15) : ((key >> 1) & 7);
+                const int vsw = ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2);
+                *reinterpret_cast<u32x4*>(kl + key * ROWB + ((ch ^ ksw) << 4)) = kst[j];
+                *reinterpret_cast<u32x4*>(vl + key * ROWB + ((ch ^ vsw) << 4)) = vst[j];
+            }
+        };
+        auto next_live = [&](int k, TileInfo& ti, int& cls) {
+            for (; k < nk; ++k)
+                if ((cls = tile_k(k, ti)) != 0) break;
+            return k;
+        };
+        // no descriptor lives across a tile's math (two of them cost the SGPRs that sent three instances to scratch): an
+        // edge tile builds its own again for the mask
+        TileInfo ti;
+        int ccls = 0, ncls = 0;
+        int k = next_live(0, ti, ccls);
+        if (k < nk) {
+            issue_loads(ti);
+            write_lds();
+        }
+        while (k < nk) {
+            const int kn = next_live(k + 1, ti, ncls);
+            if (kn < nk) issue_loads(ti);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this tile's LDS writes landed
+            TileInfo cur{};
+            if (ccls == 2) cur = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, 1, prow, pg.shift);
+            consume(cur, ccls == 2, kl);
+            if (kn < nk) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of this tile returned before the overwrite
+                write_lds();
+            }
+            k = kn, ccls = ncls;
+        }
+    }
+
+    // ---- merge the 4 waves' (m, l, O) in wave order through LDS (the rings are free after the barrier: every DMA of a
+    // wave was waited for by its last trip)
+    const float lw = half_swap_sum(l);
+    __syncthreads();
+    float* sm = reinterpret_cast<float*>(smem);      // [wave][32]
+    float* sl = sm + kWaves * 32;                    // [wave][32]
+    float* so = sl + kWaves * 32;                    // [32][DP]
+    if (h == 0) {
+        sm[wave * 32 + r] = m;
+        sl[wave * 32 + r] = lw;
+    }
+    __syncthreads();
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) mstar = fmaxf(mstar, sm[w * 32 + r]);
+    const float wgt = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mstar);
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int db = 0; db < DVB; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int col = 32 * db + 8 * (i >> 2) + 4 * h + (i & 3);
+                    if (col < D) {
+                        float* p = so + r * DP + col;
+                        *p = (w == 0 ? 0.f : *p) + o[db][i] * wgt;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    // one partial per (sequence, head of the group) and split, in the decode area (a.Mp / a.Lp / a.Op, stride a.Sw, here)
+    const int64_t row0 = ((int64_t)hk * rg.n_seq + seq) * a.G;
+    if (tid < a.G) {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) ms = fmaxf(ms, sm[w * 32 + tid]);
+        float lt = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const float mw = sm[w * 32 + tid];
+            lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
+        }
+        a.Mp[(row0 + tid) * a.Sw + split] = ms;
+        a.Lp[(row0 + tid) * a.Sw + split] = lt;
+    }
+    for (int e = tid; e < a.G * D; e += kWaves * 64) {
+        const int rr = e / D, d = e - rr * D;
+        a.Op[((row0 + rr) * a.Sw + split) * D + d] = so[rr * DP + d];
+    }
+}
+
+// the preparation launch of a call with SFA_FLAG_RAGGED_DECODE1, alone or with SFA_FLAG_RAGGED_CHUNK128 (nwb = 0: alone,
+// no wblk): ragged_prep_chunk_kernel's tables, except that the 32-row block of a decode sequence (n_i == 1) is surplus
+// too - the kernel above finds its sequences from cu_q itself and needs no table.
+__global__ __launch_bounds__(1024) void ragged_prep_dec1_kernel(RaggedArgs rg, int2* blk, int* rowseq, int2* wblk, int G,
+                                                                int nrb, int nwb, int tree) {
+    for (int64_t x = threadIdx.x; x < (int64_t)nrb + rg.T + nwb; x += 1024) {
+        const int kind = x < nrb ? 0 : (x < (int64_t)nrb + rg.T ? 1 : 2);     // blk, rowseq, wblk
+        const int id = (int)(kind == 0 ? x : kind == 1 ? x - nrb : x - nrb - rg.T);
+        const int unit = kind == 2 ? kChunkRows : 32;
+        int lo = 0, hi = rg.n_seq - 1;       // the last i with start(i) <= id; sequence 0 starts at 0
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const int c = ragged_seq(rg, mid).c0;
+            const int64_t start = kind == 1 ? c : (int64_t)G * c / unit + mid;
+            if (start <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        const RaggedSeq s = ragged_seq(rg, lo);
+        if (kind == 1) {
+            rowseq[id] = (id >= s.c0 && id < s.c0 + s.n) ? lo : -1;
+        } else {
+            const int64_t local = id - ((int64_t)G * s.c0 / unit + lo);
+            const bool chunk = nwb > 0 && chunk_seq(G, s.n, tree);
+            const bool hit = local >= 0 && local * unit < (int64_t)G * s.n && s.n != 1 && chunk == (kind == 2);
+            (kind == 2 ? wblk : blk)[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
+        }
+    }
+}
+
 // a packed (ragged) partial row: rowid = (hk * T + packed row) * G + g.  Finds the row's sequence in the table: the
 // callers go on as for B = 1 with rho = the row within the sequence, n = its length and c0 = its first packed row.
 // False: the row has no work (padding, an empty or inactive sequence); rho = the query head within the group and tp =
@@ -2073,10 +2491,24 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
         if (lg > 0) Sg = multi_plan(0, lg, 0, gr.want_g).S;
     }
     const Fill f = get_fill<Dyn, Ragged, Grouped>(a, c, rn, rg.admit, lg);
-    const int S = f.S, D = a.D;
+    int S = f.S;
+    const int D = a.D;
     const float* Mr = a.Mp + rowid * a.Sw;
     const float* Lr = a.Lp + rowid * a.Sw;
     const float* Or = a.Op + rowid * a.Sw * D;
+    // Dec1 (a trailing Dec1Args): the row of a decode sequence folds the S partials of the sequence's own plan from the
+    // second area; every other row folds as in the instance without it
+    if constexpr (has_arg<Dec1Args, RA...>) {
+        if (rn == 1) {
+            const Dec1Args& dd = arg_of<Dec1Args>(ra...);
+            const int seq = __builtin_amdgcn_readfirstlane(rg.rowseq[prow]);
+            const int64_t drow = ((int64_t)hk * rg.n_seq + seq) * a.G + rho;      // t = 0: rho is the head of the group
+            S = __builtin_amdgcn_readfirstlane(multi_plan(f.sink_len, f.wl, 1, dd.want_d).S);
+            Mr = dd.Md + drow * dd.Sdw;
+            Lr = dd.Ld + drow * dd.Sdw;
+            Or = dd.Od + drow * dd.Sdw * D;
+        }
+    }
     [[maybe_unused]] const float *Mgr = nullptr, *Lgr = nullptr, *Ogr = nullptr;
     if constexpr (Grouped) Mgr = gr.Mg + rowid * gr.Sgw, Lgr = gr.Lg + rowid * gr.Sgw, Ogr = gr.Og + rowid * gr.Sgw * D;
     const float sa = a.s_aux ? a.s_aux[head] * kLog2e : -INFINITY;
@@ -2772,6 +3204,31 @@ int launch_chunk(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool,
     return launch_status("decode_multi_chunk128");
 }
 
+// the decode-row kernel of a packed call with SFA_FLAG_RAGGED_DECODE1: behind the split launch, on Hkv * Sdw * n_seq
+// blocks whatever the pack holds.  Its MultiArgs are the call's with the decode plan and the decode area in the place of
+// want, Sw and the partials.
+template <typename T>
+int launch_dec1(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, const Dec1Args& dd, hipStream_t stream) {
+    MultiArgs ad = a;
+    ad.want = dd.want_d, ad.Sw = dd.Sdw, ad.Mp = dd.Md, ad.Lp = dd.Ld, ad.Op = dd.Od;
+    const dim3 grid((unsigned)((int64_t)a.Hkv * dd.Sdw * rg.n_seq));
+    auto go = [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        dispatch_pool(pool, [&](auto p, auto... tail) {
+            using P = decltype(p);
+            multi_decode1_mfma_kernel<T, D, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(ad, rg, tail...);
+        });
+    };
+    switch (a.D) {
+        case 64: go(std::integral_constant<int, 64>{}); break;
+        case 80: go(std::integral_constant<int, 80>{}); break;
+        case 96: go(std::integral_constant<int, 96>{}); break;
+        case 128: go(std::integral_constant<int, 128>{}); break;
+        default: set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 has no kernel for head dim %d", a.D); return SFA_ERR_UNSUPPORTED;
+    }
+    return launch_status("decode_multi_dec1");
+}
+
 // head dim 256 of a packed call: the pair kernel in the form of the pool, Tree on or off; the grid of launch_mfma
 template <typename T>
 int launch_mfma_d256(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, hipStream_t stream) {
@@ -2801,13 +3258,15 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool
 // pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
 int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream,
-                const ChunkTable* ck = nullptr) {
+                const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
     if constexpr (sizeof(T) == 2) {
         st = mfma ? launch_mfma_d<T>(a, rg, pool, grp, stream) : SFA_OK;
         // chunk sequences: their 32-row blocks left the split launch as surplus; the reduce folds either kernel's partials
         if (!st && mfma && ck) st = launch_chunk<T>(a, *rg, pool, *ck, stream);
+        // decode sequences: likewise, into the second partial area, which the reduce instance with Dec1Args folds
+        if (!st && mfma && dd) st = launch_dec1<T>(a, *rg, pool, *dd, stream);
     }
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
@@ -2837,7 +3296,8 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
                         return;
                     }
                 }
-                multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail...);
+                if (dd) multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail..., *dd);
+                else multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail...);
             });
         else if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
         else multi_reduce_kernel<T, M::Dyn, M::Slots><<<rgrid, 256, 0, stream>>>(a, nred);
@@ -2877,7 +3337,7 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
 int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
-                 const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr) {
+                 const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && (rg ? mfma_packed_head_dim(a.D) : mfma_head_dim(a.D)) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
@@ -2886,8 +3346,8 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
         return SFA_ERR_UNSUPPORTED;
     }
     if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, nullptr, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck);
-    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd);
+    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd);
 }
 
 }  // namespace
@@ -3017,6 +3477,37 @@ size_t decode_ragged_chunk_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int
     return base + al256((size_t)nwb * sizeof(int2));
 }
 
+namespace {
+
+// host-known geometry of the decode rows of a call with SFA_FLAG_RAGGED_DECODE1: nothing here depends on T or on cu_q
+struct Dec1Geom {
+    int64_t want, Sdw, P;            // P = Hkv * n_seq * G * Sdw sizes the decode partials
+};
+
+Dec1Geom dec1_geom(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t Nkv_cache) {
+    Dec1Geom g;
+    g.want = want_splits(1, Hkv, n_seq);
+    g.Sdw = max_splits(1, Hkv, n_seq, Nkv_cache + 1);   // bound of multi_plan(sink_len, window_len, 1, want).S over every fill
+    g.P = Hq * n_seq * g.Sdw;
+    return g;
+}
+
+}  // namespace
+
+// the workspace of a packed call by its flags: that of the ungrouped call, then wblk with SFA_FLAG_RAGGED_CHUNK128, then
+// the decode partials with SFA_FLAG_RAGGED_DECODE1.  0 where a flag of the two is refused for the shape: fp32, head dims
+// other than 64 / 80 / 96 / 128, and for the decode flag G > 32
+size_t decode_ragged_flags_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype,
+                                     unsigned flags) {
+    const bool chunk = (flags & SFA_FLAG_RAGGED_CHUNK128) != 0, dec = (flags & SFA_FLAG_RAGGED_DECODE1) != 0;
+    size_t sz = chunk ? decode_ragged_chunk_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype)
+                      : decode_ragged_workspace(n_seq, Hq, Hkv, T, Nkv_cache, D, dtype);
+    if (sz == 0 || !dec) return sz;
+    if (dtype == SFA_DTYPE_F32 || !mfma_head_dim((int)D) || Hq / Hkv > 32) return 0;
+    const Dec1Geom g = dec1_geom(n_seq, Hq, Hkv, Nkv_cache);
+    return sz + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)D * sizeof(float));
+}
+
 int decode_ragged_launch(const RingCall& c) {
     const int64_t T = c.q->shape[2];
     const RaggedGeom g = ragged_geom(c.n_seq, c.q->shape[1], c.k_new->shape[1], T, c.sink_len + c.window_len);
@@ -3044,10 +3535,36 @@ int decode_ragged_launch(const RingCall& c) {
     // ungrouped call's workspace, the preparation marks the chunk sequences in both block tables
     const bool chunk = (c.flags & SFA_FLAG_RAGGED_CHUNK128) != 0;
     ChunkTable ck{};
-    if (chunk) {
+    // SFA_FLAG_RAGGED_DECODE1 (refused by the API where no instance exists): the decode partials lie behind all that, the
+    // preparation marks the decode sequences as well
+    const bool dec = (c.flags & SFA_FLAG_RAGGED_DECODE1) != 0;
+    Dec1Args dd{};
+    if (chunk || dec) {
         int2* wblk = reinterpret_cast<int2*>(ws + decode_ragged_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, c.sink_len + c.window_len, a.D, c.q->dtype));
-        ck = ChunkTable{wblk, (int)(cdiv64(g.G * T, kChunkRows) + c.n_seq)};
-        ragged_prep_chunk_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, wblk, a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+        if (chunk) ck = ChunkTable{wblk, (int)(cdiv64(g.G * T, kChunkRows) + c.n_seq)};
+    }
+    if (dec) {
+        const int64_t Nc = c.sink_len + c.window_len;
+        const Dec1Geom dg = dec1_geom(c.n_seq, c.q->shape[1], a.Hkv, Nc);
+        char* dw = ws + decode_ragged_flags_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, Nc, a.D, c.q->dtype, c.flags & SFA_FLAG_RAGGED_CHUNK128);
+        dd.Md = reinterpret_cast<float*>(dw);
+        dd.Ld = reinterpret_cast<float*>(dw + al256((size_t)dg.P * sizeof(float)));
+        dd.Od = reinterpret_cast<float*>(dw + 2 * al256((size_t)dg.P * sizeof(float)));
+        dd.Sdw = (int)dg.Sdw, dd.want_d = (int)dg.want;
+        // the DMA addresses a tile by a 64-bit base and 32-bit offsets inside its 32 rows
+        const View* vs[] = {&a.sk, &a.sv, &a.wk, &a.wv, &a.kn, &a.vn};
+        for (const View* v : vs)
+            if (v->sn * 2 * kTile >= (1ll << 31)) {
+                set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 needs K/V row strides below 2^25 elements");
+                return SFA_ERR_UNSUPPORTED;
+            }
+        if ((int64_t)a.Hkv * dg.Sdw * c.n_seq >= (1ll << 31)) {
+            set_error("decode_ragged: grid too large");
+            return SFA_ERR_UNSUPPORTED;
+        }
+        ragged_prep_dec1_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+    } else if (chunk) {
+        ragged_prep_chunk_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
     } else {
         ragged_prep_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, a.G, a.nrb);
     }
@@ -3079,12 +3596,12 @@ int decode_ragged_launch(const RingCall& c) {
     }
     bool mfma;
     const char* dname;
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr, chunk ? &ck : nullptr))) return st;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr, chunk ? &ck : nullptr, dec ? &dd : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
     if (mfma)
-        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "", ad, cm,
-                 c.cu_g ? "_group" : "", pool_tag(c.pool));
+        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "", dec ? "_dec1" : "",
+                 ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }

@@ -27,6 +27,7 @@ FLAG_BWD_DKDV_ASM = 0x10      # dispatch override: hand-placed dK/dV kernel
 FLAG_BWD_DKDV_WS = 0x20       # dispatch override: wave-specialised compiled dK/dV kernel
 FLAG_RAGGED_ADMIT = 0x40      # sfa_decode_ring_ragged_slots: a sequence on a fresh slot (seen == 0) is admitted in the call
 FLAG_RAGGED_CHUNK128 = 0x80   # the packed step: sequences of >= 128 rows run the 128-row chunk kernel (include/sfa.h)
+FLAG_RAGGED_DECODE1 = 0x100   # the packed step: single-token sequences run the decode-row kernel (include/sfa.h)
 ABI_VERSION = 2
 
 # flags every backward of the ops passes to sfa_bwd / sfa_bwd_varlen (and to the workspace query): the overlap is ON by
@@ -205,6 +206,9 @@ def _bind(lib):
     # the packed step with FLAG_RAGGED_CHUNK128: the ungrouped query's arguments, 0 where the flag is refused
     lib.sfa_decode_ragged_chunk_workspace_bytes.restype = sz
     lib.sfa_decode_ragged_chunk_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i32]
+    # the packed step by its flags (FLAG_RAGGED_CHUNK128 | FLAG_RAGGED_DECODE1): the same arguments plus the flags
+    lib.sfa_decode_ragged_step_workspace_bytes.restype = sz
+    lib.sfa_decode_ragged_step_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, i64, i32, u32]
     lib.sfa_decode_ring_ragged_group_paged_slots.restype = i32
     lib.sfa_decode_ring_ragged_group_paged_slots.argtypes = [P, P, P, P, P, P, P, P, vp, vp, i32, vp, vp, vp, i32, vp, i32,
                                                              vp, i32, vp, sz, f32, u32, vp]

@@ -1371,7 +1371,8 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
     def ragged_step_dyn(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cu_q, slots,
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                         commit: bool = True, admit: bool = False, parent=None, commit_seq=None,
-                        groups=None, chunk_kernel: bool = False, force_generic: bool = False) -> torch.Tensor:
+                        groups=None, chunk_kernel: bool = False, force_generic: bool = False,
+                        decode_kernel: bool = False) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -1424,8 +1425,26 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         ``parent`` and ``commit_seq``; ``groups`` and ``chunk_kernel`` have no instance there and are refused by the
         library.  ``force_generic=True`` (``SFA_FLAG_FORCE_GENERIC``): the exact-f32 split kernel at any head dim, on a
         contiguous 16-bit pool only (no such kernel reads an FP8 or a paged pool); pool and state rows end bitwise the
-        same either way."""
+        same either way.
+
+        ``decode_kernel=True`` (``SFA_FLAG_RAGGED_DECODE1``; False: the call above, unchanged): a sequence of ONE new
+        token - a decode row, a one-node tree, a slot admitted with one token - is computed by the decode-row kernel of
+        DESIGN.md 3.3.17: K/V tiles go from global memory to LDS without passing registers (16-bit pools), and its split
+        count comes from its own state and ``(n_seq, H_kv)``, not from ``T`` or the rest of the pack.  Its output is that
+        of the default call within its tolerance and is bitwise the same wherever and beside whatever it lies; every other
+        sequence, the pool and the state rows are bitwise those of the default call.  Works with ``chunk_kernel=True``
+        (decode rows on this kernel, chunks on the 128-row one: the serving configuration), ``admit``, ``parent``,
+        ``commit_seq`` and ``commit``.  bf16 / fp16 at head dims 64 / 80 / 96 / 128 with ``H_q / H_kv <= 32``, every pool
+        kind; ``groups`` and ``force_generic`` together with ``decode_kernel`` are refused."""
         from . import _native as N
+        if decode_kernel:
+            G = q.shape[1] // max(1, k_new.shape[1]) if q.dim() == 4 and k_new.dim() == 4 else 0
+            why = ("takes no groups=" if groups is not None else "takes no force_generic=True" if force_generic else
+                   f"serves bf16 / fp16, got {q.dtype}" if q.dtype not in (torch.bfloat16, torch.float16) else
+                   f"serves head dims 64 / 80 / 96 / 128, got {q.shape[-1]}" if q.shape[-1] not in (64, 80, 96, 128) else
+                   f"serves H_q / H_kv <= 32, got {G}" if G > 32 else None)
+            if why:
+                raise ValueError(f"ragged_step_dyn(decode_kernel=True) {why}: the decode-row kernel has no such instance")
         dev_state = self._require_pool("ragged_step_dyn")
         if chunk_kernel and groups is not None:
             raise ValueError("ragged_step_dyn(chunk_kernel=True) takes no groups=: the grouped call has no chunk kernel")
@@ -1450,12 +1469,17 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         n_grp = 0 if cu_g is None else cu_g.numel() - 1
         # the grouped call keeps constants and workspace of its own, so that grouped and ungrouped steps (and graphs
         # captured of either) can alternate on one layer without replacing each other's workspace
-        attr = "_ragged_chunk_state" if chunk_kernel else "_ragged_group_state" if n_grp else "_ragged_state"
+        flags = (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) | (N.FLAG_RAGGED_DECODE1 if decode_kernel else 0)
+        attr = ("_ragged_decode_chunk_state" if chunk_kernel else "_ragged_decode_state") if decode_kernel else \
+            "_ragged_chunk_state" if chunk_kernel else "_ragged_group_state" if n_grp else "_ragged_state"
         st = getattr(self, attr, None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype) + ((n_grp,) if n_grp else ())
         if st is None or st["key"] != key:
             ws_bytes = 0
-            if chunk_kernel:
+            if decode_kernel:
+                ws_bytes = N.lib().sfa_decode_ragged_step_workspace_bytes(
+                    n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype], flags)
+            elif chunk_kernel:
                 ws_bytes = N.lib().sfa_decode_ragged_chunk_workspace_bytes(
                     n_seq, H_q, H_kv, T, self.num_sink + self.window_size, D, N.SFA_DTYPE[q.dtype])
             if n_grp:
@@ -1487,8 +1511,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             rc = getattr(st["lib"], name)(N.desc(q), sk, sv, wk, wv, N.desc(k_new), N.desc(v_new), N.desc(out), aux, *mid,
                                           1 if commit else 0, dev_state.data_ptr(), slots.data_ptr(),
                                           cu.data_ptr(), n_seq, *grp, *kvs, st["ws"].data_ptr(), st["ws"].numel(),
-                                          st["scale"], (N.FLAG_RAGGED_ADMIT if admit else 0) |
-                                          (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) |
+                                          st["scale"], (N.FLAG_RAGGED_ADMIT if admit else 0) | flags |
                                           (N.FLAG_FORCE_GENERIC if force_generic else 0), N.stream_ptr(q.device))
         N.check(rc, name)
         return out
@@ -1760,16 +1783,17 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
                         commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None,
-                        chunk_kernel: bool = False, force_generic: bool = False):
+                        chunk_kernel: bool = False, force_generic: bool = False, decode_kernel: bool = False):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
         draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
         (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel; ``force_generic``: the exact-f32
-        kernel (contiguous 16-bit pools).  Head dim 256 is served on every pool kind, without ``groups`` / ``chunk_kernel``."""
+        kernel (contiguous 16-bit pools); ``decode_kernel``: single-token rows on the decode-row kernel.  Head dim 256 is served
+        on every pool kind, without ``groups`` / ``chunk_kernel`` / ``decode_kernel``."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
                                                       commit=commit, admit=admit, parent=parent, commit_seq=commit_seq,
                                                       groups=groups, chunk_kernel=chunk_kernel,
-                                                      force_generic=force_generic)
+                                                      force_generic=force_generic, decode_kernel=decode_kernel)
 
     def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
         """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""

@@ -39,6 +39,10 @@ Variants per (W, step), alternating in one process:
     (one chunk of 2048 tokens admitted on a fresh slot; commit off, so that the slot stays fresh).  Variants ragged (the
     call without the keyword) and ragged_chunk (chunk_kernel=True) on one pool and one pack, alternating in one process.
     Prints ms per step, the spread, the ratio and the largest difference between the two outputs.
+--decode: the decode-row kernel instead (wall mode): the shape of --pool-dtypes (H_q=32, H_kv=8, D=128) and
+    the gpt-oss geometry (H_q=64, H_kv=8, D=64), Wc = 4096, 64 full rings, bf16 and FP8 pools, packs dec64 and dec63_pre512,
+    committing.  Variants ragged, ragged_dec (decode_kernel=True) and ragged_dec_chunk (+ chunk_kernel=True), alternating.
+
 --d256: head dim 256 instead (wall mode): H_q=64, H_kv=8 (G = 8), D = 256, bf16, Wc = 4096 with every
     ring full, packs dec8 (8 decode rows) and dec8_pre512 (8 decode rows + one chunk of 512 tokens), committing.  Variants
     on pools of the same content, alternating in one process: mfma (the pair kernel, contiguous bf16 pool), f32 (the same
@@ -52,7 +56,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --chunk | --d256 | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
+       [--admit | --tree | --chunk | --decode | --d256 | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -431,6 +435,57 @@ def chunk_kernel(args):
                       f"  ragged_chunk / ragged {med['ragged_chunk'] / med['ragged']:.3f}  max |o diff| {diff:.2e}", flush=True)
 
 
+DEC_GEOMS = {"serving": (32, 8, 128), "gpt-oss": (64, 8, 64)}      # (H_q, H_kv, D)
+DEC_VARIANTS = {"ragged": {}, "ragged_dec": dict(decode_kernel=True), "ragged_dec_chunk": dict(decode_kernel=True, chunk_kernel=True)}
+
+
+def decode_kernel(args):
+    """--decode: the packed step without the keyword, with decode_kernel=True and with decode_kernel + chunk_kernel, on a
+    16-bit and an FP8 pool of 64 full rings, alternating; bytes = what the format must read (pool_dtypes' count)"""
+    import torch
+    from sink_attention import SinkCacheLayer, _native
+    dev, dt = "cuda", torch.bfloat16
+    fmt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}
+    Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
+    print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nnum_sink={NS} s_aux bf16 activations, pool of {POOL_S}, rings full; device ms "
+          f"per committing step, median of {args.rounds} rounds of {args.calls} calls (events) after {WARM} warm-up calls, variants "
+          f"alternating; TB/s = bytes the format must read / median", flush=True)
+    for W in Ws:
+        for geom, (hq, hkv, d) in DEC_GEOMS.items():
+            pre = NS + W + 37                          # full ring, wrapped
+            torch.manual_seed(0)
+            k = torch.randn(1, hkv, POOL_S * pre, d, device=dev, dtype=dt)
+            v = torch.randn_like(k)
+            pools = {}
+            for n in fmt:
+                pools[n] = SinkCacheLayer(NS, W)
+                pools[n].init_pool(POOL_S, hkv, d, fmt[n], dev)
+                pools[n].prefill_slots(k, v, [pre * i for i in range(POOL_S + 1)], list(range(POOL_S)))
+            del k, v
+            sa = torch.randn(hq, device=dev) * 0.5
+            for step, lengths in POOL_STEPS.items():
+                T = sum(lengths)
+                q = torch.randn(1, hq, T, d, device=dev, dtype=dt)
+                kn, vn = (torch.randn(1, hkv, T, d, device=dev, dtype=dt) for _ in range(2))
+                cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
+                slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
+                names = [(n, vr) for n in fmt for vr in DEC_VARIANTS]
+                outs = {x: torch.empty_like(q) for x in names}
+                call = lambda x, commit: pools[x[0]].ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=outs[x], commit=commit,
+                                                                     **DEC_VARIANTS[x[1]])
+                res = _alternate(torch, args, {x: (lambda x=x: call(x, True)) for x in names}, names)
+                for x in names:         # the comparison: every variant on its pool as the timing left it, commit off
+                    call(x, False)
+                print(f"  W={W:5d} {geom} H_q={hq} H_kv={hkv} D={d} {step:12s} T={T:4d}", flush=True)
+                for n, vr in names:
+                    x = sorted(res[(n, vr)])
+                    nbytes = 2 * hkv * d * (POOL_S * (NS + W) * (1 if n == "fp8" else 2) + T * 2)
+                    diff = (outs[(n, vr)].float() - outs[(n, "ragged")].float()).abs().max().item()
+                    print(f"      {n:4s} {vr:16s} {x[len(x) // 2]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f}) {nbytes / 2 ** 20:7.1f} MiB "
+                          f"{nbytes / x[len(x) // 2] / 1e9:6.3f} TB/s  / ragged {x[len(x) // 2] / sorted(res[(n, 'ragged')])[len(x) // 2]:.3f}"
+                          f"  max |o diff| {diff:.2e}", flush=True)
+
+
 D256_PACKS = {"dec8": [1] * 8, "dec8_pre512": [1] * 8 + [512]}
 
 
@@ -551,6 +606,7 @@ def main():
     ap.add_argument("--pool-dtypes", default=None, help="bf16,fp8: the packed step on pools of these formats (wall mode)")
     ap.add_argument("--page-size", default=None, help="64,256: the packed step on a contiguous and on paged pools (wall mode)")
     ap.add_argument("--chunk", action="store_true", help="the 128-row chunk kernel (wall mode): variants ragged and ragged_chunk")
+    ap.add_argument("--decode", action="store_true", help="the decode-row kernel (wall mode): ragged, ragged_dec, ragged_dec_chunk on bf16 and FP8 pools")
     ap.add_argument("--d256", action="store_true", help="head dim 256 (wall mode): the pair kernel, the f32 kernel and the pool kinds")
     ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
@@ -558,6 +614,8 @@ def main():
         summarize(args)
     elif args.chunk:
         chunk_kernel(args)
+    elif args.decode:
+        decode_kernel(args)
     elif args.d256:
         d256(args)
     elif args.page_size and args.pool_dtypes:
