@@ -131,6 +131,16 @@ extern "C" {
  * 64 / 80 / 96 / 128, SFA_FLAG_FORCE_GENERIC, H_q / H_kv > 32, K/V row strides of 2^25 elements or more).
  * sfa_last_path(): "_dec1" behind "_ragged" (and behind "_chunk128").  Other entry points ignore the bit. */
 #define SFA_FLAG_RAGGED_DECODE1 0x100u
+/* With SFA_FLAG_RAGGED_DECODE1 on an FP8 pool: the decode-row kernel streams the RAW codes of the cache tiles to LDS by
+ * direct-to-LDS loads (a ring of tiles in flight per wave, as on a 16-bit pool), converts them behind the LDS read and
+ * folds the per-head scales into the logit scale and into O.  The three contracts of
+ * SFA_FLAG_RAGGED_DECODE1 hold unchanged, the first against the reference over the dequantised codes; where every scale is
+ * a power of two the decode rows are bitwise those of SFA_FLAG_RAGGED_DECODE1 alone.  The bit adds nothing to
+ * sfa_decode_ragged_step_workspace_bytes(..., flags).  Valid on sfa_decode_ring_ragged_fp8_slots and
+ * sfa_decode_ring_ragged_paged_fp8_slots together with SFA_FLAG_RAGGED_DECODE1 only: SFA_ERR_UNSUPPORTED, with a
+ * message that names the flag, on a 16-bit pool, without SFA_FLAG_RAGGED_DECODE1, from the _group_ entry points and with
+ * SFA_FLAG_FORCE_GENERIC.  sfa_last_path(): "_dec1raw" in the place of "_dec1". */
+#define SFA_FLAG_RAGGED_DECODE1_RAW8 0x200u
 
 /* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
  * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.

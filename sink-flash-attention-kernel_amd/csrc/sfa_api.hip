@@ -638,6 +638,12 @@ int ring_ragged(const RingCall& c) {
         return SFA_ERR_UNSUPPORTED;
     }
     const bool dec = (c.flags & SFA_FLAG_RAGGED_DECODE1) != 0;
+    if ((c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) && (!dec || !c.pool.fp8 || c.cu_g || (c.flags & SFA_FLAG_FORCE_GENERIC))) {
+        set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1_RAW8 serves an FP8 pool together with SFA_FLAG_RAGGED_DECODE1 "
+                  "(got %s pool%s%s%s)", c.pool.fp8 ? "an FP8" : "a 16-bit", dec ? "" : ", no SFA_FLAG_RAGGED_DECODE1",
+                  c.cu_g ? ", groups" : "", (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
     if (dec && (c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) || q->shape[1] > 32 * c.k_new->shape[1] ||
                 decode_ragged_flags_workspace(1, 1, 1, 1, 1, q->shape[3], q->dtype, SFA_FLAG_RAGGED_DECODE1) == 0)) {
         set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 serves bf16 / f16 at head dims 64 / 80 / 96 / 128 and H_q / H_kv <= 32 "

@@ -39,6 +39,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
@@ -2183,6 +2184,387 @@ __global__ __launch_bounds__(kWaves * 64) void multi_decode1_mfma_kernel(MultiAr
     }
 }
 
+// 8 codes (e4m3fn, byte i = element i) -> 8 elements of T, exactly: the packed conversion at scale 1 (every e4m3fn value
+// is a bf16 and an f16 value)
+template <typename T>
+__device__ __forceinline__ typename Mma<T>::frag raw8_frag(unsigned lo, unsigned hi) {
+    typename Mma<T>::frag out;
+    const unsigned w[2] = {lo, hi};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if constexpr (std::is_same_v<T, bf16_t>) {
+            const auto a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false);
+            const auto b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true);
+            out[4 * i + 0] = a[0], out[4 * i + 1] = a[1], out[4 * i + 2] = b[0], out[4 * i + 3] = b[1];
+        } else {
+            const auto a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false);
+            const auto b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true);
+            out[4 * i + 0] = a[0], out[4 * i + 1] = a[1], out[4 * i + 2] = b[0], out[4 * i + 3] = b[1];
+        }
+    }
+    return out;
+}
+
+// ---- decode-row kernel of an FP8 pool with SFA_FLAG_RAGGED_DECODE1_RAW8: the grid, the plan, the
+// wave's tiles, the merge and the partials of multi_decode1_mfma_kernel, and the data path its FP8 instances lack.
+// LDS holds RAW CODES.  A tile is 32 keys x D bytes in rows of RB = 64 (D = 64) or 128 bytes; K and V go global -> LDS by
+// 16-byte direct-to-LDS buffer loads under the per-tile descriptor of the 16-bit path (base = first row, range =
+// (count - 1) * stride + D bytes: rows past the count are clamped), the swizzle on the source side, the holes of D = 80 / 96
+// out of range.  Per wave a ring of R slots of 2 RB 32 bytes: R = 4 at D = 64 (4 KB slots), R = 2 above (8 KB slots), 64 KB
+// per workgroup either way - room for two workgroups per CU, which the registers grant at D = 64 only - behind counted
+// vmcnt waits ((R - 1) * LPT = 12 / 8).
+// K operand: the lane (key r, half h) of k-step ks reads the 8 codes [16 ks + 8 h, +8) of its row with one ds_read_b64 and
+// converts them (4 packed conversions).  K swizzle: 16-byte position = chunk ^ ((r >> 1) & 7) in 128-byte rows, chunk ^
+// ((r >> 2) & 3) in 64-byte rows: the 16 lanes of a quarter wave (16 consecutive keys, one half) hit 16 different 8-byte
+// bank pairs.
+// V operand: ds_read_b64_tr_b8.  Per 16 lanes it transposes an 8 x 16 byte matrix whose row j is the 16 bytes that lanes
+// 2 j and 2 j + 1 address; lane i receives column i (tools/probes.hip, probe 5).  Source lane i of the block (g1, h)
+// addresses key 16 st + 4 h + (j & 3) + 8 (j >> 2), j = i >> 1, bytes [32 db + 16 g1 + 8 (i & 1), +8): the lane then
+// holds V^T[d = 32 db + 16 g1 + i][the 8 keys of its half in the order of the P fragment], one read per (st, db).  V swizzle:
+// position = chunk ^ (((key >> 1) & 1) << 1 | ((key >> 3) & 1) << 2) in 128-byte rows, chunk ^ (((key >> 3) & 1) << 1) in
+// 64-byte rows: the 8 keys x 2 chunks that the two blocks of a half wave read cover 256 bytes of distinct banks.
+// Scales: folded.  Cache tiles take the logit scale c2 k_scale[hk]; O is accumulated in code units.  The sequence's own
+// token (segment 2, 16-bit, unscaled) is the last tile of the last wave that has one: it is taken straight from k_new /
+// v_new into registers behind the ring (one row: the K fragment is that row for every key, as the clamp gives it, the V
+// fragment its element d for every key), with the plain c2 and alpha v_scale[hk] in the place of alpha, which moves O
+// to real units; a wave that never meets it multiplies by v_scale[hk] in front of the merge.  Wave-uniform.
+// No FP8 MFMA: Q and P are 16-bit, the arithmetic is the register path's.  Deterministic, no atomics.
+template <typename T, int D, bool Paged, typename... KA>
+__global__ __launch_bounds__(kWaves * 64) void multi_decode1_raw8_kernel(MultiArgs a, RaggedArgs rg, KA... ka) {
+    static_assert(tail_is<false, true, Paged, KA...>, "FP8 pool: (..., Kv8Args); paged FP8 pool: (..., Kv8Args, PageArgs)");
+    const Kv8Args kv = arg_of<Kv8Args>(ka...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ka...);
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int DK = D / 16;
+    constexpr int DVB = (D + 31) / 32;
+    constexpr int CPR = D / 16;                    // 16-byte chunks of a row of codes
+    constexpr int RB = D <= 64 ? 64 : 128;
+    constexpr int PPR = RB / 16;
+    constexpr int TILE_BYTES = kTile * RB;
+    constexpr int NDMA = TILE_BYTES / 1024;
+    constexpr int LPT = 2 * NDMA;
+    constexpr int R = D <= 64 ? 4 : 2;
+    constexpr int SLOT = 2 * TILE_BYTES;
+    constexpr int DP = D + 1;
+    static_assert((R - 1) * LPT <= 63, "the counted wait must fit vmcnt");
+    static_assert(kWaves * R * SLOT <= 80 * 1024, "two workgroups per CU");
+    static_assert(2 * kWaves * 32 * 4 + 32 * DP * 4 <= kWaves * R * SLOT, "merge area must fit the tile area");
+    __shared__ __attribute__((aligned(1024))) char smem[kWaves * R * SLOT];
+
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int seq = wid % rg.n_seq;
+    const int split = (wid / rg.n_seq) % a.Sw;
+    const int hk = wid / rg.n_seq / a.Sw;
+    const RaggedSeq sq = ragged_seq(rg, seq);
+    if (__builtin_amdgcn_readfirstlane(sq.n) != 1) return;
+    const int c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (c < 0) return;
+    const int prow = __builtin_amdgcn_readfirstlane(sq.c0);
+    const Fill f = get_fill<true, true>(a, c, 1, rg.admit);
+    if (split >= f.S) return;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const bool row_live = r < a.G;
+
+    // Q, and the own token's row of k_new / v_new, arrive before the first DMA is issued (the pins below)
+    frag qf[DK];
+    {
+        const int head = hk * a.G + (row_live ? r : 0);
+        const char* qp = a.q.ptr + ((int64_t)head * a.q.sh + (int64_t)prow * a.q.sn) * 2;
+        u32x4 raw[DK];
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) raw[ks] = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            asm volatile("" : "+v"(raw[ks]));
+            if (!row_live) raw[ks] = u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(frag, raw[ks]);
+        }
+    }
+
+    char* ring = smem + wave * R * SLOT;
+    const int es = 2;
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
+    const int nk = tend - tbeg > wave ? (tend - tbeg - wave + kWaves - 1) / kWaves : 0;
+    // the own token's tile is the plan's last (n = 1: one chunk tile): the last one of the wave that holds it
+    const bool own = nk > 0 && tbeg + wave + kWaves * (nk - 1) >= f.T1;
+    const int nr = own ? nk - 1 : nk;              // this wave's cache tiles: the ring
+    auto tile_k = [&](int k, TileInfo& ti) {
+        ti = tile_info<true, true, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, 1, prow, pg.shift);
+        const int cls = tile_class(a, ti, 0, 0, f.nsk);
+        if constexpr (Paged) {
+            if (cls != 0 && ti.seg == 1) tile_page(ti, a, pg, c, 1);
+        }
+        return cls;
+    };
+
+    const int ksw_l = RB == 128 ? ((r >> 1) & 7) : ((r >> 2) & 3);
+    const int k_rowoff = r * RB + 8 * h;
+    // the V source lane: its key of step 0, the chunk of d block 0 and the swizzle of that key (the same for step 1: bit 4)
+    const int vi = lane & 15, vj = vi >> 1, g1 = (lane >> 4) & 1;
+    const int vkey = 4 * h + (vj & 3) + 8 * (vj >> 2);
+    const int vsw_l = RB == 128 ? ((((vkey >> 1) & 1) << 1) | (((vkey >> 3) & 1) << 2)) : (((vkey >> 3) & 1) << 1);
+    const int v_rowoff = vkey * RB + 8 * (vi & 1);
+
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[DVB];
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+    const float ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
+    const float c2k = c2 * ksc;
+
+    // mask, online softmax and the rescale of O for one tile's scores s (raw products); cs: the logit scale of the tile,
+    // au: the factor that goes with alpha (1, or v_scale at the own token); returns P in s
+    auto softmax = [&](f32x16& s, const TileInfo& cur, bool edge, float cs, float au) {
+        if (edge) {
+            if (admitting(f, cur)) {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible_admit(a, f, cur, kk, 0) ? s[x] : -INFINITY;
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible(a, f, cur, kk, 0) ? s[x] : -INFINITY;
+                }
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) mx = fmaxf(mx, s[x]);
+        mx = half_swap_max(mx);
+        const float m_new = fmaxf(m, mx * cs);
+        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+        float rs = 0.f;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            s[x] = __builtin_amdgcn_exp2f(fmaf(s[x], cs, -m_safe));
+            rs += s[x];
+        }
+        l = fmaf(l, alpha, rs);
+        m = m_new;
+        const float ao = alpha * au;
+#pragma unroll
+        for (int db = 0; db < DVB; ++db)
+#pragma unroll
+            for (int x = 0; x < 16; ++x) o[db][x] *= ao;
+    };
+
+    // one live cache tile from the raw image (kl, kl + TILE_BYTES)
+    auto consume = [&](const TileInfo& cur, bool edge, const char* kl) {
+        const char* vl = kl + TILE_BYTES;
+        f32x16 s;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) s[x] = 0.f;
+        {
+            u32x2 kc[DK];
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) kc[ks] = *reinterpret_cast<const u32x2*>(kl + k_rowoff + ((ks ^ ksw_l) << 4));
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) s = M::run(raw8_frag<T>(kc[ks][0], kc[ks][1]), qf[ks], s);
+        }
+        softmax(s, cur, edge, c2k, 1.f);
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            frag pf;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) pf[x] = (typename M::elem)s[8 * st + x];
+            const char* vrow = vl + 16 * st * RB + v_rowoff;
+            // written out with a wait of its own, as the 16-bit path's transposing reads: the DMAs in flight stay in flight
+            u32x2 vc[DVB];
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                const int ch = (2 * db + g1) ^ vsw_l;
+                const unsigned p1 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(vrow + (ch << 4));
+                asm volatile("ds_read_b64_tr_b8 %0, %1" : "=&v"(vc[db]) : "v"(p1) : "memory");
+            }
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vc[db])::"memory");
+                o[db] = M::run(raw8_frag<T>(vc[db][0], vc[db][1]), pf, o[db]);
+            }
+        }
+    };
+
+    // the own token's row: K as the lane's B-side k range of every k-step, V as the lane's element d of every d block
+    u32x4 kown[DK];
+    unsigned short vown[DVB];
+    if (own) {
+        TileInfo ti;
+        tile_k(nk - 1, ti);
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            kown[ks] = *reinterpret_cast<const u32x4*>(ti.k + (2 * ks + h) * 16);
+            asm volatile("" : "+v"(kown[ks]));
+        }
+#pragma unroll
+        for (int db = 0; db < DVB; ++db) {
+            const int d = 32 * db + r;
+            vown[db] = d < D ? *reinterpret_cast<const unsigned short*>(ti.v + d * 2) : (unsigned short)0;
+            asm volatile("" : "+v"(vown[db]));
+        }
+    }
+
+    {
+        unsigned cq = 0;               // the classes of the tiles in the ring, two bits per slot k mod R
+        // positions of a 128-byte LDS row that hold no chunk (D = 80 / 96): OR-ed onto the offset, which then lies out of range
+        [[maybe_unused]] unsigned khole[NDMA], vhole[NDMA];
+        if constexpr (CPR < PPR) {
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int key = (64 * j + lane) / PPR, pos = (64 * j + lane) % PPR;
+                khole[j] = (pos ^ ((key >> 1) & 7)) < CPR ? 0u : 0xFFFFFFF0u;
+                vhole[j] = (pos ^ ((((key >> 1) & 1) << 1) | (((key >> 3) & 1) << 2))) < CPR ? 0u : 0xFFFFFFF0u;
+                asm volatile("" : "+v"(khole[j]), "+v"(vhole[j]));
+            }
+        }
+        auto issue = [&](int k) {
+            TileInfo ti;
+            const int cls = tile_k(k, ti);
+            const int sl = k & (R - 1);
+            cq = (cq & ~(3u << (2 * sl))) | ((unsigned)cls << (2 * sl));
+            if (cls == 0) return;
+            // the tile's rows [0, count) of D bytes: every offset below lies inside (the launcher has bounded the row strides)
+            const unsigned ksn = (unsigned)ti.ksn, vsn = (unsigned)ti.vsn;
+            const unsigned last = (unsigned)(ti.count - 1);
+            char* kl = ring + sl * SLOT;
+            const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)ti.k, 0, (int)(last * ksn + D), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int kch = pos ^ (RB == 128 ? ((key >> 1) & 7) : ((key >> 2) & 3));
+                unsigned ko = row * ksn + (unsigned)(kch * 16);
+                if constexpr (CPR < PPR) ko |= khole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(kl + 1024 * j), 16, ko, 0, 0, 0);
+            }
+            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)ti.v, 0, (int)(last * vsn + D), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int vch = pos ^ (RB == 128 ? ((((key >> 1) & 1) << 1) | (((key >> 3) & 1) << 2)) : (((key >> 3) & 1) << 1));
+                unsigned vo = row * vsn + (unsigned)(vch * 16);
+                if constexpr (CPR < PPR) vo |= vhole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(kl + TILE_BYTES + 1024 * j), 16, vo, 0, 0, 0);
+            }
+        };
+#pragma unroll
+        for (int k = 0; k < R - 1; ++k)
+            if (k < nr) issue(k);
+#pragma unroll 1
+        for (int k = 0; k < nr; ++k) {
+            // slot (k - 1) mod R is free: every LDS read of tile k - 1 returned at the end of the last trip
+            if (k + R - 1 < nr) issue(k + R - 1);
+            int pend = 0;              // live tiles issued behind tile k: their loads may stay outstanding
+#pragma unroll
+            for (int d = 1; d < R; ++d)
+                if (k + d < nr && ((cq >> (2 * ((k + d) & (R - 1)))) & 3u) != 0) ++pend;
+            const int cls = (cq >> (2 * (k & (R - 1)))) & 3u;
+            if (cls == 0) continue;
+            if (pend >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 3 ? 3 : 0) * LPT) : "memory");
+            else if (pend == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 2 ? 2 : 0) * LPT) : "memory");
+            else if (pend == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 1 ? 1 : 0) * LPT) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            TileInfo cur{};
+            if (cls == 2) cur = tile_info<true, true, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, 1, prow, pg.shift);
+            consume(cur, cls == 2, ring + (k & (R - 1)) * SLOT);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slot may be overwritten by the next trip's DMA
+        }
+    }
+
+    if (own) {
+        // the own token: an edge tile of one key (every other key masked); O leaves code units here
+        const TileInfo cur = tile_info<true, true, Paged>(a, f, tbeg + wave + kWaves * (nk - 1), 0, c, hk, es, 1, prow, pg.shift);
+        f32x16 s;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) s[x] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) s = M::run(__builtin_bit_cast(frag, kown[ks]), qf[ks], s);
+        softmax(s, cur, true, c2, vsc);
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            frag pf;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) pf[x] = (typename M::elem)s[8 * st + x];
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                s16x8 vv;
+#pragma unroll
+                for (int x = 0; x < 8; ++x) vv[x] = (short)vown[db];
+                o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int db = 0; db < DVB; ++db)
+#pragma unroll
+            for (int x = 0; x < 16; ++x) o[db][x] *= vsc;
+    }
+
+    // ---- merge the 4 waves' (m, l, O) in wave order through LDS, as multi_decode1_mfma_kernel does
+    const float lw = half_swap_sum(l);
+    __syncthreads();
+    float* sm = reinterpret_cast<float*>(smem);      // [wave][32]
+    float* sl = sm + kWaves * 32;                    // [wave][32]
+    float* so = sl + kWaves * 32;                    // [32][DP]
+    if (h == 0) {
+        sm[wave * 32 + r] = m;
+        sl[wave * 32 + r] = lw;
+    }
+    __syncthreads();
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) mstar = fmaxf(mstar, sm[w * 32 + r]);
+    const float wgt = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mstar);
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int db = 0; db < DVB; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int col = 32 * db + 8 * (i >> 2) + 4 * h + (i & 3);
+                    if (col < D) {
+                        float* p = so + r * DP + col;
+                        *p = (w == 0 ? 0.f : *p) + o[db][i] * wgt;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    const int64_t row0 = ((int64_t)hk * rg.n_seq + seq) * a.G;
+    if (tid < a.G) {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) ms = fmaxf(ms, sm[w * 32 + tid]);
+        float lt = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const float mw = sm[w * 32 + tid];
+            lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
+        }
+        a.Mp[(row0 + tid) * a.Sw + split] = ms;
+        a.Lp[(row0 + tid) * a.Sw + split] = lt;
+    }
+    for (int e = tid; e < a.G * D; e += kWaves * 64) {
+        const int rr = e / D, d = e - rr * D;
+        a.Op[((row0 + rr) * a.Sw + split) * D + d] = so[rr * DP + d];
+    }
+}
+
 // the preparation launch of a call with SFA_FLAG_RAGGED_DECODE1, alone or with SFA_FLAG_RAGGED_CHUNK128 (nwb = 0: alone,
 // no wblk): ragged_prep_chunk_kernel's tables, except that the 32-row block of a decode sequence (n_i == 1) is surplus
 // too - the kernel above finds its sequences from cu_q itself and needs no table.
@@ -3207,8 +3589,9 @@ int launch_chunk(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool,
 // the decode-row kernel of a packed call with SFA_FLAG_RAGGED_DECODE1: behind the split launch, on Hkv * Sdw * n_seq
 // blocks whatever the pack holds.  Its MultiArgs are the call's with the decode plan and the decode area in the place of
 // want, Sw and the partials.
+// raw8 (SFA_FLAG_RAGGED_DECODE1_RAW8, an FP8 pool): multi_decode1_raw8_kernel in the place of the KV8 instances.
 template <typename T>
-int launch_dec1(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, const Dec1Args& dd, hipStream_t stream) {
+int launch_dec1(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, const Dec1Args& dd, bool raw8, hipStream_t stream) {
     MultiArgs ad = a;
     ad.want = dd.want_d, ad.Sw = dd.Sdw, ad.Mp = dd.Md, ad.Lp = dd.Ld, ad.Op = dd.Od;
     const dim3 grid((unsigned)((int64_t)a.Hkv * dd.Sdw * rg.n_seq));
@@ -3216,6 +3599,12 @@ int launch_dec1(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, 
         constexpr int D = decltype(d)::value;
         dispatch_pool(pool, [&](auto p, auto... tail) {
             using P = decltype(p);
+            if constexpr (P::KV8) {
+                if (raw8) {
+                    multi_decode1_raw8_kernel<T, D, P::Paged><<<grid, kWaves * 64, 0, stream>>>(ad, rg, tail...);
+                    return;
+                }
+            }
             multi_decode1_mfma_kernel<T, D, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(ad, rg, tail...);
         });
     };
@@ -3258,7 +3647,7 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool
 // pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
 int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream,
-                const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr) {
+                const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr, bool raw8 = false) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
     if constexpr (sizeof(T) == 2) {
@@ -3266,7 +3655,7 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
         // chunk sequences: their 32-row blocks left the split launch as surplus; the reduce folds either kernel's partials
         if (!st && mfma && ck) st = launch_chunk<T>(a, *rg, pool, *ck, stream);
         // decode sequences: likewise, into the second partial area, which the reduce instance with Dec1Args folds
-        if (!st && mfma && dd) st = launch_dec1<T>(a, *rg, pool, *dd, stream);
+        if (!st && mfma && dd) st = launch_dec1<T>(a, *rg, pool, *dd, raw8, stream);
     }
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
@@ -3346,8 +3735,9 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
         return SFA_ERR_UNSUPPORTED;
     }
     if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, nullptr, false, c.stream);
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd);
-    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd);
+    const bool raw8 = (c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) != 0;     // the API admits it with dd on an FP8 pool only
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8);
+    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8);
 }
 
 }  // namespace
@@ -3551,7 +3941,8 @@ int decode_ragged_launch(const RingCall& c) {
         dd.Ld = reinterpret_cast<float*>(dw + al256((size_t)dg.P * sizeof(float)));
         dd.Od = reinterpret_cast<float*>(dw + 2 * al256((size_t)dg.P * sizeof(float)));
         dd.Sdw = (int)dg.Sdw, dd.want_d = (int)dg.want;
-        // the DMA addresses a tile by a 64-bit base and 32-bit offsets inside its 32 rows
+        // the DMA addresses a tile by a 64-bit base and 32-bit offsets inside its 32 rows (SFA_FLAG_RAGGED_DECODE1_RAW8: rows
+        // of one byte per element, whose offsets this bound covers twice over)
         const View* vs[] = {&a.sk, &a.sv, &a.wk, &a.wv, &a.kn, &a.vn};
         for (const View* v : vs)
             if (v->sn * 2 * kTile >= (1ll << 31)) {
@@ -3600,8 +3991,8 @@ int decode_ragged_launch(const RingCall& c) {
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
     if (mfma)
-        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "", dec ? "_dec1" : "",
-                 ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
+        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "",
+                 !dec ? "" : (c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) ? "_dec1raw" : "_dec1", ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }

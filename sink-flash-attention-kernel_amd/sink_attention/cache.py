@@ -1372,7 +1372,7 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
                         s_aux: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                         commit: bool = True, admit: bool = False, parent=None, commit_seq=None,
                         groups=None, chunk_kernel: bool = False, force_generic: bool = False,
-                        decode_kernel: bool = False) -> torch.Tensor:
+                        decode_kernel: bool = False, raw_fp8: bool = False) -> torch.Tensor:
         """One step over the pool in which every sequence brings its own number of new tokens
         (``sfa_decode_ring_ragged_slots``): ``q`` ``[1, H_q, T, D]`` and ``k_new`` / ``v_new`` ``[1, H_kv, T, D]`` hold
         the new tokens of n_seq sequences back to back (the layout ``prefill_slots`` takes); sequence i is rows
@@ -1435,8 +1435,19 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         sequence, the pool and the state rows are bitwise those of the default call.  Works with ``chunk_kernel=True``
         (decode rows on this kernel, chunks on the 128-row one: the serving configuration), ``admit``, ``parent``,
         ``commit_seq`` and ``commit``.  bf16 / fp16 at head dims 64 / 80 / 96 / 128 with ``H_q / H_kv <= 32``, every pool
-        kind; ``groups`` and ``force_generic`` together with ``decode_kernel`` are refused."""
+        kind; ``groups`` and ``force_generic`` together with ``decode_kernel`` are refused.
+
+        ``raw_fp8=True`` (``SFA_FLAG_RAGGED_DECODE1_RAW8``; with ``decode_kernel=True`` on an FP8 pool, contiguous or
+        paged; False: the call above, unchanged): the decode-row kernel streams the raw FP8 codes to LDS as it streams
+        the rows of a 16-bit pool, converts them behind the LDS read and folds the per-head scales into the logit scale
+        and into the output (DESIGN.md 3.3.18).  Same contracts and the same workspace size as ``decode_kernel=True``;
+        with power-of-two scales the decode rows are bitwise those of ``decode_kernel=True`` alone."""
         from . import _native as N
+        if raw_fp8:
+            if not decode_kernel:
+                raise ValueError("ragged_step_dyn(raw_fp8=True) needs decode_kernel=True: it is a data path of the decode-row kernel")
+            if not self._kv8:
+                raise TypeError("ragged_step_dyn(raw_fp8=True) needs an FP8 pool: init_pool(..., kv_dtype=torch.float8_e4m3fn)")
         if decode_kernel:
             G = q.shape[1] // max(1, k_new.shape[1]) if q.dim() == 4 and k_new.dim() == 4 else 0
             why = ("takes no groups=" if groups is not None else "takes no force_generic=True" if force_generic else
@@ -1469,8 +1480,10 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         n_grp = 0 if cu_g is None else cu_g.numel() - 1
         # the grouped call keeps constants and workspace of its own, so that grouped and ungrouped steps (and graphs
         # captured of either) can alternate on one layer without replacing each other's workspace
-        flags = (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) | (N.FLAG_RAGGED_DECODE1 if decode_kernel else 0)
-        attr = ("_ragged_decode_chunk_state" if chunk_kernel else "_ragged_decode_state") if decode_kernel else \
+        flags = (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) | (N.FLAG_RAGGED_DECODE1 if decode_kernel else 0) | \
+            (N.FLAG_RAGGED_DECODE1_RAW8 if raw_fp8 else 0)
+        attr = ("_ragged_raw8_chunk_state" if chunk_kernel else "_ragged_raw8_state") if raw_fp8 else \
+            ("_ragged_decode_chunk_state" if chunk_kernel else "_ragged_decode_state") if decode_kernel else \
             "_ragged_chunk_state" if chunk_kernel else "_ragged_group_state" if n_grp else "_ragged_state"
         st = getattr(self, attr, None)
         key = (self.sink_k.data_ptr(), self.window_k.data_ptr(), q.shape, n_seq, q.dtype) + ((n_grp,) if n_grp else ())
@@ -1783,17 +1796,20 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
 
     def ragged_step_dyn(self, q, key_states, value_states, cu_q, slots, layer_idx: int, s_aux=None, out=None,
                         commit=True, admit: bool = False, parent=None, commit_seq=None, groups=None,
-                        chunk_kernel: bool = False, force_generic: bool = False, decode_kernel: bool = False):
+                        chunk_kernel: bool = False, force_generic: bool = False, decode_kernel: bool = False,
+                        raw_fp8: bool = False):
         """``SinkCacheLayer.ragged_step_dyn`` of one layer: a packed step, every sequence with its own token count;
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
         draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
         (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel; ``force_generic``: the exact-f32
-        kernel (contiguous 16-bit pools); ``decode_kernel``: single-token rows on the decode-row kernel.  Head dim 256 is served
+        kernel (contiguous 16-bit pools); ``decode_kernel``: single-token rows on the decode-row kernel;
+        ``raw_fp8`` (with ``decode_kernel`` on an FP8 pool): its raw-code data path.  Head dim 256 is served
         on every pool kind, without ``groups`` / ``chunk_kernel`` / ``decode_kernel``."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,
                                                       commit=commit, admit=admit, parent=parent, commit_seq=commit_seq,
                                                       groups=groups, chunk_kernel=chunk_kernel,
-                                                      force_generic=force_generic, decode_kernel=decode_kernel)
+                                                      force_generic=force_generic, decode_kernel=decode_kernel,
+                                                      raw_fp8=raw_fp8)
 
     def commit_packed_dyn(self, key_states, value_states, cu_q, slots, count, layer_idx: int, path=None) -> None:
         """``SinkCacheLayer.commit_packed_dyn`` of one layer: store the accepted prefixes / paths of a packed step."""

@@ -41,7 +41,9 @@ Variants per (W, step), alternating in one process:
     Prints ms per step, the spread, the ratio and the largest difference between the two outputs.
 --decode: the decode-row kernel instead (wall mode): the shape of --pool-dtypes (H_q=32, H_kv=8, D=128) and
     the gpt-oss geometry (H_q=64, H_kv=8, D=64), Wc = 4096, 64 full rings, bf16 and FP8 pools, packs dec64 and dec63_pre512,
-    committing.  Variants ragged, ragged_dec (decode_kernel=True) and ragged_dec_chunk (+ chunk_kernel=True), alternating.
+    committing.  Variants ragged, ragged_dec (decode_kernel=True) and ragged_dec_chunk (+ chunk_kernel=True), alternating; a
+    paged FP8 pool (pfp8, P = 64, shuffled table) beside them and, on the two FP8 pools, raw_fp8 and raw_fp8_chunk
+    (raw_fp8=True).
 
 --d256: head dim 256 instead (wall mode): H_q=64, H_kv=8 (G = 8), D = 256, bf16, Wc = 4096 with every
     ring full, packs dec8 (8 decode rows) and dec8_pre512 (8 decode rows + one chunk of 512 tokens), committing.  Variants
@@ -437,15 +439,19 @@ def chunk_kernel(args):
 
 DEC_GEOMS = {"serving": (32, 8, 128), "gpt-oss": (64, 8, 64)}      # (H_q, H_kv, D)
 DEC_VARIANTS = {"ragged": {}, "ragged_dec": dict(decode_kernel=True), "ragged_dec_chunk": dict(decode_kernel=True, chunk_kernel=True)}
+DEC_RAW = {"raw_fp8": dict(decode_kernel=True, raw_fp8=True), "raw_fp8_chunk": dict(decode_kernel=True, raw_fp8=True, chunk_kernel=True)}
+DEC_PAGE = 64                                   # the page size of the paged FP8 pool of --decode (shuffled table)
 
 
 def decode_kernel(args):
     """--decode: the packed step without the keyword, with decode_kernel=True and with decode_kernel + chunk_kernel, on a
-    16-bit and an FP8 pool of 64 full rings, alternating; bytes = what the format must read (pool_dtypes' count)"""
+    16-bit, an FP8 and a paged FP8 pool of 64 full rings, on the FP8 pools also with raw_fp8=True,
+    alternating; bytes = what the format must read (pool_dtypes' count)"""
     import torch
     from sink_attention import SinkCacheLayer, _native
     dev, dt = "cuda", torch.bfloat16
-    fmt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}
+    fmt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "pfp8": torch.float8_e4m3fn}
+    variants = {**DEC_VARIANTS, **(DEC_RAW if hasattr(_native, "FLAG_RAGGED_DECODE1_RAW8") else {})}
     Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
     print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nnum_sink={NS} s_aux bf16 activations, pool of {POOL_S}, rings full; device ms "
           f"per committing step, median of {args.rounds} rounds of {args.calls} calls (events) after {WARM} warm-up calls, variants "
@@ -459,7 +465,12 @@ def decode_kernel(args):
             pools = {}
             for n in fmt:
                 pools[n] = SinkCacheLayer(NS, W)
-                pools[n].init_pool(POOL_S, hkv, d, fmt[n], dev)
+                if n == "pfp8":
+                    pools[n].init_pool(POOL_S, hkv, d, dt, dev, page_size=DEC_PAGE, kv_dtype=fmt[n])
+                    order = torch.randperm(POOL_S * (W // DEC_PAGE), generator=torch.Generator().manual_seed(DEC_PAGE))
+                    pools[n].page_table.copy_(order.reshape(POOL_S, W // DEC_PAGE).to(torch.int32))
+                else:
+                    pools[n].init_pool(POOL_S, hkv, d, fmt[n], dev)
                 pools[n].prefill_slots(k, v, [pre * i for i in range(POOL_S + 1)], list(range(POOL_S)))
             del k, v
             sa = torch.randn(hq, device=dev) * 0.5
@@ -469,17 +480,17 @@ def decode_kernel(args):
                 kn, vn = (torch.randn(1, hkv, T, d, device=dev, dtype=dt) for _ in range(2))
                 cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
                 slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
-                names = [(n, vr) for n in fmt for vr in DEC_VARIANTS]
+                names = [(n, vr) for n in fmt for vr in variants if n != "bf16" or vr in DEC_VARIANTS]
                 outs = {x: torch.empty_like(q) for x in names}
                 call = lambda x, commit: pools[x[0]].ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=outs[x], commit=commit,
-                                                                     **DEC_VARIANTS[x[1]])
+                                                                     **variants[x[1]])
                 res = _alternate(torch, args, {x: (lambda x=x: call(x, True)) for x in names}, names)
                 for x in names:         # the comparison: every variant on its pool as the timing left it, commit off
                     call(x, False)
                 print(f"  W={W:5d} {geom} H_q={hq} H_kv={hkv} D={d} {step:12s} T={T:4d}", flush=True)
                 for n, vr in names:
                     x = sorted(res[(n, vr)])
-                    nbytes = 2 * hkv * d * (POOL_S * (NS + W) * (1 if n == "fp8" else 2) + T * 2)
+                    nbytes = 2 * hkv * d * (POOL_S * (NS + W) * (2 if n == "bf16" else 1) + T * 2)
                     diff = (outs[(n, vr)].float() - outs[(n, "ragged")].float()).abs().max().item()
                     print(f"      {n:4s} {vr:16s} {x[len(x) // 2]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f}) {nbytes / 2 ** 20:7.1f} MiB "
                           f"{nbytes / x[len(x) // 2] / 1e9:6.3f} TB/s  / ragged {x[len(x) // 2] / sorted(res[(n, 'ragged')])[len(x) // 2]:.3f}"

@@ -1,6 +1,7 @@
 // Hardware-layout probes for gfx950 (run on the GPU box): checks the lane maps the MFMA kernels rely on.
 //  1. v_mfma_f32_32x32x16_bf16 A/B/C maps        2. ds_read_b64_tr_b16 gather map
 //  3. v_permlane32_swap semantics                 4. accumulator-as-B-operand k permutation
+//  5. ds_read_b64_tr_b8 gather map                6. v_cvt_scalef32_pk_{bf16,f16}_fp8 byte order and exactness
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +67,45 @@ __global__ void k_chain(const unsigned short* A1, const unsigned short* B1, cons
     for (int i = 0; i < 16; ++i) Y[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = y[i];
 }
 
+// every lane reads the 8 bytes at LDS offset 8 * lane; byte e of source lane s holds s (mode 0) or 8 * (s & 15) + e
+// (mode 1), so the two dumps together name the source lane and byte of every result byte
+__global__ void k_tr8(unsigned char* out, int mode) {
+    __shared__ __attribute__((aligned(16))) unsigned char M[512];
+    const int l = threadIdx.x;
+    for (int e = 0; e < 8; ++e) M[8 * l + e] = (unsigned char)(mode ? 8 * (l & 15) + e : l);
+    __syncthreads();
+    const unsigned addr = (unsigned)(size_t)&M[8 * l];
+    unsigned long long v;
+    asm volatile("ds_read_b64_tr_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
+    for (int e = 0; e < 8; ++e) out[l * 8 + e] = (unsigned char)(v >> (8 * e));
+}
+
+// the packed e4m3fn -> 16-bit conversions at scale 1 against cvt_pk_f32_fp8 and the (exact) narrowing: out[t] = the
+// elements of the word of thread t that differ, NaN codes (0x7f, 0xff) left out
+__global__ void k_cvt8(unsigned* out) {
+    const unsigned t = threadIdx.x;
+    const unsigned w = t | ((255u - t) << 8) | (((t * 7u) & 255u) << 16) | (((t * 13u) & 255u) << 24);
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    unsigned bad = 0;
+    for (int hi = 0; hi < 2; ++hi) {
+        const auto f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+        const bf2 b = hi ? __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true) : __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
+        const h2 g = hi ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true) : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false);
+        for (int e = 0; e < 2; ++e) {
+            const unsigned code = (w >> (16 * hi + 8 * e)) & 255u;
+            if ((code & 127u) == 127u) continue;
+            const __bf16 rb = (__bf16)f[e];
+            const _Float16 rh = (_Float16)f[e];
+            const __bf16 gb = b[e];
+            const _Float16 gh = g[e];
+            bad += __builtin_bit_cast(unsigned short, gb) != __builtin_bit_cast(unsigned short, rb);
+            bad += __builtin_bit_cast(unsigned short, gh) != __builtin_bit_cast(unsigned short, rh);
+        }
+    }
+    out[t] = bad;
+}
+
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
 int main() {
@@ -128,6 +168,34 @@ int main() {
         CK(hipMemcpy(Y.data(), dY, 4096, hipMemcpyDeviceToHost));
         int bad = 0; for (int i = 0; i < 1024; ++i) bad += Y[i] != Yr[i];
         printf("probe4 accumulator-as-B-operand k permutation: %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+    }
+    {   // 5. byte transpose: per 16 lanes an 8 x 16 byte matrix, row j = the 16 bytes of source lanes 2j and 2j + 1
+        std::vector<unsigned char> out(2 * 512);
+        unsigned char* d; CK(hipMalloc(&d, 1024));
+        k_tr8<<<1, 64>>>(d, 0);
+        k_tr8<<<1, 64>>>(d + 512, 1);
+        CK(hipMemcpy(out.data(), d, 1024, hipMemcpyDeviceToHost));
+        int bad = 0;
+        for (int l = 0; l < 64; ++l) for (int e = 0; e < 8; ++e) {
+            const int i = l & 15, src = 2 * e + (i >> 3);
+            bad += out[l * 8 + e] != (l & 48) + src || out[512 + l * 8 + e] != 8 * src + (i & 7);
+        }
+        printf("probe5 ds_read_b64_tr_b8 (lane i gets column i of 8 rows, row j from lanes 2j, 2j+1): %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad);
+        if (bad) for (int l = 0; l < 64; ++l) {
+            printf("  lane %2d:", l);
+            for (int e = 0; e < 8; ++e) printf(" %2d.%d", out[l * 8 + e], out[512 + l * 8 + e] & 7);
+            printf("   (source lane.byte)\n");
+        }
+        fails += bad != 0;
+    }
+    {   // 6. packed e4m3fn -> bf16 / f16 conversions: byte order and exactness
+        std::vector<unsigned> out(256);
+        unsigned* d; CK(hipMalloc(&d, 1024));
+        k_cvt8<<<1, 256>>>(d);
+        CK(hipMemcpy(out.data(), d, 1024, hipMemcpyDeviceToHost));
+        int bad = 0; for (int t = 0; t < 256; ++t) bad += out[t];
+        printf("probe6 cvt_scalef32_pk_{bf16,f16}_fp8 at scale 1 = narrowed cvt_pk_f32_fp8: %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad);
+        fails += bad != 0;
     }
     printf("probes: %s\n", fails ? "SOME FAILED" : "ALL PASS");
     return fails ? 1 : 0;
