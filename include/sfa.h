@@ -141,6 +141,29 @@ extern "C" {
  * message that names the flag, on a 16-bit pool, without SFA_FLAG_RAGGED_DECODE1, from the _group_ entry points and with
  * SFA_FLAG_FORCE_GENERIC.  sfa_last_path(): "_dec1raw" in the place of "_dec1". */
 #define SFA_FLAG_RAGGED_DECODE1_RAW8 0x200u
+/* With SFA_FLAG_RAGGED_DECODE1: serve the draft rows of speculative decoding by the draft-row kernel.
+ * Sequence i of the pack is a DRAFT sequence iff n_i >= 2 and G * n_i <= 32 - decided on the device from cu_q alone.  Its
+ * (token, head) rows are ONE 32-row MFMA block (rho = t G + g) over the whole cache of the sequence, computed by
+ * workgroups of (sequence, KV head, split) on the data path of the decode-row kernel (16-bit pools: direct-to-LDS loads,
+ * the chunk tile of k_new / v_new included; FP8 pools: the converting register path - SFA_FLAG_RAGGED_DECODE1_RAW8 still
+ * applies to the single-token rows only) with a mask per row, under a plan of its own:
+ * multi_plan(sink_len, window_len, n_i, want_splits(1, H_kv, n_seq)), a function of its state row and of (n_seq, H_kv).
+ * With parent it is a tree sequence under the rule of sfa_decode_ring_ragged_tree_slots, otherwise a chain; a fresh slot
+ * admitted with such a chunk (SFA_FLAG_RAGGED_ADMIT) is included.  Single-token sequences stay on the decode-row kernel,
+ * everything else (G * n_i > 32, empty, inactive) on the split and chunk kernels.  Six contracts:
+ *   1. the o rows of a draft sequence meet the tolerance of the call without the flags against an fp64 reference (FP8
+ *      pools: against the reference over the dequantised codes);
+ *   2. every other row is bitwise the row of the call with SFA_FLAG_RAGGED_DECODE1 and the same remaining flags (a
+ *      single-token row is the decode-row kernel's own output, with SFA_FLAG_RAGGED_DECODE1_RAW8 too);
+ *   3. with commit, the pool, the page table and the state rows end bitwise as without the flags;
+ *   4. the rows of a draft sequence do not depend on its place in the pack, on its neighbours or on T (at the same
+ *      (n_seq, H_kv)), and replay bitwise from a captured graph (every launch always happens);
+ *   5. a chain-shaped parent gives bitwise the rows of parent == NULL;
+ *   6. a paged pool is bitwise its contiguous twin.
+ * Workspace: sfa_decode_ragged_step_workspace_bytes(..., flags) adds the draft partials.  SFA_ERR_UNSUPPORTED, with a
+ * message that names the flag, without SFA_FLAG_RAGGED_DECODE1, for H_q / H_kv > 16 (no sequence can qualify) and wherever
+ * SFA_FLAG_RAGGED_DECODE1 is refused.  sfa_last_path(): "_draft" behind "_dec1" / "_dec1raw". */
+#define SFA_FLAG_RAGGED_DECODE_DRAFT 0x400u
 
 /* Accepted strides.  All strides are >= 0 element counts (0 = broadcast) held as int64; the base pointer and every
  * stride of a decode / prefill-MFMA operand are multiples of 16 bytes.
@@ -606,7 +629,10 @@ size_t sfa_decode_ragged_chunk_workspace_bytes(int64_t n_seq, int64_t Hq, int64_
  * ignored): the ungrouped size, then the table of 128-row blocks if the chunk flag is set, then with the decode flag the
  * decode partials: H_q n_seq Sdw entries of m and of l and H_q n_seq Sdw D of O (floats, each area rounded up to 256
  * bytes), Sdw = the largest split count a single-token row plans over Nkv_cache + 1 keys at (n_seq, H_kv).  0 where a
- * flag is refused for the shape (as above; for the decode flag also H_q / H_kv > 32).  No GPU needed. */
+ * flag is refused for the shape (as above; for the decode flag also H_q / H_kv > 32).  SFA_FLAG_RAGGED_DECODE_DRAFT is
+ * read together with the decode flag (ignored without it): the draft partials follow, H_kv n_seq 32 Sdd entries of m and
+ * of l and that times D of O, Sdd = the largest split count over Nkv_cache + 32 / G keys at (n_seq, H_kv); 0 for
+ * H_q / H_kv > 16.  No GPU needed. */
 size_t sfa_decode_ragged_step_workspace_bytes(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache,
                                               int64_t D, int dtype, unsigned flags);
 

@@ -644,6 +644,16 @@ int ring_ragged(const RingCall& c) {
                   c.cu_g ? ", groups" : "", (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
         return SFA_ERR_UNSUPPORTED;
     }
+    if ((c.flags & SFA_FLAG_RAGGED_DECODE_DRAFT) &&
+        (!dec || c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) || q->shape[1] > 16 * c.k_new->shape[1] ||
+         decode_ragged_flags_workspace(1, 1, 1, 1, 1, q->shape[3], q->dtype, SFA_FLAG_RAGGED_DECODE1) == 0)) {
+        set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE_DRAFT serves bf16 / f16 at head dims 64 / 80 / 96 / 128 and H_q / H_kv <= 16 "
+                  "together with SFA_FLAG_RAGGED_DECODE1, without fork groups (got dtype %d, head dim %lld, H_q %lld, H_kv %lld%s%s%s)",
+                  q->dtype, (long long)q->shape[3], (long long)q->shape[1], (long long)c.k_new->shape[1],
+                  dec ? "" : ", no SFA_FLAG_RAGGED_DECODE1", c.cu_g ? ", groups" : "",
+                  (c.flags & SFA_FLAG_FORCE_GENERIC) ? ", SFA_FLAG_FORCE_GENERIC" : "");
+        return SFA_ERR_UNSUPPORTED;
+    }
     if (dec && (c.cu_g || q->dtype == SFA_DTYPE_F32 || (c.flags & SFA_FLAG_FORCE_GENERIC) || q->shape[1] > 32 * c.k_new->shape[1] ||
                 decode_ragged_flags_workspace(1, 1, 1, 1, 1, q->shape[3], q->dtype, SFA_FLAG_RAGGED_DECODE1) == 0)) {
         set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 serves bf16 / f16 at head dims 64 / 80 / 96 / 128 and H_q / H_kv <= 32 "

@@ -225,6 +225,22 @@ struct Dec1Args {
     int want_d;
 };
 
+// ---- draft rows (SFA_FLAG_RAGGED_DECODE_DRAFT).  Sequence i with n_i >= 2 and G * n_i <= 32 is a
+// DRAFT sequence: its (token, head) rows are ONE 32-row block, computed by multi_draft_mfma_kernel under the plan
+// multi_plan(sink_len, window_len, n_i, want_d) into a third partial area indexed by sequence and block row:
+// ((hk * n_seq + i) * 32 + rho) * Sdd + split, rho = t * G + g.  The last trailing argument of the reduce instance of such
+// a call: it carries the decode area of Dec1Args too (single-token rows fold as there) and takes Dec1Args' place.
+struct DraftArgs {
+    float *Md, *Ld, *Od;         // the decode area, as in Dec1Args
+    int Sdw;
+    int want_d;                  // want_splits(1, Hkv, n_seq): the cap of both plans
+    float *Mf, *Lf, *Of;         // [Hkv * n_seq * 32][Sdd], the same, [...][Sdd][D]
+    int Sdd;                     // launched draft splits: max_splits(1, Hkv, n_seq, ns + Wc + 32 / G)
+};
+
+// wave-uniform (n is): decided from cu_q alone
+__device__ __forceinline__ bool draft_seq(int G, int n) { return n >= 2 && G * n <= 32; }
+
 // The optional trailing arguments of a kernel (`RA...` behind MultiArgs, `KA...` behind a storing kernel's own): of
 // RaggedArgs, Kv8Args, PageArgs and GroupArgs, in that order, an instance takes the ones its flags name and no other - its
 // signature, argument block and code stay those of a kernel without the others.  arg_of<W>(pack...) is the member of
@@ -239,13 +255,15 @@ __device__ __forceinline__ decltype(auto) arg_of(const A0& a0, const A&... rest)
 template <typename W, typename... A>
 constexpr bool has_arg = (std::is_same_v<A, W> || ...);
 // the guard of every kernel with such a pack: exactly the arguments that the flags name (their order is dispatch_pool's);
-// GroupArgs may follow on a (Ragged, Paged) instance, Dec1Args on a Ragged one without GroupArgs
+// GroupArgs may follow on a (Ragged, Paged) instance, Dec1Args or DraftArgs (one of the two) on a Ragged one without
+// GroupArgs
 template <bool Ragged, bool KV8, bool Paged, typename... A>
 constexpr bool tail_is = sizeof...(A) == (Ragged ? 1 : 0) + (KV8 ? 1 : 0) + (Paged ? 1 : 0) + (has_arg<GroupArgs, A...> ? 1 : 0) +
-                                             (has_arg<Dec1Args, A...> ? 1 : 0) &&
+                                             (has_arg<Dec1Args, A...> ? 1 : 0) + (has_arg<DraftArgs, A...> ? 1 : 0) &&
                          has_arg<RaggedArgs, A...> == Ragged && has_arg<Kv8Args, A...> == KV8 &&
                          has_arg<PageArgs, A...> == Paged && !(has_arg<GroupArgs, A...> && !(Ragged && Paged)) &&
-                         !(has_arg<Dec1Args, A...> && (!Ragged || has_arg<GroupArgs, A...>));
+                         !(has_arg<Dec1Args, A...> && (!Ragged || has_arg<GroupArgs, A...>)) &&
+                         !(has_arg<DraftArgs, A...> && (!Ragged || has_arg<GroupArgs, A...> || has_arg<Dec1Args, A...>));
 
 // the page of ring slot `slot` (in [0, Wc)) of cache row c; -1: the entry is unmapped ((unsigned)e >= n_pages).  A read
 // of an unmapped page addresses page 0, a store to one is dropped.  The index is 64-bit; slot >> shift < stride.
@@ -2184,6 +2202,419 @@ __global__ __launch_bounds__(kWaves * 64) void multi_decode1_mfma_kernel(MultiAr
     }
 }
 
+// ---- draft-row kernel (SFA_FLAG_RAGGED_DECODE_DRAFT).  The decode-row kernel above pays for a 32-row
+// MFMA block and uses G rows of it; a draft sequence (draft_seq: 2 <= n_i, G n_i <= 32) fills the same block with its
+// (token, head) rows rho = t G + g and is, to the hardware, the same object: one block over the whole cache of one
+// sequence.  A workgroup is (draft sequence, KV head, split of the sequence's OWN plan multi_plan(sink_len, window_len,
+// n_i, want_d)); the four waves take the split's tiles round-robin.  What differs from the decode-row kernel:
+//   * the mask is per ROW: the lane's row has its own query index t (tree: depth and ancestor mask, from tree_node called
+//     by every lane of every wave), tiles are classified against [0, n_i - 1] (tree: the block's depth range and the OR
+//     of the ancestor masks).  With a full ring token t no longer sees the t + 1 slots that it and its predecessors
+//     evict, so the oldest live ring tile and the wrap tile are edge tiles with a different cut per row; the chunk tile
+//     (one: n_i <= 32) is triangular, or an ancestor mask, or key_visible_admit's on a fresh slot;
+//   * the chunk tile holds n_i rows of k_new / v_new and goes through the same DMA as the cache tiles;
+//   * the ring depth at D = 64 (kDraftRingD64).
+// Data path (source-side swizzle, per-tile descriptor, hole offsets of D = 80 / 96, counted vmcnt waits, written-out
+// transposing V reads; FP8 pools on the converting register path), merge in wave order and partial layout are the
+// decode-row kernel's, restated; the partials go to the draft area (a.Mp / a.Lp / a.Op, stride a.Sw, here) at
+// ((hk n_seq + seq) 32 + rho) Sw + split.  Rows >= G n_i carry zero Q and are never stored.  Deterministic, no atomics.
+// R = 2 at D = 64 (64 KB: two workgroups per CU) against R = 4 (128 KB, one): the measured pair is in DESIGN.md 3.3.19;
+// R = 2 is the faster one there, unlike on the single-token rows of 3.3.17.
+constexpr int kDraftRingD64 = 2;
+
+template <typename T, int D, bool KV8, bool Paged, typename... KA>
+__global__ __launch_bounds__(kWaves * 64) void multi_draft_mfma_kernel(MultiArgs a, RaggedArgs rg, KA... ka) {
+    static_assert(tail_is<false, KV8, Paged, KA...>, "FP8 pool: (..., Kv8Args); paged pool: (..., PageArgs); both: (..., Kv8Args, PageArgs)");
+    [[maybe_unused]] const Kv8Args kv = arg_of<Kv8Args>(ka...);
+    [[maybe_unused]] const PageArgs pg = arg_of<PageArgs>(ka...);
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    constexpr int DK = D / 16;
+    constexpr int DVB = (D + 31) / 32;
+    constexpr int CPR = D / 8;
+    constexpr int ROWB = D <= 64 ? 128 : 256;
+    constexpr int PPR = ROWB / 16;                 // 16-byte positions per LDS row
+    constexpr int TILE_BYTES = kTile * ROWB;
+    constexpr int NLD = kTile * CPR / 64;
+    constexpr int NDMA = TILE_BYTES / 1024;        // DMA instructions per tile and tensor: 64 lanes x 16 bytes each
+    constexpr int LPT = 2 * NDMA;                  // loads of one tile (K and V)
+    constexpr int R = KV8 ? 1 : (D <= 64 ? kDraftRingD64 : 2);
+    constexpr int SLOT = 2 * TILE_BYTES;
+    constexpr int DP = D + 1;
+    static_assert((R & (R - 1)) == 0 && R <= 4 && (R - 1) * LPT <= 63, "the counted wait must fit vmcnt");
+    static_assert(kWaves * R * SLOT <= 128 * 1024, "the rings must fit 128 KB");
+    static_assert(2 * kWaves * 32 * 4 + 32 * DP * 4 <= kWaves * R * SLOT, "merge area must fit the tile area");
+    __shared__ __attribute__((aligned(1024))) char smem[kWaves * R * SLOT];
+
+    // (sequence, split, KV head); a workgroup without work leaves at once: the grid covers every sequence at every mix
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
+    const int seq = wid % rg.n_seq;
+    const int split = (wid / rg.n_seq) % a.Sw;
+    const int hk = wid / rg.n_seq / a.Sw;
+    const RaggedSeq sq = ragged_seq(rg, seq);
+    const int n = __builtin_amdgcn_readfirstlane(sq.n);
+    if (!draft_seq(a.G, n)) return;    // not a draft sequence: the kernels above serve it
+    const int c = __builtin_amdgcn_readfirstlane(cache_row<true>(a, seq));
+    if (c < 0) return;                 // inactive sequence: the reduce writes its zeros
+    const int prow = __builtin_amdgcn_readfirstlane(sq.c0);
+    const Fill f = get_fill<true, true>(a, c, n, rg.admit);    // a.want = want_d here: the sequence's own plan
+    if (split >= f.S) return;          // surplus of the full-cache grid at this fill level
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int nrows = a.G * n;         // <= 32
+    const bool row_live = r < nrows;   // row r = (token r / G, head r % G of the group)
+    const int tq = row_live ? r / a.G : 0;
+
+    // the lane's query index for the mask (tree: its depth td and ancestor mask tvis) and the block's range [tmin, tmax]
+    // (tree: the depth range over the live rows, vor = the OR of their masks), as multi_split_mfma_kernel has them
+    int td = tq, tmin = 0, tmax = n - 1;
+    uint64_t tvis = 0, vor = 0;
+    const bool is_tree = a.parent && __builtin_amdgcn_readfirstlane((int)ragged_is_tree(a, rg, c, n)) != 0;
+    if (is_tree) {
+        const TreeNode me = tree_node(n, a.parent + prow, a.wc, lane);
+        // every lane runs the cross-lane reads (a source lane masked off by a branch would read as 0), then selects
+        td = __shfl(me.depth, tq);
+        const uint64_t v = shfl64(me.vis, tq);
+        tvis = row_live ? v : 0;
+        int lo = row_live ? td : INT_MAX, hi = row_live ? td : -1;
+        vor = tvis;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            lo = min(lo, __shfl_xor(lo, s));
+            hi = max(hi, __shfl_xor(hi, s));
+            vor |= shfl64(vor, lane ^ s);
+        }
+        tmin = __builtin_amdgcn_readfirstlane(lo);   // wave-uniform: keep the tile classification scalar
+        tmax = __builtin_amdgcn_readfirstlane(hi);
+        vor = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(vor >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((unsigned)vor);
+    }
+
+    // Q arrives before the first DMA is issued (the pin below): a register load that is first used behind DMAs would make
+    // the compiler drain them all there
+    frag qf[DK];
+    {
+        const int head = hk * a.G + (row_live ? r % a.G : 0);
+        const char* qp = a.q.ptr + ((int64_t)head * a.q.sh + (int64_t)(prow + tq) * a.q.sn) * 2;
+        u32x4 raw[DK];
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) raw[ks] = *reinterpret_cast<const u32x4*>(qp + (2 * ks + h) * 16);
+#pragma unroll
+        for (int ks = 0; ks < DK; ++ks) {
+            asm volatile("" : "+v"(raw[ks]));
+            if (!row_live) raw[ks] = u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(frag, raw[ks]);
+        }
+    }
+
+    char* ring = smem + wave * R * SLOT;
+    const int es = 2;
+    const int tbeg = split * f.tps;
+    const int tend = tbeg + f.tps < f.T ? tbeg + f.tps : f.T;
+    const int nk = tend - tbeg > wave ? (tend - tbeg - wave + kWaves - 1) / kWaves : 0;    // this wave's tiles: tbeg + wave + 4 k
+    // tile k of the wave and its class against the block's rows; a live ring tile of a paged pool gets its page
+    auto tile_k = [&](int k, TileInfo& ti) {
+        ti = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, n, prow, pg.shift);
+        const int cls = is_tree ? tile_class_t<true>(a, ti, tmin, tmax, vor, f.nsk) : tile_class(a, ti, tmin, tmax, f.nsk);
+        if constexpr (Paged) {
+            if (cls != 0 && ti.seg == 1) tile_page(ti, a, pg, c, KV8 ? 1 : es);
+        }
+        return cls;
+    };
+
+    const int ksw_l = ROWB == 256 ? (r & 15) : ((r >> 1) & 7);
+    const int k_rowoff = r * ROWB;
+    const int q4 = (lane & 15) >> 2, p4 = lane & 3, g1 = (lane >> 4) & 1;
+    const int vsw_l = ROWB == 256 ? (q4 << 2) : (((q4 >> 1) & 1) << 2);
+    const int v_rowoff = (4 * h + q4) * ROWB + (p4 & 1) * 8;
+    const int v_chunk_lo = 2 * g1 + (p4 >> 1);
+
+    float m = -INFINITY, l = 0.f;   // log2 domain; l: this half-wave's partial sum
+    f32x16 o[DVB];
+#pragma unroll
+    for (int db = 0; db < DVB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
+    const float c2 = a.scale_log2;
+
+    // one live tile from the LDS image (kl, kl + TILE_BYTES); cur: its descriptor, read by the edge mask only.  The mask
+    // is the lane's own row's: accumulator element x of lane (r, h) is key (x & 3) + 8 (x >> 2) + 4 h against row r
+    auto consume = [&](const TileInfo& cur, bool edge, const char* kl) {
+        const char* vl = kl + TILE_BYTES;
+        f32x16 s;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) s[x] = 0.f;
+        {
+            frag kf[DK];
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) kf[ks] = *reinterpret_cast<const frag*>(kl + k_rowoff + (((2 * ks + h) ^ ksw_l) << 4));
+#pragma unroll
+            for (int ks = 0; ks < DK; ++ks) s = M::run(kf[ks], qf[ks], s);
+        }
+        if (edge) {
+            if (admitting(f, cur)) {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible_admit(a, f, cur, kk, td) ? s[x] : -INFINITY;
+                }
+            } else if (is_tree && cur.seg == 2) {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible_t<true>(a, f, cur, kk, td, tvis) ? s[x] : -INFINITY;
+                }
+            } else {
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int kk = (x & 3) + 8 * (x >> 2) + 4 * h;
+                    s[x] = key_visible(a, f, cur, kk, td) ? s[x] : -INFINITY;
+                }
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) mx = fmaxf(mx, s[x]);
+        mx = half_swap_max(mx);
+        const float m_new = fmaxf(m, mx * c2);
+        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m - m_safe);
+        float rs = 0.f;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            s[x] = __builtin_amdgcn_exp2f(fmaf(s[x], c2, -m_safe));
+            rs += s[x];
+        }
+        l = fmaf(l, alpha, rs);
+        m = m_new;
+#pragma unroll
+        for (int db = 0; db < DVB; ++db)
+#pragma unroll
+            for (int x = 0; x < 16; ++x) o[db][x] *= alpha;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            frag pf;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) pf[x] = (typename M::elem)s[8 * st + x];
+            const char* vrow = vl + 16 * st * ROWB + v_rowoff;
+            // the transposing reads are written out, as in the decode-row kernel: in front of the builtin the compiler
+            // drains vmcnt(0) while a DMA is in flight.  All reads of the step are issued, then each operand is pinned
+            // behind one lgkmcnt(0)
+            s16x4 lo[DVB], hi[DVB];
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                const int ch = (4 * db + v_chunk_lo) ^ vsw_l;
+                const unsigned p1 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(vrow + (ch << 4));
+                asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
+                             : "=&v"(lo[db]), "=&v"(hi[db]) : "v"(p1), "n"(8 * ROWB) : "memory");
+            }
+#pragma unroll
+            for (int db = 0; db < DVB; ++db) {
+                s16x8 vv;
+                vv[0] = lo[db][0]; vv[1] = lo[db][1]; vv[2] = lo[db][2]; vv[3] = lo[db][3];
+                vv[4] = hi[db][0]; vv[5] = hi[db][1]; vv[6] = hi[db][2]; vv[7] = hi[db][3];
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vv)::"memory");
+                o[db] = M::run(__builtin_bit_cast(frag, vv), pf, o[db]);
+            }
+        }
+    };
+
+    if constexpr (!KV8) {
+        // ---- the DMA ring.  cq: the classes of the tiles in the ring, two bits per slot k mod R
+        unsigned cq = 0;
+        // positions of a 256-byte LDS row that hold no chunk (D = 80 / 96): OR-ed onto the offset, which then lies out of
+        // range.  Per lane and instruction, loop-invariant; pinned in VGPRs
+        [[maybe_unused]] unsigned khole[NDMA], vhole[NDMA];
+        if constexpr (CPR < PPR) {
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int key = (64 * j + lane) / PPR, pos = (64 * j + lane) % PPR;
+                khole[j] = (pos ^ (key & 15)) < CPR ? 0u : 0xFFFFFFF0u;
+                vhole[j] = (pos ^ ((key & 3) << 2)) < CPR ? 0u : 0xFFFFFFF0u;
+                asm volatile("" : "+v"(khole[j]), "+v"(vhole[j]));
+            }
+        }
+        auto issue = [&](int k) {
+            TileInfo ti;
+            const int cls = tile_k(k, ti);
+            const int sl = k & (R - 1);
+            cq = (cq & ~(3u << (2 * sl))) | ((unsigned)cls << (2 * sl));
+            if (cls == 0) return;
+            // the tile's rows [0, count) - of the cache, or of k_new / v_new from the sequence's first packed row: every
+            // offset below lies inside (the launcher has bounded the row strides), rows past the count are clamped
+            const unsigned ksn = (unsigned)ti.ksn, vsn = (unsigned)ti.vsn;
+            const unsigned last = (unsigned)(ti.count - 1);
+            char* kl = ring + sl * SLOT;
+            const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)ti.k, 0, (int)(last * ksn + D * 2), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int kch = pos ^ (ROWB == 256 ? (key & 15) : ((key >> 1) & 7));
+                unsigned ko = row * ksn + (unsigned)(kch * 16);
+                if constexpr (CPR < PPR) ko |= khole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(kl + 1024 * j), 16, ko, 0, 0, 0);
+            }
+            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)ti.v, 0, (int)(last * vsn + D * 2), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < NDMA; ++j) {
+                const int p = 64 * j + lane;
+                const int key = p / PPR, pos = p % PPR;
+                const unsigned row = (unsigned)key < last ? (unsigned)key : last;
+                const int vch = pos ^ (ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2));
+                unsigned vo = row * vsn + (unsigned)(vch * 16);
+                if constexpr (CPR < PPR) vo |= vhole[j];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(kl + TILE_BYTES + 1024 * j), 16, vo, 0, 0, 0);
+            }
+        };
+#pragma unroll
+        for (int k = 0; k < R - 1; ++k)
+            if (k < nk) issue(k);
+#pragma unroll 1
+        for (int k = 0; k < nk; ++k) {
+            // slot (k - 1) mod R is free: every LDS read of tile k - 1 returned at the end of the last trip
+            if (k + R - 1 < nk) issue(k + R - 1);
+            int pend = 0;              // live tiles issued behind tile k: their loads may stay outstanding
+#pragma unroll
+            for (int d = 1; d < R; ++d)
+                if (k + d < nk && ((cq >> (2 * ((k + d) & (R - 1)))) & 3u) != 0) ++pend;
+            const int cls = (cq >> (2 * (k & (R - 1)))) & 3u;
+            if (cls == 0) continue;
+            if (pend >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 3 ? 3 : 0) * LPT) : "memory");
+            else if (pend == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 2 ? 2 : 0) * LPT) : "memory");
+            else if (pend == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R > 1 ? 1 : 0) * LPT) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            TileInfo cur{};
+            if (cls == 2) cur = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, n, prow, pg.shift);
+            consume(cur, cls == 2, ring + (k & (R - 1)) * SLOT);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slot may be overwritten by the next trip's DMA
+        }
+    } else {
+        // ---- FP8 pool: the converting register path of the KV8 decode-row instances, one slot, one tile in flight
+        char* kl = ring;
+        char* vl = kl + TILE_BYTES;
+        u32x4 kst[NLD], vst[NLD];
+        const float ksc = kv8_scale(kv, 0, a.Hkv, hk), vsc = kv8_scale(kv, 1, a.Hkv, hk);
+        bool st8 = false;
+        auto issue_loads = [&](const TileInfo& ti) {
+            st8 = ti.seg != 2;
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) {
+                const int ci = lane + 64 * j;
+                const int key = ci / CPR, ch = ci % CPR;
+                const int row = key < ti.count ? key : ti.count - 1;
+                if (st8) {
+                    const uint2 k8 = *reinterpret_cast<const uint2*>(ti.k + row * ti.ksn + ch * 8);
+                    const uint2 v8 = *reinterpret_cast<const uint2*>(ti.v + row * ti.vsn + ch * 8);
+                    kst[j][0] = k8.x, kst[j][1] = k8.y, vst[j][0] = v8.x, vst[j][1] = v8.y;
+                } else {
+                    kst[j] = *reinterpret_cast<const u32x4*>(ti.k + row * ti.ksn + ch * 16);
+                    vst[j] = *reinterpret_cast<const u32x4*>(ti.v + row * ti.vsn + ch * 16);
+                }
+            }
+        };
+        auto write_lds = [&]() {
+            if (st8) {                 // the conversion: between the global load and the LDS store
+#pragma unroll
+                for (int j = 0; j < NLD; ++j) {
+                    kst[j] = kv8_read<T>(kst[j][0], kst[j][1], ksc);
+                    vst[j] = kv8_read<T>(vst[j][0], vst[j][1], vsc);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NLD; ++j) {
+                const int ci = lane + 64 * j;
+                const int key = ci / CPR, ch = ci % CPR;
+                const int ksw = ROWB == 256 ? (key & 15) : ((key >> 1) & 7);
+                const int vsw = ROWB == 256 ? ((key & 3) << 2) : (((key >> 1) & 1) << 2);
+                *reinterpret_cast<u32x4*>(kl + key * ROWB + ((ch ^ ksw) << 4)) = kst[j];
+                *reinterpret_cast<u32x4*>(vl + key * ROWB + ((ch ^ vsw) << 4)) = vst[j];
+            }
+        };
+        auto next_live = [&](int k, TileInfo& ti, int& cls) {
+            for (; k < nk; ++k)
+                if ((cls = tile_k(k, ti)) != 0) break;
+            return k;
+        };
+        // no descriptor lives across a tile's math: an edge tile builds its own again for the mask
+        TileInfo ti;
+        int ccls = 0, ncls = 0;
+        int k = next_live(0, ti, ccls);
+        if (k < nk) {
+            issue_loads(ti);
+            write_lds();
+        }
+        while (k < nk) {
+            const int kn = next_live(k + 1, ti, ncls);
+            if (kn < nk) issue_loads(ti);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this tile's LDS writes landed
+            TileInfo cur{};
+            if (ccls == 2) cur = tile_info<true, KV8, Paged>(a, f, tbeg + wave + kWaves * k, 0, c, hk, es, n, prow, pg.shift);
+            consume(cur, ccls == 2, kl);
+            if (kn < nk) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of this tile returned before the overwrite
+                write_lds();
+            }
+            k = kn, ccls = ncls;
+        }
+    }
+
+    // ---- merge the 4 waves' (m, l, O) in wave order through LDS (the rings are free after the barrier: every DMA of a
+    // wave was waited for by its last trip)
+    const float lw = half_swap_sum(l);
+    __syncthreads();
+    float* sm = reinterpret_cast<float*>(smem);      // [wave][32]
+    float* sl = sm + kWaves * 32;                    // [wave][32]
+    float* so = sl + kWaves * 32;                    // [32][DP]
+    if (h == 0) {
+        sm[wave * 32 + r] = m;
+        sl[wave * 32 + r] = lw;
+    }
+    __syncthreads();
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) mstar = fmaxf(mstar, sm[w * 32 + r]);
+    const float wgt = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mstar);
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int db = 0; db < DVB; ++db)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int col = 32 * db + 8 * (i >> 2) + 4 * h + (i & 3);
+                    if (col < D) {
+                        float* p = so + r * DP + col;
+                        *p = (w == 0 ? 0.f : *p) + o[db][i] * wgt;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    // one partial per (sequence, block row) and split, in the draft area
+    const int64_t row0 = ((int64_t)hk * rg.n_seq + seq) * 32;
+    if (tid < nrows) {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) ms = fmaxf(ms, sm[w * 32 + tid]);
+        float lt = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const float mw = sm[w * 32 + tid];
+            lt += mw == -INFINITY ? 0.f : sl[w * 32 + tid] * __builtin_amdgcn_exp2f(mw - ms);
+        }
+        a.Mp[(row0 + tid) * a.Sw + split] = ms;
+        a.Lp[(row0 + tid) * a.Sw + split] = lt;
+    }
+    for (int e = tid; e < nrows * D; e += kWaves * 64) {
+        const int rr = e / D, d = e - rr * D;
+        a.Op[((row0 + rr) * a.Sw + split) * D + d] = so[rr * DP + d];
+    }
+}
+
 // 8 codes (e4m3fn, byte i = element i) -> 8 elements of T, exactly: the packed conversion at scale 1 (every e4m3fn value
 // is a bf16 and an f16 value)
 template <typename T>
@@ -2594,6 +3025,37 @@ __global__ __launch_bounds__(1024) void ragged_prep_dec1_kernel(RaggedArgs rg, i
     }
 }
 
+// the preparation launch of a call with SFA_FLAG_RAGGED_DECODE_DRAFT (always with SFA_FLAG_RAGGED_DECODE1), alone or with
+// SFA_FLAG_RAGGED_CHUNK128: the tables of the kernel above, except that the one 32-row block of a draft sequence
+// (draft_seq) is surplus as well - multi_draft_mfma_kernel finds its sequences from cu_q itself.  A draft sequence has
+// fewer than kChunkRows rows, so it is never a chunk sequence.
+__global__ __launch_bounds__(1024) void ragged_prep_draft_kernel(RaggedArgs rg, int2* blk, int* rowseq, int2* wblk, int G,
+                                                                 int nrb, int nwb, int tree) {
+    for (int64_t x = threadIdx.x; x < (int64_t)nrb + rg.T + nwb; x += 1024) {
+        const int kind = x < nrb ? 0 : (x < (int64_t)nrb + rg.T ? 1 : 2);     // blk, rowseq, wblk
+        const int id = (int)(kind == 0 ? x : kind == 1 ? x - nrb : x - nrb - rg.T);
+        const int unit = kind == 2 ? kChunkRows : 32;
+        int lo = 0, hi = rg.n_seq - 1;       // the last i with start(i) <= id; sequence 0 starts at 0
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const int c = ragged_seq(rg, mid).c0;
+            const int64_t start = kind == 1 ? c : (int64_t)G * c / unit + mid;
+            if (start <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        const RaggedSeq s = ragged_seq(rg, lo);
+        if (kind == 1) {
+            rowseq[id] = (id >= s.c0 && id < s.c0 + s.n) ? lo : -1;
+        } else {
+            const int64_t local = id - ((int64_t)G * s.c0 / unit + lo);
+            const bool chunk = nwb > 0 && chunk_seq(G, s.n, tree);
+            const bool own = s.n == 1 || draft_seq(G, s.n);      // served by the decode-row or the draft-row kernel
+            const bool hit = local >= 0 && local * unit < (int64_t)G * s.n && !own && chunk == (kind == 2);
+            (kind == 2 ? wblk : blk)[id] = hit ? make_int2(lo, (int)local) : make_int2(-1, 0);
+        }
+    }
+}
+
 // a packed (ragged) partial row: rowid = (hk * T + packed row) * G + g.  Finds the row's sequence in the table: the
 // callers go on as for B = 1 with rho = the row within the sequence, n = its length and c0 = its first packed row.
 // False: the row has no work (padding, an empty or inactive sequence); rho = the query head within the group and tp =
@@ -2889,6 +3351,26 @@ __global__ __launch_bounds__(256) void multi_reduce_kernel(MultiArgs a, int nred
             Mr = dd.Md + drow * dd.Sdw;
             Lr = dd.Ld + drow * dd.Sdw;
             Or = dd.Od + drow * dd.Sdw * D;
+        }
+    }
+    // Draft (a trailing DraftArgs in Dec1Args' place): a decode row folds as above; a row of a draft sequence folds the S
+    // partials of the draft plan from the third area, at block row rho = t G + g of its sequence
+    if constexpr (has_arg<DraftArgs, RA...>) {
+        const DraftArgs& dr = arg_of<DraftArgs>(ra...);
+        if (rn == 1) {
+            const int seq = __builtin_amdgcn_readfirstlane(rg.rowseq[prow]);
+            const int64_t drow = ((int64_t)hk * rg.n_seq + seq) * a.G + rho;
+            S = __builtin_amdgcn_readfirstlane(multi_plan(f.sink_len, f.wl, 1, dr.want_d).S);
+            Mr = dr.Md + drow * dr.Sdw;
+            Lr = dr.Ld + drow * dr.Sdw;
+            Or = dr.Od + drow * dr.Sdw * D;
+        } else if (draft_seq(a.G, rn)) {
+            const int seq = __builtin_amdgcn_readfirstlane(rg.rowseq[prow]);
+            const int64_t drow = ((int64_t)hk * rg.n_seq + seq) * 32 + rho;
+            S = __builtin_amdgcn_readfirstlane(multi_plan(f.sink_len, f.wl, rn, dr.want_d).S);
+            Mr = dr.Mf + drow * dr.Sdd;
+            Lr = dr.Lf + drow * dr.Sdd;
+            Or = dr.Of + drow * dr.Sdd * D;
         }
     }
     [[maybe_unused]] const float *Mgr = nullptr, *Lgr = nullptr, *Ogr = nullptr;
@@ -3618,6 +4100,31 @@ int launch_dec1(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, 
     return launch_status("decode_multi_dec1");
 }
 
+// the draft-row kernel of a packed call with SFA_FLAG_RAGGED_DECODE_DRAFT: behind the decode launch, on Hkv * Sdd * n_seq
+// blocks whatever the pack holds.  Its MultiArgs are the call's with the draft plan's cap and the draft area in the place
+// of want, Sw and the partials.
+template <typename T>
+int launch_draft(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, const DraftArgs& dr, hipStream_t stream) {
+    MultiArgs ad = a;
+    ad.want = dr.want_d, ad.Sw = dr.Sdd, ad.Mp = dr.Mf, ad.Lp = dr.Lf, ad.Op = dr.Of;
+    const dim3 grid((unsigned)((int64_t)a.Hkv * dr.Sdd * rg.n_seq));
+    auto go = [&](auto d) {
+        constexpr int D = decltype(d)::value;
+        dispatch_pool(pool, [&](auto p, auto... tail) {
+            using P = decltype(p);
+            multi_draft_mfma_kernel<T, D, P::KV8, P::Paged><<<grid, kWaves * 64, 0, stream>>>(ad, rg, tail...);
+        });
+    };
+    switch (a.D) {
+        case 64: go(std::integral_constant<int, 64>{}); break;
+        case 80: go(std::integral_constant<int, 80>{}); break;
+        case 96: go(std::integral_constant<int, 96>{}); break;
+        case 128: go(std::integral_constant<int, 128>{}); break;
+        default: set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE_DRAFT has no kernel for head dim %d", a.D); return SFA_ERR_UNSUPPORTED;
+    }
+    return launch_status("decode_multi_draft");
+}
+
 // head dim 256 of a packed call: the pair kernel in the form of the pool, Tree on or off; the grid of launch_mfma
 template <typename T>
 int launch_mfma_d256(const MultiArgs& a, const RaggedArgs& rg, const SlotPool& pool, hipStream_t stream) {
@@ -3647,7 +4154,7 @@ int launch_mfma_d(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool
 // pool: that of a packed call (the API admits an FP8 or paged one for the MFMA instances only)
 template <typename T>
 int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, const GroupArgs* grp, bool mfma, hipStream_t stream,
-                const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr, bool raw8 = false) {
+                const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr, bool raw8 = false, const DraftArgs* dr = nullptr) {
     int st = SFA_OK;
     const int64_t rows = (int64_t)a.B * a.Hkv * a.R;
     if constexpr (sizeof(T) == 2) {
@@ -3656,6 +4163,8 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
         if (!st && mfma && ck) st = launch_chunk<T>(a, *rg, pool, *ck, stream);
         // decode sequences: likewise, into the second partial area, which the reduce instance with Dec1Args folds
         if (!st && mfma && dd) st = launch_dec1<T>(a, *rg, pool, *dd, raw8, stream);
+        // draft sequences (dr comes with dd): into the third area; the reduce instance with DraftArgs folds both
+        if (!st && mfma && dr) st = launch_draft<T>(a, *rg, pool, *dr, stream);
     }
     if (!mfma) {
         const dim3 grid((unsigned)cdiv64(rows, 4), (unsigned)a.Sw);
@@ -3685,7 +4194,8 @@ int launch_rest(const MultiArgs& a, const RaggedArgs* rg, const SlotPool& pool, 
                         return;
                     }
                 }
-                if (dd) multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail..., *dd);
+                if (dr) multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail..., *dr);
+                else if (dd) multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail..., *dd);
                 else multi_reduce_kernel<T, M::Dyn, M::Slots, true, P::KV8, P::Paged><<<rgrid, 256, 0, stream>>>(a, nred, *rg, tail...);
             });
         else if constexpr (M::Ragged) multi_reduce_kernel<T, M::Dyn, M::Slots, true><<<rgrid, 256, 0, stream>>>(a, nred, *rg);
@@ -3726,7 +4236,8 @@ MultiArgs multi_args(const RingCall& c, bool attend) {
 
 // the launches of an attention call by q's dtype; *mfma: whether the MFMA split kernel serves it
 int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bool* mfma, const char** dname,
-                 const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr) {
+                 const GroupArgs* grp = nullptr, const ChunkTable* ck = nullptr, const Dec1Args* dd = nullptr,
+                 const DraftArgs* dr = nullptr) {
     const int dt = c.q->dtype;
     *mfma = dt != SFA_DTYPE_F32 && (rg ? mfma_packed_head_dim(a.D) : mfma_head_dim(a.D)) && !(c.flags & SFA_FLAG_FORCE_GENERIC);
     *dname = dt == SFA_DTYPE_F32 ? "f32" : dt == SFA_DTYPE_F16 ? "f16" : "bf16";
@@ -3736,8 +4247,8 @@ int launch_dtype(const RingCall& c, const MultiArgs& a, const RaggedArgs* rg, bo
     }
     if (dt == SFA_DTYPE_F32) return launch_rest<float>(a, rg, SlotPool{}, nullptr, false, c.stream);
     const bool raw8 = (c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) != 0;     // the API admits it with dd on an FP8 pool only
-    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8);
-    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8);
+    if (dt == SFA_DTYPE_F16) return launch_rest<f16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8, dr);
+    return launch_rest<bf16_t>(a, rg, c.pool, grp, *mfma, c.stream, ck, dd, raw8, dr);
 }
 
 }  // namespace
@@ -3882,6 +4393,19 @@ Dec1Geom dec1_geom(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t Nkv_cache) {
     return g;
 }
 
+// the same for the draft rows of a call with SFA_FLAG_RAGGED_DECODE_DRAFT (G <= 16): a draft sequence has at most 32 / G
+// tokens and one block of 32 partial rows per KV head
+struct DraftGeom {
+    int64_t Sdd, P;                  // P = Hkv * n_seq * 32 * Sdd sizes the draft partials
+};
+
+DraftGeom draft_geom(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t Nkv_cache) {
+    DraftGeom g;
+    g.Sdd = max_splits(1, Hkv, n_seq, Nkv_cache + 32 / (Hq / Hkv));   // bound of multi_plan(sink_len, window_len, n_i, want).S
+    g.P = Hkv * n_seq * 32 * g.Sdd;
+    return g;
+}
+
 }  // namespace
 
 // the workspace of a packed call by its flags: that of the ungrouped call, then wblk with SFA_FLAG_RAGGED_CHUNK128, then
@@ -3895,7 +4419,13 @@ size_t decode_ragged_flags_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int
     if (sz == 0 || !dec) return sz;
     if (dtype == SFA_DTYPE_F32 || !mfma_head_dim((int)D) || Hq / Hkv > 32) return 0;
     const Dec1Geom g = dec1_geom(n_seq, Hq, Hkv, Nkv_cache);
-    return sz + 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)D * sizeof(float));
+    sz += 2 * al256((size_t)g.P * sizeof(float)) + al256((size_t)g.P * (size_t)D * sizeof(float));
+    if (!(flags & SFA_FLAG_RAGGED_DECODE_DRAFT)) return sz;
+    // SFA_FLAG_RAGGED_DECODE_DRAFT (read with the decode flag only): the draft partials behind the decode partials; 0 for
+    // G > 16, where no sequence can be a draft sequence and the flag is refused
+    if (Hq / Hkv > 16) return 0;
+    const DraftGeom d = draft_geom(n_seq, Hq, Hkv, Nkv_cache);
+    return sz + 2 * al256((size_t)d.P * sizeof(float)) + al256((size_t)d.P * (size_t)D * sizeof(float));
 }
 
 int decode_ragged_launch(const RingCall& c) {
@@ -3929,6 +4459,8 @@ int decode_ragged_launch(const RingCall& c) {
     // preparation marks the decode sequences as well
     const bool dec = (c.flags & SFA_FLAG_RAGGED_DECODE1) != 0;
     Dec1Args dd{};
+    const bool draft = dec && (c.flags & SFA_FLAG_RAGGED_DECODE_DRAFT) != 0;
+    DraftArgs dr{};
     if (chunk || dec) {
         int2* wblk = reinterpret_cast<int2*>(ws + decode_ragged_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, c.sink_len + c.window_len, a.D, c.q->dtype));
         if (chunk) ck = ChunkTable{wblk, (int)(cdiv64(g.G * T, kChunkRows) + c.n_seq)};
@@ -3946,14 +4478,31 @@ int decode_ragged_launch(const RingCall& c) {
         const View* vs[] = {&a.sk, &a.sv, &a.wk, &a.wv, &a.kn, &a.vn};
         for (const View* v : vs)
             if (v->sn * 2 * kTile >= (1ll << 31)) {
-                set_error("decode_ragged: SFA_FLAG_RAGGED_DECODE1 needs K/V row strides below 2^25 elements");
+                set_error("decode_ragged: %s needs K/V row strides below 2^25 elements",
+                          draft ? "SFA_FLAG_RAGGED_DECODE_DRAFT" : "SFA_FLAG_RAGGED_DECODE1");
                 return SFA_ERR_UNSUPPORTED;
             }
         if ((int64_t)a.Hkv * dg.Sdw * c.n_seq >= (1ll << 31)) {
             set_error("decode_ragged: grid too large");
             return SFA_ERR_UNSUPPORTED;
         }
-        ragged_prep_dec1_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+        if (draft) {    // SFA_FLAG_RAGGED_DECODE_DRAFT (the API admits it with the decode flag and G <= 16): the third area
+            const DraftGeom fg = draft_geom(c.n_seq, c.q->shape[1], a.Hkv, Nc);
+            char* fw = ws + decode_ragged_flags_workspace(c.n_seq, c.q->shape[1], a.Hkv, T, Nc, a.D, c.q->dtype,
+                                                          c.flags & (SFA_FLAG_RAGGED_CHUNK128 | SFA_FLAG_RAGGED_DECODE1));
+            dr.Md = dd.Md, dr.Ld = dd.Ld, dr.Od = dd.Od, dr.Sdw = dd.Sdw, dr.want_d = dd.want_d;
+            dr.Mf = reinterpret_cast<float*>(fw);
+            dr.Lf = reinterpret_cast<float*>(fw + al256((size_t)fg.P * sizeof(float)));
+            dr.Of = reinterpret_cast<float*>(fw + 2 * al256((size_t)fg.P * sizeof(float)));
+            dr.Sdd = (int)fg.Sdd;
+            if ((int64_t)a.Hkv * fg.Sdd * c.n_seq >= (1ll << 31)) {
+                set_error("decode_ragged: grid too large");
+                return SFA_ERR_UNSUPPORTED;
+            }
+            ragged_prep_draft_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+        } else {
+            ragged_prep_dec1_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
+        }
     } else if (chunk) {
         ragged_prep_chunk_kernel<<<1, 1024, 0, c.stream>>>(rg, blk, rowseq, const_cast<int2*>(ck.wblk), a.G, a.nrb, ck.nwb, c.parent ? 1 : 0);
     } else {
@@ -3987,12 +4536,14 @@ int decode_ragged_launch(const RingCall& c) {
     }
     bool mfma;
     const char* dname;
-    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr, chunk ? &ck : nullptr, dec ? &dd : nullptr))) return st;
+    if ((st = launch_dtype(c, a, &rg, &mfma, &dname, c.cu_g ? &gr : nullptr, chunk ? &ck : nullptr, dec ? &dd : nullptr,
+                           draft ? &dr : nullptr))) return st;
     const char *ad = admit ? "_admit" : "", *cm = c.commit ? "_commit" : "";
     const char* fam = c.parent ? "tree" : "multi";
     if (mfma)
-        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "",
-                 !dec ? "" : (c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) ? "_dec1raw" : "_dec1", ad, cm, c.cu_g ? "_group" : "", pool_tag(c.pool));
+        set_path("decode_%s_mfma_%s_d%d_rb%d_ragged%s%s%s%s%s%s%s", fam, dname, a.D, a.nrb, chunk ? "_chunk128" : "",
+                 !dec ? "" : (c.flags & SFA_FLAG_RAGGED_DECODE1_RAW8) ? "_dec1raw" : "_dec1", draft ? "_draft" : "", ad, cm,
+                 c.cu_g ? "_group" : "", pool_tag(c.pool));
     else set_path("decode_%s_f32_%s_d%d_ragged%s%s", fam, dname, a.D, ad, cm);
     return SFA_OK;
 }

@@ -132,7 +132,8 @@ int decode_ragged_launch(const RingCall& c);
 // exists (fp32, head dims other than 64 / 80 / 96 / 128)
 size_t decode_ragged_chunk_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype);
 // by the flags of the call (SFA_FLAG_RAGGED_CHUNK128, SFA_FLAG_RAGGED_DECODE1; other bits are ignored): the ungrouped
-// workspace, then the block table, then the decode partials; 0 where a flag is refused (the above, and G > 32 for DECODE1)
+// workspace, then the block table, then the decode partials; 0 where a flag is refused (the above, and G > 32 for DECODE1).
+// SFA_FLAG_RAGGED_DECODE_DRAFT is read with DECODE1 only: the draft partials behind the decode partials, 0 for G > 16
 size_t decode_ragged_flags_workspace(int64_t n_seq, int64_t Hq, int64_t Hkv, int64_t T, int64_t Nkv_cache, int64_t D, int dtype,
                                      unsigned flags);
 // the same with fork groups (c.cu_g): the ungrouped workspace plus the group partials and the group tables; 0 where no

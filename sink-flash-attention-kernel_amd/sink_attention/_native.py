@@ -29,6 +29,7 @@ FLAG_RAGGED_ADMIT = 0x40      # sfa_decode_ring_ragged_slots: a sequence on a fr
 FLAG_RAGGED_CHUNK128 = 0x80   # the packed step: sequences of >= 128 rows run the 128-row chunk kernel (include/sfa.h)
 FLAG_RAGGED_DECODE1 = 0x100   # the packed step: single-token sequences run the decode-row kernel (include/sfa.h)
 FLAG_RAGGED_DECODE1_RAW8 = 0x200   # with FLAG_RAGGED_DECODE1 on an FP8 pool: raw codes through the LDS DMA (include/sfa.h)
+FLAG_RAGGED_DECODE_DRAFT = 0x400   # with FLAG_RAGGED_DECODE1: sequences of 2 <= n_i, G n_i <= 32 run the draft-row kernel (include/sfa.h)
 ABI_VERSION = 2
 
 # flags every backward of the ops passes to sfa_bwd / sfa_bwd_varlen (and to the workspace query): the overlap is ON by

@@ -1441,8 +1441,22 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         paged; False: the call above, unchanged): the decode-row kernel streams the raw FP8 codes to LDS as it streams
         the rows of a 16-bit pool, converts them behind the LDS read and folds the per-head scales into the logit scale
         and into the output (DESIGN.md 3.3.18).  Same contracts and the same workspace size as ``decode_kernel=True``;
-        with power-of-two scales the decode rows are bitwise those of ``decode_kernel=True`` alone."""
+        with power-of-two scales the decode rows are bitwise those of ``decode_kernel=True`` alone.
+
+        ``decode_kernel="draft"`` (``SFA_FLAG_RAGGED_DECODE1 | SFA_FLAG_RAGGED_DECODE_DRAFT``): ``True``
+        for the single-token sequences, plus the draft-row kernel for every DRAFT sequence - ``n_i >= 2`` tokens with
+        ``G * n_i <= 32`` rows (G 4: up to 8 tokens, G 8: up to 4, MQA: up to 32), the chains and small trees of
+        speculative decoding, decided on the device from ``cu_q``.  Its (token, head) rows are one 32-row block that
+        streams the cache as a decode row does, with a mask per row (``parent``: the tree mask; a fresh slot admitted with
+        such a chunk is included) and a split count from its own state and ``(n_seq, H_kv)``: its output meets the
+        default call's tolerance and does not depend on ``T``, on its place in the pack or on its neighbours.  Every
+        other row is bitwise the row of ``decode_kernel=True``; pool and state rows end bitwise the same.  ``raw_fp8=True``
+        still applies to the single-token rows only.  Refused where ``decode_kernel=True`` is, and for
+        ``H_q / H_kv > 16`` (no sequence can qualify).  Any other value of ``decode_kernel`` is a ``ValueError``."""
         from . import _native as N
+        if not isinstance(decode_kernel, bool) and not (isinstance(decode_kernel, str) and decode_kernel == "draft"):
+            raise ValueError(f"ragged_step_dyn(decode_kernel={decode_kernel!r}): decode_kernel is False, True or \"draft\"")
+        draft = decode_kernel == "draft"
         if raw_fp8:
             if not decode_kernel:
                 raise ValueError("ragged_step_dyn(raw_fp8=True) needs decode_kernel=True: it is a data path of the decode-row kernel")
@@ -1453,9 +1467,10 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
             why = ("takes no groups=" if groups is not None else "takes no force_generic=True" if force_generic else
                    f"serves bf16 / fp16, got {q.dtype}" if q.dtype not in (torch.bfloat16, torch.float16) else
                    f"serves head dims 64 / 80 / 96 / 128, got {q.shape[-1]}" if q.shape[-1] not in (64, 80, 96, 128) else
-                   f"serves H_q / H_kv <= 32, got {G}" if G > 32 else None)
+                   f"serves H_q / H_kv <= 32, got {G}" if G > 32 else
+                   f"serves H_q / H_kv <= 16, got {G}: no sequence can have 2 tokens in 32 rows" if draft and G > 16 else None)
             if why:
-                raise ValueError(f"ragged_step_dyn(decode_kernel=True) {why}: the decode-row kernel has no such instance")
+                raise ValueError(f"ragged_step_dyn(decode_kernel={decode_kernel!r}) {why}: the decode-row kernel has no such instance")
         dev_state = self._require_pool("ragged_step_dyn")
         if chunk_kernel and groups is not None:
             raise ValueError("ragged_step_dyn(chunk_kernel=True) takes no groups=: the grouped call has no chunk kernel")
@@ -1481,8 +1496,9 @@ class SinkCacheLayer(_HFLayer if _HAS_HF else object):
         # the grouped call keeps constants and workspace of its own, so that grouped and ungrouped steps (and graphs
         # captured of either) can alternate on one layer without replacing each other's workspace
         flags = (N.FLAG_RAGGED_CHUNK128 if chunk_kernel else 0) | (N.FLAG_RAGGED_DECODE1 if decode_kernel else 0) | \
-            (N.FLAG_RAGGED_DECODE1_RAW8 if raw_fp8 else 0)
-        attr = ("_ragged_raw8_chunk_state" if chunk_kernel else "_ragged_raw8_state") if raw_fp8 else \
+            (N.FLAG_RAGGED_DECODE1_RAW8 if raw_fp8 else 0) | (N.FLAG_RAGGED_DECODE_DRAFT if draft else 0)
+        attr = ("_ragged_draft_chunk_state" if chunk_kernel else "_ragged_draft_state") if draft else \
+            ("_ragged_raw8_chunk_state" if chunk_kernel else "_ragged_raw8_state") if raw_fp8 else \
             ("_ragged_decode_chunk_state" if chunk_kernel else "_ragged_decode_state") if decode_kernel else \
             "_ragged_chunk_state" if chunk_kernel else "_ragged_group_state" if n_grp else "_ragged_state"
         st = getattr(self, attr, None)
@@ -1802,7 +1818,8 @@ class SinkAttentionCache(_HFCache if _HAS_HF else object):
         ``admit=True`` takes sequences on fresh slots from position 0 in the same call; ``parent`` / ``commit_seq``:
         draft trees in the pack and per-sequence commit; ``groups``: fork groups whose shared prompt prefix is read once
         (paged pools); ``chunk_kernel``: prompt chunks on the 128-row chunk kernel; ``force_generic``: the exact-f32
-        kernel (contiguous 16-bit pools); ``decode_kernel``: single-token rows on the decode-row kernel;
+        kernel (contiguous 16-bit pools); ``decode_kernel``: single-token rows on the decode-row kernel, ``"draft"``:
+        also the draft sequences (``n_i >= 2``, ``G * n_i <= 32``) on the draft-row kernel;
         ``raw_fp8`` (with ``decode_kernel`` on an FP8 pool): its raw-code data path.  Head dim 256 is served
         on every pool kind, without ``groups`` / ``chunk_kernel`` / ``decode_kernel``."""
         return self._layer(layer_idx).ragged_step_dyn(q, key_states, value_states, cu_q, slots, s_aux=s_aux, out=out,

@@ -45,6 +45,11 @@ Variants per (W, step), alternating in one process:
     paged FP8 pool (pfp8, P = 64, shuffled table) beside them and, on the two FP8 pools, raw_fp8 and raw_fp8_chunk
     (raw_fp8=True).
 
+--draft: the draft-row kernel instead (wall mode): the two geometries, the pools (bf16, FP8) and the rings of
+    --decode, packs draft64 (64 chain sequences of 4 tokens) and draft63_pre512 (63 of them + one chunk of 512 tokens),
+    committing.  Variants ragged, ragged_chunk (chunk_kernel=True), draft (decode_kernel="draft") and draft_chunk (both),
+    alternating; each time over ragged, the _chunk ones over ragged_chunk too.
+
 --d256: head dim 256 instead (wall mode): H_q=64, H_kv=8 (G = 8), D = 256, bf16, Wc = 4096 with every
     ring full, packs dec8 (8 decode rows) and dec8_pre512 (8 decode rows + one chunk of 512 tokens), committing.  Variants
     on pools of the same content, alternating in one process: mfma (the pair kernel, contiguous bf16 pool), f32 (the same
@@ -58,7 +63,7 @@ Variants per (W, step), alternating in one process:
 --summarize OUT/.../rstep_kernel_trace.csv: per (W, step, variant) the median per call of the summed prep / split /
   reduce / advance kernel times (the trace is cut into blocks in issue order).
 usage: python tools/kbench_ragged_step.py [--mode wall|kernels] [--W 128,4096] [--steps ...] [--variants ...]
-       [--admit | --tree | --chunk | --decode | --d256 | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
+       [--admit | --tree | --chunk | --decode | --draft | --d256 | --pool-dtypes bf16,fp8 | --page-size 64,256 | --pool-dtypes bf16,fp8 --page-size 64] [--pkg DIR]"""
 import argparse
 import csv
 import os
@@ -440,11 +445,15 @@ def chunk_kernel(args):
 DEC_GEOMS = {"serving": (32, 8, 128), "gpt-oss": (64, 8, 64)}      # (H_q, H_kv, D)
 DEC_VARIANTS = {"ragged": {}, "ragged_dec": dict(decode_kernel=True), "ragged_dec_chunk": dict(decode_kernel=True, chunk_kernel=True)}
 DEC_RAW = {"raw_fp8": dict(decode_kernel=True, raw_fp8=True), "raw_fp8_chunk": dict(decode_kernel=True, raw_fp8=True, chunk_kernel=True)}
+DRAFT_VARIANTS = {"ragged": {}, "ragged_chunk": dict(chunk_kernel=True), "draft": dict(decode_kernel="draft"),
+                  "draft_chunk": dict(decode_kernel="draft", chunk_kernel=True)}
+DRAFT_STEPS = {"draft64": [4] * 64, "draft63_pre512": [4] * 63 + [512]}
 DEC_PAGE = 64                                   # the page size of the paged FP8 pool of --decode (shuffled table)
 
 
-def decode_kernel(args):
-    """--decode: the packed step without the keyword, with decode_kernel=True and with decode_kernel + chunk_kernel, on a
+def decode_kernel(args, draft=False):
+    """--draft: DRAFT_VARIANTS on DRAFT_STEPS, on a 16-bit and an FP8 pool; otherwise
+    --decode: the packed step without the keyword, with decode_kernel=True and with decode_kernel + chunk_kernel, on a
     16-bit, an FP8 and a paged FP8 pool of 64 full rings, on the FP8 pools also with raw_fp8=True,
     alternating; bytes = what the format must read (pool_dtypes' count)"""
     import torch
@@ -452,6 +461,9 @@ def decode_kernel(args):
     dev, dt = "cuda", torch.bfloat16
     fmt = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "pfp8": torch.float8_e4m3fn}
     variants = {**DEC_VARIANTS, **(DEC_RAW if hasattr(_native, "FLAG_RAGGED_DECODE1_RAW8") else {})}
+    steps = POOL_STEPS
+    if draft:
+        fmt, variants, steps = {n: fmt[n] for n in ("bf16", "fp8")}, DRAFT_VARIANTS, DRAFT_STEPS
     Ws = [int(x) for x in args.W.split(",")] if args.W != "128,4096" else [4096]
     print(f"library {os.path.relpath(_native.LIB_PATH, ROOT)}\nnum_sink={NS} s_aux bf16 activations, pool of {POOL_S}, rings full; device ms "
           f"per committing step, median of {args.rounds} rounds of {args.calls} calls (events) after {WARM} warm-up calls, variants "
@@ -474,13 +486,13 @@ def decode_kernel(args):
                 pools[n].prefill_slots(k, v, [pre * i for i in range(POOL_S + 1)], list(range(POOL_S)))
             del k, v
             sa = torch.randn(hq, device=dev) * 0.5
-            for step, lengths in POOL_STEPS.items():
+            for step, lengths in steps.items():
                 T = sum(lengths)
                 q = torch.randn(1, hq, T, d, device=dev, dtype=dt)
                 kn, vn = (torch.randn(1, hkv, T, d, device=dev, dtype=dt) for _ in range(2))
                 cu = torch.tensor([sum(lengths[:i]) for i in range(POOL_S + 1)], dtype=torch.int32, device=dev)
                 slots = torch.arange(POOL_S, dtype=torch.int32, device=dev)
-                names = [(n, vr) for n in fmt for vr in variants if n != "bf16" or vr in DEC_VARIANTS]
+                names = [(n, vr) for n in fmt for vr in variants if draft or n != "bf16" or vr in DEC_VARIANTS]
                 outs = {x: torch.empty_like(q) for x in names}
                 call = lambda x, commit: pools[x[0]].ragged_step_dyn(q, kn, vn, cu, slots, s_aux=sa, out=outs[x], commit=commit,
                                                                      **variants[x[1]])
@@ -494,7 +506,8 @@ def decode_kernel(args):
                     diff = (outs[(n, vr)].float() - outs[(n, "ragged")].float()).abs().max().item()
                     print(f"      {n:4s} {vr:16s} {x[len(x) // 2]:7.4f} ms (min {x[0]:.4f} max {x[-1]:.4f}) {nbytes / 2 ** 20:7.1f} MiB "
                           f"{nbytes / x[len(x) // 2] / 1e9:6.3f} TB/s  / ragged {x[len(x) // 2] / sorted(res[(n, 'ragged')])[len(x) // 2]:.3f}"
-                          f"  max |o diff| {diff:.2e}", flush=True)
+                          f"  max |o diff| {diff:.2e}" + (f"  / ragged_chunk {x[len(x) // 2] / sorted(res[(n, 'ragged_chunk')])[len(x) // 2]:.3f}"
+                                                      if draft and vr.endswith("_chunk") else ""), flush=True)
 
 
 D256_PACKS = {"dec8": [1] * 8, "dec8_pre512": [1] * 8 + [512]}
@@ -618,6 +631,7 @@ def main():
     ap.add_argument("--page-size", default=None, help="64,256: the packed step on a contiguous and on paged pools (wall mode)")
     ap.add_argument("--chunk", action="store_true", help="the 128-row chunk kernel (wall mode): variants ragged and ragged_chunk")
     ap.add_argument("--decode", action="store_true", help="the decode-row kernel (wall mode): ragged, ragged_dec, ragged_dec_chunk on bf16 and FP8 pools")
+    ap.add_argument("--draft", action="store_true", help="the draft-row kernel (wall mode): ragged, ragged_chunk, draft, draft_chunk on bf16 and FP8 pools")
     ap.add_argument("--d256", action="store_true", help="head dim 256 (wall mode): the pair kernel, the f32 kernel and the pool kinds")
     ap.add_argument("--pkg", default=None, help="a checkout of another commit (built) to import sink_attention from")
     args = ap.parse_args()
@@ -627,6 +641,8 @@ def main():
         chunk_kernel(args)
     elif args.decode:
         decode_kernel(args)
+    elif args.draft:
+        decode_kernel(args, draft=True)
     elif args.d256:
         d256(args)
     elif args.page_size and args.pool_dtypes:
